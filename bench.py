@@ -18,6 +18,11 @@ step, priced on the matrix pipe it EXECUTES on (the f32 contractions are issued 
 ``profiles/<round>/pmc_hbm.json`` (tools/profile_round.sh).  ``roofline_knm`` is the K_nm kernel the metric names
 (HBM-bound): the standalone f32 launch AND the solve-precision launch the step itself runs.  ``cpu_baseline`` times the
 reference-shaped torch-CPU oracle (oracle/gdrf_oracle.py) on bounded samples of the same workload.
+
+``--dump-outputs DIR`` writes what the LAST timed step handed its caller - the loss ``SVI.step`` returned and the model's
+parameters (``state_dict()``) that step left behind - as ``DIR/<name>.npy`` (float32 / float64, at most 64 MB in all; see
+``dump_outputs``).  The inputs depend on the arguments alone (``--seed``), so two builds run with the same arguments can be
+compared array for array.
 """
 from __future__ import annotations
 
@@ -39,9 +44,10 @@ PEAK_16BIT_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: bf16 / f16 dense peak (1
 PEAK_HBM_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E spec
 PROFILE_ROUND = "r03"            # profiles/<round>/pmc_hbm.json: HBM bytes per launch from the PMC passes of this command
 SPLIT_PRODUCTS = {"bf16x6": 6, "f16x3": 3}     # MFMA products issued per f32 multiply-add (csrc/gemm_split.h)
+DUMP_BUDGET_BYTES = 64 << 20                   # --dump-outputs: the written .npy files together, headers included
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -64,7 +70,47 @@ def parse():
                     help="arithmetic of the f32 GEMM-shaped contractions: split emulation on the 16-bit matrix pipe (f16x3: two "
                          "fp16 pieces, 3 products, block-scaled - the default for float32; bf16x6: three bf16 pieces, 6 products), "
                          "or native f32 MFMA")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and the parameters the last timed step produced as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: larger parameters are replaced by a fixed, seeded sample of their elements)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write ``{name: array}`` as ``out_dir/<name>.npy``: float32 stays float32, everything else becomes float64.  The files
+    together stay within ``budget`` bytes: taking the arrays from the smallest up, each gets an equal share of what is left, and
+    one larger than its share is written as a sample of its flattened elements - sorted, distinct indices drawn from a generator
+    seeded with the array's name, so the same arguments sample the same elements in every build.  Returns {name: elements written}."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    header = 256                                   # np.save header reserve (128 bytes for a plain 1-D / N-D float array)
+    items = []
+    for name, a in arrays.items():
+        if not name or os.sep in name or name in (".", ".."):
+            raise ValueError(f"not a file name: {name!r}")
+        a = np.asarray(a)
+        items.append((name, a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)))
+    items.sort(key=lambda it: (it[1].nbytes, it[0]))
+    left, written = budget, {}
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i) - header
+        if a.nbytes > share:
+            k = share // a.itemsize
+            if k < 1:
+                raise ValueError(f"--dump-outputs: no room left for {name} within {budget} bytes")
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.unique(rng.integers(0, a.size, size=k, dtype=np.int64))
+            a = np.ascontiguousarray(a.reshape(-1)[idx])
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+        written[name] = int(a.size)
+    return written
 
 
 def csrc_sha():
@@ -229,6 +275,11 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    # ---- what the last timed step returned, taken before the passes below move the parameters on (replicated on every rank)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = {"loss": np.float64(loss)}
+        outputs.update({k: v.cpu().numpy() for k, v in model.state_dict().items()})
     # ---- second pass (untimed): per-kernel times from HIP events recorded on the launch streams inside the library
     kp = max(1, args.kernel_pass_steps)
     eng.set_timing(True)
@@ -343,6 +394,8 @@ def main():
         if world == 1 and args.cpu_baseline_n and min(args.cpu_baseline_n) > 0:
             out["cpu_baseline"] = cpu_baseline(args, M)
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()
