@@ -27,6 +27,8 @@ SIGNATURES = {
     "gdrf_set_mean": (_int, [_vp, _vp, _i64, _i64]),
     "gdrf_set_learn_inducing": (_int, [_vp, _int]),
     "gdrf_inducing_layout": (_int, [_vp, C.POINTER(_i64)]),
+    "gdrf_set_ard": (_int, [_vp, _int]),
+    "gdrf_ard_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_ctx_destroy": (None, [_vp]),
     "gdrf_param_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_red_layout": (_int, [_vp, C.POINTER(_i64)]),

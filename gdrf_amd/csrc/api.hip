@@ -91,6 +91,7 @@ struct gdrf_ctx {
   int unwhitened;             // whiten = False: u' = L^-1 u, S' = L^-1 S (solve-precision scratch below, allocated on demand)
   void *uS, *uSb, *uSc, *uU, *uUb, *Uw;
   int learn_z; double* zpart; // learnable inducing inputs: per-row-tile partial sums [ceil(ncap/128)][M][D]
+  int ard; void* Zp; double* apart;   // ARD (gdrf_set_ard): scaled inducing inputs in the N-side precision (probe, gdrf_knm); per-block sums of d / d log ls_d
   std::vector<void*> allocs;
   // optional per-kernel HIP-event timing (gdrf_set_timing): events recorded on the launch stream
   int timing;
@@ -122,27 +123,31 @@ static int64_t poff(const gdrf_ctx* c, int which) {
   const int64_t o_uloc = 4, o_phi = round_up(o_uloc + (int64_t)c->K * c->M, 4);
   const int64_t o_S = round_up(o_phi + (int64_t)c->K * c->V, 4);
   const int64_t o_Z = round_up(o_S + (int64_t)c->K * c->M * c->M, 4);          // unconstrained inducing inputs (M, D)
-  const int64_t total = round_up(o_Z + (int64_t)c->M * c->D, 4);
+  const int64_t o_ard = round_up(o_Z + (int64_t)c->M * c->D, 4);               // ARD contexts only: the D log-lengthscales
+  const int64_t total = c->ard ? round_up(o_ard + c->D, 4) : o_ard;
   switch (which) { case 0: return 0; case 1: return 1; case 2: return 2; case 3: return o_uloc; case 4: return o_phi;
-                   case 5: return o_S; case 7: return o_Z; default: return total; }
+                   case 5: return o_S; case 7: return o_Z; case 8: return o_ard; default: return total; }
 }
+// doubles of red_d: 8 scalars, the (M, D) inducing-input sums, in ARD contexts the D sums of d / d log ls_d over the rows
+static int64_t red_nd(const gdrf_ctx* c) { return 8 + (int64_t)c->M * c->D + (c->ard ? c->D : 0); }
 static int64_t roff(const gdrf_ctx* c, int which) {
   const int64_t mm = (int64_t)c->Mp * c->Mp;
   const int64_t o_ubar = 0, o_phib = round_up((int64_t)c->K * c->Mp, 4), o_A = round_up(o_phib + (int64_t)c->K * c->V, 4);
   const int64_t o_GT = o_A + c->K * mm, o_tail = o_GT + mm;
   // tail: the doubles of red_d for the step's single all-reduce (gdrf_payload_pack): as they are in f64 contexts, four float
   // pieces each in f32 ones
-  const int64_t nd = 8 + (int64_t)c->M * c->D, total = o_tail + round_up(c->esz == 8 ? nd : 4 * nd, 4);
+  const int64_t nd = red_nd(c), total = o_tail + round_up(c->esz == 8 ? nd : 4 * nd, 4);
   switch (which) { case 0: return o_ubar; case 1: return o_phib; case 2: return o_A; case 3: return o_GT; case 5: return o_tail; default: return total; }
 }
 
 int gdrf_param_layout(const gdrf_ctx* c, int64_t out[7]) { for (int i = 0; i < 7; ++i) out[i] = poff(c, i); return 0; }
 int gdrf_red_layout(const gdrf_ctx* c, int64_t out[6]) {
   for (int i = 0; i < 5; ++i) out[i] = roff(c, i);
-  out[5] = 8 + (int64_t)c->M * c->D;          // 8 scalars, then the (M, D) inducing-input sums (learnable inducing points)
+  out[5] = red_nd(c);          // 8 scalars, then the (M, D) inducing-input sums (learnable inducing points), then the ARD sums
   return 0;
 }
 int gdrf_inducing_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 7); out[1] = (int64_t)c->M * c->D; return 0; }
+int gdrf_ard_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 8); out[1] = c->ard ? c->D : 0; return 0; }
 
 // row blocks of the ubar partial kernel: ~1024 workgroups, multiples of its 256-row staging step
 static int64_t ubar_rows_per_block(int64_t n) { return std::max<int64_t>(256, round_up((n + 1023) / 1024, 256)); }
@@ -197,14 +202,14 @@ static bool tn_topics_on(const gdrf_ctx* c) {
 // forward-shaped f64 GEMM (6.7 ms alone, 13.8 ms beside fwd_t) costs what the backward GEMM with G^T inside its stalls did (53.0 vs
 // 52.5 ms/step).  Kept as an opt-in (GDRF_WD_PATH=1, covered by a parity test); the backward GEMM is the default.
 static bool wd_path(const gdrf_ctx* c) {
-  if (c->learn_z || c->kind == GDRF_RATIONALQUADRATIC) return false;
+  if (c->learn_z || c->ard || c->kind == GDRF_RATIONALQUADRATIC) return false;
   const char* e = getenv("GDRF_WD_PATH");
   return e && e[0] == '1';
 }
 // K_nm parts of the hyper-parameter gradients through Hd = dK^T Wbar on the split-fp16 TN kernel (hyper_tn.h): f16x3 contexts with the f64
 // solve, fixed inducing inputs (their gradient needs Kbar itself), kernels whose only shape parameter is the lengthscale
 static bool hyper_tn_on(const gdrf_ctx* c) {
-  return c->hyper_tn && c->split == 2 && c->ssz == 8 && !c->learn_z && c->kind != GDRF_RATIONALQUADRATIC && !c->Tst && (c->Mp / 8) <= 256 && !wd_path(c);
+  return c->hyper_tn && c->split == 2 && c->ssz == 8 && !c->learn_z && !c->ard && c->kind != GDRF_RATIONALQUADRATIC && !c->Tst && (c->Mp / 8) <= 256 && !wd_path(c);
 }
 static int tn_topics_nsplit(const gdrf_ctx* c, int64_t n) {
   if (const char* e = getenv("GDRF_TNT_NSPLIT")) { const int v = atoi(e); if (v > 0) return v; }
@@ -245,7 +250,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   c->nt = (c->Mp + GDRF_TILE - 1) / GDRF_TILE;
   c->lgam_const = 0; c->alpha_dev = nullptr; c->timing = 0;
   c->pK = c->pL = nullptr; c->Tst = nullptr; c->side = nullptr; c->Bh = c->STh = c->Wh = nullptr; c->split = 0; c->wh_pieces = 0; c->ssc = nullptr; c->smx = nullptr;
-  c->ev_fork = c->ev_loc = c->ev_fork2 = c->ev_join = c->ev_fact0 = c->ev_fact = nullptr; c->fact_pending = 0; c->learn_z = 0; c->zpart = nullptr; c->unwhitened = 0; c->mean = nullptr; c->mean_sk = c->mean_sn = 0;
+  c->ev_fork = c->ev_loc = c->ev_fork2 = c->ev_join = c->ev_fact0 = c->ev_fact = nullptr; c->fact_pending = 0; c->learn_z = 0; c->zpart = nullptr; c->ard = 0; c->Zp = nullptr; c->apart = nullptr; c->unwhitened = 0; c->mean = nullptr; c->mean_sk = c->mean_sn = 0;
   c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->side2 = nullptr; c->ev_ak = c->ev_ak_done = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->Wd = nullptr; c->wdpart = nullptr; c->ev_wd = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0;
   for (int i = 0; i < GDRF_NSLOTS; ++i) { c->t_ms[i] = 0; c->t_cnt[i] = 0; }
   const size_t mm = (size_t)c->Mp * c->Mp * c->esz, mms = (size_t)c->Mp * c->Mp * c->ssz;
@@ -260,7 +265,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   AL(c->Kuu, mms) AL(c->Lw, mms) AL(c->Lo, mms)
   c->mmslab_bytes = 8 * mms;
   c->prefact_valid = 0; c->prefact_jitter = 0;
-  AL(c->snap, (size_t)(4 + (size_t)c->M * c->D) * c->esz)
+  AL(c->snap, (size_t)(4 + (size_t)c->M * c->D + GDRF_DMAX) * c->esz)
   AL(c->mmslab, c->mmslab_bytes) AL(c->L, mms) AL(c->LT, mms) AL(c->Linv, mms) AL(c->LinvT, mms)
   AL(c->Dinv, (size_t)(c->Mp / 32) * 1024 * c->ssz)
   AL(c->t0, mms) AL(c->t1, mms) AL(c->t2, mms) AL(c->GTs, mms)
@@ -436,6 +441,24 @@ int gdrf_set_learn_inducing(gdrf_ctx* c, int on) {
   c->learn_z = on;
   return 0;
 }
+int gdrf_set_ard(gdrf_ctx* c, int on) {
+  if (on != 0 && on != 1) return fail(-1, "gdrf_set_ard", "on must be 0 or 1");
+  HIPCHK(hipSetDevice(c->dev));
+  if (on && !c->Zp) {
+    // apart: D per backward workgroup (at most dpart_len / 3 of them, gdrf_step_local checks) or per inducing point (M < dpart_len)
+    const size_t sz[] = {(size_t)c->Mp * c->D * c->esz, (size_t)c->dpart_len * c->D * sizeof(double)};
+    void** ps[] = {&c->Zp, (void**)&c->apart};
+    for (int i = 0; i < 2; ++i) {
+      void* p = nullptr;
+      hipError_t e = hipMalloc(&p, sz[i]);
+      if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(ARD scratch)", hipGetErrorString(e));
+      *ps[i] = p; c->allocs.push_back(p);
+    }
+  }
+  c->ard = on;
+  c->prefact_valid = 0;
+  return 0;
+}
 int gdrf_get_mfma_mode(const gdrf_ctx* c) { return c->split; }
 int gdrf_set_hyper_backward(gdrf_ctx* c, int mode) {
   if (mode != 0 && mode != 1) return fail(-1, "gdrf_set_hyper_backward", "mode must be 0 (f64 backward GEMM) or 1 (Hd = dK^T Wbar on the TN kernel)");
@@ -528,8 +551,15 @@ template <typename T, typename TS> struct Impl {
     const int Mp = c->Mp, M = c->M;
     ScopedTimer tm(c, 0, s);
     HIPCHK(hipMemsetAsync(c->flag + 8, 0, 32, s));
-    hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp_probe);
     dim3 g2((Mp + 255) / 256, Mp);
+    if (c->ard) {
+      const int64_t nz = (int64_t)M * c->D;
+      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp_probe);
+      hipLaunchKernelGGL((scale_z_kernel<T, T>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), P(c->Zp));
+      Z = (const T*)P(c->Zp);
+    } else {
+      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp_probe);
+    }
     hipLaunchKernelGGL(kuu_kernel<T>, g2, dim3(256), 0, s, Z, M, Mp, c->D, c->kind, c->hyp_probe, 0.0, P(c->pK));
     JitterLevels jl;
     for (int l = 0; l < 8; ++l) jl.v[l] = l < nlev ? jitters[l] : 0.0;
@@ -554,7 +584,8 @@ template <typename T, typename TS> struct Impl {
     const int Mp = c->Mp, M = c->M;
     const int64_t nzs = (int64_t)M * c->D;
     if (mode == 2 && c->prefact_valid && jitter == c->prefact_jitter) {
-      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 1, c->flag + 16);
+      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 1, c->flag + 16, params + poff(c, 8),
+                         c->ard ? c->D : 0);
       // the factorisation stays valid for further calls with the same inputs (a predictive evaluation between two steps): every reuse
       // compares again, and any fresh factorisation below invalidates it first
       LAUNCHCHK("factorize (reuse)");
@@ -563,9 +594,14 @@ template <typename T, typename TS> struct Impl {
     c->prefact_valid = 0;
     if (mode != 1) HIPCHK(hipMemsetAsync(c->flag + 16, 0, sizeof(int), s));     // this stream's own factorisation: nothing reused, no mismatch to report
     dim3 g2((Mp + 255) / 256, Mp);
-    hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp);
     const int64_t nz = (int64_t)M * c->D;
-    hipLaunchKernelGGL((cast_kernel<T, TS>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, Z, Q(c->Zs));
+    if (c->ard) {      // the scaled inducing inputs z_d / ls_d in the solve precision; ls = 1 in the hyper-parameter block
+      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp);
+      hipLaunchKernelGGL((scale_z_kernel<T, TS>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), Q(c->Zs));
+    } else {
+      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp);
+      hipLaunchKernelGGL((cast_kernel<T, TS>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, Z, Q(c->Zs));
+    }
     HIPCHK(hipEventRecord(c->ev_fact0, s));
     hipStream_t f = c->side;
     HIPCHK(hipStreamWaitEvent(f, c->ev_fact0, 0));
@@ -598,7 +634,8 @@ template <typename T, typename TS> struct Impl {
     HIPCHK(hipEventRecord(c->ev_fact, f));
     c->fact_pending = 1;
     if (mode == 1) {
-      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 0, (int*)nullptr);
+      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 0, (int*)nullptr, params + poff(c, 8),
+                         c->ard ? c->D : 0);
       c->prefact_valid = 1; c->prefact_jitter = jitter;
     }
     LAUNCHCHK("factorize");
@@ -606,7 +643,14 @@ template <typename T, typename TS> struct Impl {
   }
 
   static int knm(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, T* out, int64_t ldo, hipStream_t s) {
-    hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp);
+    if (c->ard) {
+      const int64_t nz = (int64_t)c->M * c->D;
+      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp);
+      hipLaunchKernelGGL((scale_z_kernel<T, T>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), P(c->Zp));
+      Z = (const T*)P(c->Zp);
+    } else {
+      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp);
+    }
     ScopedTimer tm(c, 1, s);
     const int VE = Vec16<T>::N;
     const int vpr = (c->M + VE - 1) / VE, rpp = vpr <= 256 ? 256 / vpr : 1;
@@ -616,7 +660,9 @@ template <typename T, typename TS> struct Impl {
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     const char* plain = getenv("GDRF_KNM_PLAIN_STORES");
-    if (plain && plain[0] == '1')
+    if (c->ard)
+      hipLaunchKernelGGL((knm_kernel<T, T, true, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
+    else if (plain && plain[0] == '1')
       hipLaunchKernelGGL((knm_kernel<T, T, true, false>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
     else
       hipLaunchKernelGGL((knm_kernel<T, T, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
@@ -858,6 +904,14 @@ template <typename T, typename TS> struct Impl {
     if (blocks < 1) blocks = 1;
     if constexpr (sizeof(TS) == 8) {
       if (c->kind == 0 && vpr <= 256) {
+        if (c->ard) {
+          if (c->D <= 2) hipLaunchKernelGGL((knm_rbf_f64_kernel<T, 2, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D,
+                                            c->hyp, (double*)Q(c->Knm), (int64_t)c->Mp);
+          else hipLaunchKernelGGL((knm_rbf_f64_kernel<T, GDRF_DMAX, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M,
+                                  c->D, c->hyp, (double*)Q(c->Knm), (int64_t)c->Mp);
+          LAUNCHCHK("knm_solve");
+          return 0;
+        }
         if (c->D <= 2) hipLaunchKernelGGL((knm_rbf_f64_kernel<T, 2>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D, c->hyp,
                                           (double*)Q(c->Knm), (int64_t)c->Mp);
         else hipLaunchKernelGGL((knm_rbf_f64_kernel<T, GDRF_DMAX>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D, c->hyp,
@@ -866,8 +920,12 @@ template <typename T, typename TS> struct Impl {
         return 0;
       }
     }
-    hipLaunchKernelGGL((knm_kernel<TS, T, false>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const TS*)Q(c->Zs), c->M, c->D, c->kind,
-                       c->hyp, Q(c->Knm), (int64_t)c->Mp);
+    if (c->ard)
+      hipLaunchKernelGGL((knm_kernel<TS, T, false, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const TS*)Q(c->Zs), c->M, c->D, c->kind,
+                         c->hyp, Q(c->Knm), (int64_t)c->Mp);
+    else
+      hipLaunchKernelGGL((knm_kernel<TS, T, false>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const TS*)Q(c->Zs), c->M, c->D, c->kind,
+                         c->hyp, Q(c->Knm), (int64_t)c->Mp);
     LAUNCHCHK("knm_solve");
     return 0;
   }
@@ -1194,7 +1252,21 @@ template <typename T, typename TS> struct Impl {
       ScopedTimer tm(c, 8, s);
       const int64_t nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
       if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
-      if (c->learn_z) {
+      if (c->ard) {
+        if (c->learn_z) {
+          BwdKnmProb<TS, T, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
+                                          c->hyp, c->dpart, c->zpart, c->apart};
+          hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
+          hipLaunchKernelGGL(reduce_parts_kernel<double>, dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, s, (const double*)c->zpart, rtiles,
+                             (int64_t)M * c->D, redd + 8);
+        } else {
+          BwdKnmProb<TS, T, false, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
+                                           c->hyp, c->dpart, nullptr, c->apart};
+          if (sizeof(TS) == 8) hipLaunchKernelGGL((gemm_nt_kernel_v160<TS, BwdKnmProb<TS, T, false, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
+          else hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, false, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
+        }
+        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D, redd + 8 + (int64_t)M * c->D);   // the ARD tail
+      } else if (c->learn_z) {
         BwdKnmProb<TS, T, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
                                   c->hyp, c->dpart, c->zpart};
         hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
@@ -1305,7 +1377,7 @@ template <typename T, typename TS> struct Impl {
                          T* redT, double* redd, hipStream_t s) {
     const int K = c->K, V = c->V;
     const int64_t ldk = c->ldk, kn = (int64_t)K * ldk, nq = (int64_t)((c->Mp + 63) / 64) * ldk;
-    const int64_t nT = roff(c, 4), nd = 8 + (int64_t)c->M * c->D;
+    const int64_t nT = roff(c, 4), nd = red_nd(c);
     int rc;
     if (!c->g_loc) {
       void** ps[] = {&c->g_loc, &c->g_tt, &c->g_qpart, &c->g_vbar, &c->g_locbar, &c->g_asum, &c->g_redT, (void**)&c->g_redd};
@@ -1432,10 +1504,19 @@ template <typename T, typename TS> struct Impl {
     // YT = Linv^T P^T ; S' = Linv^T Y
     if ((rc = mm_nt<TS>(c, Q(c->LinvT), 0, Q(c->t2), 0, Q(c->t0), 0, TS(1), 1, s))) return rc;
     if ((rc = mm_nt<TS>(c, Q(c->LinvT), 0, Q(c->t0), 0, Q(c->t1), 0, TS(1), 1, s))) return rc;
-    hipLaunchKernelGGL(kuu_bar_reduce_kernel<TS>, dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind,
-                       c->hyp, c->dpart);
+    if (c->ard) {          // K_uu sums of d / d log ls_d -> dsmall[3..3+D)
+      hipLaunchKernelGGL((kuu_bar_reduce_kernel<TS, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind,
+                         c->hyp, c->dpart, c->apart);
+      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, (int64_t)M, c->D, c->dsmall + 3);
+    } else {
+      hipLaunchKernelGGL(kuu_bar_reduce_kernel<TS>, dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind,
+                         c->hyp, c->dpart);
+    }
     hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)M, 3, c->dsmall);
-    if (c->learn_z)
+    if (c->learn_z && c->ard)
+      hipLaunchKernelGGL((grad_z_kernel<TS, T, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind, c->hyp,
+                         redd + 8, -1.0 / n_global, grads + poff(c, 7), Z);
+    else if (c->learn_z)
       hipLaunchKernelGGL((grad_z_kernel<TS, T>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind, c->hyp,
                          redd + 8, -1.0 / n_global, grads + poff(c, 7));
     // Sbar_k = 2 A_k S_k (N-side precision: well conditioned)
@@ -1447,6 +1528,9 @@ template <typename T, typename TS> struct Impl {
     }
     hipLaunchKernelGGL(grad_small_kernel<T>, dim3(1), dim3(256), 0, s, M, Mp, K, V, c->hyp, redd, c->dsmall, ubar, phib, P(c->phi),
                        c->alpha_dev, c->lgam_const, ll_const, n_global, grads, grads + poff(c, 3), grads + poff(c, 4), c->flag, out_d);
+    if (c->ard)
+      hipLaunchKernelGGL(grad_ard_kernel<T>, dim3(1), dim3(64), 0, s, c->D, (const double*)redd + 8 + (int64_t)M * c->D, (const double*)c->dsmall + 3,
+                         n_global, grads, grads + poff(c, 8));
     if (c->unwhitened)       // overwrite the u_loc / u_scale_tril blocks with the gradients chained through L^-T
       hipLaunchKernelGGL((grad_unwhitened_kernel<TS, T>), g3, dim3(256), 0, s, (const TS*)Q(c->uSc), (const TS*)Q(c->uUb), params + poff(c, 5), K, M,
                          Mp, -1.0 / n_global, grads + poff(c, 5), grads + poff(c, 3));
@@ -1487,10 +1571,14 @@ template <typename T, typename TS> struct Impl {
         const int64_t groups = (n + 15) / 16;
         int64_t blocks = (groups + 3) / 4; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
         const int64_t ldo = mode == 0 ? n : (mode == 1 ? K : V);
-#define GDRF_PM(DDv, NBv) { if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)predict_mfma_kernel<TS, T, DDv, NBv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                            hipLaunchKernelGGL((predict_mfma_kernel<TS, T, DDv, NBv>), dim3((unsigned)blocks), dim3(256), lds, s, X, n, (const TS*)Q(c->Zs), M, M4, c->D, c->kind, \
+#define GDRF_PM(DDv, NBv, ARDv) { if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)predict_mfma_kernel<TS, T, DDv, NBv, ARDv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+                            hipLaunchKernelGGL((predict_mfma_kernel<TS, T, DDv, NBv, ARDv>), dim3((unsigned)blocks), dim3(256), lds, s, X, n, (const TS*)Q(c->Zs), M, M4, c->D, c->kind, \
                                                c->hyp, (const TS*)Q(c->CfT), K, V, (const T*)P(c->phi), ws, mode, out, ldo, c->dpart); }
-        if (DDt == 2) { if (NB == 1) GDRF_PM(2, 1) else GDRF_PM(2, 2) } else { if (NB == 1) GDRF_PM(GDRF_DMAX, 1) else GDRF_PM(GDRF_DMAX, 2) }
+        if (c->ard) {
+          if (DDt == 2) { if (NB == 1) GDRF_PM(2, 1, true) else GDRF_PM(2, 2, true) } else { if (NB == 1) GDRF_PM(GDRF_DMAX, 1, true) else GDRF_PM(GDRF_DMAX, 2, true) }
+        } else {
+          if (DDt == 2) { if (NB == 1) GDRF_PM(2, 1, false) else GDRF_PM(2, 2, false) } else { if (NB == 1) GDRF_PM(GDRF_DMAX, 1, false) else GDRF_PM(GDRF_DMAX, 2, false) }
+        }
 #undef GDRF_PM
         if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, blocks, 2, out_d);
         LAUNCHCHK("predict (mfma)");
@@ -1503,18 +1591,20 @@ template <typename T, typename TS> struct Impl {
     if (K > GDRF_KMAX) {
       const size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)128 * (V + 1)) * sizeof(TS);
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V + 128*(V+1) solve-precision elements exceed the LDS budget (150 KB)");
+      auto kfn = c->ard ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
       if (lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)predict_rows_bigk_kernel<TS, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((predict_rows_bigk_kernel<TS, T>), dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,
+        HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,
                          c->hyp, (const TS*)Q(c->Cf), K, V, (const T*)P(c->phi), ws, mode, out, ldo, c->dpart);
     } else {
       size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)K * M) * sizeof(TS);
       int in_lds = 1;
       if (lds > 64 * 1024) { in_lds = 0; lds -= (size_t)K * M * sizeof(TS); }
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V solve-precision elements exceed the LDS budget (150 KB)");
+      auto kfn = c->ard ? predict_rows_kernel<TS, T, true> : predict_rows_kernel<TS, T>;
       if (lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)predict_rows_kernel<TS, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((predict_rows_kernel<TS, T>), dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,
+        HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,
                          c->hyp, (const TS*)Q(c->Cf), K, V, (const T*)P(c->phi), ws, mode, out, ldo, c->dpart, in_lds);
     }
     if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, blocks, 2, out_d);
@@ -1541,10 +1631,10 @@ int gdrf_fill_eps(gdrf_ctx* c, uint64_t seed, uint32_t step, int64_t n_offset, i
   return 0;
 }
 
-// red_d (8 + M*D doubles) -> tail of red_T, and back after the all-reduce
+// red_d (red_nd(c) doubles) -> tail of red_T, and back after the all-reduce
 int gdrf_payload_pack(gdrf_ctx* c, void* redT, const double* redd, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
-  const int nd = 8 + c->M * c->D;
+  const int nd = (int)red_nd(c);
   if (c->esz == 8) hipLaunchKernelGGL(payload_pack_kernel<double>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, redd, nd, (double*)redT + roff(c, 5));
   else hipLaunchKernelGGL(payload_pack_kernel<float>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, redd, nd, (float*)redT + roff(c, 5));
   LAUNCHCHK("payload_pack");
@@ -1552,7 +1642,7 @@ int gdrf_payload_pack(gdrf_ctx* c, void* redT, const double* redd, void* stream)
 }
 int gdrf_payload_unpack(gdrf_ctx* c, const void* redT, double* redd, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
-  const int nd = 8 + c->M * c->D;
+  const int nd = (int)red_nd(c);
   if (c->esz == 8) hipLaunchKernelGGL(payload_unpack_kernel<double>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const double*)redT + roff(c, 5), nd, redd);
   else hipLaunchKernelGGL(payload_unpack_kernel<float>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)redT + roff(c, 5), nd, redd);
   LAUNCHCHK("payload_unpack");

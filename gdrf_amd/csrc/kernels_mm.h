@@ -13,7 +13,8 @@
 namespace gdrf {
 
 // hyper-parameter block kept on the device (double): filled by prep_hyper
-struct Hyper { double ls, var, noise, inv_ls2, alpha; };     // alpha: RationalQuadratic scale_mixture (parameter slot 3)
+// sc: ARD contexts only (gdrf_set_ard): the per-dimension coordinate scales 1 / ls_d; the isotropic forms then run with ls = 1
+struct Hyper { double ls, var, noise, inv_ls2, alpha; double sc[GDRF_DMAX]; };     // alpha: RationalQuadratic scale_mixture (parameter slot 3)
 
 template <typename T>
 __global__ void prep_hyper_kernel(const T* __restrict__ params, Hyper* h) {
@@ -23,19 +24,39 @@ __global__ void prep_hyper_kernel(const T* __restrict__ params, Hyper* h) {
   }
 }
 
-// the values a factorisation depends on - the first four parameters (log lengthscale, variance, noise, scale mixture) and the inducing inputs -
+// ARD (pyro Isotropy._scale with a (D,) lengthscale: X / lengthscale broadcast over the input axes): r2 = sum_d ((x_d - z_d) / ls_d)^2 is
+// the isotropic r2 of the scaled coordinates x_d / ls_d at ls = 1.  The inducing inputs are scaled once per factorisation (scale_z_kernel),
+// the observations as they are loaded by the kernels' ARD instantiations (coordinate times sc[d]).  log_ls: the D log-lengthscales of
+// the ARD segment of the parameter vector; slot 0 is not read.
+template <typename T>
+__global__ void prep_hyper_ard_kernel(const T* __restrict__ params, const T* __restrict__ log_ls, int D, Hyper* h) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    h->ls = 1.0; h->var = exp((double)params[1]); h->noise = exp((double)params[2]); h->inv_ls2 = 1.0; h->alpha = exp((double)params[3]);
+    for (int d = 0; d < GDRF_DMAX; ++d) h->sc[d] = d < D ? exp(-(double)log_ls[d]) : 0.0;
+  }
+}
+// out[i][d] = Z[i][d] / ls_d in the output precision (computed in double)
+template <typename T, typename TO>
+__global__ void scale_z_kernel(int64_t nz, int D, const T* __restrict__ Z, const T* __restrict__ log_ls, TO* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nz) out[i] = (TO)((double)Z[i] * exp(-(double)log_ls[i % D]));
+}
+
+// the values a factorisation depends on - the first four parameters (log lengthscale, variance, noise, scale mixture), the inducing inputs and,
+// in ARD contexts, the nextra log-lengthscales of the ARD segment (`extra`) -
 // copied aside (mode 0) or compared bit for bit with that copy (mode 1: *mismatch = 1 if any differs, 0 otherwise - written
 // unconditionally, so the word needs no clearing by anyone else: a memset queued on another stream could land after this kernel and
 // erase a mismatch).  One workgroup.
 template <typename T>
-__global__ void fact_snapshot_kernel(const T* __restrict__ params, const T* __restrict__ Z, int64_t nz, T* __restrict__ snap, int mode, int* __restrict__ mismatch) {
+__global__ void fact_snapshot_kernel(const T* __restrict__ params, const T* __restrict__ Z, int64_t nz, T* __restrict__ snap, int mode, int* __restrict__ mismatch,
+                                     const T* __restrict__ extra, int nextra) {
   if (mode == 1) {
     if (threadIdx.x == 0) *mismatch = 0;
     __syncthreads();
   }
   int bad = 0;
-  for (int64_t e = threadIdx.x; e < nz + 4; e += blockDim.x) {
-    const T v = e < 4 ? params[e] : Z[e - 4];
+  for (int64_t e = threadIdx.x; e < nz + 4 + nextra; e += blockDim.x) {
+    const T v = e < 4 ? params[e] : (e < nz + 4 ? Z[e - 4] : extra[e - 4 - nz]);
     if (mode == 0) snap[e] = v;
     else if (!(v == snap[e]) && !(v != v && snap[e] != snap[e])) bad = 1;     // equal values (a NaN only matches a NaN)
   }
@@ -734,13 +755,15 @@ __global__ void phi_tril_kernel(const T* __restrict__ Q, int Mp, T* __restrict__
   P[(int64_t)i * Mp + j] = (j < i) ? q : ((j == i) ? T(0.5) * q : T(0));
 }
 // sum_{ij} Kuu_bar * K0,  sum_{ij} Kuu_bar * dK0/dlog(ls)  and  sum_{ij} Kuu_bar * dK0/dlog(alpha), Kuu_bar = (S' + S'^T)/2 ;
-// one partial triple per block
-template <typename T>
+// one partial triple per block.  ARD (Z = the scaled inducing inputs, ls = 1): also the D sums
+// sum_j Kuu_bar * dK0/dlog(ls_d) = sum_j Kuu_bar * dk/dr2 * (-2) (z_id - z_jd)^2 into apart[D * i + d]
+template <typename T, bool ARD = false>
 __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restrict__ Z, int M, int Mp, int D, int kind,
-                                      const Hyper* __restrict__ h, double* __restrict__ part) {
+                                      const Hyper* __restrict__ h, double* __restrict__ part, double* __restrict__ apart = nullptr) {
   __shared__ double scratch[16];
   const int i = blockIdx.x;
   double s1 = 0, s2 = 0, s3 = 0;
+  double sd[ARD ? GDRF_DMAX : 1] = {};
   const T var = (T)h->var, ils2 = (T)h->inv_ls2, al = (T)h->alpha;
   for (int j = threadIdx.x; j < M; j += blockDim.x) {
     const T kb = T(0.5) * (Sp[(int64_t)i * Mp + j] + Sp[(int64_t)j * Mp + i]);
@@ -749,11 +772,21 @@ __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restr
     s1 += (double)(kb * k0);
     s2 += (double)(kb * dcov_dlogls<T>(kind, k0, r2, var, al));
     s3 += (double)(kb * dcov_dlogalpha_from_k<T>(kind, k0, r2, al));
+    if constexpr (ARD) {
+      const T w = T(-2) * kb * dcov_dr2_from_k<T>(kind, k0, r2, al);
+      for (int d = 0; d < D; ++d) { const T t = Z[(int64_t)i * D + d] - Z[(int64_t)j * D + d]; sd[d] += (double)(w * t * t); }
+    }
   }
   s1 = block_sum(s1, scratch);
   s2 = block_sum(s2, scratch);
   s3 = block_sum(s3, scratch);
   if (threadIdx.x == 0) { part[3 * i] = s1; part[3 * i + 1] = s2; part[3 * i + 2] = s3; }
+  if constexpr (ARD) {
+    for (int d = 0; d < D; ++d) {
+      const double v = block_sum(sd[d], scratch);
+      if (threadIdx.x == 0) apart[(int64_t)D * i + d] = v;
+    }
+  }
 }
 
 // ---- whiten = False (pyro conditional's unwhitened branch; sparse_gdrf.py:30): the variational mean and scale factor are
@@ -818,9 +851,12 @@ __global__ void grad_unwhitened_kernel(const T* __restrict__ Sbar, const T* __re
 //   Zbar[i][d] = 2/ls^2 * ( G[i][d] + 2 * sum_j Kuu_bar[i][j] * dk/dr2(z_i, z_j) * (z_id - z_jd) ),  Kuu_bar = (S' + S'^T)/2,
 // G = the observation-side sums of gemm_nt<BwdKnmProb<.., true>> (all-reduced), then the chain through z = sigmoid(u):
 // g = -1/N * Zbar * z (1 - z).  One block per inducing point.
-template <typename T, typename TP>
+// ARD: Z and G are in the scaled coordinates z_d / ls_d (ls = 1), d r2 / d z_d carries one more factor 1 / ls_d = sc[d], and the
+// sigmoid Jacobian takes the unscaled inputs Zr.
+template <typename T, typename TP, bool ARD = false>
 __global__ void grad_z_kernel(const T* __restrict__ Sp, const T* __restrict__ Z, int M, int Mp, int D, int kind,
-                              const Hyper* __restrict__ h, const double* __restrict__ G, double neg_inv_n, TP* __restrict__ g) {
+                              const Hyper* __restrict__ h, const double* __restrict__ G, double neg_inv_n, TP* __restrict__ g,
+                              const TP* __restrict__ Zr = nullptr) {
   __shared__ double scratch[16];
   const int i = blockIdx.x;
   const T var = (T)h->var, ils2 = (T)h->inv_ls2, al = (T)h->alpha;
@@ -836,8 +872,8 @@ __global__ void grad_z_kernel(const T* __restrict__ Sp, const T* __restrict__ Z,
   for (int d = 0; d < D; ++d) {
     const double hsum = block_sum(hs[d], scratch);
     if (threadIdx.x == 0) {
-      const double z = (double)Z[(int64_t)i * D + d];
-      const double zbar = 2.0 * (double)ils2 * (G[(int64_t)i * D + d] + 2.0 * hsum);
+      const double z = ARD ? (double)Zr[(int64_t)i * D + d] : (double)Z[(int64_t)i * D + d];
+      const double zbar = (ARD ? 2.0 * h->sc[d] : 2.0 * (double)ils2) * (G[(int64_t)i * D + d] + 2.0 * hsum);
       g[(int64_t)i * D + d] = (TP)(neg_inv_n * zbar * z * (1.0 - z));
     }
   }

@@ -44,7 +44,8 @@ __device__ __forceinline__ double exp2_poly(double t) {
 // 132 registers (3 workgroups per CU): the generic loop branches on the kernel kind per element around the library exp().
 // Straight-line form, 4 rows x 2 columns = 8 independent chains per lane: k = 2^t, t = log2 var - sum_d (a x_d - a z_d)^2
 // with the coordinates pre-scaled by a = sqrt(log2(e) / 2) / ls (exp2_poly above).  Needs ldo % 2 == 0 and ldo / 2 <= 256.
-template <typename TX, int DD, bool NT = true>
+// ARD: Z holds the scaled inducing inputs and ls = 1; the rows are scaled by a_d = a / ls_d instead.
+template <typename TX, int DD, bool NT = true, bool ARD = false>
 __global__ __launch_bounds__(256, 4) void knm_rbf_f64_kernel(const TX* __restrict__ X, int64_t N, const double* __restrict__ Z, int M, int D,
                                                           const Hyper* __restrict__ h, double* __restrict__ out, int64_t ldo) {
   typedef double V __attribute__((ext_vector_type(2)));
@@ -59,6 +60,9 @@ __global__ __launch_bounds__(256, 4) void knm_rbf_f64_kernel(const TX* __restric
   double* __restrict__ ob = out + rb * ldo;
   const TX* __restrict__ xb = X + rb * D;
   const double a = sqrt(0.5 * 1.4426950408889634074 * h->inv_ls2), lv = log2(h->var);
+  double ax[DD];
+#pragma unroll
+  for (int d = 0; d < DD; ++d) ax[d] = ARD ? a * h->sc[d] : a;
   double z[2][DD];       // coordinates beyond D are zero on both sides; a padding column sits at 1e160: t = -inf, clamped, 2^-1100 = 0
 #pragma unroll
   for (int e = 0; e < 2; ++e)
@@ -71,7 +75,7 @@ __global__ __launch_bounds__(256, 4) void knm_rbf_f64_kernel(const TX* __restric
     for (int u = 0; u < 4; ++u) {
       const int rr = r0 + u * rpp;
 #pragma unroll
-      for (int d = 0; d < DD; ++d) x[u][d] = (rr < nr && d < D) ? a * (double)xb[rr * D + d] : 0.0;
+      for (int d = 0; d < DD; ++d) x[u][d] = (rr < nr && d < D) ? ax[d] * (double)xb[rr * D + d] : 0.0;
     }
     V o[4];
 #pragma unroll
@@ -96,12 +100,17 @@ __global__ __launch_bounds__(256, 4) void knm_rbf_f64_kernel(const TX* __restric
 
 // T: output / arithmetic type, TX: type of X, FAST: v_exp_f32-based exponential (roofline kernel) or exact exp
 // (the solve-precision copy of K_nm that feeds W = K_nm L^-T).  Columns M..ldo-1 of every row are written as zeros.
-template <typename T, typename TX, bool FAST, bool NT = true>
+// ARD: Z holds the scaled inducing inputs, ls = 1, and every row coordinate is scaled by 1 / ls_d as it is loaded.
+template <typename T, typename TX, bool FAST, bool NT = true, bool ARD = false>
 __global__ __launch_bounds__(256) void knm_kernel(const TX* __restrict__ X, int64_t N, const T* __restrict__ Z, int M, int D,
                                                   int kind, const Hyper* __restrict__ h, T* __restrict__ out, int64_t ldo) {
   using V = typename Vec16<T>::type;
   constexpr int VE = Vec16<T>::N;
   const T var = (T)h->var, ils2 = (T)h->inv_ls2, al = (T)h->alpha;
+  T xs[GDRF_DMAX];
+#pragma unroll
+  for (int d = 0; d < GDRF_DMAX; ++d) xs[d] = ARD ? (T)h->sc[d] : T(1);
+  auto xl = [&](int d, T v) -> T { if constexpr (ARD) return v * xs[d]; else return v; };
   const int vpr = (int)((ldo + VE - 1) / VE);          // 16-byte vectors per output row (ldo >= M)
   const bool aligned = (ldo % VE) == 0;
   if (vpr <= 256) {
@@ -136,7 +145,7 @@ __global__ __launch_bounds__(256) void knm_kernel(const TX* __restrict__ X, int6
           for (int u = 0; u < 4; ++u) {
             const int64_t row = row0 + u * stride;
 #pragma unroll
-            for (int d = 0; d < GDRF_DMAX; ++d) x[u][d] = (row < N && d < D) ? a * (float)X[row * D + d] : 0.0f;
+            for (int d = 0; d < GDRF_DMAX; ++d) x[u][d] = (row < N && d < D) ? a * xl(d, (float)X[row * D + d]) : 0.0f;
           }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
@@ -165,7 +174,7 @@ __global__ __launch_bounds__(256) void knm_kernel(const TX* __restrict__ X, int6
       for (int u = 0; u < 4; ++u) {
         const int64_t row = row0 + u * stride;
 #pragma unroll
-        for (int d = 0; d < GDRF_DMAX; ++d) x[u][d] = (row < N && d < D) ? (T)X[row * D + d] : T(0);
+        for (int d = 0; d < GDRF_DMAX; ++d) x[u][d] = (row < N && d < D) ? xl(d, (T)X[row * D + d]) : T(0);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -190,7 +199,7 @@ __global__ __launch_bounds__(256) void knm_kernel(const TX* __restrict__ X, int6
   for (int64_t row = blockIdx.x; row < N; row += gridDim.x) {
     T x[GDRF_DMAX];
 #pragma unroll
-    for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (T)X[row * D + d] : T(0);
+    for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? xl(d, (T)X[row * D + d]) : T(0);
     T* orow = out + row * ldo;
     for (int cv = threadIdx.x; cv < vpr; cv += 256) {
       const int i0 = cv * VE;
@@ -725,7 +734,10 @@ template <typename T> struct BwdWbarTProb : NTXcdPairMap, NTPlainA<T> {
 // (4) Knm_bar = Wbar Linv (never stored) -> sum Knm_bar*Knm and sum Knm_bar*dKnm/dlog(ls) per workgroup
 // LZ: also the per-inducing-point sums  G[j][d] = sum_n Kbar[n][j] * dk/dr2(x_n, z_j) * (z_jd - x_nd)  that the gradient of
 // learnable inducing inputs needs (sparse_gdrf.py:79-88, fixed_inducing_points=False); one partial per (row tile, column).
-template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRowMap, NTNoExtra {
+// ARD: Z holds the scaled inducing inputs, ls = 1, the rows are scaled by 1 / ls_d as they are loaded, and the lengthscale sum splits
+// into the D sums  sum Kbar * dk/dr2 * (-2) (x_d - z_d)^2  (= d / d log ls_d; their total is the isotropic sum), one partial per
+// workgroup in apart[D * block + d].  Every other sum is the isotropic one in the scaled coordinates.
+template <typename T, typename TN, bool LZ = false, bool ARD = false> struct BwdKnmProb : NTXcdRowMap, NTNoExtra {
   using V = typename Vec16<T>::type;
   static constexpr int MIN_WGS = (sizeof(T) == 8 && !LZ) ? 3 : 2;   // f64: three workgroups per CU hide each other's epilogues
 #ifndef GDRF_NO_TRI
@@ -740,8 +752,11 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
   const TN* X; const T* Z; const Hyper* h;
   double* part;                    // [gridDim.x][3]: sum Kbar*K, sum Kbar*dK/dlog(ls), sum Kbar*dK/dlog(alpha)
   double* zpart;                   // LZ: [row tiles][M][D]
+  double* apart = nullptr;         // ARD: [gridDim.x][D]
   struct ACtx { const TN* p[NTCfg<T>::VPT]; };
-  struct ECtx { T s1, s2, s3; T zs[LZ ? NTCfg<T>::NB : 1][LZ ? GDRF_DMAX : 1]; int n0; };
+  struct ECtxIso { T s1, s2, s3; T zs[LZ ? NTCfg<T>::NB : 1][LZ ? GDRF_DMAX : 1]; int n0; };
+  struct ECtxArd : ECtxIso { T sd[GDRF_DMAX]; };             // the per-axis sums exist in the ARD instantiations only
+  using ECtx = std::conditional_t<ARD, ECtxArd, ECtxIso>;
   __device__ __forceinline__ int col_tiles() const { return (Mp + NTCfg<T>::CW - 1) / NTCfg<T>::CW; }
   __device__ __forceinline__ bool loop_cols() const { return false; }
   __device__ __forceinline__ int a_reuse() const { return 1; }
@@ -755,6 +770,10 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
   }
   __device__ __forceinline__ void prepE(ECtx& e, int64_t, int) const {
     e.s1 = 0; e.s2 = 0; e.s3 = 0; e.n0 = 0;
+    if constexpr (ARD) {
+#pragma unroll
+      for (int d = 0; d < GDRF_DMAX; ++d) e.sd[d] = 0;
+    }
     if constexpr (LZ) {
 #pragma unroll
       for (int b = 0; b < NTCfg<T>::NB; ++b)
@@ -785,7 +804,7 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
   template <int KD, int DD, int NR>
   __device__ __forceinline__ void strip_math(const KT2 (&kv)[NR], const T* __restrict__ trow, int tstride, const TN (&x)[NR][DD],
                                              const T (&zc)[2][DD], const bool (&rok)[NR], const bool (&cok)[2],
-                                             T ils2, T al, ECtx& e) const {
+                                             T ils2, T al, ECtx& e, const T (&xsc)[DD]) const {
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
       const KT2 kb = *reinterpret_cast<const KT2*>(trow + 4 * i * tstride);
@@ -795,15 +814,21 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
         const T kvv = kv[i][j];
         T r2 = 0;
 #pragma unroll
-        for (int d = 0; d < DD; ++d) { const T t = (d < D ? (T)x[i][d] : T(0)) - zc[j][d]; r2 += t * t; }
+        for (int d = 0; d < DD; ++d) { const T t = (d < D ? (ARD ? (T)x[i][d] * xsc[d] : (T)x[i][d]) : T(0)) - zc[j][d]; r2 += t * t; }
         r2 *= ils2;
         e.s1 += kbar * kvv;
-        e.s2 += kbar * dcov_dlogls_from_k<T>(KD, kvv, r2, al);
+        if constexpr (ARD) {
+          const T w = T(-2) * kbar * dcov_dr2_from_k<T>(KD, kvv, r2, al);
+#pragma unroll
+          for (int d = 0; d < DD; ++d) { const T t = (d < D ? (T)x[i][d] * xsc[d] : T(0)) - zc[j][d]; e.sd[d] += w * t * t; }
+        } else {
+          e.s2 += kbar * dcov_dlogls_from_k<T>(KD, kvv, r2, al);
+        }
         if constexpr (KD == 4) e.s3 += kbar * dcov_dlogalpha_from_k<T>(KD, kvv, r2, al);
         if constexpr (LZ) {
           const T w = kbar * dcov_dr2_from_k<T>(KD, kvv, r2, al);
 #pragma unroll
-          for (int d = 0; d < DD; ++d) e.zs[j][d] += w * (zc[j][d] - (d < D ? (T)x[i][d] : T(0)));
+          for (int d = 0; d < DD; ++d) e.zs[j][d] += w * (zc[j][d] - (d < D ? (ARD ? (T)x[i][d] * xsc[d] : (T)x[i][d]) : T(0)));
         }
       }
     }
@@ -817,6 +842,9 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
   __device__ __forceinline__ void epi_f64(Acc (&acc)[4][NB_], int64_t m0, int n0, ECtx& e, int wr, int wc, int lane) const {
     if (m0 >= nrows) return;                                // a padding workgroup of the XCD-aware grid (uniform: no barrier is skipped by a part of it)
     const T ils2 = (T)h->inv_ls2, al = (T)h->alpha;
+    T xsc[DD];
+#pragma unroll
+    for (int d = 0; d < DD; ++d) xsc[d] = ARD ? (T)h->sc[d] : T(1);
     extern __shared__ __attribute__((aligned(16))) char nt_smem[];
     constexpr int TS_ = 48;                                 // tile row stride in doubles: consecutive rows 128 B apart mod 256
     T* tile = reinterpret_cast<T*>(nt_smem) + (threadIdx.x >> 6) * (16 * TS_);
@@ -860,11 +888,11 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
         }
         const T* trow = tile + (lg + 4 * hb * NR) * TS_ + 2 * lr;   // slot i: row lg + 4 * (hb * NR + i) of the strip
         switch (kind) {
-          case 0: strip_math<0, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e); break;
-          case 1: strip_math<1, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e); break;
-          case 2: strip_math<2, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e); break;
-          case 3: strip_math<3, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e); break;
-          default: strip_math<4, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e); break;
+          case 0: strip_math<0, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
+          case 1: strip_math<1, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
+          case 2: strip_math<2, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
+          case 3: strip_math<3, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
+          default: strip_math<4, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);                  // one batch at a time
@@ -898,7 +926,7 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
         if (m >= nrows) continue;
         T x[GDRF_DMAX];
 #pragma unroll
-        for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (T)X[m * D + d] : T(0);
+        for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (ARD ? (T)X[m * D + d] * (T)h->sc[d] : (T)X[m * D + d]) : T(0);
 #pragma unroll
         for (int b = 0; b < NTCfg<T>::NB; ++b) {
           const int n = n0 + nt_acc_col<T>(wc, b, lane);
@@ -909,7 +937,13 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
           r2 *= ils2;
           const T kv = Knm[m * Mp + n];
           e.s1 += acc[a][b][r] * kv;
-          e.s2 += acc[a][b][r] * dcov_dlogls_from_k<T>(kind, kv, r2, al);
+          if constexpr (ARD) {
+            const T w = T(-2) * acc[a][b][r] * dcov_dr2_from_k<T>(kind, kv, r2, al);
+#pragma unroll
+            for (int d = 0; d < GDRF_DMAX; ++d) if (d < D) { const T t = x[d] - z[b][d]; e.sd[d] += w * t * t; }
+          } else {
+            e.s2 += acc[a][b][r] * dcov_dlogls_from_k<T>(kind, kv, r2, al);
+          }
           if (kind == 4) e.s3 += acc[a][b][r] * dcov_dlogalpha_from_k<T>(kind, kv, r2, al);
           if constexpr (LZ) {
             const T w = acc[a][b][r] * dcov_dr2_from_k<T>(kind, kv, r2, al);
@@ -931,6 +965,12 @@ template <typename T, typename TN, bool LZ = false> struct BwdKnmProb : NTXcdRow
     const double b = block_sum((double)e.s2, scratch);
     const double c3 = block_sum((double)e.s3, scratch);
     if (threadIdx.x == 0) { part[3 * (int64_t)blockIdx.x] = a; part[3 * (int64_t)blockIdx.x + 1] = b; part[3 * (int64_t)blockIdx.x + 2] = c3; }
+    if constexpr (ARD) {
+      for (int d = 0; d < D; ++d) {
+        const double v = block_sum((double)e.sd[d], scratch);
+        if (threadIdx.x == 0) apart[(int64_t)D * blockIdx.x + d] = v;
+      }
+    }
     if constexpr (LZ) {
       // column sums: the 4 lane groups of a wave hold 16 rows each, the two waves wr = 0, 1 the two halves of the row tile
       double* zb = reinterpret_cast<double*>(smem + 1024);       // [CW][DMAX]
@@ -1604,6 +1644,16 @@ __global__ void grad_small_kernel(int M, int Mp, int K, int V, const Hyper* __re
   }
 }
 
+// ARD contexts, behind grad_small_kernel: slot 0 (the isotropic log lengthscale, not a parameter of an ARD kernel) gets 0, the ARD
+// segment d loss / d log ls_d from the K_nm sums (red_ard, all-reduced with the payload) and the K_uu sums (kuu_ard)
+template <typename T>
+__global__ void grad_ard_kernel(int D, const double* __restrict__ red_ard, const double* __restrict__ kuu_ard, double n_global,
+                                T* __restrict__ g_hyper, T* __restrict__ g_ard) {
+  const int d = threadIdx.x;
+  if (d == 0) g_hyper[0] = T(0);
+  if (d < D) g_ard[d] = (T)((-1.0 / n_global) * (red_ard[d] + kuu_ard[d]));
+}
+
 // =====================================================================================
 // optimizers on the flat unconstrained parameter vector; predicated on the Cholesky flag
 // mode 0 Adam, 1 AdamW (decoupled decay), 2 ClippedAdam
@@ -1639,7 +1689,7 @@ __global__ void predict_coeff_kernel(const T* __restrict__ Linv, const TN* __res
 }
 
 // mode 0: write loc (K,N) ; 1: topic_probs (N,K) ; 2: word_probs (N,V) ; 3: perplexity partial sums
-template <typename T, typename TN>
+template <typename T, typename TN, bool ARD = false>
 __global__ __launch_bounds__(128) void predict_rows_kernel(const TN* __restrict__ X, int64_t nrows, const T* __restrict__ Z, int M, int D,
                                                            int kind, const Hyper* __restrict__ h, const T* __restrict__ Cf, int K, int V,
                                                            const TN* __restrict__ phi, const int32_t* __restrict__ ws, int mode,
@@ -1660,7 +1710,7 @@ __global__ __launch_bounds__(128) void predict_rows_kernel(const TN* __restrict_
   for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < nrows; n += (int64_t)gridDim.x * blockDim.x) {
     T x[GDRF_DMAX];
 #pragma unroll
-    for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (T)X[n * D + d] : T(0);
+    for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (ARD ? (T)X[n * D + d] * (T)h->sc[d] : (T)X[n * D + d]) : T(0);
     T lc[GDRF_KMAX];
 #pragma unroll
     for (int k = 0; k < GDRF_KMAX; ++k) lc[k] = 0;
@@ -1728,7 +1778,7 @@ __global__ __launch_bounds__(128) void predict_rows_kernel(const TN* __restrict_
 
 // the same for K > GDRF_KMAX: topics in chunks of GDRF_KMAX (the covariance row is re-evaluated per chunk), softmax over all K
 // in two sweeps (running maximum and sum, then the normalised values); word_probs accumulate in an LDS row per thread
-template <typename T, typename TN>
+template <typename T, typename TN, bool ARD = false>
 __global__ __launch_bounds__(128) void predict_rows_bigk_kernel(const TN* __restrict__ X, int64_t nrows, const T* __restrict__ Z, int M, int D,
                                                                 int kind, const Hyper* __restrict__ h, const T* __restrict__ Cf, int K, int V,
                                                                 const TN* __restrict__ phi, const int32_t* __restrict__ ws, int mode,
@@ -1747,7 +1797,7 @@ __global__ __launch_bounds__(128) void predict_rows_bigk_kernel(const TN* __rest
   for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < nrows; n += (int64_t)gridDim.x * blockDim.x) {
     T x[GDRF_DMAX];
 #pragma unroll
-    for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (T)X[n * D + d] : T(0);
+    for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (ARD ? (T)X[n * D + d] * (T)h->sc[d] : (T)X[n * D + d]) : T(0);
     T lc[GDRF_KMAX];
     auto chunk = [&](int k0) {
 #pragma unroll

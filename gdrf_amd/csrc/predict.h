@@ -41,7 +41,8 @@ __global__ __launch_bounds__(64) void predict_coeff_t_kernel(const T* __restrict
 
 // mode 0: loc (K, n) ; 1: topic_probs (n, K) ; 2: word_probs (n, V) ; 3: perplexity partial sums {sum w log p, sum w} per workgroup
 // NB: 16-topic column blocks (K <= 16 NB).  LDS: scratch[16] doubles | Zs[M4][DD] | phiS[K V] | per-wave tile [16][16 NB + 1]
-template <typename T, typename TN, int DD, int NB>
+// ARD: Z holds the scaled inducing inputs, ls = 1, and the row coordinates are scaled by 1 / ls_d as they are loaded
+template <typename T, typename TN, int DD, int NB, bool ARD = false>
 __global__ __launch_bounds__(256) void predict_mfma_kernel(const TN* __restrict__ X, int64_t nrows, const T* __restrict__ Z, int M, int M4, int D,
                                                            int kind, const Hyper* __restrict__ h, const T* __restrict__ CfT, int K, int V,
                                                            const TN* __restrict__ phi, const int32_t* __restrict__ ws, int mode,
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(256) void predict_mfma_kernel(const TN* __restrict_
     T x[DD];
 #pragma unroll
     for (int d = 0; d < DD; ++d) {
-      x[d] = (n < nrows && d < D) ? (T)X[n * D + d] : T(0);
+      x[d] = (n < nrows && d < D) ? (ARD ? (T)X[n * D + d] * (T)h->sc[d] : (T)X[n * D + d]) : T(0);
       if (rbf64) x[d] = (T)(a * (double)x[d]);
     }
     acc_t acc[NB];

@@ -35,7 +35,7 @@ class Engine:
     def __init__(self, n_cap: int, M: int, K: int, V: int, D: int, *, dtype=torch.float32, kernel: str = "rbf",
                  device="cuda:0", jitter: float = 1e-8, maxjitter: int = 15, process_group="auto", pure_fp32: bool = False,
                  store_t="auto", mfma_mode: str = "auto", learn_inducing: bool = False, whiten: bool = True,
-                 hyper_backward: str = "auto", allreduce_fn=None):
+                 hyper_backward: str = "auto", allreduce_fn=None, ard: bool = False):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.GdrfHipError("gdrf_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
@@ -82,12 +82,21 @@ class Engine:
         self._allreduce_cb = None
         if allreduce_fn is not None:
             self.set_allreduce(allreduce_fn)
+        # ARD kernel (one lengthscale per input dimension, gdrf_set_ard): "log_lengthscale" is then the (D,) segment of the parameter
+        # vector that exists only in ARD contexts; slot 0 stays 0 and receives a zero gradient
+        self.ard = bool(ard)
+        if self.ard:
+            _lib.check(self.lib.gdrf_set_ard(self.ctx, 1), "gdrf_set_ard")
         lay = (C.c_int64 * 7)()
         _lib.check(self.lib.gdrf_param_layout(self.ctx, lay), "gdrf_param_layout")
         zl = (C.c_int64 * 2)()
         _lib.check(self.lib.gdrf_inducing_layout(self.ctx, zl), "gdrf_inducing_layout")
         self.layout = dict(log_lengthscale=lay[0], log_variance=lay[1], log_noise=lay[2], log_scale_mixture=3, u_loc=lay[3],
                            phi_unc=lay[4], u_scale_tril_unc=lay[5], inducing_unc=zl[0], total=lay[6])
+        if self.ard:
+            al = (C.c_int64 * 2)()
+            _lib.check(self.lib.gdrf_ard_layout(self.ctx, al), "gdrf_ard_layout")
+            self.layout["log_lengthscale"] = al[0]
         # fixed_inducing_points=False of the reference: Z = sigmoid(unconstrained block), refreshed before every evaluation
         self.learn_inducing = bool(learn_inducing)
         if self.learn_inducing:
@@ -136,7 +145,7 @@ class Engine:
 
     @property
     def hyper_backward(self) -> str:
-        """The form the next step uses ("tn" needs f16x3, fixed inducing inputs, a kernel other than RationalQuadratic)."""
+        """The form the next step uses ("tn" needs f16x3, fixed inducing inputs, an isotropic kernel other than RationalQuadratic)."""
         return "tn" if self.lib.gdrf_get_hyper_backward(self.ctx) else "f64"
 
     def __del__(self):
@@ -152,6 +161,8 @@ class Engine:
         buf = self.params if buf is None else buf
         o = self.layout[name]
         K, M, V = self.K, self.M, self.V
+        if name == "log_lengthscale" and self.ard:
+            return buf[o:o + self.D].view(self.D)
         if name in ("log_lengthscale", "log_variance", "log_noise", "log_scale_mixture"):
             return buf[o:o + 1].view(())
         if name == "u_loc":

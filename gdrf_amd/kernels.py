@@ -18,15 +18,33 @@ class Kernel:
             raise NotImplementedError("active_dims other than all input dimensions")
         self.input_dim = int(input_dim)
         self.variance = torch.as_tensor(1.0 if variance is None else variance, dtype=torch.float64).detach().cpu().reshape(())
-        self.lengthscale = torch.as_tensor(1.0 if lengthscale is None else lengthscale, dtype=torch.float64).detach().cpu().reshape(())
-        if not (self.variance > 0 and self.lengthscale > 0):
+        self.lengthscale = self._lengthscale(lengthscale, self.input_dim)
+        if not (self.variance > 0 and bool((self.lengthscale > 0).all())):
             raise ValueError("variance and lengthscale must be positive")
+
+    @staticmethod
+    def _lengthscale(lengthscale, input_dim: int) -> torch.Tensor:
+        """One element (shape () or (1,)): the isotropic kernel, stored with shape ().  ``input_dim`` elements along one axis: one
+        lengthscale per input dimension (ARD), stored with shape (input_dim,) - pyro's Isotropy._scale divides each input axis by its
+        own entry.  Any other shape is an error."""
+        t = torch.as_tensor(1.0 if lengthscale is None else lengthscale, dtype=torch.float64).detach().cpu()
+        if t.dim() <= 1 and t.numel() == 1:
+            return t.reshape(())
+        if t.dim() == 1 and t.numel() == input_dim:
+            return t.clone()
+        raise ValueError(f"lengthscale must have 1 or input_dim = {input_dim} elements along one axis, got shape {tuple(t.shape)}")
+
+    @property
+    def ard(self) -> bool:
+        """One lengthscale per input dimension."""
+        return self.lengthscale.dim() == 1
 
     def to(self, device):
         return self
 
     def __repr__(self):
-        return f"{type(self).__name__}(input_dim={self.input_dim}, lengthscale={float(self.lengthscale)}, variance={float(self.variance)})"
+        ls = self.lengthscale.tolist() if self.ard else float(self.lengthscale)
+        return f"{type(self).__name__}(input_dim={self.input_dim}, lengthscale={ls}, variance={float(self.variance)})"
 
 
 class RBF(Kernel):

@@ -115,7 +115,9 @@ class ModelSnapshot:
         m = self.meta
         if self._model is not None and device is None and mean_function is None and link_function is None:
             return self._model
-        kern = KERNEL_DICT[m["kernel"]](input_dim=int(m["D"]), lengthscale=1.0, variance=1.0)
+        ls = self._state[_PARAM_KEYS["log_lengthscale"]]
+        # an ARD checkpoint stores (D,) log-lengthscales: rebuild an ARD kernel (the values come from load_state_dict below)
+        kern = KERNEL_DICT[m["kernel"]](input_dim=int(m["D"]), lengthscale=torch.ones(int(m["D"])) if ls.dim() == 1 else 1.0, variance=1.0)
         dtype = getattr(torch, m["dtype"])
         model = SparseMultinomialGDRF(
             num_observation_categories=int(m["V"]), num_topic_categories=int(m["K"]), world=[tuple(w) for w in m["world"]],
@@ -247,7 +249,8 @@ class SparseMultinomialGDRF:
             return e
         new = Engine(n, self.M, self._K, self._V, self.D, dtype=self.dtype, kernel=self._kernel.name, device=self.device,
                      jitter=self._jitter, maxjitter=self._maxjitter, pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode,
-                     learn_inducing=not self._fixed_inducing_points, whiten=self._whiten, hyper_backward=self._hyper_backward)
+                     learn_inducing=not self._fixed_inducing_points, whiten=self._whiten, hyper_backward=self._hyper_backward,
+                     ard=self._kernel.ard)
         new.set_inducing_points(self._inducing_points)
         new.set_dirichlet(self._dirichlet_param)
         new.link_function = self._link_function
@@ -264,7 +267,10 @@ class SparseMultinomialGDRF:
     def _init_params(self, eng: Engine):
         """sparse_gdrf.py:96-122 and abstract_gdrf.py:57-84."""
         with torch.no_grad():
-            eng.view("log_lengthscale").fill_(float(self._kernel.lengthscale.log()))
+            if self._kernel.ard:
+                eng.view("log_lengthscale").copy_(self._kernel.lengthscale.log())
+            else:
+                eng.view("log_lengthscale").fill_(float(self._kernel.lengthscale.log()))
             eng.view("log_variance").fill_(float(self._kernel.variance.log()))
             eng.view("log_noise").fill_(float(torch.tensor(self._init_noise, dtype=torch.float64).log()))
             if self._kernel.name == "rationalquadratic":
@@ -438,7 +444,8 @@ class SparseMultinomialGDRF:
         return u.tril(-1) + torch.diag_embed(u.diagonal(dim1=-2, dim2=-1).exp())
 
     def artifacts(self, xs, ws, all: bool = False):
-        """gdrf/models/sparse_gdrf.py:146-158: the two kernel scalars, plus the inducing inputs when they are learnable."""
+        """gdrf/models/sparse_gdrf.py:146-158: the kernel variance and lengthscale (a (D,) array for an ARD kernel), plus the inducing
+        inputs when they are learnable."""
         ret = {"kernel variance": self.kernel_variance, "kernel lengthscale": self.kernel_lengthscale}
         if not self._fixed_inducing_points:
             ret["inducing_points"] = self.inducing_points.detach().cpu().numpy()

@@ -61,15 +61,27 @@ def load_csv(path: str, dimensions: int):
     return xs.astype(np.float32), df.values.astype(np.int32)
 
 
+def kernel_lengthscale_arg(kernel_lengthscale, dimensions: int) -> torch.Tensor:
+    """``kernel_lengthscale`` of train(): a float (isotropic kernel) or a sequence of ``dimensions`` floats, one per input axis (an ARD
+    kernel; a list in the reference's ``wandb.config.kernel_lengthscale`` reaches pyro the same way, train_script.py:290-296)."""
+    ls = torch.as_tensor(kernel_lengthscale, dtype=torch.float64)
+    if ls.dim() == 1 and ls.numel() != 1 and ls.numel() != int(dimensions):
+        raise ValueError(f"kernel_lengthscale must be a float or a sequence of {dimensions} floats (one per dimension), got {ls.numel()}")
+    if ls.dim() > 1:
+        raise ValueError(f"kernel_lengthscale must be a float or a sequence of {dimensions} floats, got shape {tuple(ls.shape)}")
+    return ls
+
+
 def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Optional[np.ndarray] = None, device: str = "cuda:0",
           dimensions: int = 1, epochs: int = 3000, model_type: str = "sparsemultinomialgdrf", num_topics: int = 1,
           dirichlet_param: float = 0.01, num_inducing_points: Union[int, Sequence[int]] = 25, fixed_inducing_points: bool = True,
           inducing_initialization_method: str = "random", jitter: float = 1e-8, max_jitter: int = 15, kernel_type: str = "rbf",
-          kernel_lengthscale: float = 0.1, kernel_variance: float = 25.0, optimizer_type: str = "adamw", optimizer_lr: float = 0.001,
+          kernel_lengthscale: Union[float, Sequence[float]] = 0.1, kernel_variance: float = 25.0, optimizer_type: str = "adamw", optimizer_lr: float = 0.001,
           objective_type: str = "graphelbo", objective_num_particles: int = 1, streaming_inference: str = "",
           streaming_weight: float = 0.1, streaming_exp: float = 1.0, streaming_truncate: int = -1, streaming_size: int = 1,
           streaming_subepochs: int = 1, streaming_batch_splits: int = -1, randomize_wt_matrix: bool = False, seed: int = 1,
           dtype: torch.dtype = torch.float32, perplexity_every: int = 1) -> Dict[str, object]:
+    kernel_ls = kernel_lengthscale_arg(kernel_lengthscale, dimensions)
     if data is not None:
         xs, ws = load_csv(data, dimensions)
     xs_t = torch.as_tensor(xs).float().to(device)
@@ -86,7 +98,7 @@ def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Op
         epochs = streaming_batch_splits
     rng = np.random.RandomState(seed)                                   # init_seeds(1) seeds numpy (utils/general.py:103-108)
 
-    kernel = KERNEL_DICT[kernel_type](input_dim=xs_t.shape[1], lengthscale=torch.tensor(kernel_lengthscale),
+    kernel = KERNEL_DICT[kernel_type](input_dim=xs_t.shape[1], lengthscale=kernel_ls,
                                       variance=torch.tensor(kernel_variance)).to(device)
     model = GDRF_MODEL_DICT[model_type](
         xs=xs_t, ws=ws_t, world=world, kernel=kernel, num_observation_categories=ws_t.shape[1], device=device,
@@ -115,6 +127,8 @@ def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Op
             loss = svi.step(xs=xs_t, ws=ws_t, subsample=False)
         model.eval()
         perplexity = float(model.perplexity(xs_t, ws_t).item()) if (epoch % perplexity_every == 0 or epoch == epochs - 1) else float("nan")
-        history.append([float(loss), perplexity, float(model.kernel_lengthscale), float(model.kernel_variance)])
+        history.append([float(loss), perplexity, *np.atleast_1d(model.kernel_lengthscale).tolist(), float(model.kernel_variance)])
+    # an ARD kernel records one column per lengthscale entry
+    ls_keys = ["x/kernel.lengthscale"] if not kernel.ard else [f"x/kernel.lengthscale.{d}" for d in range(kernel.input_dim)]
     return {"model": model, "svi": svi, "optimizer": optimizer, "history": np.asarray(history),
-            "keys": ["train/loss", "metrics/perplexity", "x/kernel.lengthscale", "x/kernel.variance"]}
+            "keys": ["train/loss", "metrics/perplexity", *ls_keys, "x/kernel.variance"]}

@@ -90,6 +90,17 @@ int gdrf_set_mean(gdrf_ctx* ctx, const void* mean, int64_t stride_k, int64_t str
  * with on = 0 (default) that block of grads stays zero. */
 int gdrf_set_learn_inducing(gdrf_ctx* ctx, int on);
 int gdrf_inducing_layout(const gdrf_ctx* ctx, int64_t out[2]);
+/* ARD kernels (one lengthscale per input dimension): pyro.contrib.gp.kernels.Isotropy with a lengthscale of shape (input_dim,), whose
+ * _scale(X) = X / lengthscale divides every input axis by its own lengthscale before the squared distance
+ * r2 = sum_d ((x_d - z_d) / ls_d)^2 (pyro 1.8.0 kernels/isotropic.py; the reference passes a list through
+ * wandb.config.kernel_lengthscale, gdrf/train_script.py:290-296).  With on = 1 the flat parameter vector grows by a segment of D
+ * log-lengthscales (gdrf_ard_layout -> {offset, D}; {offset of the would-be segment, 0} when off), slot 0 is then unused (its gradient
+ * is 0), red_d grows by D doubles at 8 + M*D (the per-axis K_nm sums, all-reduced with the rest), and every covariance evaluation uses the
+ * per-axis scales.  Call it before reading gdrf_param_layout / gdrf_red_layout.  The opt-in hyper-gradient forms
+ * (gdrf_set_hyper_backward(1), GDRF_WD_PATH=1) fall back to the default f64 form.  Default 0: the layouts are those of a context that
+ * never called it. */
+int gdrf_set_ard(gdrf_ctx* ctx, int on);
+int gdrf_ard_layout(const gdrf_ctx* ctx, int64_t out[2]);
 void gdrf_ctx_destroy(gdrf_ctx* ctx);
 
 /* Flat unconstrained-parameter vector (the PyroParam storage of gdrf/models/sparse_gdrf.py:96-122
@@ -99,7 +110,7 @@ void gdrf_ctx_destroy(gdrf_ctx* ctx);
  * kernels.isotropic.RationalQuadratic: variance * (1 + r2 / (2 scale_mixture))^(-scale_mixture)); the other kernels
  * ignore it and its gradient is 0. */
 int gdrf_param_layout(const gdrf_ctx* ctx, int64_t out[7]);
-/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}. */
+/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}; total_d = 8 + M*D (+ D in ARD contexts). */
 int gdrf_red_layout(const gdrf_ctx* ctx, int64_t out[6]);
 /* The step's ONE collective ("one ncclAllReduce(sum) per step over a flat buffer"): gdrf_payload_pack copies the
  * 8 + M*D doubles of red_d into the tail of red_T (total_T of gdrf_red_layout includes it) in red_T's element type - as they
