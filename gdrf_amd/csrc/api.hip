@@ -92,6 +92,7 @@ struct gdrf_ctx {
   void *uS, *uSb, *uSc, *uU, *uUb, *Uw;
   int learn_z; double* zpart; // learnable inducing inputs: per-row-tile partial sums [ceil(ncap/128)][M][D]
   int ard; void* Zp; double* apart;   // ARD (gdrf_set_ard): scaled inducing inputs in the N-side precision (probe, gdrf_knm); per-block sums of d / d log ls_d
+  int64_t mean_count;         // trainable mean_function parameters (gdrf_set_mean_params): elements of their segment, 0 = none
   std::vector<void*> allocs;
   // optional per-kernel HIP-event timing (gdrf_set_timing): events recorded on the launch stream
   int timing;
@@ -124,12 +125,15 @@ static int64_t poff(const gdrf_ctx* c, int which) {
   const int64_t o_S = round_up(o_phi + (int64_t)c->K * c->V, 4);
   const int64_t o_Z = round_up(o_S + (int64_t)c->K * c->M * c->M, 4);          // unconstrained inducing inputs (M, D)
   const int64_t o_ard = round_up(o_Z + (int64_t)c->M * c->D, 4);               // ARD contexts only: the D log-lengthscales
-  const int64_t total = c->ard ? round_up(o_ard + c->D, 4) : o_ard;
+  const int64_t o_mean = c->ard ? round_up(o_ard + c->D, 4) : o_ard;           // contexts with gdrf_set_mean_params only: mean_function parameters
+  const int64_t total = c->mean_count ? round_up(o_mean + c->mean_count, 4) : o_mean;
   switch (which) { case 0: return 0; case 1: return 1; case 2: return 2; case 3: return o_uloc; case 4: return o_phi;
-                   case 5: return o_S; case 7: return o_Z; case 8: return o_ard; default: return total; }
+                   case 5: return o_S; case 7: return o_Z; case 8: return o_ard; case 9: return o_mean; default: return total; }
 }
-// doubles of red_d: 8 scalars, the (M, D) inducing-input sums, in ARD contexts the D sums of d / d log ls_d over the rows
-static int64_t red_nd(const gdrf_ctx* c) { return 8 + (int64_t)c->M * c->D + (c->ard ? c->D : 0); }
+// doubles of red_d: 8 scalars, the (M, D) inducing-input sums, in ARD contexts the D sums of d / d log ls_d over the rows, then the
+// caller's sums of d elbo / d theta of the mean_function parameters (gdrf_set_mean_params)
+static int64_t red_nd(const gdrf_ctx* c) { return 8 + (int64_t)c->M * c->D + (c->ard ? c->D : 0) + c->mean_count; }
+static int64_t red_mean_off(const gdrf_ctx* c) { return red_nd(c) - c->mean_count; }
 static int64_t roff(const gdrf_ctx* c, int which) {
   const int64_t mm = (int64_t)c->Mp * c->Mp;
   const int64_t o_ubar = 0, o_phib = round_up((int64_t)c->K * c->Mp, 4), o_A = round_up(o_phib + (int64_t)c->K * c->V, 4);
@@ -143,11 +147,12 @@ static int64_t roff(const gdrf_ctx* c, int which) {
 int gdrf_param_layout(const gdrf_ctx* c, int64_t out[7]) { for (int i = 0; i < 7; ++i) out[i] = poff(c, i); return 0; }
 int gdrf_red_layout(const gdrf_ctx* c, int64_t out[6]) {
   for (int i = 0; i < 5; ++i) out[i] = roff(c, i);
-  out[5] = red_nd(c);          // 8 scalars, then the (M, D) inducing-input sums (learnable inducing points), then the ARD sums
+  out[5] = red_nd(c);          // 8 scalars, then the (M, D) inducing-input sums (learnable inducing points), then the ARD sums, then the mean segment
   return 0;
 }
 int gdrf_inducing_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 7); out[1] = (int64_t)c->M * c->D; return 0; }
 int gdrf_ard_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 8); out[1] = c->ard ? c->D : 0; return 0; }
+int gdrf_mean_param_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 9); out[1] = c->mean_count; return 0; }
 
 // row blocks of the ubar partial kernel: ~1024 workgroups, multiples of its 256-row staging step
 static int64_t ubar_rows_per_block(int64_t n) { return std::max<int64_t>(256, round_up((n + 1023) / 1024, 256)); }
@@ -252,6 +257,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   c->pK = c->pL = nullptr; c->Tst = nullptr; c->side = nullptr; c->Bh = c->STh = c->Wh = nullptr; c->split = 0; c->wh_pieces = 0; c->ssc = nullptr; c->smx = nullptr;
   c->ev_fork = c->ev_loc = c->ev_fork2 = c->ev_join = c->ev_fact0 = c->ev_fact = nullptr; c->fact_pending = 0; c->learn_z = 0; c->zpart = nullptr; c->ard = 0; c->Zp = nullptr; c->apart = nullptr; c->unwhitened = 0; c->mean = nullptr; c->mean_sk = c->mean_sn = 0;
   c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->side2 = nullptr; c->ev_ak = c->ev_ak_done = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->Wd = nullptr; c->wdpart = nullptr; c->ev_wd = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0;
+  c->mean_count = 0;
   for (int i = 0; i < GDRF_NSLOTS; ++i) { c->t_ms[i] = 0; c->t_cnt[i] = 0; }
   const size_t mm = (size_t)c->Mp * c->Mp * c->esz, mms = (size_t)c->Mp * c->Mp * c->ssz;
   auto A = [&](void** p, size_t bytes) -> int {
@@ -358,7 +364,8 @@ int gdrf_set_dirichlet(gdrf_ctx* c, const double* alpha) {
   return 0;
 }
 
-// which = 0 W, 1 Wbar, 2 q, 3 loc, 4 tt, 5 vbar, 6 locbar, 7 asum, 8 Kuu, 9 L, 10 Linv, 11 S, 12 B, 13 phi, 14 mu, 15 LinvT, 16 ST, 17 Knm (solve precision)
+// which = 0 W, 1 Wbar, 2 q, 3 loc, 4 tt, 5 vbar, 6 locbar, 7 asum, 8 Kuu, 9 L, 10 Linv, 11 S, 12 B, 13 phi, 14 mu, 15 LinvT, 16 ST, 17 Knm (solve precision),
+// 18 the guide-side locbar of gdrf_step_local2 (0 elements before its first call)
 static int ws_lookup(gdrf_ctx* c, int which, void** ptr, int64_t* nelem, int* esz) {
   const int64_t mm = (int64_t)c->Mp * c->Mp, kn = (int64_t)c->K * c->ldk;
   void* p = nullptr; int64_t n = 0; int e = (int)c->esz;
@@ -373,6 +380,7 @@ static int ws_lookup(gdrf_ctx* c, int which, void** ptr, int64_t* nelem, int* es
     case 14: p = c->mu; n = kn; break;                case 15: p = c->LinvT; n = mm; e = (int)c->ssz; break;
     case 16: p = c->ST; n = mm * c->K; break;
     case 17: p = c->Knm; n = c->ncap * c->Mp; e = (int)c->ssz; break;
+    case 18: p = c->g_locbar; n = c->g_locbar ? kn : 0; break;
     default: return fail(-1, "gdrf_ws_ptr", "unknown buffer id");
   }
   *ptr = p; *nelem = n; *esz = e;
@@ -457,6 +465,13 @@ int gdrf_set_ard(gdrf_ctx* c, int on) {
   }
   c->ard = on;
   c->prefact_valid = 0;
+  return 0;
+}
+int gdrf_set_mean_params(gdrf_ctx* c, int64_t count) {
+  if (count < 0) return fail(-1, "gdrf_set_mean_params", "count must be >= 0");
+  // the two-point scratch (gdrf_step_local2) holds a copy of red_d sized on its first use
+  if (c->g_loc && count != c->mean_count) return fail(-1, "gdrf_set_mean_params", "call it before the first gdrf_step_local2");
+  c->mean_count = count;
   return 0;
 }
 int gdrf_get_mfma_mode(const gdrf_ctx* c) { return c->split; }
@@ -1427,7 +1442,8 @@ template <typename T, typename TS> struct Impl {
     };
     add(roff(c, 0), roff(c, 1) - roff(c, 0));
     add(roff(c, 2), roff(c, 5) - roff(c, 2));
-    hipLaunchKernelGGL(add_into_kernel<double>, dim3((unsigned)((nd - 4 + 255) / 256)), dim3(256), 0, s, nd - 4, (const double*)c->g_redd + 4, redd + 4);
+    const int64_t ndk = nd - 4 - c->mean_count;      // the mean segment is the caller's to write (gdrf_set_mean_params)
+    hipLaunchKernelGGL(add_into_kernel<double>, dim3((unsigned)((ndk + 255) / 256)), dim3(256), 0, s, ndk, (const double*)c->g_redd + 4, redd + 4);
     LAUNCHCHK("step_local2");
     return 0;
   }
@@ -1531,6 +1547,9 @@ template <typename T, typename TS> struct Impl {
     if (c->ard)
       hipLaunchKernelGGL(grad_ard_kernel<T>, dim3(1), dim3(64), 0, s, c->D, (const double*)redd + 8 + (int64_t)M * c->D, (const double*)c->dsmall + 3,
                          n_global, grads, grads + poff(c, 8));
+    if (c->mean_count)
+      hipLaunchKernelGGL(grad_mean_kernel<T>, dim3((unsigned)((c->mean_count + 255) / 256)), dim3(256), 0, s, c->mean_count,
+                         (const double*)redd + red_mean_off(c), n_global, grads + poff(c, 9));
     if (c->unwhitened)       // overwrite the u_loc / u_scale_tril blocks with the gradients chained through L^-T
       hipLaunchKernelGGL((grad_unwhitened_kernel<TS, T>), g3, dim3(256), 0, s, (const TS*)Q(c->uSc), (const TS*)Q(c->uUb), params + poff(c, 5), K, M,
                          Mp, -1.0 / n_global, grads + poff(c, 5), grads + poff(c, 3));

@@ -1654,6 +1654,14 @@ __global__ void grad_ard_kernel(int D, const double* __restrict__ red_ard, const
   if (d < D) g_ard[d] = (T)((-1.0 / n_global) * (red_ard[d] + kuu_ard[d]));
 }
 
+// trainable mean_function parameters (gdrf_set_mean_params): the caller's reduced sums of d elbo / d theta -> d loss / d theta, the scaling
+// of every other block (loss = -elbo / n_global)
+template <typename T>
+__global__ void grad_mean_kernel(int64_t count, const double* __restrict__ red_mean, double n_global, T* __restrict__ g_mean) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) g_mean[i] = (T)((-1.0 / n_global) * red_mean[i]);
+}
+
 // =====================================================================================
 // optimizers on the flat unconstrained parameter vector; predicated on the Cholesky flag
 // mode 0 Adam, 1 AdamW (decoupled decay), 2 ClippedAdam

@@ -22,7 +22,7 @@ KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "rationa
 OPT_MODES = {"adam": 0, "adamw": 1, "clippedadam": 2}
 
 _WS_IDS = dict(W=0, Wbar=1, q=2, loc=3, tt=4, vbar=5, locbar=6, asum=7, Kuu=8, L=9, Linv=10, S=11, B=12, phi=13,
-               mu=14, LinvT=15, ST=16, Knm=17)
+               mu=14, LinvT=15, ST=16, Knm=17, g_locbar=18)
 
 
 def _stream_ptr(device) -> int:
@@ -35,7 +35,7 @@ class Engine:
     def __init__(self, n_cap: int, M: int, K: int, V: int, D: int, *, dtype=torch.float32, kernel: str = "rbf",
                  device="cuda:0", jitter: float = 1e-8, maxjitter: int = 15, process_group="auto", pure_fp32: bool = False,
                  store_t="auto", mfma_mode: str = "auto", learn_inducing: bool = False, whiten: bool = True,
-                 hyper_backward: str = "auto", allreduce_fn=None, ard: bool = False):
+                 hyper_backward: str = "auto", allreduce_fn=None, ard: bool = False, mean_params: Optional[Dict[str, tuple]] = None):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.GdrfHipError("gdrf_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
@@ -97,6 +97,21 @@ class Engine:
             al = (C.c_int64 * 2)()
             _lib.check(self.lib.gdrf_ard_layout(self.ctx, al), "gdrf_ard_layout")
             self.layout["log_lengthscale"] = al[0]
+        # trainable mean_function parameters (gdrf_set_mean_params): {name: shape} in order, one segment of the parameter vector; their
+        # sums of d elbo / d theta are written by the host into the last doubles of red_d (_write_mean_grads)
+        self.mean_shapes = {str(k): torch.Size(v) for k, v in (mean_params or {}).items()}
+        self.mean_count = sum(math.prod(v) for v in self.mean_shapes.values())
+        self._mean_offsets = {}
+        if self.mean_count:
+            _lib.check(self.lib.gdrf_set_mean_params(self.ctx, self.mean_count), "gdrf_set_mean_params")
+            _lib.check(self.lib.gdrf_param_layout(self.ctx, lay), "gdrf_param_layout")
+            ml = (C.c_int64 * 2)()
+            _lib.check(self.lib.gdrf_mean_param_layout(self.ctx, ml), "gdrf_mean_param_layout")
+            self.layout["mean"], self.layout["total"] = ml[0], lay[6]
+            o = ml[0]
+            for name, shape in self.mean_shapes.items():
+                self._mean_offsets[name] = o
+                o += math.prod(shape)
         # fixed_inducing_points=False of the reference: Z = sigmoid(unconstrained block), refreshed before every evaluation
         self.learn_inducing = bool(learn_inducing)
         if self.learn_inducing:
@@ -106,7 +121,7 @@ class Engine:
             _lib.check(self.lib.gdrf_set_whiten(self.ctx, 0), "gdrf_set_whiten")
         red = (C.c_int64 * 6)()
         _lib.check(self.lib.gdrf_red_layout(self.ctx, red), "gdrf_red_layout")
-        self.red_layout = dict(ubar=red[0], phibar=red[1], A=red[2], GT=red[3], total_T=red[4], total_d=red[5])
+        self.red_layout = dict(ubar=red[0], phibar=red[1], A=red[2], GT=red[3], total_T=red[4], total_d=red[5], mean=red[5] - self.mean_count)
         z = lambda n, dt: torch.zeros(int(n), dtype=dt, device=self.device)
         self.params = z(lay[6], dtype)
         self.grads = z(lay[6], dtype)
@@ -126,6 +141,8 @@ class Engine:
         # a caller-supplied link (the reference's `link_function`, abstract_gdrf.py:34-50): a callable on the (K, n) tensor mu returning the
         # (K, n) topic weights; None = the softmax link fused into the row kernel.  Evaluated with torch between three library calls.
         self.link_function = None
+        self._mean_vjp = None
+        self._adjoints: Dict[str, torch.Tensor] = {}      # host copies of the row adjoints the mean's vector-Jacobian product reads
 
     def set_allreduce(self, fn):
         """Register the step's collective behind the C ABI (gdrf_set_allreduce): ``fn(buf_ptr, count, is_double, stream_ptr)`` sums the flat
@@ -159,6 +176,8 @@ class Engine:
     # ---- parameter views (natural shapes) ---------------------------------------------------------
     def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
         buf = self.params if buf is None else buf
+        if name in self.mean_shapes:
+            return self._mean_view(name, buf)
         o = self.layout[name]
         K, M, V = self.K, self.M, self.V
         if name == "log_lengthscale" and self.ard:
@@ -175,13 +194,18 @@ class Engine:
             return buf[o:o + M * self.D].view(M, self.D)
         raise KeyError(name)
 
+    def _mean_view(self, name: str, buf: torch.Tensor) -> torch.Tensor:
+        o, shape = self._mean_offsets[name], self.mean_shapes[name]
+        return buf[o:o + math.prod(shape)].view(shape)
+
     PARAM_NAMES = ("log_lengthscale", "log_variance", "log_noise", "u_loc", "phi_unc", "u_scale_tril_unc")
 
     @property
     def param_names(self):
-        """PARAM_NAMES plus the blocks only some configurations learn (RationalQuadratic's scale_mixture, inducing inputs)."""
+        """PARAM_NAMES plus the blocks only some configurations learn (RationalQuadratic's scale_mixture, inducing inputs, the
+        mean_function's parameters)."""
         extra = (("log_scale_mixture",) if self.kernel == "rationalquadratic" else ()) + \
-                (("inducing_unc",) if self.learn_inducing else ())
+                (("inducing_unc",) if self.learn_inducing else ()) + tuple(self.mean_shapes)
         return self.PARAM_NAMES + extra
 
     def named_views(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -323,13 +347,17 @@ class Engine:
 
     def loss_and_grads(self, xs, ws, eps, n_global: Optional[int] = None, ll_const: Optional[float] = None,
                        force_level: Optional[int] = None, renyi_alpha: Optional[float] = None, mean: Optional[torch.Tensor] = None,
-                       xs_guide: Optional[torch.Tensor] = None, mean_guide: Optional[torch.Tensor] = None):
+                       xs_guide: Optional[torch.Tensor] = None, mean_guide: Optional[torch.Tensor] = None, mean_vjp=None):
         """One ELBO evaluation + backward.  Leaves d loss/d unconstrained in self.grads (device) and
         returns nothing host-side; call read_out() for the loss.  ``mean``: the values of the model's mean_function on these
         rows, broadcastable to (K, n) (gdrf/models/sparse_gdrf.py:346,395); None = zero_mean.  ``xs_guide``: the inputs the
         GUIDE's predictive is evaluated at when they differ from the model's (quirk Q3: the reference's guide scales twice,
-        sparse_gdrf.py:376-380), with ``mean_guide`` the mean_function values there; None = the same inputs (one evaluation)."""
+        sparse_gdrf.py:376-380), with ``mean_guide`` the mean_function values there; None = the same inputs (one evaluation).
+        ``mean_vjp(adj, adj_guide)`` (engines with mean_params): called after every particle's local evaluation with the (K, n) row
+        adjoints d elbo / d mean of the model-side values and, with ``xs_guide``, of the guide-side ones (else None); returns the flat
+        (mean_count,) vector-Jacobian product for the mean parameters' segment.  None: that segment's gradient is 0."""
         self._chk_rows(xs, ws)
+        self._mean_vjp = mean_vjp if self.mean_count else None
         n = xs.shape[0]
         self._set_mean(mean, n)
         self._xs_guide = None
@@ -390,6 +418,7 @@ class Engine:
                 self.factorize(None)
                 self._local_and_finish(xs, ws, eps, P, n, ng, llc, s, renyi_alpha)
         self._guess_level = self.last_jitter_level if force_level is None else None
+        self._mean_vjp = None
 
     def _set_mean(self, mean, n: int, guide: bool = False):
         fn = self.lib.gdrf_set_mean_guide if guide else self.lib.gdrf_set_mean
@@ -446,6 +475,8 @@ class Engine:
                 _lib.check(self.lib.gdrf_step_local2(self.ctx, xs.data_ptr(), xg.data_ptr(), ws.data_ptr(), eps[p].data_ptr(), n,
                                                      self.Z.data_ptr(), self.params.data_ptr(), self.red_T.data_ptr(),
                                                      self.red_d.data_ptr(), s), "gdrf_step_local2")
+            if self.mean_count:
+                self._write_mean_grads(n, xg is not None)
             if renyi_alpha is not None:
                 Ts.append(self.red_T.clone()); ds.append(self.red_d.clone())
             elif P > 1:                                           # Trace_ELBO: a running sum of the payloads, no per-particle copies
@@ -481,6 +512,25 @@ class Engine:
             dist.all_reduce(self.red_T, group=pg)    # RCCL over xGMI (backend "nccl" on ROCm)
             _lib.check(self.lib.gdrf_payload_unpack(self.ctx, self.red_T.data_ptr(), self.red_d.data_ptr(), s), "gdrf_payload_unpack")
         self._finish(ng, None)
+
+    def _adjoint(self, which: str, n: int) -> torch.Tensor:
+        """(K, n) view of a copy of a row-adjoint workspace, enqueued on the current stream (no host synchronisation)."""
+        buf = self._adjoints.get(which)
+        ldk = (self.n_cap + 3) // 4 * 4
+        if buf is None:
+            buf = self._adjoints[which] = torch.empty(self.K, ldk, dtype=self.dtype, device=self.device)
+        _lib.check(self.lib.gdrf_ws_copy(self.ctx, _WS_IDS[which], buf.data_ptr(), buf.numel(), _stream_ptr(self.device)), "gdrf_ws_copy")
+        return buf[:, :n]
+
+    def _write_mean_grads(self, n: int, two_point: bool):
+        """This particle's sums of d elbo / d theta of the mean parameters -> the mean segment of red_d, before the particle combination
+        and the collective.  The mean enters mu where f_loc does, so its row adjoint is the row kernel's locbar (guide side: g_locbar)."""
+        seg = self.red_d[self.red_layout["mean"]:]
+        if self._mean_vjp is None:
+            seg.zero_()
+            return
+        g = self._mean_vjp(self._adjoint("locbar", n), self._adjoint("g_locbar", n) if two_point else None)
+        seg.copy_(g.reshape(-1))
 
     def _step_local_link(self, xs, ws, eps_p, n: int, s: int):
         """gdrf_step_local with the link and its Jacobian evaluated here: theta = link(mu) and mubar = J^T thetabar by autograd

@@ -90,9 +90,11 @@ class SVI:
         n = xs_s.shape[0]
         eps = self._eps(eng, eps, n)
         xs_g = model._guide_inputs(xs_s)
+        mean, mean_g, mean_vjp = model._step_means(xs_s, xs_g)
         eng.loss_and_grads(xs_s, ws_d, eps, n_global=1.0 / self.scale, renyi_alpha=getattr(self.loss, "alpha", None),
-                           mean=model._mean_values(xs_s), xs_guide=xs_g, mean_guide=None if xs_g is None else model._mean_values(xs_g))
+                           mean=mean, xs_guide=xs_g, mean_guide=mean_g, mean_vjp=mean_vjp)
         self.optim._step()
+        model._mean_to_module()                  # a torch.nn.Module mean_function's trained parameters (no-op otherwise)
         out = eng.read_out()
         self.steps_taken += 1
         self.last = out

@@ -27,6 +27,17 @@ _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convent
     "inducing_unc": "_inducing_points_unconstrained",          # only when fixed_inducing_points=False
     "log_scale_mixture": "_kernel.scale_mixture_unconstrained",  # only with the RationalQuadratic kernel
 }
+MEAN_PREFIX = "_mean_function."      # + the name from named_parameters(): a trainable parameter of a torch.nn.Module mean_function
+
+
+def learnable_mean_parameters(mean_function) -> List[Tuple[str, torch.nn.Parameter]]:
+    """The parameters of a mean_function that SVI.step trains, as (state_dict name, parameter): those of a ``torch.nn.Module`` whose
+    ``requires_grad`` is set.  In the reference the mean_function is an attribute of a gp.Parameterized (abstract_gdrf.py:33-48), so
+    pyro.module puts a Module's parameters into the param store and SVI.step updates them; frozen ones get no gradient and stay.  Plain
+    callables, None and modules without trainable parameters give [] (their values are data to the step)."""
+    if not isinstance(mean_function, torch.nn.Module):
+        return []
+    return [(MEAN_PREFIX + n, p) for n, p in mean_function.named_parameters() if p.requires_grad]
 
 
 def validate_dirichlet_param(b: torch.Tensor, K: int, V: int) -> torch.Tensor:
@@ -110,7 +121,8 @@ class ModelSnapshot:
 
     # ---- the part that does: a device model with these parameters, built on first use
     def restore(self, device: Optional[str] = None, mean_function: Callable = None, link_function: Callable = None):
-        """A ``SparseMultinomialGDRF`` on ``device`` (default: the device the snapshot was taken on) holding these parameters."""
+        """A ``SparseMultinomialGDRF`` on ``device`` (default: the device the snapshot was taken on) holding these parameters.  A
+        ``torch.nn.Module`` mean_function receives the stored ``_mean_function.*`` values; without one those entries are not used."""
         from ..kernels import KERNEL_DICT
         m = self.meta
         if self._model is not None and device is None and mean_function is None and link_function is None:
@@ -126,7 +138,8 @@ class ModelSnapshot:
             mean_function=mean_function, link_function=link_function, noise=1.0, device=device or m["device"],
             whiten=bool(m["whiten"]), jitter=float(m["jitter"]), maxjitter=int(m["maxjitter"]), dtype=dtype,
             pure_fp32=bool(m["pure_fp32"]), mfma_mode=m["mfma_mode"], seed=int(m["seed"]), guide_rescale=bool(m["guide_rescale"]))
-        model.load_state_dict({k: v.to(dtype) for k, v in self._state.items()})
+        keys = {_PARAM_KEYS.get(n, n) for n in model._param_names()}
+        model.load_state_dict({k: v.to(dtype) for k, v in self._state.items() if k in keys or not k.startswith(MEAN_PREFIX)})
         if device is None and mean_function is None and link_function is None:
             self._model = model
         return model
@@ -184,9 +197,13 @@ class SparseMultinomialGDRF:
             raise TypeError("mean_function must be callable")
         if randomize_metric is not None and not callable(randomize_metric):
             raise TypeError("randomize_metric must be callable")
-        # abstract_gdrf.py:38-48: evaluated on the scaled inputs every step; its values are data to the fused step (no gradient
-        # flows into a mean_function's own parameters)
+        # abstract_gdrf.py:38-48: evaluated on the scaled inputs every step; its values are data to the fused step.  The trainable
+        # parameters of a torch.nn.Module mean (learnable_mean_parameters) are one more segment of the engine's parameter vector: the
+        # step chains the row adjoints of the mean values through the module by autograd (_step_means) and the optimizer updates them
+        # with the rest; after every step the module holds the engine's values (_mean_to_module)
         self._mean_function = mean_function
+        self._mean_params = learnable_mean_parameters(mean_function)
+        self._mean_versions = None
         # quirk Q3 (sparse_gdrf.py:376-380): the reference's guide scales its inputs twice.  True reproduces that (for a world
         # other than the unit cube the step then evaluates the GP predictive at two input sets, gdrf_step_local2); False scales
         # once on both sides.  No effect for the unit-cube world train() builds.
@@ -199,6 +216,10 @@ class SparseMultinomialGDRF:
         self._world = [(float(a), float(b)) for a, b in world]
         self._n_dims = len(self._world)
         self.device = torch.device(device)
+        for name, p in self._mean_params:
+            if p.device.type != self.device.type or (self.device.index is not None and p.device.index != self.device.index):
+                raise ValueError(f"mean_function parameter {name[len(MEAN_PREFIX):]!r} is on {p.device}, the model on {self.device}: "
+                                 "move the module to the model's device")
         self.dtype = dtype
         self._pure_fp32 = bool(pure_fp32)
         self._mfma_mode = mfma_mode          # Engine(mfma_mode=...): "auto" | "f32" | "bf16x6" | "f16x3"
@@ -250,7 +271,7 @@ class SparseMultinomialGDRF:
         new = Engine(n, self.M, self._K, self._V, self.D, dtype=self.dtype, kernel=self._kernel.name, device=self.device,
                      jitter=self._jitter, maxjitter=self._maxjitter, pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode,
                      learn_inducing=not self._fixed_inducing_points, whiten=self._whiten, hyper_backward=self._hyper_backward,
-                     ard=self._kernel.ard)
+                     ard=self._kernel.ard, mean_params={n: tuple(p.shape) for n, p in self._mean_params})
         new.set_inducing_points(self._inducing_points)
         new.set_dirichlet(self._dirichlet_param)
         new.link_function = self._link_function
@@ -293,6 +314,7 @@ class SparseMultinomialGDRF:
             L = eng.workspace("L").to(eng.dtype)
             unc = L.tril(-1) + torch.diag(L.diagonal().log())             # lower_cholesky transform inverse
             eng.view("u_scale_tril_unc").copy_(unc.unsqueeze(0).expand(self._K, -1, -1))
+        self._mean_from_module()
 
     @property
     def inducing_points(self) -> torch.Tensor:
@@ -352,6 +374,52 @@ class SparseMultinomialGDRF:
             return None
         with torch.no_grad():
             return torch.as_tensor(self._mean_function(xs_scaled))
+
+    # ------------------------------------------------------------------ trainable mean_function parameters
+    def _mean_from_module(self):
+        """The module's current parameter values -> the engine's mean segment."""
+        with torch.no_grad():
+            for name, p in self._mean_params:
+                self._engine.view(name).copy_(p.detach())
+        self._mean_versions = [p._version for _, p in self._mean_params]
+
+    def _mean_to_module(self):
+        """The engine's mean segment (after the optimizer update) -> the module's parameters, in their own dtype."""
+        if not self._mean_params:
+            return
+        with torch.no_grad():
+            for name, p in self._mean_params:
+                p.copy_(self._engine.view(name))
+        self._mean_versions = [p._version for _, p in self._mean_params]
+
+    def _mean_graph(self, xs_scaled: torch.Tensor, n: int) -> torch.Tensor:
+        out = torch.as_tensor(self._mean_function(xs_scaled)).to(device=self.device, dtype=self.dtype)
+        try:
+            return out.expand(self._K, n)
+        except RuntimeError:
+            raise ValueError(f"mean_function returned shape {tuple(out.shape)}, not broadcastable to ({self._K}, {n})") from None
+
+    def _step_means(self, xs_scaled: torch.Tensor, xs_guide: Optional[torch.Tensor]):
+        """(mean, mean_guide, mean_vjp) of one training step.  Without trainable mean parameters: the values as data, mean_vjp None.
+        With them: the values evaluated with grad enabled (model side; guide side too in a non-unit world), passed detached, and the
+        vector-Jacobian product that Engine.loss_and_grads calls with the device's row adjoints after every particle - autograd through
+        the module, so a broadcast shape's reduction comes from the expand.  The graph is kept for every particle (and a redone step)."""
+        if not self._mean_params:
+            return self._mean_values(xs_scaled), None if xs_guide is None else self._mean_values(xs_guide), None
+        if self._mean_versions != [p._version for _, p in self._mean_params]:
+            self._mean_from_module()                 # written outside the step since the last update
+        n = xs_scaled.shape[0]
+        with torch.enable_grad():
+            outs = [self._mean_graph(xs_scaled, n)] + ([] if xs_guide is None else [self._mean_graph(xs_guide, n)])
+        params = [p for _, p in self._mean_params]
+
+        def mean_vjp(adj, adj_guide):
+            pairs = [(o, a) for o, a in zip(outs, (adj, adj_guide)) if o.requires_grad]
+            gs = torch.autograd.grad([o for o, _ in pairs], params, grad_outputs=[a for _, a in pairs], retain_graph=True,
+                                     allow_unused=True) if pairs else [None] * len(params)
+            return torch.cat([(torch.zeros(p.numel(), dtype=torch.float64, device=self.device) if g is None
+                               else g.detach().reshape(-1).to(device=self.device, dtype=torch.float64)) for g, p in zip(gs, params)])
+        return outs[0].detach(), None if xs_guide is None else outs[1].detach(), mean_vjp
 
     # ------------------------------------------------------------------ SVI handles
     def model(self, xs, ws, subsample=False):
@@ -453,16 +521,20 @@ class SparseMultinomialGDRF:
 
     # ------------------------------------------------------------------ state (train_script.py:338-363,490-506)
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {_PARAM_KEYS[n]: self._engine.view(n).detach().clone() for n in self._param_names()}
+        return {_PARAM_KEYS.get(n, n): self._engine.view(n).detach().clone() for n in self._param_names()}
 
     def _param_names(self):
         return tuple(self._engine.param_names)
 
     def load_state_dict(self, state: Dict[str, torch.Tensor], strict: bool = True):
         v = {n: self._engine.view(n) for n in self._param_names()}
+        if strict:
+            unexpected = sorted(k for k in state if k.startswith(MEAN_PREFIX) and k not in v)
+            if unexpected:
+                raise RuntimeError(f"unexpected keys: {unexpected}")
         missing = []
         for n in self._param_names():
-            key = _PARAM_KEYS[n]
+            key = _PARAM_KEYS.get(n, n)
             if key not in state:
                 missing.append(key)
                 continue
@@ -474,6 +546,7 @@ class SparseMultinomialGDRF:
             v[n].copy_(t.to(v[n]))
         if strict and missing:
             raise RuntimeError(f"missing keys: {missing}")
+        self._mean_to_module()
         return missing
 
     def parameters(self):

@@ -101,6 +101,23 @@ int gdrf_inducing_layout(const gdrf_ctx* ctx, int64_t out[2]);
  * never called it. */
 int gdrf_set_ard(gdrf_ctx* ctx, int on);
 int gdrf_ard_layout(const gdrf_ctx* ctx, int64_t out[2]);
+/* Trainable mean_function parameters (gdrf/models/abstract_gdrf.py:33-48: the mean_function is an attribute of a gp.Parameterized, so the
+ * parameters of a torch.nn.Module mean - registered by pyro.module - or a PyroModule mean's own PyroParams land in the param store and
+ * SVI.step trains them with the optimizer of every other parameter, gdrf/train_script.py:365-371,467).  The library never evaluates the
+ * mean_function: the caller does, and chains the row adjoints through it.  With count > 0 the flat parameter vector (and grads, and the
+ * two moment vectors of gdrf_adam) grows by a segment of `count` elements (gdrf_mean_param_layout -> {offset, count}; {offset of the
+ * would-be segment, 0} when count = 0), and red_d by `count` doubles at total_d - count (total_d of gdrf_red_layout).  Per step the caller
+ *   - after each gdrf_step_local / gdrf_step_local2 / phase 2 of gdrf_step_local_link reads the row adjoints of the mean values it passed:
+ *     locbar (gdrf_ws_ptr 6) = d elbo / d (model-side mean), and in gdrf_step_local2 also gdrf_ws_ptr 18 = d elbo / d (guide-side mean),
+ *     (K, n) arrays with leading dimension round_up(n_cap, 4), elbo = the unscaled sum of the per-row ELBO terms (the loss is
+ *     -elbo / n_global).  Through a mean that enters both sides at the same inputs, locbar alone is the whole adjoint;
+ *   - writes the vector-Jacobian product sum_kn adjoint[k][n] d mean[k][n] / d theta into that red_d segment (the step calls do not touch
+ *     it), where it takes part in the particle combination and the collective like every other sum;
+ *   - gdrf_step_finish then writes -segment / n_global into the segment of grads, and gdrf_adam updates it with the rest.
+ * Call it before reading gdrf_param_layout / gdrf_red_layout and before the first gdrf_step_local2.  Default 0: the layouts are those of a
+ * context that never called it. */
+int gdrf_set_mean_params(gdrf_ctx* ctx, int64_t count);
+int gdrf_mean_param_layout(const gdrf_ctx* ctx, int64_t out[2]);
 void gdrf_ctx_destroy(gdrf_ctx* ctx);
 
 /* Flat unconstrained-parameter vector (the PyroParam storage of gdrf/models/sparse_gdrf.py:96-122
@@ -110,7 +127,8 @@ void gdrf_ctx_destroy(gdrf_ctx* ctx);
  * kernels.isotropic.RationalQuadratic: variance * (1 + r2 / (2 scale_mixture))^(-scale_mixture)); the other kernels
  * ignore it and its gradient is 0. */
 int gdrf_param_layout(const gdrf_ctx* ctx, int64_t out[7]);
-/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}; total_d = 8 + M*D (+ D in ARD contexts). */
+/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}; total_d = 8 + M*D (+ D in ARD contexts)
+ * (+ the count of gdrf_set_mean_params, the last doubles). */
 int gdrf_red_layout(const gdrf_ctx* ctx, int64_t out[6]);
 /* The step's ONE collective ("one ncclAllReduce(sum) per step over a flat buffer"): gdrf_payload_pack copies the
  * 8 + M*D doubles of red_d into the tail of red_T (total_T of gdrf_red_layout includes it) in red_T's element type - as they
@@ -225,7 +243,8 @@ int gdrf_predict(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev,
 int gdrf_chol_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
 
 /* Borrowed pointers into the workspace (for parity tests): which = 0 W, 1 Wbar, 2 q, 3 loc, 4 tt,
- * 5 vbar, 6 locbar, 7 asum, 8 Kuu, 9 L, 10 Linv, 11 S, 12 B, 13 phi, 14 mu, 15 LinvT, 16 ST, 17 the step's K_nm. */
+ * 5 vbar, 6 locbar, 7 asum, 8 Kuu, 9 L, 10 Linv, 11 S, 12 B, 13 phi, 14 mu, 15 LinvT, 16 ST, 17 the step's K_nm, 18 the guide-side
+ * locbar of gdrf_step_local2 (d elbo / d guide-side loc and mean; 0 elements before its first call). */
 int gdrf_ws_ptr(gdrf_ctx* ctx, int which, void** ptr, int64_t* nelem);
 /* Element size (4 or 8 bytes) of that buffer: Kuu, L, Linv, LinvT and the step's K_nm live in the solve precision. */
 int gdrf_ws_elem_size(gdrf_ctx* ctx, int which);
