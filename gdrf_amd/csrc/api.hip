@@ -6,7 +6,6 @@
 #include "gemm_split.h"
 #include "gemm_tn_topics.h"
 #include "gemm_tn_topics1.h"
-#include "gemm_fwd_t1.h"
 #include "kernels_mm.h"
 #include "kernels_n.h"
 #include "predict.h"
@@ -63,9 +62,7 @@ struct gdrf_ctx {
   void *W, *Wbar, *q, *loc, *tt, *vbar, *locbar, *asum, *mu;
   void *g_loc, *g_tt, *g_qpart, *g_vbar, *g_locbar, *g_asum, *g_redT; double* g_redd;   // two-point evaluation (quirk Q3), allocated on first use
   const void* mean_g; int64_t mean_g_sk, mean_g_sn;
-  void *Wd;                   // W' = (dK_nm / d log lengthscale) Linv^T, allocated on first use (fixed inducing inputs, kernels without a third hyper-parameter)
-  double* wdpart; hipEvent_t ev_wd;
-  void* dKh; hipStream_t side2; hipEvent_t ev_ak, ev_ak_done;    // pieces of dK_nm / d log ls (hyper_tn.h), allocated on first use; third stream: A_k beside the f64 backward GEMM
+  void* dKh;                  // pieces of dK_nm / d log ls (hyper_tn.h), allocated on first use
   gdrf_allreduce_fn allreduce; void* allreduce_user;      // the caller's collective (gdrf_set_allreduce), or null
   int hyper_tn; double* hpart;   // K_nm parts of the hyper-parameter gradients through Hd = dK^T Wbar on the TN kernel (hyper_tn.h) instead of the f64 backward GEMM
   void* vbs = nullptr;        // vbar x block scale, zero-padded to a multiple of 64 rows (gemm_tn_topics1.h)
@@ -160,7 +157,6 @@ static int64_t ubar_rows_per_block(int64_t n) { return std::max<int64_t>(256, ro
 // number of row splits of the TN kernels: fill the chip's resident-workgroup slots (256 CUs x 3) with as
 // little last-round idling as possible, keep >= 8 chunks per split, cap the slab memory
 static int tn_nsplit(const gdrf_ctx* c, int64_t n, int BR, int wg_per_cu = 3) {
-  if (const char* e = getenv("GDRF_TN_NSPLIT")) { const int v = atoi(e); if (v > 0) return v; }   // tuning knob (tools/)
   const int tiles = c->K * c->nt * (c->nt + 1) / 2;
   const double slots = 256.0 * wg_per_cu;
   int64_t maxs = (n + 8 * BR - 1) / (8 * BR);
@@ -182,7 +178,6 @@ static int tn_nsplit_gt(const gdrf_ctx* c, int64_t n, int BR) {
   int64_t maxs = (n + 8 * BR - 1) / (8 * BR);
   if (maxs > 64) maxs = 64;
   if (maxs < 8) return tn_nsplit(c, n, BR, 2);
-  if (const char* e = getenv("GDRF_TN_NSPLIT")) { const int v = atoi(e); if (v > 0) return v; }
   const int tiles = c->nt * c->nt;
   int best = 8; double best_eff = 0;
   for (int ns = 8; ns <= maxs; ns += 8) {
@@ -193,31 +188,14 @@ static int tn_nsplit_gt(const gdrf_ctx* c, int64_t n, int BR) {
   return best;
 }
 
-// Row splits of the all-topics A_k kernel (gemm_tn_topics.h): one 512-thread workgroup per CU, tiles x topic groups x splits
-// workgroups; fill the 256 CUs' rounds, >= 16 chunks per split, at most 64 splits
-static bool tn_topics_on(const gdrf_ctx* c) {
-  if (c->split != 2) return false;
-  const char* e = getenv("GDRF_TN_TOPICS");
-  return !(e && e[0] == '0');
-}
-// K_nm parts of the hyper-parameter gradients through W' = (dK/dlog ls) Linv^T (forward-shaped GEMM + two dot products with Wbar)
-// instead of the backward GEMM Kbar = Wbar Linv: fixed inducing inputs (their gradient needs Kbar itself) and kernels whose only
-// shape parameter is the lengthscale
-// Measured at the headline size (profiles/r02): correct, but NOT faster - the step is work-conserving on the matrix pipe, so the second
-// forward-shaped f64 GEMM (6.7 ms alone, 13.8 ms beside fwd_t) costs what the backward GEMM with G^T inside its stalls did (53.0 vs
-// 52.5 ms/step).  Kept as an opt-in (GDRF_WD_PATH=1, covered by a parity test); the backward GEMM is the default.
-static bool wd_path(const gdrf_ctx* c) {
-  if (c->learn_z || c->ard || c->kind == GDRF_RATIONALQUADRATIC) return false;
-  const char* e = getenv("GDRF_WD_PATH");
-  return e && e[0] == '1';
-}
 // K_nm parts of the hyper-parameter gradients through Hd = dK^T Wbar on the split-fp16 TN kernel (hyper_tn.h): f16x3 contexts with the f64
 // solve, fixed inducing inputs (their gradient needs Kbar itself), kernels whose only shape parameter is the lengthscale
 static bool hyper_tn_on(const gdrf_ctx* c) {
-  return c->hyper_tn && c->split == 2 && c->ssz == 8 && !c->learn_z && !c->ard && c->kind != GDRF_RATIONALQUADRATIC && !c->Tst && (c->Mp / 8) <= 256 && !wd_path(c);
+  return c->hyper_tn && c->split == 2 && c->ssz == 8 && !c->learn_z && !c->ard && c->kind != GDRF_RATIONALQUADRATIC && !c->Tst && (c->Mp / 8) <= 256;
 }
+// Row splits of the all-topics A_k kernel (gemm_tn_topics.h): one 512-thread workgroup per CU, tiles x topic groups x splits
+// workgroups; fill the 256 CUs' rounds, >= 16 chunks per split, at most 64 splits
 static int tn_topics_nsplit(const gdrf_ctx* c, int64_t n) {
-  if (const char* e = getenv("GDRF_TNT_NSPLIT")) { const int v = atoi(e); if (v > 0) return v; }
   const int units = tnt_ntiles(c->Mp) * ((c->K + TNT_KT - 1) / TNT_KT);
   int64_t maxs = (n + 16 * 32 - 1) / (16 * 32);
   if (maxs > 64) maxs = 64;
@@ -256,7 +234,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   c->lgam_const = 0; c->alpha_dev = nullptr; c->timing = 0;
   c->pK = c->pL = nullptr; c->Tst = nullptr; c->side = nullptr; c->Bh = c->STh = c->Wh = nullptr; c->split = 0; c->wh_pieces = 0; c->ssc = nullptr; c->smx = nullptr;
   c->ev_fork = c->ev_loc = c->ev_fork2 = c->ev_join = c->ev_fact0 = c->ev_fact = nullptr; c->fact_pending = 0; c->learn_z = 0; c->zpart = nullptr; c->ard = 0; c->Zp = nullptr; c->apart = nullptr; c->unwhitened = 0; c->mean = nullptr; c->mean_sk = c->mean_sn = 0;
-  c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->side2 = nullptr; c->ev_ak = c->ev_ak_done = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->Wd = nullptr; c->wdpart = nullptr; c->ev_wd = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0;
+  c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0;
   c->mean_count = 0;
   for (int i = 0; i < GDRF_NSLOTS; ++i) { c->t_ms[i] = 0; c->t_cnt[i] = 0; }
   const size_t mm = (size_t)c->Mp * c->Mp * c->esz, mms = (size_t)c->Mp * c->Mp * c->ssz;
@@ -316,18 +294,16 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
 #undef AL
   {
     // the side stream carries the factorisation chain (small launches the step's first GEMM waits for): highest priority, so that its
-    // workgroups are placed ahead of the K_nm kernel's 16 384 on the main stream (GDRF_SIDE_PRIO=0: default priority)
+    // workgroups are placed ahead of the K_nm kernel's 16 384 on the main stream
     int least = 0, greatest = 0;
-    const char* sp = getenv("GDRF_SIDE_PRIO");
-    if (!(sp && sp[0] == '0') && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least) {
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least) {
       HIPCHK(hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, greatest));
     } else {
       HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
     }
   }
-  for (hipEvent_t* e : {&c->ev_fork, &c->ev_loc, &c->ev_fork2, &c->ev_join, &c->ev_fact0, &c->ev_fact, &c->ev_wd, &c->ev_ak, &c->ev_ak_done})
+  for (hipEvent_t* e : {&c->ev_fork, &c->ev_loc, &c->ev_fork2, &c->ev_join, &c->ev_fact0, &c->ev_fact})
     HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  HIPCHK(hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
   HIPCHK(hipMemset(c->flag, 0, 128));
   HIPCHK(hipMemset(c->W, 0, (size_t)n_cap * c->Mp * c->esz));
   std::vector<double> a((size_t)K * V, 1.0);
@@ -341,9 +317,8 @@ void gdrf_ctx_destroy(gdrf_ctx* c) {
   for (void* p : c->allocs) (void)hipFree(p);
   for (auto& t : c->tev) { (void)hipEventDestroy(t.second.first); (void)hipEventDestroy(t.second.second); }
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {c->ev_fork, c->ev_loc, c->ev_fork2, c->ev_join, c->ev_fact0, c->ev_fact, c->ev_wd, c->ev_ak, c->ev_ak_done}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev_fork, c->ev_loc, c->ev_fork2, c->ev_join, c->ev_fact0, c->ev_fact}) if (e) (void)hipEventDestroy(e);
   if (c->side) (void)hipStreamDestroy(c->side);
-  if (c->side2) (void)hipStreamDestroy(c->side2);
   delete c;
 }
 
@@ -538,12 +513,11 @@ template <typename T, typename TS> struct Impl {
     // a single M x M product is 16 workgroups of the NT core (45 us at M = 512 in double, four of them in a row in every step's
     // Cholesky backward), a batch of K = 10 is 160 (one per CU for the whole reduction): the reduction is split over S slices into
     // slabs, which are added in double in a fixed order.  S: 8 for a single product, 4 for small batches.
-    static const bool splitk = !(getenv("GDRF_MM_SPLITK") && getenv("GDRF_MM_SPLITK")[0] == '0');
     const int64_t mm = (int64_t)c->Mp * c->Mp;
     const int tiles = c->nt * nct<E>(c);
     const int S = batch == 1 ? 8 : 4, kw = c->Mp / S;
     // (batches: measured SLOWER - 160 workgroups already fill most CUs and the slab sum of K matrices costs more than the split saves)
-    if (splitk && batch == 1 && c->mmslab && tiles * batch <= 256 && c->Mp >= 256 && c->Mp % S == 0 && kw % NTCfg<E>::BK == 0 &&
+    if (batch == 1 && c->mmslab && tiles * batch <= 256 && c->Mp >= 256 && c->Mp % S == 0 && kw % NTCfg<E>::BK == 0 &&
         (size_t)S * batch * mm * sizeof(E) <= c->mmslab_bytes) {
       MMProb<E> p{{}, {}, {}, A, abs_, Bt, bbs, (E*)c->mmslab, mm, c->Mp, alpha, kw, batch};
       dim3 grid(tiles, S * batch);
@@ -625,24 +599,14 @@ template <typename T, typename TS> struct Impl {
       HIPCHK(hipMemsetAsync(c->flag, 0, 32, f));
       hipLaunchKernelGGL(kuu_kernel<TS>, g2, dim3(256), 0, f, (const TS*)Q(c->Zs), M, Mp, c->D, c->kind, c->hyp, jitter, Q(c->Kuu));
       HIPCHK(hipMemcpyAsync(c->Lw, c->Kuu, (size_t)Mp * Mp * sizeof(TS), hipMemcpyDeviceToDevice, f));
-      bool have_dinv = false;
-      static const bool panelwise = !(getenv("GDRF_CHOL_PANEL") && getenv("GDRF_CHOL_PANEL")[0] == '0');    // A/B knob: 0 = the single-workgroup kernel
-      if (panelwise) {
-        // one launch per 32-column panel, one small workgroup per trailing tile (kernels_mm.h: chol_panel_kernel)
-        const int nt = (M + 31) / 32;
-        for (int k = 0; k < nt; ++k) {
-          const int n = nt - k - 1, wgs = n > 0 ? n * (n + 1) / 2 : 1;
-          hipLaunchKernelGGL(chol_panel_kernel<TS>, dim3((unsigned)wgs), dim3(128), 0, f, Q(c->Lw), Q(c->Lo), Q(c->Dinv), M, Mp, k, c->flag);
-        }
-        hipLaunchKernelGGL(finalize_l_kernel<TS>, g2, dim3(256), 0, f, (const TS*)Q(c->Lo), M, Mp, Q(c->L), Q(c->LT));
-        have_dinv = true;            // the inverses of the diagonal blocks came out of the panel launches
-      } else {
-        if (chol_lds_bytes<TS>(M) > 48 * 1024)
-          HIPCHK(hipFuncSetAttribute((const void*)chol_kernel<TS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chol_lds_bytes<TS>(M)));
-        hipLaunchKernelGGL(chol_kernel<TS>, dim3(1), dim3(1024), chol_lds_bytes<TS>(M), f, Q(c->Lw), M, Mp, c->flag, (int64_t)0);
-        hipLaunchKernelGGL(finalize_l_kernel<TS>, g2, dim3(256), 0, f, (const TS*)Q(c->Lw), M, Mp, Q(c->L), Q(c->LT));
+      // one launch per 32-column panel, one small workgroup per trailing tile (kernels_mm.h: chol_panel_kernel); the inverses of the
+      // diagonal blocks come out of the panel launches
+      const int nt = (M + 31) / 32;
+      for (int k = 0; k < nt; ++k) {
+        const int n = nt - k - 1, wgs = n > 0 ? n * (n + 1) / 2 : 1;
+        hipLaunchKernelGGL(chol_panel_kernel<TS>, dim3((unsigned)wgs), dim3(128), 0, f, Q(c->Lw), Q(c->Lo), Q(c->Dinv), M, Mp, k, c->flag);
       }
-      if (!have_dinv) hipLaunchKernelGGL(trinv_diag_kernel<TS>, dim3(Mp / 32), dim3(64), 0, f, (const TS*)Q(c->L), M, Mp, Q(c->Dinv));
+      hipLaunchKernelGGL(finalize_l_kernel<TS>, g2, dim3(256), 0, f, (const TS*)Q(c->Lo), M, Mp, Q(c->L), Q(c->LT));
       hipLaunchKernelGGL(trinv_cols_kernel<TS>, dim3(Mp / 32), dim3(1024), 0, f, (const TS*)Q(c->L), (const TS*)Q(c->Dinv), M, Mp, Q(c->Linv),
                          Q(c->LinvT));
     }
@@ -670,15 +634,11 @@ template <typename T, typename TS> struct Impl {
     const int VE = Vec16<T>::N;
     const int vpr = (c->M + VE - 1) / VE, rpp = vpr <= 256 ? 256 / vpr : 1;
     int64_t blocks = (n + 4 * rpp - 1) / (4 * rpp);
-    int64_t cap = 256 * 64;          // swept on MI355X (tools/knm_sweep.py): 2048 blocks 0.60-0.65 of HBM peak, 16384 0.67-0.79
-    if (const char* e = getenv("GDRF_KNM_BLOCKS")) cap = atoll(e);
+    const int64_t cap = 256 * 64;          // swept on MI355X: 2048 blocks 0.60-0.65 of HBM peak, 16384 0.67-0.79
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    const char* plain = getenv("GDRF_KNM_PLAIN_STORES");
     if (c->ard)
       hipLaunchKernelGGL((knm_kernel<T, T, true, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
-    else if (plain && plain[0] == '1')
-      hipLaunchKernelGGL((knm_kernel<T, T, true, false>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
     else
       hipLaunchKernelGGL((knm_kernel<T, T, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
     LAUNCHCHK("knm");
@@ -709,79 +669,17 @@ template <typename T, typename TS> struct Impl {
       ScopedTimer tm(c, 5, s);
       // topics per group: as many lower-triangular S^T piece panels (NP x ~0.6 Mp^2 halfwords each) as fit in 2 MB
       const double panel = 0.625 * 2.0 * SP::NP * (double)Mp * Mp;
-      int KG = std::max(1, std::min(K, (int)(2.0 * 1024 * 1024 / panel)));
-      if (const char* e = getenv("GDRF_FWDT_KG")) { const int v = atoi(e); if (v > 0) KG = std::min(K, v); }   // tuning knob (tools/)
+      const int KG = std::max(1, std::min(K, (int)(2.0 * 1024 * 1024 / panel)));
       // two row tiles per 512-thread workgroup (two phase-shifted wave groups, LDS-DMA staging): 6 operand images
       const int64_t pairs = (rtiles + 1) / 2;
       const int rt8 = (int)((pairs + 7) / 8);
-      FwdTSplitArgs<SP> a{(const E*)c->Wh, (int64_t)c->ncap * Mp, n, Mp, K, KG, rt8, (const E*)c->STh, nb, (float*)c->tt, c->ldk, (const float*)c->ssc, nullptr};
-      constexpr int lds2 = 6 * SplitCfg<SP>::IMG * 2;
-#ifdef GDRF_DIAG   // diagnostic builds only (make DIAG=1): these paths synchronise the stream and allocate inside the step
-      if (getenv("GDRF_STAMP")) {           // diagnostic: per-phase s_memtime stamps of one workgroup (tools/), never in a timed run
-        unsigned long long* d = nullptr;
-        HIPCHK(hipMalloc((void**)&d, 2 * 64 * 4 * 8)); HIPCHK(hipMemset(d, 0, 2 * 64 * 4 * 8));
-        a.stamps = d;
-        HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_2g_kernel<SP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2 + 4096));
-        hipLaunchKernelGGL((fwd_t_split_2g_kernel<SP, true>), dim3((unsigned)(8 * K * rt8)), dim3(512), lds2 + 4096, s, a);
-        std::vector<unsigned long long> h(2 * 64 * 4);
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost)); (void)hipFree(d);
-        for (int gpi = 0; gpi < 2; ++gpi) {
-          double sm = 0, sv = 0, sb = 0, so = 0; int cnt = 0; std::string line;
-          for (int t = 1; t < 40; ++t) {
-            const unsigned long long* q = &h[(gpi * 64 + t) * 4];
-            const long long m = q[1] - q[0], v = q[2] - q[1], b = q[3] - q[2], o = q[0] - h[(gpi * 64 + t - 1) * 4 + 3];
-            sm += m; sv += v; sb += b; so += o; ++cnt;
-            line += " " + std::to_string(m) + "/" + std::to_string(o);
-          }
-          fprintf(stderr, "fwd_t stamps group %d: mean mult %.0f vmcnt %.0f barrier %.0f other-group-phase %.0f | mult/other per chunk:%s\n", gpi, sm / cnt, sv / cnt,
-                  sb / cnt, so / cnt, line.c_str());
-        }
-        return 0;
-      }
-      if constexpr (SP::NP == 2) {
-        if (const char* sw = getenv("GDRF_STAMP_Q4")) {      // diagnostic: s_memtime stamps of wave <value> of one workgroup of the 256 x 256 form
-          unsigned long long* d = nullptr;
-          HIPCHK(hipMalloc((void**)&d, 64 * 5 * 8)); HIPCHK(hipMemset(d, 0, 64 * 5 * 8));
-          FwdTSplitArgs<SP> as = a; as.stamps = d; as.KG = KG | (atoi(sw) << 16);
-          constexpr int lds4 = 8 * SplitCfg<SP>::IMG * 2 + 8 * GDRF_TILE * 4 + 64 * 5 * 8;
-          HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_q4_kernel<SP, 17>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4));
-          hipLaunchKernelGGL((fwd_t_split_q4_kernel<SP, 17>), dim3((unsigned)(8 * K * rt8)), dim3(1024), lds4, s, as);
-          std::vector<unsigned long long> h(64 * 5);
-          HIPCHK(hipStreamSynchronize(s));
-          HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost)); (void)hipFree(d);
-          double m[5] = {0, 0, 0, 0, 0}; int cnt = 0; std::string line;
-          for (int t = 1; t < 24; ++t) {
-            const unsigned long long* q = &h[t * 5];
-            if (!q[4]) break;
-            m[0] += q[1] - q[0]; m[1] += q[2] - q[1]; m[2] += q[3] - q[2]; m[3] += q[4] - q[3]; m[4] += q[0] - h[(t - 1) * 5 + 4]; ++cnt;
-            line += " " + std::to_string(q[4] - h[(t - 1) * 5 + 4]);
-          }
-          if (cnt) fprintf(stderr, "fwd_t q4 stamps wave %d (%d phases): dma+frag issue %.0f  mfma loop %.0f  vmcnt+lgkm %.0f  barrier %.0f  between %.0f | phase lengths:%s\n",
-                           atoi(sw), cnt, m[0] / cnt, m[1] / cnt, m[2] / cnt, m[3] / cnt, m[4] / cnt, line.c_str());
-          return 0;
-        }
-      }
-#endif
-      const char* alt = getenv("GDRF_FWDT_ALTERNATING");          // A/B knob: the phase-alternating form
-      if (alt && alt[0] == '1') {
-        HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_2g_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-        hipLaunchKernelGGL(fwd_t_split_2g_kernel<SP>, dim3((unsigned)(8 * K * rt8)), dim3(512), lds2, s, a);
-      } else if (std::is_same<SP, SplitF16>::value && (Mp % 256) == 0 && getenv("GDRF_FWDT_W1") && getenv("GDRF_FWDT_W1")[0] == '1') {     // opt-in: measured slower than the 16-wave form (gemm_fwd_t1.h)
-        if constexpr (std::is_same<SP, SplitF16>::value) {       // one wave per SIMD, 64 rows x 256 columns per wave (gemm_fwd_t1.h)
-          HIPCHK(hipFuncSetAttribute((const void*)fwd_t_w1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ft1_lds_bytes()));
-          hipLaunchKernelGGL(fwd_t_w1_kernel, dim3((unsigned)(8 * K * rt8)), dim3(256), ft1_lds_bytes(), s, a);
-        }
-      } else if (SP::NP == 2 && !(getenv("GDRF_FWDT_Q4") && getenv("GDRF_FWDT_Q4")[0] == '0')) {
-        if constexpr (SP::NP == 2) {       // 256 x 256 workgroup tiles (two-piece modes: eight operand images in 128 KB)
-          constexpr int lds4 = 8 * SplitCfg<SP>::IMG * 2 + 8 * GDRF_TILE * 4;      // + the row-sum slots
-          static const int var = getenv("GDRF_Q4_VAR") ? atoi(getenv("GDRF_Q4_VAR")) : 1;      // A/B knob; 1 (requests first) measured best
-#define GDRF_Q4(X) { HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_q4_kernel<SP, X>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4)); \
-                     hipLaunchKernelGGL((fwd_t_split_q4_kernel<SP, X>), dim3((unsigned)(8 * K * rt8)), dim3(1024), lds4, s, a); }
-          if (var == 1) GDRF_Q4(1) else if (var == 2) GDRF_Q4(2) else if (var == 3) GDRF_Q4(3) else if (var == 5) GDRF_Q4(5) else if (var == 33) GDRF_Q4(33) else GDRF_Q4(0)
-#undef GDRF_Q4
-        }
+      FwdTSplitArgs<SP> a{(const E*)c->Wh, (int64_t)c->ncap * Mp, n, Mp, K, KG, rt8, (const E*)c->STh, nb, (float*)c->tt, c->ldk, (const float*)c->ssc};
+      if constexpr (SP::NP == 2) {       // 256 x 256 workgroup tiles (two-piece modes: eight operand images in 128 KB)
+        constexpr int lds4 = 8 * SplitCfg<SP>::IMG * 2 + 8 * GDRF_TILE * 4;      // + the row-sum slots
+        HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_q4_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4));
+        hipLaunchKernelGGL(fwd_t_split_q4_kernel<SP>, dim3((unsigned)(8 * K * rt8)), dim3(1024), lds4, s, a);
       } else {
+        constexpr int lds2 = 6 * SplitCfg<SP>::IMG * 2;
         HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_cc_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
         hipLaunchKernelGGL(fwd_t_split_cc_kernel<SP>, dim3((unsigned)(8 * K * rt8)), dim3(512), lds2, s, a);
       }
@@ -828,66 +726,27 @@ template <typename T, typename TS> struct Impl {
       const int nct_ = (Mp + GDRF_TILE - 1) / GDRF_TILE;
       if (K >= 2 && 2 * grp <= 160 * 1024) {   // two phase-shifted wave groups per workgroup (own A images, shared double-buffered B, LDS-DMA staging)
         const int64_t pairs = (rtiles + 1) / 2;
-        const char* alt = getenv("GDRF_WBAR_ALTERNATING");          // A/B knob: the phase-alternating form
         const size_t tabb = ((size_t)K * GDRF_TILE * sizeof(float) + 15) & ~(size_t)15;
         const size_t lds_cc = 6 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * tabb;
-#ifdef GDRF_DIAG
-        if (getenv("GDRF_STAMP_WBAR")) {      // diagnostic: per-phase s_memtime stamps of one workgroup, never in a timed run
-          unsigned long long* d = nullptr;
-          HIPCHK(hipMalloc((void**)&d, 2 * 64 * 4 * 8)); HIPCHK(hipMemset(d, 0, 2 * 64 * 4 * 8));
-          a.stamps = d;
-          HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_cc_kernel<SP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_cc + 4096)));
-          hipLaunchKernelGGL((bwd_wbar_split_cc_kernel<SP, true>), dim3((unsigned)round_up(pairs * nct_, 8)), dim3(512), lds_cc + 4096, s, a);
-          std::vector<unsigned long long> h(2 * 64 * 4);
-          HIPCHK(hipStreamSynchronize(s));
-          HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost)); (void)hipFree(d);
-          for (int gpi = 0; gpi < 2; ++gpi) {
-            double sd = 0, sm = 0, sv = 0, sb = 0; int cnt = 0; std::string line;
-            for (int t = 1; t < 63; ++t) {
-              const unsigned long long* q = &h[(gpi * 64 + t) * 4];
-              const long long dd = q[1] - q[0], m = q[2] - q[1], v = q[3] - q[2], b = h[(gpi * 64 + t + 1) * 4] - q[3];
-              sd += dd; sm += m; sv += v; sb += b; ++cnt;
-              if (t < 24) line += " " + std::to_string(dd) + "/" + std::to_string(m) + "/" + std::to_string(v) + "/" + std::to_string(b);
-            }
-            fprintf(stderr, "wbar_cc stamps group %d: mean dma-issue %.0f mult %.0f vmcnt %.0f barrier %.0f | dma/mult/vmcnt/barrier per phase:%s\n", gpi, sd / cnt,
-                    sm / cnt, sv / cnt, sb / cnt, line.c_str());
-          }
-        } else
-#endif
-        if (std::is_same<SP, SplitF16>::value && !(alt && alt[0] != '0') && K >= 2 && (Mp % 64) == 0 &&
-                   8 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * tabb <= 160 * 1024) {
+        if (std::is_same<SP, SplitF16>::value && K >= 2 && (Mp % 64) == 0 && 8 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * tabb <= 160 * 1024) {
           if constexpr (std::is_same<SP, SplitF16>::value) {
             const size_t lds64 = 8 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * tabb;
-#ifdef GDRF_DIAG
-            const char* ab = getenv("GDRF_WBAR_ABLATE");         // timing-only variants with WRONG results: diagnostic builds only
-            const int abl = ab ? atoi(ab) : 0;
-            if (abl) { static bool warned = false; if (!warned) { warned = true; fprintf(stderr, "libgdrf_hip: GDRF_WBAR_ABLATE=%d is active - Wbar and every gradient are WRONG (timing-only build)\n", abl); } }
-#else
-            constexpr int abl = 0;
-#endif
             // few rows (streaming mini-batches): a handful of workgroups would each walk all K x Mp / 64 chunks one after the other
             // (0.19 ms at n = 64); the reduction blocks are split over gridDim.y slices into slabs, summed in a fixed order
             const int nkb = Mp / 64;
-            static const bool wsplit = !(getenv("GDRF_WBAR_SLICES") && getenv("GDRF_WBAR_SLICES")[0] == '0');
             int nslice = 1;
-            if (wsplit && pairs * nct_ <= 32 && nkb >= 2 && !abl) nslice = std::min(nkb, 8);
+            if (pairs * nct_ <= 32 && nkb >= 2) nslice = std::min(nkb, 8);
             if ((size_t)nslice * n * Mp * sizeof(float) > (size_t)c->nsplit_cap * (K + 1) * Mp * Mp * sizeof(float)) nslice = 1;   // the TN slab buffer is idle now
             if (nslice > 1) { a.slab = (float*)c->slab; a.slab_stride = (int64_t)round_up(n, 256) * Mp; a.nslice = nslice; }
-#define GDRF_K64(X) { HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_f16_k64_kernel<X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64)); \
-                      hipLaunchKernelGGL(bwd_wbar_f16_k64_kernel<X>, dim3((unsigned)round_up(pairs * nct_, 8), (unsigned)nslice), dim3(512), lds64, s, a); }
-#ifdef GDRF_DIAG
-            if (abl == 1) GDRF_K64(1) else if (abl == 2) GDRF_K64(2) else if (abl == 3) GDRF_K64(3) else if (abl == 4) GDRF_K64(4)
-            else if (abl == 7) GDRF_K64(7) else if (abl == 8) GDRF_K64(8) else if (abl == 16) GDRF_K64(16) else if (abl == 64) GDRF_K64(64) else if (abl == 256) GDRF_K64(256) else
-#endif
-            GDRF_K64(0)
-#undef GDRF_K64
+            HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_f16_k64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
+            hipLaunchKernelGGL(bwd_wbar_f16_k64_kernel, dim3((unsigned)round_up(pairs * nct_, 8), (unsigned)nslice), dim3(512), lds64, s, a);
             if (nslice > 1) {
               const int64_t n4 = n * Mp / 4;
               hipLaunchKernelGGL(wbar_slab_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float*)a.slab, a.slab_stride, nslice, n4,
                                  (float*)c->Wbar, a.wbar_max);
             }
           }
-        } else if (!(alt && alt[0] == '1') && lds_cc <= 160 * 1024) {
+        } else if (lds_cc <= 160 * 1024) {
           HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_cc_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cc));
           hipLaunchKernelGGL((bwd_wbar_split_cc_kernel<SP>), dim3((unsigned)round_up(pairs * nct_, 8)), dim3(512), lds_cc, s, a);
         } else {
@@ -914,7 +773,7 @@ template <typename T, typename TS> struct Impl {
     const int VE = Vec16<TS>::N;
     const int vpr = (c->Mp + VE - 1) / VE, rpp = vpr <= 256 ? 256 / vpr : 1;
     int64_t blocks = (n + 4 * rpp - 1) / (4 * rpp);
-    static const int64_t kcap = getenv("GDRF_KNM_SOLVE_BLOCKS") ? atoll(getenv("GDRF_KNM_SOLVE_BLOCKS")) : 256 * 64;
+    const int64_t kcap = 256 * 64;
     if (blocks > kcap) blocks = kcap;
     if (blocks < 1) blocks = 1;
     if constexpr (sizeof(TS) == 8) {
@@ -997,7 +856,6 @@ template <typename T, typename TS> struct Impl {
       }
     }
     const int64_t rtiles = (n + GDRF_TILE - 1) / GDRF_TILE;
-    const bool use_wd = wd_path(c);
     if (mask & SL_FORWARD) {
     // (1) W = Knm Linv^T in the solve precision, stored in the N-side precision
     {
@@ -1008,35 +866,15 @@ template <typename T, typename TS> struct Impl {
       if (c->split && sizeof(TS) == 8 && sizeof(T) == 4) {      // pieces of W from the same epilogue
         p.Wh = c->Wh; p.wh_stride = (int64_t)c->ncap * Mp; p.wh_mode = c->split; p.wh_scale = c->ssc + SplitLay{K}.w();
       }
-#ifdef GDRF_NT_TRACE   // diagnostic builds only: per-workgroup phase stamps of this launch written to $GDRF_NT_TRACE_FILE (tools/nt_trace.py)
-      unsigned long long* trace_d = nullptr; const size_t trace_n = (size_t)nt_xcd_row_grid(rtiles, nct<TS>(c)) * 8;
-      if (getenv("GDRF_NT_TRACE_FILE") && sizeof(TS) == 8) {
-        HIPCHK(hipMalloc((void**)&trace_d, trace_n * 8)); HIPCHK(hipMemset(trace_d, 0, trace_n * 8));
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_nt_trace), &trace_d, sizeof(trace_d)));
-        HIPCHK(hipDeviceSynchronize());
-      }
-#endif
       hipLaunchKernelGGL((gemm_nt_kernel<TS, FwdWProb<TS, T>>), dim3(nt_xcd_row_grid(rtiles, nct<TS>(c))), dim3(256), CS::LDS_BYTES, s, p);
-#ifdef GDRF_NT_TRACE
-      if (trace_d) {
-        HIPCHK(hipDeviceSynchronize());
-        std::vector<unsigned long long> h(trace_n);
-        HIPCHK(hipMemcpy(h.data(), trace_d, trace_n * 8, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(getenv("GDRF_NT_TRACE_FILE"), "wb")) { fwrite(h.data(), 8, trace_n, f); fclose(f); }
-        unsigned long long* z = nullptr;
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_nt_trace), &z, sizeof(z)));
-        (void)hipFree(trace_d);
-      }
-#endif
     }
     // loc = W U^T, on the side stream beside fwd_t (both only read W)
     HIPCHK(hipEventRecord(c->ev_fork, s));
     HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
     {
       ScopedTimer tm(c, 4, c->side);
-      static const bool loc_rows = !(getenv("GDRF_LOC_ROWS") && getenv("GDRF_LOC_ROWS")[0] == '0');      // A/B knob: 0 = the NT core
       const size_t ulds = (size_t)K * Mp * sizeof(T);
-      if (loc_rows && K <= LOC_KMAX && Mp % (16 * Vec16<T>::N) == 0 && ulds <= 150 * 1024) {
+      if (K <= LOC_KMAX && Mp % (16 * Vec16<T>::N) == 0 && ulds <= 150 * 1024) {
         if (ulds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)loc_rows_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ulds));
         const int64_t blocks = std::min<int64_t>((n + 31) / 32, 256 * 8);
         hipLaunchKernelGGL(loc_rows_kernel<T>, dim3((unsigned)blocks), dim3(256), ulds, c->side, (const T*)P(c->W), n, Mp, K, (const T*)P(c->Upad), P(c->loc), ldk);
@@ -1066,30 +904,6 @@ template <typename T, typename TS> struct Impl {
         LAUNCHCHK("dk_pieces");
       }
     }
-    // W' = (dK_nm / d log lengthscale) Linv^T on the side stream, beside the K-fold contractions (its f64 MFMAs fill their stalls);
-    // with it the K_nm parts of the hyper-parameter gradients are two dot products with Wbar (wbar_dot_kernel) and the backward
-    // GEMM Kbar = Wbar Linv with its pass over K_nm is not needed
-    if (use_wd) {
-      if (!c->Wd) {
-        void* pw = nullptr;
-        hipError_t e = hipMalloc(&pw, (size_t)c->ncap * Mp * c->esz);
-        if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(Wd)", hipGetErrorString(e));
-        c->Wd = pw; c->allocs.push_back(pw);
-        HIPCHK(hipMalloc(&pw, (size_t)2 * 2048 * sizeof(double))); c->wdpart = (double*)pw; c->allocs.push_back(pw);
-      }
-      ScopedTimer tm(c, 8, c->side);
-      const size_t zl = (size_t)Mp * (c->D <= 2 ? 2 : 4) * sizeof(TS);
-      if (c->D <= 2) {
-        FwdWProb<TS, T, true, 2> p{{}, {}, (const TS*)Q(c->Knm), n, Mp, (const TS*)Q(c->Linv), P(c->Wd), nullptr, 0, X, (const TS*)Q(c->Zs), c->hyp, M, c->D, c->kind};
-        HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_kernel<TS, FwdWProb<TS, T, true, 2>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CS::LDS_BYTES + zl)));
-        hipLaunchKernelGGL((gemm_nt_kernel<TS, FwdWProb<TS, T, true, 2>>), dim3(nt_xcd_row_grid(rtiles, nct<TS>(c))), dim3(256), CS::LDS_BYTES + zl, c->side, p);
-      } else {
-        FwdWProb<TS, T, true, 4> p{{}, {}, (const TS*)Q(c->Knm), n, Mp, (const TS*)Q(c->Linv), P(c->Wd), nullptr, 0, X, (const TS*)Q(c->Zs), c->hyp, M, c->D, c->kind};
-        HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_kernel<TS, FwdWProb<TS, T, true, 4>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CS::LDS_BYTES + zl)));
-        hipLaunchKernelGGL((gemm_nt_kernel<TS, FwdWProb<TS, T, true, 4>>), dim3(nt_xcd_row_grid(rtiles, nct<TS>(c))), dim3(256), CS::LDS_BYTES + zl, c->side, p);
-      }
-      LAUNCHCHK("fwd_wd");
-    }
     // (2) tt_kn = ||S_k^T w_n||^2
     if (c->split) {
       if ((rc = (c->split == 2 ? fwd_t_split<SplitF16>(c, n, rtiles, s) : fwd_t_split<SplitBf16>(c, n, rtiles, s)))) return rc;
@@ -1106,9 +920,8 @@ template <typename T, typename TS> struct Impl {
     if (mask & SL_ROWS) {
       ScopedTimer tm(c, 6, s);
       // matrix-core form (rows_mfma.h): 16 rows per wave, the three K x V products of a row block as 16x16x4 matrix instructions on
-      // register-resident operands; K <= 32, V <= 64.  GDRF_ROWS_MFMA=0: the one-thread-per-row kernel (which serves the other sizes)
-      static const bool rows_mfma = !(getenv("GDRF_ROWS_MFMA") && getenv("GDRF_ROWS_MFMA")[0] == '0');
-      if (rows_mfma && K <= 32 && V <= 64) {
+      // register-resident operands; K <= 32, V <= 64.  The one-thread-per-row kernel serves the other sizes
+      if (K <= 32 && V <= 64) {
         const int nkt = K <= 16 ? 1 : 2, nvt = V <= 32 ? 2 : 4;
         const size_t lds = rows_mfma_lds<T>(K, V, nkt, nvt, 4);
         const int64_t groups = (n + 15) / 16;
@@ -1124,27 +937,21 @@ template <typename T, typename TS> struct Impl {
                            (int64_t)K * V, redT + roff(c, 1));
       } else {
       const bool kreg = K <= GDRF_KMAX;
-      auto lds_for = [&](int rb, bool wsep) {
-        return 128 + ((size_t)2 * K * V + (size_t)rb * (K + 1) * (kreg ? 1 : 2) + (size_t)rb * (V + 1) * (wsep ? 2 : 1)) * sizeof(T);
-      };
+      auto lds_for = [&](int rb) { return 128 + ((size_t)2 * K * V + (size_t)rb * (K + 1) * (kreg ? 1 : 2) + (size_t)rb * (V + 1)) * sizeof(T); };
       int RB = 128;
-      const char* wst = getenv("GDRF_ROWS_STAGE_WS");
-      bool wsep = kreg && wst && wst[0] == '1' && lds_for(128, true) <= 150 * 1024;      // A/B knob: the counts staged through LDS (measured slower)
-      while (RB > 32 && lds_for(RB, wsep) > 150 * 1024) RB >>= 1;
-      const size_t lds = lds_for(RB, wsep);
+      while (RB > 32 && lds_for(RB) > 150 * 1024) RB >>= 1;
+      const size_t lds = lds_for(RB);
       if (lds > 150 * 1024)
         return fail(-1, "gdrf_step_local", "num_topic_categories x num_observation_categories too large: the row kernel keeps the "
                                            "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB)");
-      const void* kfn = !kreg ? (const void*)elbo_rows_kernel<T, false, false>
-                              : (wsep ? (const void*)elbo_rows_kernel<T, true, true> : (const void*)elbo_rows_kernel<T, true, false>);
+      const void* kfn = kreg ? (const void*)elbo_rows_kernel<T, true> : (const void*)elbo_rows_kernel<T, false>;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       int64_t nblk = (n + RB - 1) / RB;
       egrid = (int)std::min<int64_t>(nblk, c->erows_grid_cap);
 #define GDRF_ROWS_ARGS n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt), eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk, c->mean_sn, \
                        P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart, P(c->phibar_part)
-      if (!kreg) hipLaunchKernelGGL((elbo_rows_kernel<T, false, false>), dim3(egrid), dim3(RB), lds, s, GDRF_ROWS_ARGS);
-      else if (wsep) hipLaunchKernelGGL((elbo_rows_kernel<T, true, true>), dim3(egrid), dim3(RB), lds, s, GDRF_ROWS_ARGS);
-      else hipLaunchKernelGGL((elbo_rows_kernel<T, true, false>), dim3(egrid), dim3(RB), lds, s, GDRF_ROWS_ARGS);
+      if (kreg) hipLaunchKernelGGL((elbo_rows_kernel<T, true>), dim3(egrid), dim3(RB), lds, s, GDRF_ROWS_ARGS);
+      else hipLaunchKernelGGL((elbo_rows_kernel<T, false>), dim3(egrid), dim3(RB), lds, s, GDRF_ROWS_ARGS);
 #undef GDRF_ROWS_ARGS
       LAUNCHCHK("elbo_rows");
       hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)egrid, 4, redd);
@@ -1165,9 +972,11 @@ template <typename T, typename TS> struct Impl {
       }
     }
     // ubar = locbar W needs only the row kernel's locbar: on the side stream BESIDE the Wbar contraction (a vector / HBM pass next to a
-    // matrix-pipe kernel that leaves half of each SIMD's registers free) instead of inside bwd_knm with G^T (GDRF_UBAR_EARLY=0: there)
-    static const bool ubar_early = !(getenv("GDRF_UBAR_EARLY") && getenv("GDRF_UBAR_EARLY")[0] == '0');
-    auto launch_ubar = [&](hipStream_t ss) -> int {
+    // matrix-pipe kernel that leaves half of each SIMD's registers free) instead of inside bwd_knm with G^T
+    HIPCHK(hipEventRecord(c->ev_fork, s));
+    HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    {
+      hipStream_t ss = c->side;
       ScopedTimer tm(c, 12, ss);
       const int64_t rpb = ubar_rows_per_block(n), nb = (n + rpb - 1) / rpb;
       if (nb > c->ubar_blocks_cap) return fail(-1, "gdrf_step_local", "ubar partial buffer too small");
@@ -1178,12 +987,6 @@ template <typename T, typename TS> struct Impl {
 #undef GDRF_UBAR
       hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * Mp + 255) / 256), dim3(256), 0, ss, P(c->ubar_part), nb, (int64_t)K * Mp,
                          redT + roff(c, 0));
-      return 0;
-    };
-    if (ubar_early) {
-      HIPCHK(hipEventRecord(c->ev_fork, s));
-      HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-      if ((rc = launch_ubar(c->side))) return rc;
     }
     // (3) Wbar
     {
@@ -1228,7 +1031,6 @@ template <typename T, typename TS> struct Impl {
       { ScopedTimer tm(c, 11, ss);
         dim3 gr1((Mp + 255) / 256, Mp, 1);
         hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr1, dim3(256), 0, ss, (const T*)slab_gt, ns, 1, Mp, 0, redT + roff(c, 3)); }
-      if (!ubar_early && (rc = launch_ubar(ss))) return rc;
     }
     HIPCHK(hipEventRecord(c->ev_join, c->side));
     // (4) kernel hyper-parameter partials through K_nm
@@ -1255,15 +1057,7 @@ template <typename T, typename TS> struct Impl {
         hyper_done = true;
       }
     }
-    if (hyper_done) {
-    } else if (use_wd) {
-      // on the side stream, behind W' and G^T / ubar: sum Wbar o W -> red_d[4], sum Wbar o W' -> red_d[5]; red_d[6] = 0
-      hipStream_t ss = c->side;
-      hipLaunchKernelGGL(wbar_dot_kernel<T>, dim3(2048), dim3(256), 0, ss, (const T*)P(c->Wbar), (const T*)P(c->W), (const T*)P(c->Wd), n, Mp, c->wdpart);
-      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, ss, c->wdpart, (int64_t)2048, 2, redd + 4);
-      HIPCHK(hipMemsetAsync(redd + 6, 0, sizeof(double), ss));
-      HIPCHK(hipEventRecord(c->ev_join, c->side));           // the join event now also covers these
-    } else {
+    if (!hyper_done) {
       ScopedTimer tm(c, 8, s);
       const int64_t nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
       if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
@@ -1298,16 +1092,8 @@ template <typename T, typename TS> struct Impl {
       hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, nb, 3, redd + 4);      // red_d[4..6]
     }
     LAUNCHCHK("backward");
-    // (5) A_k = W^T diag(vbar_k) W.  It needs W and vbar only - not Wbar - and could run on a third stream BESIDE the f64 backward GEMM
-    // (GDRF_AK_ASIDE=1).  Measured (profiles/r03): no gain - 48.57 vs 48.71 ms/step; the two kernels time-slice the CUs (A_k 9.2 -> 18.0 ms,
-    // bwd_knm 8.7 -> 10.7 ms beside each other) instead of filling each other's stalls as the register-capped G^T kernel does.  Off.
-    static const bool ak_aside = getenv("GDRF_AK_ASIDE") && getenv("GDRF_AK_ASIDE")[0] == '1';
-    const bool ak_on_side = ak_aside && !hyper_done && !use_wd && c->split == 2 && sizeof(TS) == 8;
-    hipStream_t s_main = s;
-    if (ak_on_side) {
-      HIPCHK(hipStreamWaitEvent(c->side2, c->ev_fork2, 0));       // recorded on the caller's stream right behind the Wbar contraction
-      s = c->side2;
-    }
+    // (5) A_k = W^T diag(vbar_k) W.  It needs W and vbar only - not Wbar - but stays on the caller's stream: beside the f64 backward GEMM
+    // the two kernels time-slice the CUs instead of filling each other's stalls
     {
       const int BR = TNCfg<T>::BR;
       const int ns = std::min(tn_nsplit(c, n, BR, c->split ? 2 : 3), c->nsplit_cap);
@@ -1315,7 +1101,7 @@ template <typename T, typename TS> struct Impl {
       TNArgs<T> a{P(c->W), Mp, P(c->W), Mp, P(c->vbar), ldk, n, rps, Mp, 1, P(c->slab), K, ns};
       int red_ns = ns, red_qd = GDRF_TILE / 2;
       { ScopedTimer tm(c, 9, s);
-        if (tn_topics_on(c)) {
+        if (c->split == 2) {
           if constexpr (std::is_same<T, float>::value) {
             const SplitLay SL{K};
             const int nst = std::min(tn_topics_nsplit(c, n), c->nsplit_cap);
@@ -1325,42 +1111,31 @@ template <typename T, typename TS> struct Impl {
                             (float*)c->slab, K, nst, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
             // The one-wave forms run every stage of their 10-topic groups whatever K: with more than 40 % of the topic slots empty (K <= 5, K = 11 .. 12)
             // the two-wave form, which walks the topic pairs that exist, is the faster one.
-            const int w1 = getenv("GDRF_TNT_W1") ? atoi(getenv("GDRF_TNT_W1")) : (10 * K >= 6 * kgroups * TNT_KT ? 2 : 0);   // one-wave-per-SIMD forms (gemm_tn_topics1.h): 2 = 128 rows per wave, 1 = 64; 0: the two-wave form
-            if (w1) {
+            if (10 * K >= 6 * kgroups * TNT_KT) {      // one-wave-per-SIMD form (gemm_tn_topics1.h): 128 rows per wave
               int ns1 = c->nsplit_cap < 64 ? c->nsplit_cap : 64;                            // 8 k splits: every XCD owns whole splits
-              if (const char* e = getenv("GDRF_TNT_NSPLIT")) { const int v = atoi(e); if (v > 0 && v <= c->nsplit_cap) ns1 = v; }
               while (ns1 > 8 && (n + ns1 - 1) / ns1 < 8 * TN1_CH) ns1 -= 8;                 // at least 8 chunks per split
               if (ns1 >= 8) ns1 &= ~7;
               const int64_t rps1 = round_up((n + ns1 - 1) / ns1, TN1_CH);
-              const int ntl1 = w1 == 2 ? tnt_ntiles(Mp) : tn1_ntiles(Mp);
               const int64_t lds64 = round_up(c->ncap, 64);
               hipLaunchKernelGGL(tn1_scale_rows_kernel, dim3(256, K), dim3(256), 0, s, (const float*)c->vbar, ldk, n, (float*)c->vbs, lds64,
                                  (const float*)c->ssc, SL.v(0));
               TNTopicsArgs t1{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbs, lds64, n, rps1, Mp,
-                              (float*)c->slab, K, ns1, ntl1, (const float*)c->ssc, SL.w(), SL.v(0)};
-              if (w1 == 2) {
-                // two launches: the tiles whose upper 64 rows lie above the diagonal (J = 2 I + 1) multiply half the A tiles (gemm_tn_topics1.h)
-                const int nth = tn2_ntiles_half(Mp);
-                TNTopicsArgs t0 = t1, t4 = t1;
-                t0.ntiles = ntl1 - nth; t4.ntiles = nth;
-                HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
-                HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
-                if (t0.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<0>, dim3((unsigned)(t0.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t0);
-                if (t4.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<4>, dim3((unsigned)(t4.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t4);
-              } else {
-                HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tn1_lds_bytes()));
-                hipLaunchKernelGGL(tn_topics_w1_kernel, dim3((unsigned)(ntl1 * kgroups * ns1)), dim3(256), tn1_lds_bytes(), s, t1);
-              }
-              LAUNCHCHK("tn_topics_w1");
+                              (float*)c->slab, K, ns1, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
+              // two launches: the tiles whose upper 64 rows lie above the diagonal (J = 2 I + 1) multiply half the A tiles (gemm_tn_topics1.h)
+              const int nth = tn2_ntiles_half(Mp);
+              TNTopicsArgs t0 = t1, t4 = t1;
+              t0.ntiles = ntl - nth; t4.ntiles = nth;
+              HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
+              HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
+              if (t0.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<0>, dim3((unsigned)(t0.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t0);
+              if (t4.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<4>, dim3((unsigned)(t4.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t4);
+              LAUNCHCHK("tn_topics_w2");
               red_ns = ns1; red_qd = 32;
             } else {
-            static const int pph = getenv("GDRF_TNT_PPH") ? atoi(getenv("GDRF_TNT_PPH")) : 3;     // topic pairs per phase (A/B knob)
-#define GDRF_TNT(X) { HIPCHK(hipFuncSetAttribute((const void*)tn_topics_f16_kernel<X>, hipFuncAttributeMaxDynamicSharedMemorySize, tnt_lds_bytes(X))); \
-                      hipLaunchKernelGGL(tn_topics_f16_kernel<X>, dim3((unsigned)(ntl * kgroups * nst)), dim3(512), tnt_lds_bytes(X), s, ta); }
-            if (pph == 1) GDRF_TNT(1) else if (pph == 2) GDRF_TNT(2) else GDRF_TNT(3)
-#undef GDRF_TNT
-            LAUNCHCHK("tn_topics");
-            red_ns = nst; red_qd = 32;
+              HIPCHK(hipFuncSetAttribute((const void*)tn_topics_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tnt_lds_bytes()));
+              hipLaunchKernelGGL(tn_topics_f16_kernel, dim3((unsigned)(ntl * kgroups * nst)), dim3(512), tnt_lds_bytes(), s, ta);
+              LAUNCHCHK("tn_topics");
+              red_ns = nst; red_qd = 32;
             }
           }
         } else if (c->split) {
@@ -1373,11 +1148,6 @@ template <typename T, typename TS> struct Impl {
       { ScopedTimer tm(c, 11, s);
         dim3 gr((Mp + 255) / 256, Mp, K);
         hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr, dim3(256), 0, s, P(c->slab), red_ns, K, Mp, 1, redT + roff(c, 2), red_qd); }
-    }
-    if (ak_on_side) {
-      HIPCHK(hipEventRecord(c->ev_ak_done, c->side2));
-      s = s_main;
-      HIPCHK(hipStreamWaitEvent(s, c->ev_ak_done, 0));
     }
     HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
     LAUNCHCHK("reductions");
@@ -1581,10 +1351,9 @@ template <typename T, typename TS> struct Impl {
     {
       // matrix-core form (predict.h): a wave owns 16 rows, one covariance value per lane and step is the A operand of the 16x16x4
       // matrix instruction, the padded transposed coefficients CfT its B operand.  K <= 32, the scaled inducing inputs in LDS.
-      static const bool mfma_on = !(getenv("GDRF_PREDICT_MFMA") && getenv("GDRF_PREDICT_MFMA")[0] == '0');     // A/B knob: 0 = one thread per row
       const int M4 = (int)round_up(M, 4), NB = K <= 16 ? 1 : 2, DDt = c->D <= 2 ? 2 : GDRF_DMAX;
       const size_t lds = 128 + ((size_t)M4 * DDt + (size_t)K * V + (size_t)4 * 16 * (16 * NB + 1)) * sizeof(TS);
-      if (mfma_on && K <= 32 && lds <= 64 * 1024) {
+      if (K <= 32 && lds <= 64 * 1024) {
         const int ldc = 16 * NB;
         hipLaunchKernelGGL((predict_coeff_t_kernel<TS, T>), dim3(M4), dim3(64), 0, s, (const TS*)Q(c->LinvT), U, M, Mp, M4, K, ldc, Q(c->CfT));
         const int64_t groups = (n + 15) / 16;

@@ -31,7 +31,7 @@
 namespace gdrf {
 
 template <typename T> struct NTCfg {
-  static constexpr int BK = GDRF_KBYTES_F64 > 0 && sizeof(T) == 8 ? GDRF_KBYTES_F64 / 8 : GDRF_KBYTES / (int)sizeof(T);   // 32 (f32) / 16 or 32 (f64)
+  static constexpr int BK = GDRF_KBYTES / (int)sizeof(T);   // 32 (f32) / 16 (f64)
   static constexpr int VE = 16 / (int)sizeof(T);            // elements per 16-byte vector
   static constexpr int LDK = BK + VE;                       // padded LDS row: 144 bytes
   static constexpr int KG = BK / 4;                         // k indices per lane group per chunk
@@ -62,15 +62,6 @@ template <class P, class = void> struct NTMinWgs { static constexpr int value = 
 template <class P> struct NTMinWgs<P, decltype((void)P::MIN_WGS)> { static constexpr int value = P::MIN_WGS; };
 
 template <typename T, class P> __device__ __forceinline__ void gemm_nt_body(P& p);
-
-#ifdef GDRF_NT_TRACE   // diagnostic builds only: per-workgroup phase stamps of the problems that declare TRACE (tools/nt_trace.py)
-__device__ unsigned long long* g_nt_trace = nullptr;       // [workgroup][8]: block | column tile << 32, hw id, xcc id, t start, t first chunk staged, t loop end, t tile end, t end
-template <class P, class = void> struct NTTrace { static constexpr bool value = false; };
-template <class P> struct NTTrace<P, decltype((void)P::TRACE)> { static constexpr bool value = P::TRACE; };
-#define NT_STAMP(slot) do { if (NTTrace<P>::value && g_nt_trace && threadIdx.x == 0 && blockIdx.y == 0) g_nt_trace[(size_t)blockIdx.x * 8 + (slot)] = wall_clock64(); } while (0)
-#else
-#define NT_STAMP(slot) do {} while (0)
-#endif
 
 template <typename T, class P>
 __global__ __launch_bounds__(256, NTMinWgs<P>::value) void gemm_nt_kernel(P p) { gemm_nt_body<T, P>(p); }
@@ -103,14 +94,6 @@ __device__ __forceinline__ void gemm_nt_body(P& p) {
   const int bz = p.batch_index(blockIdx.x, blockIdx.y);
   const int R = p.a_reuse();
 
-#ifdef GDRF_NT_TRACE
-  if (NTTrace<P>::value && g_nt_trace && threadIdx.x == 0 && blockIdx.y == 0) {
-    g_nt_trace[(size_t)blockIdx.x * 8 + 0] = blockIdx.x | ((unsigned long long)ct_first << 32);
-    g_nt_trace[(size_t)blockIdx.x * 8 + 1] = __builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_ID: wave, SIMD, CU, SH, SE
-    g_nt_trace[(size_t)blockIdx.x * 8 + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 20);     // XCC_ID
-  }
-  NT_STAMP(3);
-#endif
   typename P::ACtx actx;
   p.prepA(actx, m0, bz, extra);
   typename P::ECtx ectx;
@@ -199,7 +182,6 @@ __device__ __forceinline__ void gemm_nt_body(P& p) {
 #pragma unroll
       for (int i = 0; i < C::VPTB; ++i) *reinterpret_cast<V*>(&Bs[nt_stage_row<T>(i) * C::LDK + srow_k]) = rb[i];
       __syncthreads();
-      if (c == 0) NT_STAMP(4);
       if (c + P::DEPTH < nchunks) gload(ra, rb, c + P::DEPTH);      // refill the set just consumed
       compute(rep, kA);
     };
@@ -222,12 +204,9 @@ __device__ __forceinline__ void gemm_nt_body(P& p) {
       __syncthreads();
       compute(-1);
     }
-    NT_STAMP(5);
     p.tile_done(acc, m0, n0, bz, ectx, wr, wc, lane);
-    NT_STAMP(6);
   }
   p.finish(m0, bz, ectx, smem, wr, wc, lane);
-  NT_STAMP(7);
 }
 
 // element (row, col) of accumulator register r of MFMA tile (a, b) inside the workgroup tile
@@ -275,7 +254,7 @@ struct NTXcdMap {
 // Grid: nt_xcd_row_grid(rtiles, nct); padding blocks get rtile >= rtiles.
 //
 // The ORDER of the column tiles inside an XCD's sequence matters for triangular reductions (column tile ct costing ct + 1 or nct - ct
-// units).  Measured with per-workgroup stamps (tools/nt_trace.py, profiles/r03/README.md): workgroup b of a launch runs on XCD b mod 8
+// units).  Measured with per-workgroup stamps (profiles/r03/README.md): workgroup b of a launch runs on XCD b mod 8
 // and, inside it, on shader engine (b / 8) mod 4 - a STATIC round robin - and workgroups are placed in order, so the engine that is
 // handed the most work is always full (24 workgroups on its 8 CUs) while the launch waits for it and the three others starve.  In
 // plain order (ct = 0, 1, 2, ...) engine e of every XCD only ever sees the column tiles ct = e mod 4 - 6 : 8 : 10 : 12 units - and
@@ -290,9 +269,7 @@ struct NTXcdRowMap {
     const unsigned xcd = bid & 7u, idx = bid >> 3;
     rtile = (int64_t)(idx / (unsigned)nct) * 8 + xcd;
     ct = (int)(idx % (unsigned)nct);
-#ifndef GDRF_NT_PLAIN_ORDER
     if ((nct & 3) == 0 && ((idx >> 2) & 1u)) ct = (ct & ~3) + 3 - (ct & 3);      // odd group of four: reversed (idx / 4 counts groups across row tiles)
-#endif
   }
 };
 

@@ -21,7 +21,7 @@
 //
 //   split_kernel / split_blocked_kernel   W, B_k = S_k S_k^T and S_k^T -> pieces, once per step (W's come from fwd_w's epilogue)
 //   bwd_wbar_split_kernel    Wbar = sum_k diag(2 vbar_k) W B_k + locbar^T U - 2 diag(asum) W   (replaces gemm_nt<BwdWbarProb>)
-//   fwd_t_split_2g_kernel    tt[k][n] = |S_k^T w_n|^2                                           (replaces gemm_nt<FwdTProb>)
+//   fwd_t_split_cc_kernel / fwd_t_split_q4_kernel   tt[k][n] = |S_k^T w_n|^2                      (replace gemm_nt<FwdTProb>)
 //   gemm_tn_split_kernel     A_k = W^T diag(vbar_k) W  and  GT = W^T Wbar                        (replaces gemm_tn_kernel<float>)
 //
 // All keep the tiling, block maps, deterministic slab reduction and epilogues of the f32 forms they replace.
@@ -158,11 +158,6 @@ __device__ __forceinline__ void glds16_asm(const void* gsrc, unsigned lds_dst) {
 __device__ __forceinline__ void glds16_asm_s(const void* sbase, unsigned voff, unsigned lds_dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
-__device__ __forceinline__ unsigned long long split_stamp() {          // diagnostic builds only
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  return t;
-}
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
 }
@@ -221,7 +216,6 @@ template <class SP> struct BwdWbarSplitArgs {
   const float* asum; const float* U; float* Wbar;
   const float* sc;                             // block scales (SplitLay)
   unsigned* wbar_max;                          // max |Wbar| (bits), for the scale of the G^T contraction's operand
-  unsigned long long* stamps = nullptr;        // diagnostic builds only (STAMP)
   // bwd_wbar_f16_k64_kernel only, few rows (mini-batches): gridDim.y = nslice slices of the reduction blocks, slice y writes its partial
   // sum to slab + y * slab_stride (slice 0 carries the rank-K and the -2 a W terms); wbar_slab_sum_kernel adds them into Wbar
   float* slab = nullptr; int64_t slab_stride = 0; int nslice = 1;
@@ -520,7 +514,7 @@ __global__ __launch_bounds__(256 * NG, 2) void bwd_wbar_split_kernel(BwdWbarSpli
 // topic rep) chunk for all 8 waves; the next chunk's B image (shared, double-buffered) and - when the next chunk opens a new
 // reduction block - the groups' next A images (double-buffered) are requested by asm LDS-DMA at the top of the phase and retired
 // by the vmcnt(0) in front of the barrier that ends it.
-template <class SP, bool STAMP = false>
+template <class SP>
 __global__ __launch_bounds__(512, 2) void bwd_wbar_split_cc_kernel(BwdWbarSplitArgs<SP> g) {
   using CF = SplitCfg<SP>;
   using E = typename SP::E;
@@ -591,16 +585,9 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_split_cc_kernel(BwdWbarSplitA
   for (int p = 0; p < NP; ++p) { dma_a1(0, 0, p); dma_a1(0, 1, p); dma_b1(0, p); }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();                        // also publishes the scale table
-  const bool stamping = STAMP && blockIdx.x == 6000 && (wave == 0) && lane == 0;
-  unsigned long long* lstamp = reinterpret_cast<unsigned long long*>(smem + (size_t)6 * IMG * 2 + 2 * tab);   // [2][64][4]
-  auto stamp = [&](int c, int i) {
-    if (STAMP) { __builtin_amdgcn_sched_barrier(0); if (stamping && c >= 20 && c < 84) lstamp[(gp * 64 + c - 20) * 4 + i] = split_stamp(); __builtin_amdgcn_sched_barrier(0); }
-  };
   for (int c = 0; c < nchunks; ++c) {
     const int q = c / K, rep = c - q * K;
-    stamp(c, 0);
     const bool more = c + 1 < nchunks, more_a = more && rep == K - 1;
-    stamp(c, 1);
     const E* Ab = As + (q & 1) * IMG;
     const E* Bb = Bs + (c & 1) * IMG;
     if (rep == 0) {
@@ -640,13 +627,10 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_split_cc_kernel(BwdWbarSplitA
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P[a][r];
     }
-    stamp(c, 2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(c, 3);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     gdrf_raw_barrier();
   }
-  if (STAMP) { if (stamping) for (int i = 0; i < 64 * 4; ++i) g.stamps[gp * 256 + i] = lstamp[gp * 256 + i]; }
   // rank-K epilogue term locbar^T U on the native f32 matrix instruction (exact f32, no split, no range question): lane
   // (lr, lg) supplies A[row lr][k = lg] and B[k = lg][col lr] of v_mfma_f32_16x16x4_f32, whose C/D layout is the accumulators'
   for (int k0 = 0; k0 < K; k0 += 4) {
@@ -717,9 +701,6 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_split_cc_kernel(BwdWbarSplitA
 // k-steps per (reduction block, topic) halve that update per MFMA: 96 MFMAs, one update, one barrier per phase.  LDS: the A image
 // (this group's rows x 64 k, 32 KB) is SINGLE-buffered - its fragments live in registers for the K topic phases of a block, so the
 // next block's image is requested in the phase after they were read (K >= 2) -; B (shared, 32 KB) is double-buffered.
-// ABL (timing-only diagnostic builds, results wrong): 1 = no acc += s P update (MFMAs accumulate straight into acc), 2 = no LDS-DMA after
-// the prologue, 4 = B fragments read once per phase group (b = 0) only
-template <int ABL = 0>
 __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitArgs<SplitF16> g) {
   using SP = SplitF16;
   using CF = SplitCfg<SP>;
@@ -820,8 +801,8 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
       for (int p = 0; p < NP; ++p) fbq[0][ks][p] = *reinterpret_cast<const V8*>(Bb + (ks * NP + p) * CF::PIECE + (wc * 64) * 32 + frag);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      V8 (&fb)[2][NP] = fbq[(ABL & 4) ? 0 : (b & 1)];
-      if (b + 1 < 4 && !(ABL & 4)) {
+      V8 (&fb)[2][NP] = fbq[b & 1];
+      if (b + 1 < 4) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -829,77 +810,33 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
             fbq[(b + 1) & 1][ks][p] = *reinterpret_cast<const V8*>(Bb + (ks * NP + p) * CF::PIECE + (wc * 64 + (b + 1) * 16) * 32 + frag);
       }
       f32x4 P[4];
-      if (ABL & 16) {
-        // timing-only: the same matrix-pipe cycles from HALF as many instructions (32x32x16 instead of two 16x16x32; operands and results
-        // are garbage) - does the kernel wait for the pipe or for the issue slots the MFMAs hold?
-        typedef float f32x16 __attribute__((ext_vector_type(16)));
-#pragma unroll
-        for (int a2 = 0; a2 < 2; ++a2) {
-          f32x16 P2;
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int t = 0; t < SP::NPROD; ++t)
-              P2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][2 * a2][SP::pa(t)], fb[ks][SP::pb(t)],
-                                                          (ks == 0 && t == 0) ? f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0} : P2, 0, 0, 0);
-#pragma unroll
-          for (int a = 2 * a2; a < 2 * a2 + 2; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P2[(a & 1) * 8 + r] + 1e-30f * P2[(a & 1) * 8 + 4 + r];
-        }
-      } else
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int t = 0; t < SP::NPROD; ++t)
 #pragma unroll
-          for (int a = 0; a < 4; ++a) {
-            if (ABL & 1) acc[a][b] = SP::mma(fa[ks][a][SP::pa(t)], fb[ks][SP::pb(t)], acc[a][b]);
-            else P[a] = SP::mma(fa[ks][a][SP::pa(t)], fb[ks][SP::pb(t)], (ks == 0 && t == 0) ? f32x4{0, 0, 0, 0} : P[a]);
-          }
+          for (int a = 0; a < 4; ++a) P[a] = SP::mma(fa[ks][a][SP::pa(t)], fb[ks][SP::pb(t)], (ks == 0 && t == 0) ? f32x4{0, 0, 0, 0} : P[a]);
       // the next chunk's requests behind the first two column groups' MFMAs, so that they have the second half of the phase to land: an
       // LDS-DMA instruction stalls its wave at issue, but spread over all four groups (one or two each) the last request was issued just
-      // in front of the phase's closing vmcnt(0) and its whole latency showed - 13.3 -> 12.1 ms.  (ABL & 8, timing A/B: the two wave
-      // groups staggered - group 0 behind b = 0, 1, group 1 behind b = 2, 3: 13.7 ms; ABL & 64: everything behind b = 0.)
-      {
-        const int bb = (ABL & 8) ? (gp ? b - 2 : b) : b;
-        if (ABL & 64) {
-          if (b == 0 && !(ABL & 2)) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-              if (more) { dma_b1(c + 1, ks, 0); dma_b1(c + 1, ks, 1); }
-              if (more_a) { dma_a1(q + 1, ks, 0, 0); dma_a1(q + 1, ks, 1, 0); dma_a1(q + 1, ks, 0, 1); dma_a1(q + 1, ks, 1, 1); }
-            }
-          }
-        } else if (bb >= 0 && bb < 2 && !(ABL & 2)) {
-          if (more) { dma_b1(c + 1, bb, 0); dma_b1(c + 1, bb, 1); }
-          if (more_a) { dma_a1(q + 1, bb, 0, 0); dma_a1(q + 1, bb, 1, 0); dma_a1(q + 1, bb, 0, 1); dma_a1(q + 1, bb, 1, 1); }
-        }
+      // in front of the phase's closing vmcnt(0) and its whole latency showed - 13.3 -> 12.1 ms.  (Also measured: the two wave groups
+      // staggered - group 0 behind b = 0, 1, group 1 behind b = 2, 3: 13.7 ms.)
+      if (b < 2) {
+        if (more) { dma_b1(c + 1, b, 0); dma_b1(c + 1, b, 1); }
+        if (more_a) { dma_a1(q + 1, b, 0, 0); dma_a1(q + 1, b, 1, 0); dma_a1(q + 1, b, 0, 1); dma_a1(q + 1, b, 1, 1); }
       }
-      if (!(ABL & 1) && !(ABL & 16)) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
+      for (int a = 0; a < 4; ++a)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P[a][r];
-      } else if (b == 3 && (ABL & 1)) asm volatile("" :: "v"(s4[0][0] + s4[1][1] + s4[2][2] + s4[3][3]));
+        for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P[a][r];
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     gdrf_raw_barrier();
   }
-  if (ABL & 256) {                                           // timing-only: no epilogue at all (one store keeps the loop alive; results wrong)
-    float z = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) z += (acc[a][b][0] + acc[a][b][1]) + (acc[a][b][2] + acc[a][b][3]);
-    if (z == 123.456f) g.Wbar[0] = z;
-    return;
-  }
   // ---- epilogue.  One workgroup per CU: nothing else runs on the CU while it reads and writes, so every global load it needs is issued up
   // front, from clamped addresses and unconditionally (the fragment registers of the loop are free now) - the W tile of both 32-row halves,
   // asum, and the locbar / U values of the rank-K term - and their latencies overlap instead of following one another: five dependent round
-  // trips to HBM per workgroup were 0.9 ms of the 12.3 (timing-only build without the epilogue: 11.4).
+  // trips to HBM per workgroup were 0.9 ms of the 12.3 (measured without the epilogue: 11.4).
   f32x4 wv[2][8];
   float as2v[2][8];
 #pragma unroll
@@ -961,9 +898,7 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
         for (int b = 0; b < 4; ++b)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            float v = acc[2 * h + a2][b][r];
-            if (ABL) v = (fabsf(v) < 1e30f) ? v * 1e-30f : 0.0f;     // ablated builds compute garbage: keep it finite and tiny
-            tile[(a2 * 16 + lg * 4 + r) * TS + b * 16 + lr] = v;
+            tile[(a2 * 16 + lg * 4 + r) * TS + b * 16 + lr] = acc[2 * h + a2][b][r];
           }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // same wave writes and reads: LDS is in order per wave
 #pragma unroll
@@ -1023,194 +958,16 @@ template <class SP> struct FwdTSplitArgs {
   const typename SP::E* STh; int64_t piece_stride;    // STh[p][k][i / 32][j][i % 32] = pieces of S_k[i][j] (k-blocked)
   float* tt; int64_t ldt;
   const float* sc;
-  unsigned long long* stamps;                 // diagnostic builds only (template parameter STAMP): [2 groups][phases][4] s_memtime values of one workgroup
 };
 
 
-// tt in the two-group LDS-DMA structure of bwd_wbar_split_kernel<2>: a 512-thread workgroup holds two adjacent row tiles of
-// one topic, one per wave group; both walk the same (column tile, reduction chunk) sequence, so the S_k^T chunk is staged once
-// (by group 1) into a double-buffered image both read, and every group double-buffers its own W chunk.  Chunk c is multiplied
-// by group 0 in phase 2c and by group 1 in phase 2c+1; DMAs are issued in a group's idle phase two chunks ahead (group 0) / one
-// chunk ahead (group 1), land during its next multiply phase and are retired by the vmcnt(0) that ends it.
+// tt[k][n] = |S_k^T w_n|^2: a 512-thread workgroup holds two adjacent row tiles of one topic, one per wave group, with BOTH wave
+// groups multiplying in every phase ("concurrent" form).  Both walk the same (column tile, reduction chunk) sequence, so the S_k^T
+// chunk is staged once into a double-buffered image both read, and every group double-buffers its own W chunk.
 // Grid: 8 * K * rt8 with rt8 = ceil(row-tile pairs / 8).  Block map: XCD = blockIdx & 7 owns the pairs r * 8 + xcd; topics go
 // in groups of KG, group-major (every XCD first runs all its pairs for topics [0, KG), then [KG, 2 KG), ...) so that only KG
 // topics' S^T pieces are live in its 4 MB L2 at a time; the KG workgroups of one pair are adjacent.
-template <class SP, bool STAMP = false>
-__global__ __launch_bounds__(512, 2) void fwd_t_split_2g_kernel(FwdTSplitArgs<SP> g) {
-  using CF = SplitCfg<SP>;
-  using E = typename SP::E;
-  using V8 = typename SP::V8;
-  constexpr int NP = SP::NP;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int IMG = CF::IMG;
-  const int gp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lg = lane >> 4;
-  E* As = reinterpret_cast<E*>(smem) + gp * 2 * IMG;      // [2 buffers][NP][128][32] of this group
-  E* Bs = reinterpret_cast<E*>(smem) + 4 * IMG;           // [2 buffers][NP][128][32] shared
-  const int Mp = g.Mp;
-  const int nct = (Mp + GDRF_TILE - 1) / GDRF_TILE;
-  const unsigned xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-  const unsigned per_group = (unsigned)g.KG * (unsigned)g.rt8;
-  const int grp = (int)(idx / per_group);
-  const unsigned rem = idx - (unsigned)grp * per_group;
-  const int kg = min(g.KG, g.K - grp * g.KG);
-  const int64_t rtile = 2 * ((int64_t)(rem / (unsigned)kg) * 8 + xcd) + gp;
-  const int bz = grp * g.KG + (int)(rem % (unsigned)kg);
-  const int64_t m0 = rtile * GDRF_TILE;                        // a tile past the end runs on clamped rows; its tt is never stored
-
-  int nch = 0;                                                 // chunks of the triangular walk: column tile ct covers k in [128 ct, Mp)
-  for (int ct = 0; ct < nct; ++ct) nch += (Mp - ct * GDRF_TILE) / CF::BK;
-  auto decode = [&](int c, int& ct, int& kA, bool& first, bool& last) {
-    for (ct = 0;; ++ct) {
-      const int len = (Mp - ct * GDRF_TILE) / CF::BK;
-      if (c < len) { kA = ct * GDRF_TILE + c * CF::BK; first = c == 0; last = c == len - 1; return; }
-      c -= len;
-    }
-  };
-  const int drow = lane >> 2, dq = ((lane & 3) ^ split_swz(drow)) * 8;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);     // provably wave-uniform: the DMA's LDS base goes to M0 without a waterfall loop
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
-  auto dma_b = [&](int c) {
-    if (c >= nch) return;
-    int ct, kA; bool f, l;
-    decode(c, ct, kA, f, l);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int rbk = wave_u + 4 * i, row = rbk * 16 + drow;
-      const int col = (ct * GDRF_TILE + row < Mp) ? ct * GDRF_TILE + row : 0;      // columns >= Mp are skipped when the tile is folded
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-        __builtin_amdgcn_global_load_lds((gptr_t)(g.STh + p * g.piece_stride + (((int64_t)bz * (Mp >> 5) + (kA >> 5)) * Mp + col) * 32 + dq),
-                                         (lptr_t)(Bs + ((c & 1) * NP + p) * CF::PIECE + rbk * 512), 16, 0, 0);
-    }
-  };
-  auto dma_a = [&](int c) {
-    if (c >= nch) return;
-    int ct, kA; bool f, l;
-    decode(c, ct, kA, f, l);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int rbk = wave_u + 4 * i;
-      int64_t row = m0 + rbk * 16 + drow;
-      row = row < g.nrows ? row : 0;
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-        __builtin_amdgcn_global_load_lds((gptr_t)(g.Wh + p * g.w_stride + row * Mp + kA + dq),
-                                         (lptr_t)(As + ((c & 1) * NP + p) * CF::PIECE + rbk * 512), 16, 0, 0);
-    }
-  };
-  float rs[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rs[a][r] = 0;
-  f32x4 acc[4][4];
-  const int frag = lr * 32 + ((lg ^ split_swz(lr)) << 3);
-  const bool stamping = STAMP && blockIdx.x == 20000 && wave == 0 && lane == 0;
-  unsigned long long* lstamp = reinterpret_cast<unsigned long long*>(smem + 6 * IMG * 2);     // stamps stay in LDS until the end: a global store would sit in vmcnt
-  auto mult = [&](int c) {
-    int ct, kA; bool first, last;
-    decode(c, ct, kA, first, last);
-    if (STAMP) { __builtin_amdgcn_sched_barrier(0); if (stamping && c < 64) lstamp[(gp * 64 + c) * 4 + 0] = split_stamp(); __builtin_amdgcn_sched_barrier(0); }
-    if (first) {
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0, 0, 0, 0};
-    }
-    const E* Ab = As + (c & 1) * IMG;
-    const E* Bb = Bs + (c & 1) * IMG;
-    V8 fb[NP][4];
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) fb[p][b] = *reinterpret_cast<const V8*>(Bb + p * CF::PIECE + (wc * 64 + b * 16) * 32 + frag);
-    V8 faq[2][NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) faq[0][p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64) * 32 + frag);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      V8 (&fa)[NP] = faq[a & 1];
-      if (a + 1 < 4) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) faq[(a + 1) & 1][p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64 + (a + 1) * 16) * 32 + frag);
-      }
-#pragma unroll
-      for (int t = 0; t < SP::NPROD; ++t)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = SP::mma(fa[SP::pa(t)], fb[SP::pb(t)][b], acc[a][b]);
-    }
-    if (last) {                                                 // fold the finished column tile into the row sums
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const bool cok = ct * GDRF_TILE + wc * 64 + b * 16 + lr < Mp;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) rs[a][r] += cok ? acc[a][b][r] * acc[a][b][r] : 0.0f;
-      }
-    }
-    if (STAMP) { __builtin_amdgcn_sched_barrier(0); if (stamping && c < 64) lstamp[(gp * 64 + c) * 4 + 1] = split_stamp(); __builtin_amdgcn_sched_barrier(0); }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (STAMP) { __builtin_amdgcn_sched_barrier(0); if (stamping && c < 64) lstamp[(gp * 64 + c) * 4 + 2] = split_stamp(); __builtin_amdgcn_sched_barrier(0); }
-  };
-  auto phase_barrier = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    gdrf_raw_barrier();
-  };
-  dma_a(0);
-  if (gp == 0) dma_a(1); else dma_b(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  phase_barrier();
-  for (int ph = 0; ph < 2 * nch; ++ph) {
-    const int t = ph >> 1;
-    if ((ph & 1) == gp) {
-      mult(t);
-    } else if (gp == 0) {
-      dma_a(t + 2);                        // phase 2t+1: buffer (t+2)&1 was last read in phase 2t
-    } else {
-      dma_a(t + 1);                        // phase 2t: own buffer (t+1)&1 last read in phase 2t-1; so was the shared B buffer
-      dma_b(t + 1);
-    }
-    phase_barrier();
-    if (STAMP) { __builtin_amdgcn_sched_barrier(0); if (stamping && (ph & 1) == gp && t < 64) lstamp[(gp * 64 + t) * 4 + 3] = split_stamp(); __builtin_amdgcn_sched_barrier(0); }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (STAMP) { if (stamping) for (int i = 0; i < 64 * 4; ++i) g.stamps[gp * 256 + i] = lstamp[gp * 256 + i]; }
-  // row sums: 16-lane groups, then the two waves of a group that share the rows, through LDS; the block scales come off here
-  float* rsum = reinterpret_cast<float*>(smem) + gp * GDRF_TILE;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rs[a][r] = group16_sum(rs[a][r]);
-  __syncthreads();
-  if (wc == 0 && lr == 0) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) rsum[wr * 64 + a * 16 + lg * 4 + r] = rs[a][r];
-  }
-  __syncthreads();
-  if (wc == 1 && lr == 0) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) rsum[wr * 64 + a * 16 + lg * 4 + r] += rs[a][r];
-  }
-  __syncthreads();
-  if (tid < GDRF_TILE) {
-    const int64_t m = m0 + tid;
-    const SplitLay SL{g.K};
-    const float un = g.sc[SL.w() + 1] * g.sc[SL.st(bz) + 1];
-    if (m < g.nrows) g.tt[(int64_t)bz * g.ldt + m] = rsum[tid] * (un * un);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// The same contraction with BOTH wave groups multiplying in every phase ("concurrent" form).  fwd_t_split_2g_kernel alternates
-// the groups so that a SIMD's matrix pipe serves one wave at a time; measured per phase (s_memtime, f16x3, mid-launch
+// A removed form alternated the groups so that a SIMD's matrix pipe served one wave at a time; measured per phase (s_memtime, f16x3, mid-launch
 // workgroup): multiply 1184 cycles for 768 cycles of MFMA, + ~110 (vmcnt) + ~180 (barrier) + ~400 (loop / address code) = ~1900
 // cycles during which the OTHER group's wave on that SIMD idles - the pipe is busy 40 %.  That structure paid off when a chunk was
 // 96 MFMAs (bf16x6) and staging went through ds_write; with 48 MFMAs per chunk the fixed per-phase costs dominate.  Here a chunk
@@ -1369,9 +1126,9 @@ __global__ __launch_bounds__(512, 2) void fwd_t_split_cc_kernel(FwdTSplitArgs<SP
 // The triangle is kept at 128-column granularity: column group 1 of a pair starts 128 reduction indices later than group 0
 // (S_k^T is zero above), sits those chunks out (its waves only issue their share of the DMAs) and its B image is not fetched.
 // 8 images of NP x 8 KB: two-piece modes only (128 KB).
-// VAR (A/B knob): bit 0 = the next chunk's requests at the top of the phase instead of behind the first two MFMA groups (8.8 vs 9.0 ms),
-// bit 1 = without the scheduling barrier per row block (9.2 ms)
-template <class SP, int VAR = 0>
+// The next chunk's requests are issued at the top of the phase (8.8 ms; behind the first two MFMA groups instead: 9.0 ms), and a
+// scheduling barrier opens every row block (without it: 9.2 ms).
+template <class SP>
 __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> g) {
   using CF = SplitCfg<SP>;
   using E = typename SP::E;
@@ -1390,13 +1147,12 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
   const int Mp = g.Mp;
   const int nct = (Mp + GDRF_TILE - 1) / GDRF_TILE, ncp = (nct + 1) / 2;
   const unsigned xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-  const int KGv = (VAR & 16) ? (g.KG & 0xffff) : g.KG;     // (the stamped build carries the wave to stamp in the high half)
-  const unsigned per_group = (unsigned)KGv * (unsigned)g.rt8;
+  const unsigned per_group = (unsigned)g.KG * (unsigned)g.rt8;
   const int grp = (int)(idx / per_group);
   const unsigned rem = idx - (unsigned)grp * per_group;
-  const int kg = min(KGv, g.K - grp * KGv);
+  const int kg = min(g.KG, g.K - grp * g.KG);
   const int64_t rt0 = 2 * ((int64_t)(rem / (unsigned)kg) * 8 + xcd);   // the pair's first row tile
-  const int bz = grp * KGv + (int)(rem % (unsigned)kg);
+  const int bz = grp * g.KG + (int)(rem % (unsigned)kg);
   const int64_t m0 = (rt0 + gr) * GDRF_TILE;                   // a tile past the end runs on clamped rows; its tt is never stored
 
   const int drow = lane >> 2, dq = ((lane & 3) ^ split_swz(drow)) * 8;
@@ -1413,7 +1169,6 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
     b_off[sl] = (unsigned)(r * 32 + dq) * 2u;
   }
   auto dma1 = [&](int cp, int kA, int buf, int slot) {
-    if ((VAR & 32) && (cp > 0 || kA > 0)) return;            // timing-only ablation (results wrong): no requests after the prologue
     const int sl = slot < NP ? slot : slot - NP;
     const int rq = w16 * NP + sl, gi = rq / (8 * NP), rm = rq - gi * 8 * NP, p = rm >> 3, rbk = rm & 7;
     if (slot < NP) {
@@ -1434,13 +1189,6 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
   // is folded into it by its own wave (no other writer), so the order of the additions is fixed
   float* rsum = reinterpret_cast<float*>(smem + (size_t)8 * IMG * 2) + (gp * 2 + wc) * GDRF_TILE;
   rsum[wr * 64 + lane] = 0.0f;                            // this wave's 64 rows (ordered before its own later updates: same wave, LDS in order)
-  // diagnostic builds (VAR & 16): s_memtime at five points of every multiply phase of one wave of one workgroup, kept in LDS
-  unsigned long long* lstamp = reinterpret_cast<unsigned long long*>(smem + (size_t)8 * IMG * 2 + 8 * GDRF_TILE * 4);   // [64][5]
-  const bool stamping = (VAR & 16) && blockIdx.x == 20000 && w16 == (int)(g.KG >> 16) && lane == 0;
-  int sphase = 0;
-  auto stamp = [&](int i) {
-    if (VAR & 16) { __builtin_amdgcn_sched_barrier(0); if (stamping && sphase < 64) lstamp[sphase * 5 + i] = split_stamp(); __builtin_amdgcn_sched_barrier(0); }
-  };
   f32x4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -1485,50 +1233,27 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
       next_chunk(cp, kA, cp1, kA1);
       const E* Ab = Asm + (gr * 2 + buf) * IMG;
       const E* Bb = Bsm + (gc * 2 + buf) * IMG;
-      stamp(0);
-      if ((VAR & 1) && !(VAR & 4)) {
 #pragma unroll
-        for (int sl = 0; sl < 2 * NP; ++sl) dma1(cp1, kA1, buf ^ 1, sl);
-      }
+      for (int sl = 0; sl < 2 * NP; ++sl) dma1(cp1, kA1, buf ^ 1, sl);
       V8 fb[NP][4];
 #pragma unroll
       for (int p = 0; p < NP; ++p)
 #pragma unroll
         for (int b = 0; b < 4; ++b) fb[p][b] = *reinterpret_cast<const V8*>(Bb + p * CF::PIECE + (wc * 64 + b * 16) * 32 + frag);
-      V8 fa0[NP];
-      if (VAR & 4) {                                             // the first fragments are requested BEFORE the DMAs: their latency runs under the request stalls
-#pragma unroll
-        for (int p = 0; p < NP; ++p) fa0[p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64) * 32 + frag);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int sl = 0; sl < 2 * NP; ++sl) dma1(cp1, kA1, buf ^ 1, sl);
-      }
-      stamp(1);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
-        if (!(VAR & 2)) __builtin_amdgcn_sched_barrier(0);       // keeps hipcc from hoisting the later row blocks' reads
+        __builtin_amdgcn_sched_barrier(0);                       // keeps hipcc from hoisting the later row blocks' reads
         V8 fa[NP];                                               // one row block at a time: the SIMD's other three waves cover the read
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          if ((VAR & 4) && a == 0) fa[p] = fa0[p];
-          else fa[p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64 + a * 16) * 32 + frag);
-        }
+        for (int p = 0; p < NP; ++p) fa[p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64 + a * 16) * 32 + frag);
 #pragma unroll
         for (int t = 0; t < SP::NPROD; ++t)
 #pragma unroll
           for (int b = 0; b < 4; ++b) acc[a][b] = SP::mma(fa[SP::pa(t)], fb[SP::pb(t)][b], acc[a][b]);
-        if (a < 2 && !(VAR & 1)) {                               // the next chunk's requests behind the first two MFMA groups
-#pragma unroll
-          for (int sl = a * NP; sl < (a + 1) * NP; ++sl) dma1(cp1, kA1, buf ^ 1, sl);
-        }
       }
-      stamp(2);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's DMAs of the next chunk have landed (they had the whole phase)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp(3);
       gdrf_raw_barrier();
-      stamp(4);
-      if (VAR & 16) ++sphase;
       buf ^= 1;
     }
     if (ct < nct) {                                             // fold the finished column tile into the row sums, restart the accumulators
@@ -1555,16 +1280,13 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
   }
   // the four partial sums of a row (2 column groups x 2 wave columns), added in a fixed order
   __syncthreads();
-  if (VAR & 16) { if (stamping) for (int i = 0; i < 64 * 5; ++i) g.stamps[i] = lstamp[i]; }
   if (gc == 0 && tid < GDRF_TILE) {
     const float* q = reinterpret_cast<const float*>(smem + (size_t)8 * IMG * 2) + (gr * 2) * 2 * GDRF_TILE + tid;
     const float v = (q[0] + q[GDRF_TILE]) + (q[2 * GDRF_TILE] + q[3 * GDRF_TILE]);
     const int64_t m = m0 + tid;
     const SplitLay SL{g.K};
     const float un = g.sc[SL.w() + 1] * g.sc[SL.st(bz) + 1];
-    float o = v * (un * un);
-    if (VAR & 32) o = 1.0f + ((o == o && fabsf(o) < 1e30f) ? o * 1e-30f : 0.0f);       // ablated builds compute garbage: keep it finite and positive
-    if (m < g.nrows) g.tt[(int64_t)bz * g.ldt + m] = o;
+    if (m < g.nrows) g.tt[(int64_t)bz * g.ldt + m] = v * (un * un);
   }
 }
 

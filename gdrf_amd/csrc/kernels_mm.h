@@ -124,12 +124,6 @@ __global__ __launch_bounds__(1024) void chol_kernel(T* __restrict__ A, int M, in
   flag += blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6, lr = lane & 15, lg = lane >> 4;
-#ifdef GDRF_CHOL_PROF
-  unsigned long long tph[4] = {0, 0, 0, 0}, t0 = __builtin_readcyclecounter();
-#define CHOL_TICK(i) { const unsigned long long t1 = __builtin_readcyclecounter(); tph[i] += t1 - t0; t0 = t1; }
-#else
-#define CHOL_TICK(i)
-#endif
   for (int c0 = 0; c0 < M; c0 += 32) {
     // ---- (a) panel update.  The panel rows are staged in column chunks of CHOL_PC; a wave keeps the accumulators
     //      of up to NS of its strips across the chunks (more strips: another pass over the chunks).
@@ -191,7 +185,6 @@ __global__ __launch_bounds__(1024) void chol_kernel(T* __restrict__ A, int M, in
       }
       __syncthreads();
     }
-    CHOL_TICK(0)
     // ---- (b) factor the 32x32 diagonal block: one wave, rows in registers
     if (wave == 0 && sizeof(T) == 8) {
       // f64: a row per lane PAIR - lane l holds the even columns of row l, lane l + 32 the odd ones - so that the 31-column update
@@ -305,8 +298,6 @@ __global__ __launch_bounds__(1024) void chol_kernel(T* __restrict__ A, int M, in
       }
     }
     __syncthreads();
-    CHOL_TICK(1)
-    CHOL_TICK(2)
     // ---- (c) rows below the block: x Ld^T = u, one row per thread by forward substitution in registers; the factored block
     //      (Sa) and the reciprocal pivots (Scol) are broadcast reads from LDS
     for (int i0 = c0 + 32; i0 < M; i0 += 1024) {
@@ -328,11 +319,7 @@ __global__ __launch_bounds__(1024) void chol_kernel(T* __restrict__ A, int M, in
       }
     }
     __syncthreads();
-    CHOL_TICK(3)
   }
-#ifdef GDRF_CHOL_PROF
-  if (tid == 0 && blockIdx.x == 0) printf("chol<%d> cycles: update %llu  diag %llu  inverse %llu  apply %llu\n", (int)sizeof(T), tph[0], tph[1], tph[2], tph[3]);
-#endif
 }
 
 // dynamic LDS bytes of chol_kernel<T>
@@ -551,34 +538,6 @@ __global__ void finalize_l_kernel(const T* __restrict__ A, int M, int Mp, T* __r
   const T v = (i < M && j <= i) ? A[(int64_t)i * Mp + j] : T(0);
   L[(int64_t)i * Mp + j] = v;
   LT[(int64_t)j * Mp + i] = v;
-}
-
-// inverse of every 32x32 diagonal block of L (identity on the padding)
-template <typename T>
-__global__ __launch_bounds__(64) void trinv_diag_kernel(const T* __restrict__ L, int M, int Mp, T* __restrict__ Dinv) {
-  __shared__ T Sl[32][33];
-  __shared__ T Sx[32][33];
-  const int b = blockIdx.x, c = threadIdx.x;
-  for (int e = c; e < 1024; e += 64) {
-    const int r = e >> 5, q = e & 31;
-    const int gi = b * 32 + r, gj = b * 32 + q;
-    Sl[r][q] = (gi < M && gj < M) ? L[(int64_t)gi * Mp + gj] : ((r == q) ? T(1) : T(0));
-    Sx[r][q] = 0;
-  }
-  __syncthreads();
-  if (c < 32) {
-    Sx[c][c] = T(1) / Sl[c][c];
-    for (int r = c + 1; r < 32; ++r) {
-      T s = 0;
-      for (int p = c; p < r; ++p) s += Sl[r][p] * Sx[p][c];
-      Sx[r][c] = -s / Sl[r][r];
-    }
-  }
-  __syncthreads();
-  for (int e = c; e < 1024; e += 64) {
-    const int r = e >> 5, q = e & 31;
-    Dinv[(int64_t)b * 1024 + e] = Sx[r][q];
-  }
 }
 
 // block ROW I of X = L^{-1}; one 256-thread workgroup per block row, one wave per 16x16 quadrant of a 32x32 block.  From X L = 1:

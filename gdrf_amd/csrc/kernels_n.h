@@ -127,7 +127,6 @@ __global__ __launch_bounds__(256) void knm_kernel(const TX* __restrict__ X, int6
       for (int d = 0; d < GDRF_DMAX; ++d) z[e][d] = (i0 + e < M && d < D) ? Z[(int64_t)(i0 + e) * D + d] : T(0);
     const int64_t stride = (int64_t)gridDim.x * rpp;
     const bool vec_ok = aligned && (i0 + VE <= ldo);
-#ifndef GDRF_KNM_NO_RBF_FAST
     if constexpr (FAST && sizeof(T) == 4) {
       if (kind == 0) {
         // RBF on the roofline path: k = var * exp(-r2 / (2 ls^2)) = 2^(log2 var - sum_d (a x_d - a z_d)^2), a = sqrt(log2(e) / 2) / ls:
@@ -167,7 +166,6 @@ __global__ __launch_bounds__(256) void knm_kernel(const TX* __restrict__ X, int6
         return;
       }
     }
-#endif
     for (int64_t row0 = (int64_t)blockIdx.x * rpp + rsub; row0 < N; row0 += 4 * stride) {
       T x[4][GDRF_DMAX];
 #pragma unroll
@@ -239,29 +237,19 @@ template <> __device__ __forceinline__ float cov_fast<float>(int kind, float r2,
 //     stores W and the per-column-tile partial of q_n = ||w_n||^2.
 // T = solve precision (f64 in the default fp32 mode: the triangular solve cancels terms ~|Linv||k| >> |w|),
 // TN = precision of the N-sized outputs (W, qpart)
-// DERIV: the A operand is dK_nm / d log(lengthscale) instead of K_nm, formed from the K_nm chunk when it is written to LDS
-// (dcov_dlogls_from_k: no second exponential); the product W' = K' Linv^T gives the K_nm part of the lengthscale gradient as
-// sum W' o Wbar, and sum W o Wbar is the variance part (Kbar = Wbar Linv, so sum_m Kbar_nm K_nm = sum_j Wbar_nj W_nj): no
-// backward GEMM, no second pass over K_nm.  Z (solve precision, [M][D]) sits in the problem-owned LDS behind the tiles.
-template <typename T, typename TN, bool DERIV = false, int DD = 2> struct FwdWProb : NTXcdRowMap, NTNoExtra {
+template <typename T, typename TN> struct FwdWProb : NTXcdRowMap, NTNoExtra {
   using V = typename Vec16<T>::type;
   using AVec = V;
   static constexpr bool SCALE_A = false;
   static constexpr bool A_PER_REP = false;
-  static constexpr int DEPTH = (sizeof(T) == 8 && !DERIV) ? GDRF_FWDW_DEPTH : 1;
-  static constexpr int MIN_WGS = (sizeof(T) == 8 && !DERIV) ? GDRF_FWDW_WGS : 2;
-#ifdef GDRF_NT_TRACE
-  static constexpr bool TRACE = sizeof(T) == 8 && !DERIV;
-#endif
-#ifndef GDRF_NO_TRI
+  static constexpr int DEPTH = sizeof(T) == 8 ? GDRF_FWDW_DEPTH : 1;
+  static constexpr int MIN_WGS = sizeof(T) == 8 ? GDRF_FWDW_WGS : 2;
   static constexpr int TRI = 1;            // W[n][col] = sum_{k <= col} K_nm[n][k] Linv[col][k]
-#endif
   const T* Knm; int64_t nrows; int Mp;
   const T* Linv; TN* W; TN* qpart; int64_t ldq;      // qpart [col_tiles][ldq]
-  const TN* X = nullptr; const T* Z = nullptr; const Hyper* h = nullptr; int M = 0, D = 0, kind = 0;   // DERIV only
   void* Wh = nullptr; int64_t wh_stride = 0;          // optional: the 16-bit pieces of W (gemm_split.h), written by the same epilogue
   int wh_mode = 0; const float* wh_scale = nullptr;   // 1: three bf16 pieces; 2: two fp16 pieces of W * wh_scale[0]
-  struct ACtx { const T* p[NTCfg<T>::VPT]; T x[DERIV ? NTCfg<T>::VPT : 1][DD]; const T* zS; T ils2, al; };
+  struct ACtx { const T* p[NTCfg<T>::VPT]; };
   struct ECtx { T rs[4][4]; int ct; };
   __device__ __forceinline__ int col_tiles() const { return (Mp + NTCfg<T>::CW - 1) / NTCfg<T>::CW; }
   __device__ __forceinline__ bool loop_cols() const { return false; }
@@ -269,37 +257,14 @@ template <typename T, typename TN, bool DERIV = false, int DD = 2> struct FwdWPr
   __device__ __forceinline__ void krange(int64_t, int n0, int, int& kb, int& ke) const {
     kb = 0; ke = n0 + NTCfg<T>::CW; if (ke > Mp) ke = Mp;
   }
-  __device__ __forceinline__ void prepA(ACtx& c, int64_t m0, int, char* extra) const {
+  __device__ __forceinline__ void prepA(ACtx& c, int64_t m0, int, char*) const {
 #pragma unroll
     for (int i = 0; i < NTCfg<T>::VPT; ++i) {
       const int64_t r = m0 + nt_stage_row<T>(i);
       c.p[i] = (r < nrows) ? Knm + r * Mp : nullptr;
-      if constexpr (DERIV) {
-#pragma unroll
-        for (int d = 0; d < DD; ++d) c.x[i][d] = (r < nrows && d < D) ? (T)X[r * D + d] : T(0);
-      }
-    }
-    if constexpr (DERIV) {
-      T* zs = reinterpret_cast<T*>(extra);                  // [Mp][DD], zero beyond (M, D)
-      for (int e = threadIdx.x; e < Mp * DD; e += 256) { const int m = e / DD, d = e - m * DD; zs[e] = (m < M && d < D) ? Z[m * D + d] : T(0); }
-      c.zS = zs; c.ils2 = (T)h->inv_ls2; c.al = (T)h->alpha;
-      __syncthreads();
     }
   }
-  __device__ __forceinline__ V a_to_lds(const V& v, const ACtx& c, int i, int k) const {
-    if constexpr (!DERIV) return v;
-    else {
-      V o;
-#pragma unroll
-      for (int e = 0; e < Vec16<T>::N; ++e) {
-        T r2 = 0;
-#pragma unroll
-        for (int d = 0; d < DD; ++d) { const T t = c.x[i][d] - c.zS[(k + e) * DD + d]; r2 += t * t; }
-        o[e] = dcov_dlogls_from_k<T>(kind, v[e], r2 * c.ils2, c.al);
-      }
-      return o;
-    }
-  }
+  __device__ __forceinline__ V a_to_lds(const V& v, const ACtx&, int, int) const { return v; }
   __device__ __forceinline__ void prepE(ECtx& e, int64_t, int) const {
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -397,27 +362,6 @@ template <typename T, typename TN, bool DERIV = false, int DD = 2> struct FwdWPr
     }
   }
 };
-
-// sum_n,j Wbar[n][j] W[n][j] and sum Wbar[n][j] Wd[n][j] (per-workgroup partials [grid][2], deterministic order): the K_nm parts of the
-// variance / lengthscale gradients when W' = (dK_nm / d log ls) Linv^T is available (FwdWProb<.., DERIV>)
-template <typename T>
-__global__ __launch_bounds__(256) void wbar_dot_kernel(const T* __restrict__ Wbar, const T* __restrict__ W, const T* __restrict__ Wd, int64_t nrows,
-                                                       int Mp, double* __restrict__ part) {
-  using V = typename Vec16<T>::type;
-  constexpr int VE = Vec16<T>::N;
-  __shared__ double scratch[16];
-  const int64_t nvec = nrows * Mp / VE;                     // Mp is a multiple of 32; padded columns hold zeros
-  double s1 = 0, s2 = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
-    const V b = reinterpret_cast<const V*>(Wbar)[i], w = reinterpret_cast<const V*>(W)[i], d = reinterpret_cast<const V*>(Wd)[i];
-    T a1 = 0, a2 = 0;
-#pragma unroll
-    for (int e = 0; e < VE; ++e) { a1 += b[e] * w[e]; a2 += b[e] * d[e]; }
-    s1 += (double)a1; s2 += (double)a2;
-  }
-  const double t1 = block_sum(s1, scratch), t2 = block_sum(s2, scratch);
-  if (threadIdx.x == 0) { part[2 * (int64_t)blockIdx.x] = t1; part[2 * (int64_t)blockIdx.x + 1] = t2; }
-}
 
 // (1b) loc = W U^T on the matrix cores: Bt = zero-padded u_loc [128][Mp]; stores loc[k][n] for k < K
 // loc = W U^T for a handful of topics as a streaming pass over W (K <= LOC_KMAX): on the NT core the K columns are padded to a 128-wide
@@ -740,9 +684,7 @@ template <typename T> struct BwdWbarTProb : NTXcdPairMap, NTPlainA<T> {
 template <typename T, typename TN, bool LZ = false, bool ARD = false> struct BwdKnmProb : NTXcdRowMap, NTNoExtra {
   using V = typename Vec16<T>::type;
   static constexpr int MIN_WGS = (sizeof(T) == 8 && !LZ) ? 3 : 2;   // f64: three workgroups per CU hide each other's epilogues
-#ifndef GDRF_NO_TRI
   static constexpr int TRI = 2;            // Kbar[n][col] = sum_{k >= col} Wbar[n][k] LinvT[col][k]
-#endif
   static constexpr bool SCALE_A = false;
   static constexpr bool A_PER_REP = false;
   static constexpr int DEPTH = 1;
@@ -903,14 +845,12 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
   __device__ __forceinline__ void tile_done(Acc (&acc)[4][NB_], int64_t m0, int n0, int, ECtx& e, int wr, int wc, int lane) const {
     const T ils2 = (T)h->inv_ls2, al = (T)h->alpha;
     e.n0 = n0;
-#ifndef GDRF_BWDKNM_SCALAR_EPILOGUE
     if constexpr (sizeof(T) == 8 && !LZ) {
       if (D <= 2) {            // the reference's worlds are 1-D (time) or 2-D (space); more dimensions take the generic form below
         epi_f64<2>(acc, m0, n0, e, wr, wc, lane);
         return;
       }
     }
-#endif
     T z[4][GDRF_DMAX];
 #pragma unroll
     for (int b = 0; b < NTCfg<T>::NB; ++b) {
@@ -1009,13 +949,13 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
 // log-likelihood, both Normal site terms, and the row-local part of the backward.
 // One thread per row.  Each lane walks its own row of counts (V int32, contiguous) straight from global memory: the lanes of a wave are
 // V * 4 bytes apart, but every lane consumes whole lines over its V iterations, so the 200 MB stream is read once (0.87 ms at the
-// headline size); staging the workgroup's rows through LDS with whole-line 16-byte loads (WSTAGE) was measured SLOWER (1.1-1.5 ms: an
-// extra pass and barrier in a kernel that lives on occupancy), it is kept for A/B runs only.  KREG: K <= GDRF_KMAX, the per-topic values of a row live in registers; otherwise
+// headline size); staging the workgroup's rows through LDS with whole-line 16-byte loads was measured SLOWER (1.1-1.5 ms: an
+// extra pass and barrier in a kernel that lives on occupancy).  KREG: K <= GDRF_KMAX, the per-topic values of a row live in registers; otherwise
 // they are re-read from the (K, n) arrays (coalesced over the rows) and the softmax pull-back goes through LDS - any K.
 // =====================================================================================
 #define GDRF_KMAX 32
 
-template <typename T, bool KREG, bool WSTAGE = false>
+template <typename T, bool KREG>
 __global__ __launch_bounds__(128) void elbo_rows_kernel(
     int64_t nrows, int K, int V, const Hyper* __restrict__ h,
     const T* __restrict__ qpart, int nqpart, const T* __restrict__ loc, const T* __restrict__ tt, const T* __restrict__ eps,
@@ -1033,7 +973,6 @@ __global__ __launch_bounds__(128) void elbo_rows_kernel(
   T* thS = accS + K * V;                                // [RB][K+1]
   T* pbS = thS + RB * (K + 1);                          // [RB][V+1]
   T* tbS = pbS + RB * (V + 1);                          // [RB][K+1], !KREG only
-  T* wS = tbS + (KREG ? 0 : RB * (K + 1));              // [RB][V+1] the counts, WSTAGE only
   for (int e = threadIdx.x; e < K * V; e += RB) { phiS[e] = phi[e]; accS[e] = 0; }
   __syncthreads();
   const T var = (T)h->var, eta = (T)h->noise;
@@ -1046,23 +985,6 @@ __global__ __launch_bounds__(128) void elbo_rows_kernel(
     T* th = thS + threadIdx.x * (K + 1);
     T* pb = pbS + threadIdx.x * (V + 1);
     T* tbl = tbS + threadIdx.x * (K + 1);
-    const T* wrow = wS + threadIdx.x * (V + 1);
-    if constexpr (WSTAGE) {   // counts of this block's rows -> LDS (as T) with whole-line loads
-      const int64_t e0 = blk * RB * (int64_t)V;
-      int64_t cnt = (nrows - blk * RB < RB ? nrows - blk * RB : (int64_t)RB) * V;
-      const int32_t* src = ws + e0;
-      const int head = (int)((4 - (e0 & 3)) & 3);         // elements in front of the first 16-byte aligned one
-      for (int64_t e = threadIdx.x; e < head && e < cnt; e += RB) wS[(e / V) * (V + 1) + e % V] = (T)src[e];
-      typedef int i32x4 __attribute__((ext_vector_type(4)));
-      const int64_t nvec = cnt > head ? (cnt - head) >> 2 : 0;
-      for (int64_t q = threadIdx.x; q < nvec; q += RB) {
-        const i32x4 w4 = *reinterpret_cast<const i32x4*>(src + head + 4 * q);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int64_t e = head + 4 * q + j; wS[(e / V) * (V + 1) + e % V] = (T)w4[j]; }
-      }
-      for (int64_t e = head + 4 * nvec + threadIdx.x; e < cnt; e += RB) wS[(e / V) * (V + 1) + e % V] = (T)src[e];
-      __syncthreads();
-    }
     T v[KR], mu[KR], ep[KR];
     T a = 0, vd = 0;
     if (ok) {
@@ -1106,7 +1028,7 @@ __global__ __launch_bounds__(128) void elbo_rows_kernel(
       for (int vv = 0; vv < V; ++vv) {
         const T p = pb[vv];
         const T ph = p * ips;
-        const T wv = WSTAGE ? wrow[vv] : (T)ws[n * V + vv];
+        const T wv = (T)ws[n * V + vv];
         const bool inr = (ph > feps) && (ph < T(1) - feps);
         const T phc = fmin(fmax(ph, feps), T(1) - feps);
         llw += wv * t_log<T>(phc);

@@ -10,7 +10,6 @@ Reference behaviour mirrored here (paths under /root/reference):
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
 from typing import Dict, Optional
 
@@ -137,7 +136,7 @@ class Engine:
         self._guess_level: Optional[int] = None      # jitter level of the previous step: this step starts on it speculatively
         self._probe_stream = torch.cuda.Stream(device=self.device)
         self.speculate = True
-        self.prefactorize = os.environ.get("GDRF_PREFACTORIZE", "1") != "0"      # factorise for the next step right behind the optimizer update
+        self.prefactorize = True      # factorise for the next step right behind the optimizer update
         # a caller-supplied link (the reference's `link_function`, abstract_gdrf.py:34-50): a callable on the (K, n) tensor mu returning the
         # (K, n) topic weights; None = the softmax link fused into the row kernel.  Evaluated with torch between three library calls.
         self.link_function = None

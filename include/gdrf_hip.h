@@ -96,8 +96,8 @@ int gdrf_inducing_layout(const gdrf_ctx* ctx, int64_t out[2]);
  * wandb.config.kernel_lengthscale, gdrf/train_script.py:290-296).  With on = 1 the flat parameter vector grows by a segment of D
  * log-lengthscales (gdrf_ard_layout -> {offset, D}; {offset of the would-be segment, 0} when off), slot 0 is then unused (its gradient
  * is 0), red_d grows by D doubles at 8 + M*D (the per-axis K_nm sums, all-reduced with the rest), and every covariance evaluation uses the
- * per-axis scales.  Call it before reading gdrf_param_layout / gdrf_red_layout.  The opt-in hyper-gradient forms
- * (gdrf_set_hyper_backward(1), GDRF_WD_PATH=1) fall back to the default f64 form.  Default 0: the layouts are those of a context that
+ * per-axis scales.  Call it before reading gdrf_param_layout / gdrf_red_layout.  The opt-in hyper-gradient form
+ * (gdrf_set_hyper_backward(1)) falls back to the default f64 form.  Default 0: the layouts are those of a context that
  * never called it. */
 int gdrf_set_ard(gdrf_ctx* ctx, int on);
 int gdrf_ard_layout(const gdrf_ctx* ctx, int64_t out[2]);
