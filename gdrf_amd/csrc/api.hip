@@ -920,8 +920,8 @@ template <typename T, typename TS> struct Impl {
     if (mask & SL_ROWS) {
       ScopedTimer tm(c, 6, s);
       // matrix-core form (rows_mfma.h): 16 rows per wave, the three K x V products of a row block as 16x16x4 matrix instructions on
-      // register-resident operands; K <= 32, V <= 64.  The one-thread-per-row kernel serves the other sizes
-      if (K <= 32 && V <= 64) {
+      // register-resident operands; K <= 32, V <= 64 and 32-bit offsets.  The one-thread-per-row kernel serves the other sizes
+      if (K <= 32 && V <= 64 && rows_mfma_offsets_fit<T>(K, nct<TS>(c), ldk, n)) {
         const int nkt = K <= 16 ? 1 : 2, nvt = V <= 32 ? 2 : 4;
         const size_t lds = rows_mfma_lds<T>(K, V, nkt, nvt, 4);
         const int64_t groups = (n + 15) / 16;

@@ -39,6 +39,15 @@ template <typename T> static inline size_t rows_mfma_lds(int K, int V, int nkt, 
   return 128 + ((size_t)K * V + (size_t)waves * (16 * (16 * nkt + 1) + 16 * (16 * nvt + 1)) + (size_t)waves * K * V) * sizeof(T);
 }
 
+// The kernel addresses the [topic][ldk] arrays (loc, tt, vbar, locbar, mu; qpart as [chunk][ldk]) and eps ([topic][lde]) by a 32-bit BYTE
+// offset from the row group's first row: the largest one it forms, row max(K, nqpart) - 1 plus at most 15 rows, must not wrap.  The host
+// takes this form only when that holds; other sizes run the one-thread-per-row kernel, which indexes in 64 bits.
+template <typename T> static inline bool rows_mfma_offsets_fit(int K, int nqpart, int64_t ldk, int64_t lde) {
+  const uint64_t lim = (uint64_t)1 << 32, grp = 16 * sizeof(T);
+  const uint64_t top = (uint64_t)((K > nqpart ? K : nqpart) - 1);
+  return top * (uint64_t)ldk * sizeof(T) + grp < lim && (uint64_t)(K - 1) * (uint64_t)lde * sizeof(T) + grp < lim;
+}
+
 // element at a 32-bit BYTE offset from a wave-uniform base: global_load with the base in scalar registers and one offset register
 template <typename P> __device__ __forceinline__ P at_u32(const P* base, unsigned byte_off) {
   return *reinterpret_cast<const P*>(reinterpret_cast<const char*>(base) + byte_off);
@@ -98,7 +107,7 @@ __global__ __launch_bounds__(256) void elbo_rows_mfma_kernel(
   // every load of a group is unconditional, from clamped addresses (a load inside `if (row and topic valid)` costs its own branch and its
   // own wait: ~40 dependent round trips per group), and issued one group AHEAD: the next group's 30 values travel while this one computes
   // addressing: a wave-uniform base (the group's first row) in scalar registers + ONE 32-bit lane offset per own topic / word - the host
-  // routes sizes whose offsets would not fit 32 bits to the one-thread-per-row kernel
+  // routes sizes whose offsets would not fit 32 bits to the one-thread-per-row kernel (rows_mfma_offsets_fit)
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   unsigned otop[NKT][4], oeps[NKT][4], owrd[NVT][4];
 #pragma unroll
