@@ -54,6 +54,7 @@ SIGNATURES = {
     "gdrf_set_mean_guide": (_int, [_vp, _vp, _i64, _i64]),
     "gdrf_step_finish": (_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp]),
     "gdrf_adam": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _vp]),
+    "gdrf_optim_step": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdrf_predict": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "gdrf_chol_failed": (_int, [_vp, C.POINTER(_int), _vp]),
     "gdrf_ws_ptr": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_i64)]),
@@ -62,6 +63,14 @@ SIGNATURES = {
     "gdrf_set_timing": (_int, [_vp, _int]),
     "gdrf_get_timing": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_i64), _int]),
 }
+
+
+
+class OptSeg(C.Structure):
+    """gdrf_opt_seg of include/gdrf_hip.h: one parameter tensor of gdrf_optim_step and its scalars for this step."""
+    _fields_ = [("offset", _i64), ("length", _i64), ("clip_norm", _dbl), ("clip_value", _dbl), ("flags", C.c_int32),
+                ("reserved", C.c_int32), ("a", _dbl * 8)]
+
 
 ALLREDUCE_FN = C.CFUNCTYPE(_int, _vp, _i64, _int, _vp, _vp)       # gdrf_allreduce_fn of include/gdrf_hip.h
 

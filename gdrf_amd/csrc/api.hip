@@ -11,6 +11,7 @@
 #include "predict.h"
 #include "rows_mfma.h"
 #include "hyper_tn.h"
+#include "optim.h"
 
 #include <algorithm>
 #include <cmath>
@@ -90,6 +91,7 @@ struct gdrf_ctx {
   int learn_z; double* zpart; // learnable inducing inputs: per-row-tile partial sums [ceil(ncap/128)][M][D]
   int ard; void* Zp; double* apart;   // ARD (gdrf_set_ard): scaled inducing inputs in the N-side precision (probe, gdrf_knm); per-block sums of d / d log ls_d
   int64_t mean_count;         // trainable mean_function parameters (gdrf_set_mean_params): elements of their segment, 0 = none
+  double* opt_part; int64_t opt_part_cap;   // gdrf_optim_step: per-workgroup sums of squares of the clip_norm pass, allocated on first use
   std::vector<void*> allocs;
   // optional per-kernel HIP-event timing (gdrf_set_timing): events recorded on the launch stream
   int timing;
@@ -234,7 +236,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   c->lgam_const = 0; c->alpha_dev = nullptr; c->timing = 0;
   c->pK = c->pL = nullptr; c->Tst = nullptr; c->side = nullptr; c->Bh = c->STh = c->Wh = nullptr; c->split = 0; c->wh_pieces = 0; c->ssc = nullptr; c->smx = nullptr;
   c->ev_fork = c->ev_loc = c->ev_fork2 = c->ev_join = c->ev_fact0 = c->ev_fact = nullptr; c->fact_pending = 0; c->learn_z = 0; c->zpart = nullptr; c->ard = 0; c->Zp = nullptr; c->apart = nullptr; c->unwhitened = 0; c->mean = nullptr; c->mean_sk = c->mean_sn = 0;
-  c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0;
+  c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0; c->opt_part = nullptr; c->opt_part_cap = 0;
   c->mean_count = 0;
   for (int i = 0; i < GDRF_NSLOTS; ++i) { c->t_ms[i] = 0; c->t_cnt[i] = 0; }
   const size_t mm = (size_t)c->Mp * c->Mp * c->esz, mms = (size_t)c->Mp * c->Mp * c->ssz;
@@ -1567,6 +1569,69 @@ int gdrf_adam(gdrf_ctx* c, int mode, void* params, const void* grads, void* m, v
     hipLaunchKernelGGL(adam_kernel<double>, grid, dim3(256), 0, s, n, (double*)params, (const double*)grads, (double*)m, (double*)v, mode,
                        lr, b1, b2, eps, wd, clip, bc1, bc2, (const int*)c->flag);
   LAUNCHCHK("adam");
+  return 0;
+}
+
+int gdrf_optim_step(gdrf_ctx* c, int rule, const gdrf_opt_seg* segs, int nseg, void* params, const void* grads, void* s1, void* s2, void* s3,
+                    void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (rule < GDRF_ADAM || rule > GDRF_ADAGRAD_RMSPROP) return fail(-1, "gdrf_optim_step", "unknown rule");
+  if (nseg < 0 || (nseg > 0 && !segs)) return fail(-1, "gdrf_optim_step", "segment table");
+  if (!params || !grads || !s1 || !s2) return fail(-1, "gdrf_optim_step", "params, grads, s1 and s2 are required");
+  const int64_t total = poff(c, 6);
+  // every segment inside the vector, no two overlapping (an element is updated at most once)
+  std::vector<std::pair<int64_t, int64_t>> iv;
+  int64_t npart = 0;
+  for (int k = 0; k < nseg; ++k) {
+    const gdrf_opt_seg& g = segs[k];
+    if (g.offset < 0 || g.length < 0 || g.offset > total - g.length) return fail(-1, "gdrf_optim_step", "segment outside the parameter vector");
+    if ((g.flags & GDRF_OPT_CLIP_NORM) && !(g.clip_norm >= 0)) return fail(-1, "gdrf_optim_step", "clip_norm must be >= 0");
+    if ((g.flags & GDRF_OPT_CLIP_VALUE) && !(g.clip_value >= 0)) return fail(-1, "gdrf_optim_step", "clip_value must be >= 0");
+    if (rule == GDRF_RMSPROP && (g.flags & GDRF_OPT_MOMENTUM) && (g.flags & GDRF_OPT_CENTERED) && !s3)
+      return fail(-1, "gdrf_optim_step", "RMSprop with momentum and centered needs s3");
+    if (g.length) iv.push_back({g.offset, g.length});
+    if (g.flags & GDRF_OPT_CLIP_NORM) npart += (g.length + OPT_NRM - 1) / OPT_NRM;
+  }
+  std::sort(iv.begin(), iv.end());
+  for (size_t k = 1; k < iv.size(); ++k)
+    if (iv[k - 1].first + iv[k - 1].second > iv[k].first) return fail(-1, "gdrf_optim_step", "segments overlap");
+  if (npart > c->opt_part_cap) {                 // first use (the partials of all segments of a call fit; chunks reuse the buffer)
+    void* pw = nullptr;
+    const int64_t cap = total / OPT_NRM + nseg + 1;
+    hipError_t e = hipMalloc(&pw, (size_t)cap * sizeof(double));
+    if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(opt_part)", hipGetErrorString(e));
+    c->allocs.push_back(pw);
+    c->opt_part = (double*)pw; c->opt_part_cap = cap;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer tm(c, 14, s);
+  for (int k0 = 0; k0 < nseg; k0 += OPT_MAX_SEGS) {
+    OptTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    tab.nseg = std::min(OPT_MAX_SEGS, nseg - k0);
+    int64_t ub = 0, nb = 0;
+    for (int k = 0; k < tab.nseg; ++k) {
+      tab.seg[k] = segs[k0 + k];
+      tab.ub[k] = (int)ub; tab.nb[k] = (int)nb;
+      ub += (tab.seg[k].length + OPT_UPD - 1) / OPT_UPD;
+      if (tab.seg[k].flags & GDRF_OPT_CLIP_NORM) nb += (tab.seg[k].length + OPT_NRM - 1) / OPT_NRM;
+    }
+    tab.ub[tab.nseg] = (int)ub; tab.nb[tab.nseg] = (int)nb;
+    if (ub == 0) continue;
+    if (ub > INT32_MAX / 2) return fail(-1, "gdrf_optim_step", "segments too long");
+    if (c->esz == 4) {
+      if (nb) hipLaunchKernelGGL(opt_sumsq_kernel<float>, dim3((unsigned)nb), dim3(OPT_THREADS), 0, s, tab, (const float*)grads, c->opt_part,
+                                 (const int*)c->flag);
+      hipLaunchKernelGGL(opt_update_kernel<float>, dim3((unsigned)ub), dim3(OPT_THREADS), 0, s, tab, rule, (float*)params, (const float*)grads,
+                         (float*)s1, (float*)s2, (float*)s3, (const double*)c->opt_part, (const int*)c->flag);
+    } else {
+      if (nb) hipLaunchKernelGGL(opt_sumsq_kernel<double>, dim3((unsigned)nb), dim3(OPT_THREADS), 0, s, tab, (const double*)grads, c->opt_part,
+                                 (const int*)c->flag);
+      hipLaunchKernelGGL(opt_update_kernel<double>, dim3((unsigned)ub), dim3(OPT_THREADS), 0, s, tab, rule, (double*)params,
+                         (const double*)grads, (double*)s1, (double*)s2, (double*)s3, (const double*)c->opt_part, (const int*)c->flag);
+    }
+    LAUNCHCHK("optim_step");
+  }
   return 0;
 }
 

@@ -19,6 +19,10 @@ from . import _lib
 
 KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "rationalquadratic": 4}
 OPT_MODES = {"adam": 0, "adamw": 1, "clippedadam": 2}
+# update rules of gdrf_optim_step (include/gdrf_hip.h)
+OPT_RULES = {"adam": 0, "adamw": 1, "clippedadam": 2, "adamax": 3, "rmsprop": 4, "adagrad": 5, "adadelta": 6, "asgd": 7, "rprop": 8,
+             "adagradrmsprop": 9}
+OPT_CLIP_NORM, OPT_CLIP_VALUE, OPT_MOMENTUM, OPT_CENTERED = 1, 2, 4, 8
 
 _WS_IDS = dict(W=0, Wbar=1, q=2, loc=3, tt=4, vbar=5, locbar=6, asum=7, Kuu=8, L=9, Linv=10, S=11, B=12, phi=13,
                mu=14, LinvT=15, ST=16, Knm=17, g_locbar=18)
@@ -30,6 +34,8 @@ def _stream_ptr(device) -> int:
 
 class Engine:
     """One device context for fixed (n_cap, M, K, V, D, dtype, kernel)."""
+
+    opt_extra: Optional[torch.Tensor] = None     # third optimizer state vector (RMSprop with momentum and centered), on demand
 
     def __init__(self, n_cap: int, M: int, K: int, V: int, D: int, *, dtype=torch.float32, kernel: str = "rbf",
                  device="cuda:0", jitter: float = 1e-8, maxjitter: int = 15, process_group="auto", pure_fp32: bool = False,
@@ -126,6 +132,7 @@ class Engine:
         self.grads = z(lay[6], dtype)
         self.exp_avg = z(lay[6], dtype)
         self.exp_avg_sq = z(lay[6], dtype)
+        self.opt_extra = None
         self.red_T = z(red[4], dtype)
         self.red_d = z(red[5], torch.float64)
         self.out_d = z(8, torch.float64)
@@ -574,6 +581,40 @@ class Engine:
         _lib.check(self.lib.gdrf_adam(self.ctx, OPT_MODES[mode], self.params.data_ptr(), self.grads.data_ptr(),
                                       self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.opt_step, lr, betas[0], betas[1],
                                       eps, weight_decay, clip, _stream_ptr(self.device)), "gdrf_adam")
+        self._prefactorize()
+
+    def segments(self) -> Dict[str, tuple]:
+        """{name: (offset, length)} of every learnt parameter tensor in the flat vector (the segments of optim_step)."""
+        base, esz = self.params.data_ptr(), self.params.element_size()
+        return {n: ((v.data_ptr() - base) // esz, v.numel()) for n, v in self.named_views().items()}
+
+    def state_buffer(self, slot: int) -> torch.Tensor:
+        """Optimizer state vector 1 (exp_avg), 2 (exp_avg_sq) or 3 (opt_extra, allocated on first use)."""
+        if slot == 3 and self.opt_extra is None:
+            self.opt_extra = torch.zeros_like(self.params)
+        return (self.exp_avg, self.exp_avg_sq, self.opt_extra)[slot - 1]
+
+    def optim_step(self, rule: str, segs):
+        """One update of ``segs`` (gdrf_optim_step): a sequence of dicts {offset, length, a (up to 8 scalars of this step, include/gdrf_hip.h),
+        flags, clip_norm, clip_value}, one per parameter tensor.  The state vectors are exp_avg, exp_avg_sq and opt_extra; elements outside
+        every segment do not change.  Counts the step and queues the next factorisation like adam()."""
+        arr = (_lib.OptSeg * max(1, len(segs)))()
+        for k, sg in enumerate(segs):
+            e = arr[k]
+            e.offset, e.length = int(sg["offset"]), int(sg["length"])
+            e.flags = int(sg.get("flags", 0))
+            e.clip_norm, e.clip_value = float(sg.get("clip_norm", 0.0)), float(sg.get("clip_value", 0.0))
+            for j, x in enumerate(sg["a"]):
+                e.a[j] = float(x)
+        s3 = self.opt_extra.data_ptr() if self.opt_extra is not None else None
+        self.opt_step += 1
+        _lib.check(self.lib.gdrf_optim_step(self.ctx, OPT_RULES[rule], C.cast(arr, C.c_void_p), len(segs), self.params.data_ptr(),
+                                            self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), s3,
+                                            _stream_ptr(self.device)), "gdrf_optim_step")
+        self._prefactorize()
+
+    def _prefactorize(self):
+        """The next step's factorisation, queued right behind the optimizer update."""
         # The next step's factorisation depends only on what this update just wrote (kernel hyper-parameters, inducing inputs): start it now,
         # on the guessed jitter level, so that its serial chain runs while the host reads the loss and enqueues the step.  The step checks
         # on the device that the inputs are still the same (anything may write the parameters in between) and redoes itself otherwise.

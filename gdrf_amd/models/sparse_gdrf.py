@@ -280,6 +280,8 @@ class SparseMultinomialGDRF:
             self._init_params(new)
         else:                                   # grow the workspaces, keep parameters and optimizer state
             new.params.copy_(e.params); new.exp_avg.copy_(e.exp_avg); new.exp_avg_sq.copy_(e.exp_avg_sq)
+            if e.opt_extra is not None:
+                new.state_buffer(3).copy_(e.opt_extra)
             new.opt_step = e.opt_step
         self._engine = new
         self._inducing_points = new.Z

@@ -5,6 +5,9 @@ Logging to W&B, plots, checkpoints-to-disk and early stopping are outside this b
 the function returns what the loggers would have recorded.
 
 The keyword names are the reference's (``train_script.py:102-145``) for the options that reach the hot path.
+``optimizer_type`` names an entry of ``gdrf_amd.optim.OPTIMIZER_DICT``: "adam", "adamw", "clippedadam", "adamax", "rmsprop",
+"adagrad", "adadelta", "asgd" and "rprop" train; "adagradrmsprop" has no ``lr`` argument, so ``{"lr": optimizer_lr}`` is rejected with
+ValueError (the reference fails at its first step); "sgd", "sparseadam" and "dctadam" raise NotImplementedError.
 """
 from __future__ import annotations
 

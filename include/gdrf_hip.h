@@ -228,6 +228,33 @@ int gdrf_step_finish(gdrf_ctx* ctx, const void* Z_dev, const void* params_dev, c
 int gdrf_adam(gdrf_ctx* ctx, int mode, void* params_dev, const void* grads_dev, void* m_dev, void* v_dev, int64_t t,
               double lr, double beta1, double beta2, double eps, double weight_decay, double clip, void* stream);
 
+/* The pyro.optim rules of train_script.py:73-87 per named parameter tensor, with pyro's clip_args and per-parameter optim_args
+ * (PyroOptim keeps one torch optimizer per tensor).  A segment is one parameter tensor: elements [offset, offset + length) of the flat
+ * vector; elements outside every segment are not touched.  The caller computes each segment's scalars a[] in double for every step:
+ *   GDRF_ADAM, GDRF_ADAMW, GDRF_CLIPPED_ADAM  {lr, beta1, beta2, eps, weight_decay, clip, 1 - beta1^t, 1 - beta2^t}  (gdrf_adam's arithmetic)
+ *   GDRF_ADAMAX            {lr / (1 - beta1^t), beta1, beta2, eps, weight_decay}           s1 exp_avg, s2 exp_inf
+ *   GDRF_RMSPROP           {lr, alpha, eps, weight_decay, momentum}                        s2 square_avg, s1 momentum_buffer (flag MOMENTUM),
+ *                          grad_avg (flag CENTERED) in s3 when both flags are set, else in s1
+ *   GDRF_ADAGRAD           {lr / (1 + (t - 1) lr_decay), eps, weight_decay}                s2 sum
+ *   GDRF_ADADELTA          {lr, rho, eps, weight_decay}                                    s2 square_avg, s1 acc_delta
+ *   GDRF_ASGD              {eta, mu, lambd, weight_decay} (eta, mu: the values stored before this step)   s1 ax
+ *   GDRF_RPROP             {eta_minus, eta_plus, step_size_min, step_size_max}             s1 prev, s2 step_size
+ *   GDRF_ADAGRAD_RMSPROP   {eta t^(-1/2 + delta), t (the mixing rate), 1 at the first step else 0}   s2 sum
+ * Flag CLIP_NORM scales the segment's gradient by clip_norm / (|g|_2 + 1e-6) when that is below 1 (torch clip_grad_norm_), then
+ * CLIP_VALUE clamps it to +-clip_value (clip_grad_value_); the gradient buffer itself is not written.  Up to 24 segments take one launch
+ * (two with CLIP_NORM: a sum of squares per 8192 elements, summed in a fixed order - bitwise reproducible); more take one such pair per 24.
+ * s3 may be NULL unless an RMSprop segment sets both MOMENTUM and CENTERED.  Skipped on the device when the step's Cholesky failed. */
+enum { GDRF_ADAMAX = 3, GDRF_RMSPROP = 4, GDRF_ADAGRAD = 5, GDRF_ADADELTA = 6, GDRF_ASGD = 7, GDRF_RPROP = 8, GDRF_ADAGRAD_RMSPROP = 9 };
+enum { GDRF_OPT_CLIP_NORM = 1, GDRF_OPT_CLIP_VALUE = 2, GDRF_OPT_MOMENTUM = 4, GDRF_OPT_CENTERED = 8 };
+typedef struct gdrf_opt_seg {
+  int64_t offset, length;
+  double clip_norm, clip_value;
+  int32_t flags, reserved;
+  double a[8];
+} gdrf_opt_seg;
+int gdrf_optim_step(gdrf_ctx* ctx, int rule, const gdrf_opt_seg* segs_host, int nseg, void* params_dev, const void* grads_dev,
+                    void* s1_dev, void* s2_dev, void* s3_dev, void* stream);
+
 /* Predictive mean path: log_topic_probs / topic_probs / word_probs / perplexity
  * (gdrf/models/sparse_gdrf.py:161-186, abstract_gdrf.py:113-139).  mode 0: out (K,n) ;
  * 1: out (n,K) ; 2: out (n,V) ; 3: out_d_dev[0..1] = {sum w log p, sum w}.  Modes 0-3 never form the variance (the reference
@@ -253,7 +280,7 @@ int gdrf_ws_copy(gdrf_ctx* ctx, int which, void* dst_dev, int64_t nelem, void* s
 
 /* Per-kernel timing with HIP events recorded on the launch stream (off by default).  Slots:
  * 0 probe, 1 k_nm, 2 transforms+B_k, 3 fwd_w, 4 loc (W U^T), 5 fwd_t, 6 elbo_rows, 7 bwd_wbar,
- * 8 bwd_knm, 9 tn_sym (A_k), 10 tn_gt, 11 slab reductions, 12 ubar, 13 step_finish, 14 adam, 15 factorize.
+ * 8 bwd_knm, 9 tn_sym (A_k), 10 tn_gt, 11 slab reductions, 12 ubar, 13 step_finish, 14 adam / gdrf_optim_step, 15 factorize.
  * gdrf_get_timing synchronises on the recorded events and returns accumulated ms and counts. */
 int gdrf_set_timing(gdrf_ctx* ctx, int enable);
 int gdrf_get_timing(gdrf_ctx* ctx, double* ms_out, int64_t* count_out, int nslots);
