@@ -10,6 +10,7 @@
 #include "kernels_n.h"
 #include "predict.h"
 #include "rows_mfma.h"
+#include "rows_vstream.h"
 #include "hyper_tn.h"
 #include "optim.h"
 
@@ -92,6 +93,9 @@ struct gdrf_ctx {
   int ard; void* Zp; double* apart;   // ARD (gdrf_set_ard): scaled inducing inputs in the N-side precision (probe, gdrf_knm); per-block sums of d / d log ls_d
   int64_t mean_count;         // trainable mean_function parameters (gdrf_set_mean_params): elements of their segment, 0 = none
   double* opt_part; int64_t opt_part_cap;   // gdrf_optim_step: per-workgroup sums of squares of the clip_norm pass, allocated on first use
+  int rows_form;              // gdrf_set_rows_form: 0 the LDS row forms, 1 the vocabulary-streamed form (rows_vstream.h)
+  void *vs_tmp, *vs_part, *vs_cpart, *vs_rs;   // form 1, allocated on first use: (K, ldk) mubar / topic_probs, Phi-bar slots [vs_gcap][K*V],
+  int64_t vs_gcap;                             // link-constant slots [vs_gcap][K], row sums of Phi and their reduced constants [2][K]
   std::vector<void*> allocs;
   // optional per-kernel HIP-event timing (gdrf_set_timing): events recorded on the launch stream
   int timing;
@@ -238,6 +242,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   c->ev_fork = c->ev_loc = c->ev_fork2 = c->ev_join = c->ev_fact0 = c->ev_fact = nullptr; c->fact_pending = 0; c->learn_z = 0; c->zpart = nullptr; c->ard = 0; c->Zp = nullptr; c->apart = nullptr; c->unwhitened = 0; c->mean = nullptr; c->mean_sk = c->mean_sn = 0;
   c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0; c->opt_part = nullptr; c->opt_part_cap = 0;
   c->mean_count = 0;
+  c->rows_form = 0; c->vs_tmp = c->vs_part = c->vs_cpart = c->vs_rs = nullptr; c->vs_gcap = 0; c->phibar_part = nullptr;
   for (int i = 0; i < GDRF_NSLOTS; ++i) { c->t_ms[i] = 0; c->t_cnt[i] = 0; }
   const size_t mm = (size_t)c->Mp * c->Mp * c->esz, mms = (size_t)c->Mp * c->Mp * c->ssz;
   auto A = [&](void** p, size_t bytes) -> int {
@@ -282,8 +287,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   AL(c->hpart, (size_t)std::max(4096, c->Mp + 2048) * sizeof(double))
   c->ubar_blocks_cap = std::min<int64_t>(1025, (n_cap + 255) / 256);     // upper bound of ubar_blocks(n) over n <= n_cap
   AL(c->ubar_part, (size_t)c->ubar_blocks_cap * K * c->Mp * c->esz)
-  c->erows_grid_cap = 1024;
-  AL(c->phibar_part, (size_t)c->erows_grid_cap * K * V * c->esz)
+  c->erows_grid_cap = 1024;          // phibar_part ([erows_grid_cap][K*V]) is allocated by the first LDS-form row kernel that writes it
   const int64_t rtiles = (n_cap + GDRF_TILE - 1) / GDRF_TILE;
   // users: bwd_knm 3 per workgroup, kuu_bar_reduce 3 per inducing point, elbo_rows 4 per workgroup, predict / ll_const <= 2 x 2048
   c->dpart_len = std::max<int64_t>({((rtiles + 8) * ((c->Mp + 63) / 64) + 16) * 3, (int64_t)3 * c->Mp + 16, 4 * c->erows_grid_cap, (int64_t)8192});
@@ -458,6 +462,39 @@ int gdrf_set_hyper_backward(gdrf_ctx* c, int mode) {
   return 0;
 }
 int gdrf_get_hyper_backward(const gdrf_ctx* c) { return hyper_tn_on(c) ? 1 : 0; }
+int gdrf_set_rows_form(gdrf_ctx* c, int form) {
+  if (form != 0 && form != 1) return fail(-1, "gdrf_set_rows_form", "form must be 0 (the LDS row forms) or 1 (vocabulary-streamed)");
+  c->rows_form = form;
+  return 0;
+}
+int gdrf_get_rows_form(const gdrf_ctx* c) { return c->rows_form; }
+
+// the LDS row forms' Phi-bar partials, [erows_grid_cap][K*V]: allocated on the first launch that writes them
+static int phibar_part_ensure(gdrf_ctx* c) {
+  if (c->phibar_part) return 0;
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, (size_t)c->erows_grid_cap * c->K * c->V * c->esz);
+  if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(phibar_part)", hipGetErrorString(e));
+  c->phibar_part = p; c->allocs.push_back(p);
+  return 0;
+}
+// form 1 scratch on first use.  The grid of the streamed kernels is capped so that its Phi-bar slots take at most
+// max(256 MiB, 16 K V elements), never 1024 K V: vs_gcap = min(1024, max(16, 256 MiB / (K V esz)), ceil(n_cap / 64))
+static int vs_ensure(gdrf_ctx* c) {
+  if (c->vs_part) return 0;
+  const size_t kv = (size_t)c->K * c->V * c->esz;
+  c->vs_gcap = std::min<int64_t>({(int64_t)1024, std::max<int64_t>(16, (int64_t)((size_t)256 << 20) / (int64_t)kv), (c->ncap + 63) / 64});
+  void** ps[] = {&c->vs_tmp, &c->vs_cpart, &c->vs_rs, &c->vs_part};
+  const size_t sz[] = {(size_t)c->K * c->ldk * c->esz, (size_t)c->vs_gcap * c->K * c->esz, (size_t)2 * c->K * c->esz, (size_t)c->vs_gcap * kv};
+  for (int i = 0; i < 4; ++i) {
+    if (*ps[i]) continue;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, sz[i]);
+    if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(streamed row form scratch)", hipGetErrorString(e));
+    *ps[i] = p; c->allocs.push_back(p);
+  }
+  return 0;
+}
 int gdrf_ws_elem_size(gdrf_ctx* c, int which) { void* p; int64_t n; int e; return ws_lookup(c, which, &p, &n, &e) ? -1 : e; }
 
 int gdrf_set_timing(gdrf_ctx* c, int enable) {
@@ -821,6 +858,49 @@ template <typename T, typename TS> struct Impl {
     return 0;
   }
 
+  // ---- the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_vstream.h) ----
+  static int vs_grid(const gdrf_ctx* c, int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, c->vs_gcap)); }
+  template <int MODE>
+  static int vs_launch(gdrf_ctx* c, int64_t n, int grid, const T* src, int64_t sk, int64_t sn, const int32_t* ws, T* dst, int64_t dld,
+                       double* dpart, int dacc, hipStream_t s) {
+    const size_t lds = vs_lds<T>(c->K);
+    auto go = [&](auto kern) -> int {
+      if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, n, c->K, c->V, src, sk, sn, ws, (const T*)P(c->phi), (const T*)c->vs_rs, dst, dld,
+                         dpart, dacc, (T*)c->vs_part, (T*)c->vs_cpart);
+      return 0;
+    };
+    int rc;
+    if constexpr (MODE == VS_SOFTMAX || MODE == VS_LINK) rc = c->K <= 32 ? go(rows_vstream_kernel<T, MODE, 8>) : go(rows_vstream_kernel<T, MODE, 32>);
+    else rc = go(rows_vstream_kernel<T, MODE, 1>);
+    if (rc) return rc;
+    LAUNCHCHK("rows_vstream");
+    return 0;
+  }
+  // the V-free phases 0 / 2 of elbo_rows_link_kernel (no Phi in LDS) on the streamed form's grid
+  static void vs_link_phase(gdrf_ctx* c, int phase, int64_t n, int grid, const T* eps, const int32_t* ws, const T* qpart, const T* loc,
+                            const T* tt, const T* mean, int64_t msk, int64_t msn, const T* ext, int64_t ext_ld, hipStream_t s) {
+    hipLaunchKernelGGL(elbo_rows_link_kernel<T>, dim3(grid), dim3(64), 128, s, phase, n, c->K, c->V, c->hyp, qpart, nct<TS>(c), loc, tt, eps,
+                       c->ldk, n, ws, P(c->phi), mean, msk, msn, ext, ext_ld, P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart,
+                       (T*)nullptr);
+  }
+  // gdrf_step_local's row terms in form 1: q, mu (link phase 0) ; Phi row sums ; theta = softmax(mu) through the streamed likelihood
+  // -> mubar ; the Normal sites and the row-local backward (link phase 2 with ext = mubar) ; reductions
+  static int rows_streamed(gdrf_ctx* c, const int32_t* ws, const T* eps, int64_t n, T* redT, double* redd, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    if (int rc = vs_ensure(c)) return rc;
+    const int G = vs_grid(c, n);
+    vs_link_phase(c, 0, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), (const T*)c->mean, c->mean_sk, c->mean_sn, nullptr, 0, s);
+    hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, (T*)c->vs_rs);
+    if (int rc = vs_launch<VS_SOFTMAX>(c, n, G, P(c->mu), c->ldk, 1, ws, (T*)c->vs_tmp, c->ldk, c->dpart, 0, s)) return rc;
+    vs_link_phase(c, 2, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), nullptr, 0, 0, (const T*)c->vs_tmp, c->ldk, s);
+    LAUNCHCHK("elbo_rows (streamed)");
+    hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
+    hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, (const T*)c->vs_part, (int64_t)G,
+                       (int64_t)K * V, redT + roff(c, 1));
+    return 0;
+  }
+
   // parts of one evaluation: the parameter transforms, the forward over the rows (K_nm, W, loc, tt), the per-row terms, the backward
   // over the rows.  gdrf_step_local runs them all; the two-point evaluation (step_local2: guide and model on different inputs) runs
   // them selectively.
@@ -881,8 +961,18 @@ template <typename T, typename TS> struct Impl {
         const int64_t blocks = std::min<int64_t>((n + 31) / 32, 256 * 8);
         hipLaunchKernelGGL(loc_rows_kernel<T>, dim3((unsigned)blocks), dim3(256), ulds, c->side, (const T*)P(c->W), n, Mp, K, (const T*)P(c->Upad), P(c->loc), ldk);
       } else {
-        LocProb<T> p{{}, {}, {}, P(c->W), n, Mp, K, P(c->Upad), P(c->loc), ldk};
-        hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T>>), dim3((unsigned)rtiles), dim3(256), C::LDS_BYTES, c->side, p);
+        bool wide = false;
+        if constexpr (sizeof(T) == 8) {
+          if (K > C::CW) {       // f64 with K > 64: two column tiles
+            LocProb<T, true> p{{}, {}, {}, P(c->W), n, Mp, K, P(c->Upad), P(c->loc), ldk};
+            hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T, true>>), dim3((unsigned)rtiles), dim3(256), C::LDS_BYTES, c->side, p);
+            wide = true;
+          }
+        }
+        if (!wide) {
+          LocProb<T> p{{}, {}, {}, P(c->W), n, Mp, K, P(c->Upad), P(c->loc), ldk};
+          hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T>>), dim3((unsigned)rtiles), dim3(256), C::LDS_BYTES, c->side, p);
+        }
       }
     }
     HIPCHK(hipEventRecord(c->ev_loc, c->side));
@@ -919,8 +1009,12 @@ template <typename T, typename TS> struct Impl {
     }
     // per-row ELBO terms and row-local backward
     int egrid;
-    if (mask & SL_ROWS) {
+    if ((mask & SL_ROWS) && c->rows_form == 1) {
       ScopedTimer tm(c, 6, s);
+      if (int rc = rows_streamed(c, ws, eps, n, redT, redd, s)) return rc;
+    } else if (mask & SL_ROWS) {
+      ScopedTimer tm(c, 6, s);
+      if (int rc = phibar_part_ensure(c)) return rc;
       // matrix-core form (rows_mfma.h): 16 rows per wave, the three K x V products of a row block as 16x16x4 matrix instructions on
       // register-resident operands; K <= 32, V <= 64 and 32-bit offsets.  The one-thread-per-row kernel serves the other sizes
       if (K <= 32 && V <= 64 && rows_mfma_offsets_fit<T>(K, nct<TS>(c), ldk, n)) {
@@ -945,7 +1039,8 @@ template <typename T, typename TS> struct Impl {
       const size_t lds = lds_for(RB);
       if (lds > 150 * 1024)
         return fail(-1, "gdrf_step_local", "num_topic_categories x num_observation_categories too large: the row kernel keeps the "
-                                           "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB)");
+                                           "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB); "
+                                           "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit");
       const void* kfn = kreg ? (const void*)elbo_rows_kernel<T, true> : (const void*)elbo_rows_kernel<T, false>;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       int64_t nblk = (n + RB - 1) / RB;
@@ -1182,11 +1277,31 @@ template <typename T, typename TS> struct Impl {
     HIPCHK(hipMemcpyAsync(c->g_tt, c->tt, (size_t)kn * c->esz, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->g_qpart, c->qpart, (size_t)nq * c->esz, hipMemcpyDeviceToDevice, s));
     if ((rc = step_local(c, Xm, ws, eps, n, Z, params, redT, redd, s, SL_FORWARD))) return rc;
-    {
+    if (c->rows_form == 1) {
+      // form 1: the guide-side mu (link phase 0 on the guide's arrays; its q is rewritten below), the streamed likelihood -> mubar, the
+      // two-point sites (V-free)
+      ScopedTimer tm(c, 6, s);
+      if ((rc = vs_ensure(c))) return rc;
+      const int G = vs_grid(c, n);
+      vs_link_phase(c, 0, n, G, eps, ws, (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, (const T*)c->mean_g, c->mean_g_sk,
+                    c->mean_g_sn, nullptr, 0, s);
+      hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, (T*)c->vs_rs);
+      if ((rc = vs_launch<VS_SOFTMAX>(c, n, G, P(c->mu), ldk, 1, ws, (T*)c->vs_tmp, ldk, c->dpart, 0, s))) return rc;
+      hipLaunchKernelGGL(elbo_rows2_sites_kernel<T>, dim3(G), dim3(64), 0, s, n, K, c->hyp, nct<TS>(c), P(c->qpart), P(c->loc), P(c->tt),
+                         (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, eps, ldk, n, (const T*)c->vs_tmp, (const T*)c->mean,
+                         c->mean_sk, c->mean_sn, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum),
+                         (T*)c->g_vbar, (T*)c->g_locbar, (T*)c->g_asum, P(c->mu), c->dpart);
+      LAUNCHCHK("elbo_rows2 (streamed)");
+      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
+      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, (const T*)c->vs_part, (int64_t)G,
+                         (int64_t)K * V, redT + roff(c, 1));
+    } else {
       ScopedTimer tm(c, 6, s);
       const int RB = 64;
       const size_t lds = 128 + ((size_t)2 * K * V + (size_t)2 * RB * (K + 1) + (size_t)RB * (V + 1)) * sizeof(T);
-      if (lds > 150 * 1024) return fail(-1, "gdrf_step_local2", "num_topic_categories x num_observation_categories too large for the row kernel's LDS");
+      if (lds > 150 * 1024) return fail(-1, "gdrf_step_local2", "num_topic_categories x num_observation_categories too large for the row kernel's LDS; "
+                                                                "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit");
+      if ((rc = phibar_part_ensure(c))) return rc;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)elbo_rows2_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const int egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
       hipLaunchKernelGGL(elbo_rows2_kernel<T>, dim3(egrid), dim3(RB), lds, s, n, K, V, c->hyp, nct<TS>(c), P(c->qpart), P(c->loc), P(c->tt),
@@ -1229,9 +1344,34 @@ template <typename T, typename TS> struct Impl {
     const int64_t ldk = c->ldk;
     int rc;
     if (phase == 0 && (rc = step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_TRANSFORMS | SL_FORWARD))) return rc;
+    if (c->rows_form == 1) {
+      // form 1: phases 0 and 2 are V-free; phase 1 is the streamed likelihood on ext = theta, thetabar -> locbar, its Phi-bar's constant
+      // part subtracted after the reduction
+      if ((rc = vs_ensure(c))) return rc;
+      const int G = vs_grid(c, n);
+      if (phase != 1) {
+        vs_link_phase(c, phase, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), (const T*)c->mean, c->mean_sk, c->mean_sn, ext, ext_ld, s);
+        LAUNCHCHK("elbo_rows_link (streamed)");
+        if (phase == 0) return 0;
+        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
+        return step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD);
+      }
+      T* rs = (T*)c->vs_rs;
+      hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, rs);
+      if ((rc = vs_launch<VS_LINK>(c, n, G, ext, ext_ld, 1, ws, P(c->locbar), ldk, c->dpart, 0, s))) return rc;
+      T* phib = redT + roff(c, 1);
+      const unsigned gkv = (unsigned)(((int64_t)K * V + 255) / 256);
+      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3(gkv), dim3(256), 0, s, (const T*)c->vs_part, (int64_t)G, (int64_t)K * V, phib);
+      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K + 255) / 256), dim3(256), 0, s, (const T*)c->vs_cpart, (int64_t)G, (int64_t)K, rs + K);
+      hipLaunchKernelGGL(vs_sub_rows_kernel<T>, dim3(gkv), dim3(256), 0, s, K, V, (const T*)(rs + K), phib);
+      LAUNCHCHK("elbo_rows_link (streamed)");
+      return 0;
+    }
     const int RB = 64;
     const size_t lds = 128 + ((size_t)2 * K * V + (size_t)RB * (K + 1) + (size_t)RB * (V + 1)) * sizeof(T);
-    if (lds > 150 * 1024) return fail(-1, "gdrf_step_local_link", "num_topic_categories x num_observation_categories too large for the row kernel's LDS");
+    if (lds > 150 * 1024) return fail(-1, "gdrf_step_local_link", "num_topic_categories x num_observation_categories too large for the row kernel's LDS; "
+                                                                  "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit");
+    if ((rc = phibar_part_ensure(c))) return rc;
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)elbo_rows_link_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
     hipLaunchKernelGGL(elbo_rows_link_kernel<T>, dim3(egrid), dim3(RB), lds, s, phase, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt),
@@ -1350,6 +1490,38 @@ template <typename T, typename TS> struct Impl {
       return 0;
     }
     if (mode >= 2) hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + poff(c, 4), K, V, P(c->phi));
+    if (c->rows_form == 1) {
+      // form 1: the any-K row kernel without Phi in LDS gives f_loc / topic_probs; for word_probs and perplexity it writes topic_probs of
+      // up to n_cap rows at a time into the form's scratch and the streamed product over Phi tiles (rows_vstream.h) finishes them
+      hipLaunchKernelGGL((predict_coeff_kernel<TS, T>), dim3((M + 127) / 128, K), dim3(128), 0, s, (const TS*)Q(c->Linv), U, M, Mp, K, Q(c->Cf));
+      const size_t lds = 128 + (size_t)M * c->D * sizeof(TS);
+      if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D solve-precision elements exceed the LDS budget (150 KB)");
+      auto kfn = c->ard ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
+      if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      auto rows = [&](const T* Xc, int64_t m, int md, T* o, int64_t ldo) {
+        int64_t blocks = (m + 127) / 128; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, Xc, m, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf),
+                           K, V, (const T*)P(c->phi), ws, md, o, ldo, c->dpart);
+      };
+      if (mode <= 1) {
+        rows(X, n, mode, out, mode == 0 ? n : K);
+        LAUNCHCHK("predict (streamed form)");
+        return 0;
+      }
+      if (int rc = vs_ensure(c)) return rc;
+      const int G = vs_grid(c, std::min<int64_t>(n, c->ncap));
+      for (int64_t off = 0; off < n; off += c->ncap) {
+        const int64_t m = std::min<int64_t>(c->ncap, n - off);
+        rows(X + off * c->D, m, 1, (T*)c->vs_tmp, K);
+        int rc;
+        if (mode == 2) rc = vs_launch<VS_WORDP>(c, m, G, (const T*)c->vs_tmp, 1, K, nullptr, out + off * V, V, nullptr, 0, s);
+        else rc = vs_launch<VS_PERP>(c, m, G, (const T*)c->vs_tmp, 1, K, ws + off * V, nullptr, 0, c->dpart, off > 0, s);
+        if (rc) return rc;
+      }
+      if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 2, out_d);
+      LAUNCHCHK("predict (streamed form)");
+      return 0;
+    }
     {
       // matrix-core form (predict.h): a wave owns 16 rows, one covariance value per lane and step is the A operand of the 16x16x4
       // matrix instruction, the padded transposed coefficients CfT its B operand.  K <= 32, the scaled inducing inputs in LDS.

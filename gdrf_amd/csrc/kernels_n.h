@@ -408,7 +408,8 @@ __global__ __launch_bounds__(256) void loc_rows_kernel(const T* __restrict__ W, 
   }
 }
 
-template <typename T> struct LocProb : NTDefaultMap, NTPlainA<T>, NTNoExtra {
+// WIDE: K wider than one column tile (f64, K > 64): the row tile's workgroup walks ceil(K / CW) column tiles
+template <typename T, bool WIDE = false> struct LocProb : NTDefaultMap, NTPlainA<T>, NTNoExtra {
   using V = typename Vec16<T>::type;
   static constexpr bool SCALE_A = false;
   static constexpr bool A_PER_REP = false;
@@ -417,8 +418,8 @@ template <typename T> struct LocProb : NTDefaultMap, NTPlainA<T>, NTNoExtra {
   const T* Upad; T* loc; int64_t ldk;
   struct ACtx { const T* p[NTCfg<T>::VPT]; };
   struct ECtx {};
-  __device__ __forceinline__ int col_tiles() const { return 1; }
-  __device__ __forceinline__ bool loop_cols() const { return false; }
+  __device__ __forceinline__ int col_tiles() const { return WIDE ? (K + NTCfg<T>::CW - 1) / NTCfg<T>::CW : 1; }
+  __device__ __forceinline__ bool loop_cols() const { return WIDE; }
   __device__ __forceinline__ int a_reuse() const { return 1; }
   __device__ __forceinline__ void krange(int64_t, int, int, int& kb, int& ke) const { kb = 0; ke = Mp; }
   __device__ __forceinline__ void prepA(ACtx& c, int64_t m0, int, char*) const {
@@ -432,11 +433,11 @@ template <typename T> struct LocProb : NTDefaultMap, NTPlainA<T>, NTNoExtra {
   __device__ __forceinline__ V loadA(const ACtx& c, int i, int k, int, int) const {
     return c.p[i] ? *reinterpret_cast<const V*>(c.p[i] + k) : vzero<T>();
   }
-  __device__ __forceinline__ V loadB(int, int i, int k, int, int) const {
-    return *reinterpret_cast<const V*>(Upad + (int64_t)nt_stage_row<T>(i) * Mp + k);
+  __device__ __forceinline__ V loadB(int n0, int i, int k, int, int) const {
+    return *reinterpret_cast<const V*>(Upad + (int64_t)((WIDE ? n0 : 0) + nt_stage_row<T>(i)) * Mp + k);
   }
   template <class Acc, int NB_>
-  __device__ __forceinline__ void tile_done(Acc (&acc)[4][NB_], int64_t m0, int, int, ECtx&, int wr, int wc, int lane) const {
+  __device__ __forceinline__ void tile_done(Acc (&acc)[4][NB_], int64_t m0, int n0, int, ECtx&, int wr, int wc, int lane) const {
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -445,7 +446,7 @@ template <typename T> struct LocProb : NTDefaultMap, NTPlainA<T>, NTNoExtra {
         if (m >= nrows) continue;
 #pragma unroll
         for (int b = 0; b < NTCfg<T>::NB; ++b) {
-          const int k = nt_acc_col<T>(wc, b, lane);
+          const int k = (WIDE ? n0 : 0) + nt_acc_col<T>(wc, b, lane);
           if (k < K) loc[(int64_t)k * ldk + m] = acc[a][b][r];
         }
       }
@@ -1247,6 +1248,28 @@ __global__ __launch_bounds__(64) void elbo_rows_link_kernel(
 // s_m = v_m + noise, d = mu - loc_m (- the model-side mean).  With mub the pull-back of the likelihood through the softmax link:
 //   locbar_g = mub - d / s_m^2 ;  vbar_g = locbar_g eps + 1 / v_g ;  locbar_m = d / s_m^2 ;  vbar_m = -1 / s_m + d^2 / s_m^3 (= d/d noise)
 // (for identical inputs their sums are the single-point formulas of elbo_rows_kernel).  One thread per row, any K; not a hot path.
+// the model- and guide-side terms of topic k of a row, given mub (the likelihood's pull-back through the softmax link): shared by
+// elbo_rows2_kernel and the streamed form's V-free elbo_rows2_sites_kernel
+template <typename T>
+__device__ __forceinline__ void rows2_topic(int k, int64_t n, T mu, T vg, T ek, T mub, T v0m, T eta, int64_t ldk,
+                                            const T* __restrict__ tt_m, const T* __restrict__ loc_m,
+                                            const T* __restrict__ mean_m, int64_t mm_sk, int64_t mm_sn,
+                                            T* __restrict__ vbar_m, T* __restrict__ locbar_m, T* __restrict__ vbar_g, T* __restrict__ locbar_g,
+                                            T* __restrict__ mu_out, T& site, T& ng, T& vsm, T& vsg) {
+  const T vm = v0m + tt_m[(int64_t)k * ldk + n], sm = vm + eta;
+  T lm = loc_m[(int64_t)k * ldk + n];
+  if (mean_m) lm += mean_m[(int64_t)k * mm_sk + n * mm_sn];
+  const T d = mu - lm;
+  site += -t_log<T>(sm) - T(0.5) * (d / sm) * (d / sm) + t_log<T>(vg) + T(0.5) * ek * ek;
+  const T lbm = d / (sm * sm), vbm = -T(1) / sm + d * d / (sm * sm * sm);
+  const T lbg = mub - lbm, vbg = lbg * ek + T(1) / vg;
+  ng += vbm;
+  vbar_m[(int64_t)k * ldk + n] = vbm; locbar_m[(int64_t)k * ldk + n] = lbm;
+  vbar_g[(int64_t)k * ldk + n] = vbg; locbar_g[(int64_t)k * ldk + n] = lbg;
+  if (mu_out) mu_out[(int64_t)k * ldk + n] = mu;
+  vsm += vbm; vsg += vbg;
+}
+
 template <typename T>
 __global__ __launch_bounds__(64) void elbo_rows2_kernel(
     int64_t nrows, int K, int V, const Hyper* __restrict__ h, int nqpart,
@@ -1320,18 +1343,8 @@ __global__ __launch_bounds__(64) void elbo_rows2_kernel(
       for (int k = 0; k < K; ++k) {
         T vg, ek;
         const T mu = mu_of(k, vg, ek);
-        const T vm = v0m + tt_m[(int64_t)k * ldk + n], sm = vm + eta;
-        T lm = loc_m[(int64_t)k * ldk + n];
-        if (mean_m) lm += mean_m[(int64_t)k * mm_sk + n * mm_sn];
-        const T d = mu - lm, mub = th[k] * ((tb[k] - cref) + dot);
-        site += -t_log<T>(sm) - T(0.5) * (d / sm) * (d / sm) + t_log<T>(vg) + T(0.5) * ek * ek;
-        const T lbm = d / (sm * sm), vbm = -T(1) / sm + d * d / (sm * sm * sm);
-        const T lbg = mub - lbm, vbg = lbg * ek + T(1) / vg;
-        ng += vbm;
-        vbar_m[(int64_t)k * ldk + n] = vbm; locbar_m[(int64_t)k * ldk + n] = lbm;
-        vbar_g[(int64_t)k * ldk + n] = vbg; locbar_g[(int64_t)k * ldk + n] = lbg;
-        if (mu_out) mu_out[(int64_t)k * ldk + n] = mu;
-        vsm += vbm; vsg += vbg;
+        rows2_topic<T>(k, n, mu, vg, ek, th[k] * ((tb[k] - cref) + dot), v0m, eta, ldk, tt_m, loc_m, mean_m, mm_sk, mm_sn,
+                       vbar_m, locbar_m, vbar_g, locbar_g, mu_out, site, ng, vsm, vsg);
       }
       asum_m[n] = am * vsm; asum_g[n] = ag * vsg;
       s_site += (double)site; s_noise += (double)ng; s_vd += (double)(am * vsm + ag * vsg);
@@ -1355,6 +1368,45 @@ __global__ __launch_bounds__(64) void elbo_rows2_kernel(
     dpart[4 * (int64_t)blockIdx.x + 2] = b2; dpart[4 * (int64_t)blockIdx.x + 3] = b3;
   }
   for (int e = threadIdx.x; e < K * V; e += RB) phibar_part[(int64_t)blockIdx.x * K * V + e] = accS[e];
+}
+
+// The V-free part of elbo_rows2_kernel for the vocabulary-streamed form (rows_vstream.h): mub (K, ldk) comes from the streamed kernel,
+// which took theta from the guide-side mu (phase 0 of elbo_rows_link_kernel on the guide's arrays).  Writes slots 0, 2, 3 of dpart; the
+// streamed kernel writes slot 1 on the same grid.  One thread per row, any K.
+template <typename T>
+__global__ __launch_bounds__(64) void elbo_rows2_sites_kernel(
+    int64_t nrows, int K, const Hyper* __restrict__ h, int nqpart,
+    const T* __restrict__ qpart_m, const T* __restrict__ loc_m, const T* __restrict__ tt_m,
+    const T* __restrict__ qpart_g, const T* __restrict__ loc_g, const T* __restrict__ tt_g,
+    const T* __restrict__ eps, int64_t ldk, int64_t lde, const T* __restrict__ mub,
+    const T* __restrict__ mean_m, int64_t mm_sk, int64_t mm_sn, const T* __restrict__ mean_g, int64_t mg_sk, int64_t mg_sn,
+    T* __restrict__ qout, T* __restrict__ vbar_m, T* __restrict__ locbar_m, T* __restrict__ asum_m,
+    T* __restrict__ vbar_g, T* __restrict__ locbar_g, T* __restrict__ asum_g, T* __restrict__ mu_out, double* __restrict__ dpart /*[grid][4]*/) {
+  __shared__ double scratch[16];
+  const T var = (T)h->var, eta = (T)h->noise;
+  double s_site = 0, s_noise = 0, s_vd = 0;
+  for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < nrows; n += (int64_t)gridDim.x * blockDim.x) {
+    T qm = 0, qg = 0;
+    for (int c = 0; c < nqpart; ++c) { qm += qpart_m[(int64_t)c * ldk + n]; qg += qpart_g[(int64_t)c * ldk + n]; }
+    qout[n] = qm;
+    const T am = (var - qm > T(0)) ? T(1) : T(0), ag = (var - qg > T(0)) ? T(1) : T(0);
+    const T v0m = am * (var - qm), v0g = ag * (var - qg);
+    T site = 0, ng = 0, vsm = 0, vsg = 0;
+    for (int k = 0; k < K; ++k) {
+      const T ek = eps[(int64_t)k * lde + n];
+      const T vg = v0g + tt_g[(int64_t)k * ldk + n];
+      T mu = loc_g[(int64_t)k * ldk + n] + vg * ek;
+      if (mean_g) mu += mean_g[(int64_t)k * mg_sk + n * mg_sn];
+      rows2_topic<T>(k, n, mu, vg, ek, mub[(int64_t)k * ldk + n], v0m, eta, ldk, tt_m, loc_m, mean_m, mm_sk, mm_sn,
+                     vbar_m, locbar_m, vbar_g, locbar_g, mu_out, site, ng, vsm, vsg);
+    }
+    asum_m[n] = am * vsm; asum_g[n] = ag * vsg;
+    s_site += (double)site; s_noise += (double)ng; s_vd += (double)(am * vsm + ag * vsg);
+  }
+  const double b0 = block_sum(s_site, scratch), b2 = block_sum(s_noise, scratch), b3 = block_sum(s_vd, scratch);
+  if (threadIdx.x == 0) {
+    dpart[4 * (int64_t)blockIdx.x + 0] = b0; dpart[4 * (int64_t)blockIdx.x + 2] = b2; dpart[4 * (int64_t)blockIdx.x + 3] = b3;
+  }
 }
 
 // y[i] += x[i]

@@ -40,7 +40,8 @@ class Engine:
     def __init__(self, n_cap: int, M: int, K: int, V: int, D: int, *, dtype=torch.float32, kernel: str = "rbf",
                  device="cuda:0", jitter: float = 1e-8, maxjitter: int = 15, process_group="auto", pure_fp32: bool = False,
                  store_t="auto", mfma_mode: str = "auto", learn_inducing: bool = False, whiten: bool = True,
-                 hyper_backward: str = "auto", allreduce_fn=None, ard: bool = False, mean_params: Optional[Dict[str, tuple]] = None):
+                 hyper_backward: str = "auto", allreduce_fn=None, ard: bool = False, mean_params: Optional[Dict[str, tuple]] = None,
+                 rows_form: str = "auto"):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.GdrfHipError("gdrf_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
@@ -82,6 +83,12 @@ class Engine:
             raise ValueError("hyper_backward must be 'auto', 'tn' or 'f64'")
         _lib.check(self.lib.gdrf_set_hyper_backward(self.ctx, 1 if hyper_backward == "tn" else 0), "gdrf_set_hyper_backward")
         self._hyper_backward_request = hyper_backward
+        # the per-row terms that touch the vocabulary (gdrf_set_rows_form): "auto" = the LDS row forms (Phi and its gradient in LDS; K x V
+        # bounded, larger shapes fail with "too large"); "streamed" = Phi through LDS in tiles of words, any V and K <= 128 (csrc/rows_vstream.h)
+        if rows_form not in ("auto", "streamed"):
+            raise ValueError("rows_form must be 'auto' or 'streamed'")
+        if rows_form == "streamed":
+            _lib.check(self.lib.gdrf_set_rows_form(self.ctx, 1), "gdrf_set_rows_form")
         # a caller-owned collective behind the C ABI (gdrf_set_allreduce): fn(buf_ptr, count, is_double, stream_ptr) -> 0 sums the flat payload in
         # place over the caller's ranks (e.g. a ctypes wrapper of ncclAllReduce on its RCCL communicator); None = torch.distributed (default)
         self._allreduce_cb = None
@@ -170,6 +177,11 @@ class Engine:
     def hyper_backward(self) -> str:
         """The form the next step uses ("tn" needs f16x3, fixed inducing inputs, an isotropic kernel other than RationalQuadratic)."""
         return "tn" if self.lib.gdrf_get_hyper_backward(self.ctx) else "f64"
+
+    @property
+    def rows_form(self) -> str:
+        """The row form the steps and gdrf_predict use: "auto" (LDS forms) or "streamed"."""
+        return "streamed" if self.lib.gdrf_get_rows_form(self.ctx) == 1 else "auto"
 
     def __del__(self):
         try:

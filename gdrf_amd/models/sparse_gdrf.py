@@ -137,7 +137,8 @@ class ModelSnapshot:
             fixed_inducing_points=bool(m["fixed_inducing_points"]), inducing_points=torch.as_tensor(m["inducing_points"]),
             mean_function=mean_function, link_function=link_function, noise=1.0, device=device or m["device"],
             whiten=bool(m["whiten"]), jitter=float(m["jitter"]), maxjitter=int(m["maxjitter"]), dtype=dtype,
-            pure_fp32=bool(m["pure_fp32"]), mfma_mode=m["mfma_mode"], seed=int(m["seed"]), guide_rescale=bool(m["guide_rescale"]))
+            pure_fp32=bool(m["pure_fp32"]), mfma_mode=m["mfma_mode"], seed=int(m["seed"]), guide_rescale=bool(m["guide_rescale"]),
+            rows_form=m.get("rows_form", "auto"))
         keys = {_PARAM_KEYS.get(n, n) for n in model._param_names()}
         model.load_state_dict({k: v.to(dtype) for k, v in self._state.items() if k in keys or not k.startswith(MEAN_PREFIX)})
         if device is None and mean_function is None and link_function is None:
@@ -182,6 +183,7 @@ class SparseMultinomialGDRF:
         pure_fp32: bool = False,
         mfma_mode: str = "auto",
         hyper_backward: str = "auto",
+        rows_form: str = "auto",
         inducing_points: Optional[torch.Tensor] = None,
         seed: Optional[int] = None,
         guide_rescale: bool = True,
@@ -224,6 +226,9 @@ class SparseMultinomialGDRF:
         self._pure_fp32 = bool(pure_fp32)
         self._mfma_mode = mfma_mode          # Engine(mfma_mode=...): "auto" | "f32" | "bf16x6" | "f16x3"
         self._hyper_backward = hyper_backward   # Engine(hyper_backward=...): "auto" | "tn" | "f64" (csrc/hyper_tn.h)
+        if rows_form not in ("auto", "streamed"):
+            raise ValueError("rows_form must be 'auto' or 'streamed'")
+        self._rows_form = rows_form          # Engine(rows_form=...): "auto" (LDS row forms) | "streamed" (any V, csrc/rows_vstream.h)
         self._kernel = kernel
         if kernel.input_dim != self._n_dims:
             raise ValueError("kernel.input_dim does not match the world's dimensionality")
@@ -271,7 +276,8 @@ class SparseMultinomialGDRF:
         new = Engine(n, self.M, self._K, self._V, self.D, dtype=self.dtype, kernel=self._kernel.name, device=self.device,
                      jitter=self._jitter, maxjitter=self._maxjitter, pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode,
                      learn_inducing=not self._fixed_inducing_points, whiten=self._whiten, hyper_backward=self._hyper_backward,
-                     ard=self._kernel.ard, mean_params={n: tuple(p.shape) for n, p in self._mean_params})
+                     ard=self._kernel.ard, mean_params={n: tuple(p.shape) for n, p in self._mean_params},
+                     rows_form=self._rows_form)
         new.set_inducing_points(self._inducing_points)
         new.set_dirichlet(self._dirichlet_param)
         new.link_function = self._link_function
@@ -566,5 +572,5 @@ class SparseMultinomialGDRF:
                     jitter=self._jitter, maxjitter=self._maxjitter, dirichlet_param=self._dirichlet_param.detach().cpu().clone(),
                     inducing_points=self._engine.Z.detach().cpu().clone(), dtype=str(self.dtype).replace("torch.", ""),
                     device=str(self.device), pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode, seed=self.rng_seed,
-                    guide_rescale=self._guide_rescale)
+                    guide_rescale=self._guide_rescale, rows_form=self._rows_form)
         return ModelSnapshot(self.state_dict(), meta)

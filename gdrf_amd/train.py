@@ -83,7 +83,7 @@ def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Op
           objective_type: str = "graphelbo", objective_num_particles: int = 1, streaming_inference: str = "",
           streaming_weight: float = 0.1, streaming_exp: float = 1.0, streaming_truncate: int = -1, streaming_size: int = 1,
           streaming_subepochs: int = 1, streaming_batch_splits: int = -1, randomize_wt_matrix: bool = False, seed: int = 1,
-          dtype: torch.dtype = torch.float32, perplexity_every: int = 1) -> Dict[str, object]:
+          dtype: torch.dtype = torch.float32, perplexity_every: int = 1, rows_form: str = "auto") -> Dict[str, object]:
     kernel_ls = kernel_lengthscale_arg(kernel_lengthscale, dimensions)
     if data is not None:
         xs, ws = load_csv(data, dimensions)
@@ -107,7 +107,7 @@ def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Op
         xs=xs_t, ws=ws_t, world=world, kernel=kernel, num_observation_categories=ws_t.shape[1], device=device,
         num_topic_categories=num_topics, dirichlet_param=dirichlet_param, n_points=num_inducing_points,
         fixed_inducing_points=fixed_inducing_points, inducing_init=inducing_initialization_method, maxjitter=max_jitter,
-        jitter=jitter, randomize_wt_matrix=randomize_wt_matrix, dtype=dtype, seed=seed)
+        jitter=jitter, randomize_wt_matrix=randomize_wt_matrix, dtype=dtype, seed=seed, rows_form=rows_form)
     optimizer = OPTIMIZER_DICT[optimizer_type]({"lr": optimizer_lr})
     objective = OBJECTIVE_DICT[objective_type](max_plate_nesting=1, vectorize_particles=True, num_particles=objective_num_particles)
     scale = poutine.scale(scale=1.0 / len(xs_t))
