@@ -31,6 +31,8 @@ SIGNATURES = {
     "gdrf_inducing_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_set_ard": (_int, [_vp, _int]),
     "gdrf_ard_layout": (_int, [_vp, C.POINTER(_i64)]),
+    "gdrf_set_period_count": (_int, [_vp, _int]),
+    "gdrf_periodic_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_set_mean_params": (_int, [_vp, _i64]),
     "gdrf_mean_param_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_ctx_destroy": (None, [_vp]),

@@ -91,6 +91,9 @@ struct gdrf_ctx {
   void *uS, *uSb, *uSc, *uU, *uUb, *Uw;
   int learn_z; double* zpart; // learnable inducing inputs: per-row-tile partial sums [ceil(ncap/128)][M][D]
   int ard; void* Zp; double* apart;   // ARD (gdrf_set_ard): scaled inducing inputs in the N-side precision (probe, gdrf_knm); per-block sums of d / d log ls_d
+  // Periodic kernel (kernel_id GDRF_PERIODIC): D = 2 Dr embedded coordinates per raw input axis pair (kernels_mm.h: prep_hyper_per_kernel), np
+  // log-periods (1 or Dr; 0 in other contexts), the embedded rows of the current call (Xe, xe_cap rows), the inducing phases t_d z_d (Zph)
+  int per, Dr, np; void *Xe, *Zph; int64_t xe_cap;
   int64_t mean_count;         // trainable mean_function parameters (gdrf_set_mean_params): elements of their segment, 0 = none
   double* opt_part; int64_t opt_part_cap;   // gdrf_optim_step: per-workgroup sums of squares of the clip_norm pass, allocated on first use
   int rows_form;              // gdrf_set_rows_form: 0 the LDS row forms, 1 the vocabulary-streamed form (rows_vstream.h)
@@ -127,15 +130,20 @@ static int64_t poff(const gdrf_ctx* c, int which) {
   const int64_t o_uloc = 4, o_phi = round_up(o_uloc + (int64_t)c->K * c->M, 4);
   const int64_t o_S = round_up(o_phi + (int64_t)c->K * c->V, 4);
   const int64_t o_Z = round_up(o_S + (int64_t)c->K * c->M * c->M, 4);          // unconstrained inducing inputs (M, D)
-  const int64_t o_ard = round_up(o_Z + (int64_t)c->M * c->D, 4);               // ARD contexts only: the D log-lengthscales
-  const int64_t o_mean = c->ard ? round_up(o_ard + c->D, 4) : o_ard;           // contexts with gdrf_set_mean_params only: mean_function parameters
+  const int64_t o_ard = round_up(o_Z + (int64_t)c->M * c->Dr, 4);              // ARD contexts only: the D log-lengthscales
+  const int64_t o_per = o_ard + (c->ard ? c->Dr : 0);                          // periodic contexts only: the np log-periods, right behind them
+  const int64_t o_mean = (c->ard || c->per) ? round_up(o_per + c->np, 4) : o_ard;   // contexts with gdrf_set_mean_params only: mean_function parameters
   const int64_t total = c->mean_count ? round_up(o_mean + c->mean_count, 4) : o_mean;
   switch (which) { case 0: return 0; case 1: return 1; case 2: return 2; case 3: return o_uloc; case 4: return o_phi;
-                   case 5: return o_S; case 7: return o_Z; case 8: return o_ard; case 9: return o_mean; default: return total; }
+                   case 5: return o_S; case 7: return o_Z; case 8: return o_ard; case 9: return o_mean; case 10: return o_per;
+                   default: return total; }
 }
 // doubles of red_d: 8 scalars, the (M, D) inducing-input sums, in ARD contexts the D sums of d / d log ls_d over the rows, then the
 // caller's sums of d elbo / d theta of the mean_function parameters (gdrf_set_mean_params)
-static int64_t red_nd(const gdrf_ctx* c) { return 8 + (int64_t)c->M * c->D + (c->ard ? c->D : 0) + c->mean_count; }
+// periodic contexts: D (= 2 Dr) embedded-coordinate sums in place of the ARD ones, then the Dr sums of d / d log p_d
+static int64_t red_nd(const gdrf_ctx* c) {
+  return 8 + (int64_t)c->M * c->D + ((c->ard || c->per) ? c->D : 0) + (c->per ? c->Dr : 0) + c->mean_count;
+}
 static int64_t red_mean_off(const gdrf_ctx* c) { return red_nd(c) - c->mean_count; }
 static int64_t roff(const gdrf_ctx* c, int which) {
   const int64_t mm = (int64_t)c->Mp * c->Mp;
@@ -153,8 +161,11 @@ int gdrf_red_layout(const gdrf_ctx* c, int64_t out[6]) {
   out[5] = red_nd(c);          // 8 scalars, then the (M, D) inducing-input sums (learnable inducing points), then the ARD sums, then the mean segment
   return 0;
 }
-int gdrf_inducing_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 7); out[1] = (int64_t)c->M * c->D; return 0; }
-int gdrf_ard_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 8); out[1] = c->ard ? c->D : 0; return 0; }
+int gdrf_inducing_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 7); out[1] = (int64_t)c->M * c->Dr; return 0; }
+int gdrf_ard_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 8); out[1] = c->ard ? c->Dr : 0; return 0; }
+int gdrf_periodic_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 10); out[1] = c->np; return 0; }
+// the covariance forms of the forward and predictive paths: ARD scales on the rows (a periodic context's embedding carries its own)
+static bool ard_fwd(const gdrf_ctx* c) { return c->ard && !c->per; }
 int gdrf_mean_param_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 9); out[1] = c->mean_count; return 0; }
 
 // row blocks of the ubar partial kernel: ~1024 workgroups, multiples of its 256-row staging step
@@ -197,7 +208,7 @@ static int tn_nsplit_gt(const gdrf_ctx* c, int64_t n, int BR) {
 // K_nm parts of the hyper-parameter gradients through Hd = dK^T Wbar on the split-fp16 TN kernel (hyper_tn.h): f16x3 contexts with the f64
 // solve, fixed inducing inputs (their gradient needs Kbar itself), kernels whose only shape parameter is the lengthscale
 static bool hyper_tn_on(const gdrf_ctx* c) {
-  return c->hyper_tn && c->split == 2 && c->ssz == 8 && !c->learn_z && !c->ard && c->kind != GDRF_RATIONALQUADRATIC && !c->Tst && (c->Mp / 8) <= 256;
+  return c->hyper_tn && c->split == 2 && c->ssz == 8 && !c->learn_z && !c->ard && !c->per && c->kind != GDRF_RATIONALQUADRATIC && !c->Tst && (c->Mp / 8) <= 256;
 }
 // Row splits of the all-topics A_k kernel (gemm_tn_topics.h): one 512-thread workgroup per CU, tiles x topic groups x splits
 // workgroups; fill the 256 CUs' rounds, >= 16 chunks per split, at most 64 splits
@@ -229,11 +240,15 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   if (K > GDRF_TILE) return fail(-1, "gdrf_ctx_create", "num_topic_categories > 128 not supported (loc = W U^T runs as one 128-wide column tile)");
   if (D > GDRF_DMAX) return fail(-1, "gdrf_ctx_create", "more than 4 input dimensions not supported");
   if (dtype != GDRF_F32 && dtype != GDRF_F64 && dtype != GDRF_F32_PURE) return fail(-1, "gdrf_ctx_create", "dtype");
-  if (kernel_id < GDRF_RBF || kernel_id > GDRF_RATIONALQUADRATIC) return fail(-1, "gdrf_ctx_create", "kernel_id");
+  if (kernel_id < GDRF_RBF || kernel_id > GDRF_PERIODIC) return fail(-1, "gdrf_ctx_create", "kernel_id");
+  if (kernel_id == GDRF_PERIODIC && 2 * D > GDRF_DMAX) return fail(-1, "gdrf_ctx_create", "the Periodic kernel supports at most 2 input dimensions");
+  const int Dr = D;
+  if (kernel_id == GDRF_PERIODIC) D = 2 * D;       // the embedded coordinates (cos, sin) of every raw axis
   HIPCHK(hipSetDevice(device));
   gdrf_ctx* c = new gdrf_ctx();
-  c->dev = device; c->M = M; c->Mp = (int)round_up(M, GDRF_MPAD); c->K = K; c->V = V; c->D = D;
-  c->dtype = dtype; c->kind = kernel_id; c->ncap = n_cap; c->ldk = round_up(n_cap, 4);
+  c->dev = device; c->M = M; c->Mp = (int)round_up(M, GDRF_MPAD); c->K = K; c->V = V; c->D = D; c->Dr = Dr;
+  c->per = kernel_id == GDRF_PERIODIC; c->np = c->per ? 1 : 0; c->Xe = c->Zph = nullptr; c->xe_cap = 0;
+  c->dtype = dtype; c->kind = c->per ? GDRF_RBF : kernel_id; c->ncap = n_cap; c->ldk = round_up(n_cap, 4);   // periodic: the RBF forms, embedded
   c->esz = dtype == GDRF_F64 ? 8 : 4;
   c->ssz = dtype == GDRF_F32_PURE ? 4 : 8;
   c->nt = (c->Mp + GDRF_TILE - 1) / GDRF_TILE;
@@ -295,7 +310,13 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   AL(c->dsmall, 16 * sizeof(double))
   AL(c->llpart, 2048 * sizeof(double))
   AL(c->alpha_dev, (size_t)K * V * sizeof(double))
-  AL(c->hyp, sizeof(Hyper)) AL(c->hyp_probe, sizeof(Hyper)) AL(c->flag, 128)
+  AL(c->hyp, sizeof(HyperPer)) AL(c->hyp_probe, sizeof(HyperPer)) AL(c->flag, 128)
+  if (c->per) {
+    // apart: D coordinate sums and Dr period sums per backward workgroup or per inducing point
+    AL(c->Xe, (size_t)n_cap * D * c->esz) AL(c->Zp, (size_t)c->Mp * D * c->esz) AL(c->Zph, (size_t)c->Mp * Dr * c->ssz)
+    AL(c->apart, (size_t)c->dpart_len * (D + Dr) * sizeof(double))
+    c->xe_cap = n_cap;
+  }
   AL(c->ssc, (size_t)SplitLay{K}.nfloats() * sizeof(float)) AL(c->smx, (size_t)SplitLay{K}.nmax() * sizeof(unsigned))
 #undef AL
   {
@@ -448,6 +469,14 @@ int gdrf_set_ard(gdrf_ctx* c, int on) {
   c->prefact_valid = 0;
   return 0;
 }
+int gdrf_set_period_count(gdrf_ctx* c, int count) {
+  if (!c->per) return fail(-1, "gdrf_set_period_count", "not a periodic context (kernel_id GDRF_PERIODIC)");
+  if (count != 1 && count != c->Dr) return fail(-1, "gdrf_set_period_count", "count must be 1 or the number of input dimensions");
+  if (c->g_loc) return fail(-1, "gdrf_set_period_count", "call it before the first gdrf_step_local2");
+  c->np = count;
+  c->prefact_valid = 0;
+  return 0;
+}
 int gdrf_set_mean_params(gdrf_ctx* c, int64_t count) {
   if (count < 0) return fail(-1, "gdrf_set_mean_params", "count must be >= 0");
   // the two-point scratch (gdrf_step_local2) holds a copy of red_d sized on its first use
@@ -575,12 +604,43 @@ template <typename T, typename TS> struct Impl {
   // nlev (<= 8) Cholesky attempts in ONE launch, in the N-side precision (what the reference's fp32
   // torch.linalg.cholesky would see): K_uu built once, one workgroup per cumulative jitter; flags in c->flag[8..8+nlev)
   // (slot 0 is the solve factorisation's, so a probe may run on another stream beside gdrf_factorize)
+  // periodic contexts: the hyper-parameter block h and the embedded inducing inputs zout (M, 2 Dr) in precision TO, with their phases
+  // t_d z_d (M, Dr) when ph is given
+  template <typename TO>
+  static void per_prep(gdrf_ctx* c, const T* Z, const T* params, Hyper* h, void* zout, void* ph, hipStream_t s) {
+    const T* lls = c->ard ? params + poff(c, 8) : params;
+    const T* lp = params + poff(c, 10);
+    const int ls_step = c->ard ? 1 : 0, p_step = c->np > 1 ? 1 : 0;
+    const int64_t nz = (int64_t)c->M * c->Dr;
+    hipLaunchKernelGGL(prep_hyper_per_kernel<T>, dim3(1), dim3(64), 0, s, params, lls, ls_step, lp, p_step, c->Dr, (HyperPer*)h);
+    hipLaunchKernelGGL((embed_per_kernel<T, TO>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, (int64_t)c->M, c->Dr, Z, lls, ls_step, lp,
+                       p_step, (TO*)zout, (TO*)ph);
+  }
+  // periodic contexts: the embedded rows (n, 2 Dr) of this call into c->Xe.  More rows than it holds (gdrf_knm, gdrf_predict) grow it; the
+  // old buffer stays allocated until gdrf_ctx_destroy, since work queued before may still read it.
+  static int per_rows(gdrf_ctx* c, const T* X, int64_t n, const T* params, hipStream_t s) {
+    if (n > c->xe_cap) {
+      void* p = nullptr;
+      hipError_t e = hipMalloc(&p, (size_t)n * c->D * c->esz);
+      if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(embedded rows)", hipGetErrorString(e));
+      c->allocs.push_back(p); c->Xe = p; c->xe_cap = n;
+    }
+    const int64_t nx = n * c->Dr;
+    if (nx > 0)
+      hipLaunchKernelGGL((embed_per_kernel<T, T>), dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, n, c->Dr, X,
+                         c->ard ? params + poff(c, 8) : params, c->ard ? 1 : 0, params + poff(c, 10), c->np > 1 ? 1 : 0, (T*)c->Xe, (T*)nullptr);
+    LAUNCHCHK("embed rows (periodic)");
+    return 0;
+  }
   static int probe(gdrf_ctx* c, const T* Z, const T* params, const double* jitters, int nlev, hipStream_t s) {
     const int Mp = c->Mp, M = c->M;
     ScopedTimer tm(c, 0, s);
     HIPCHK(hipMemsetAsync(c->flag + 8, 0, 32, s));
     dim3 g2((Mp + 255) / 256, Mp);
-    if (c->ard) {
+    if (c->per) {
+      per_prep<T>(c, Z, params, c->hyp_probe, P(c->Zp), nullptr, s);
+      Z = (const T*)P(c->Zp);
+    } else if (c->ard) {
       const int64_t nz = (int64_t)M * c->D;
       hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp_probe);
       hipLaunchKernelGGL((scale_z_kernel<T, T>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), P(c->Zp));
@@ -610,10 +670,10 @@ template <typename T, typename TS> struct Impl {
   // failure flag by gdrf_chol_failed: a mismatch makes the caller redo the step, like a wrong jitter guess); otherwise as mode 0.
   static int factorize(gdrf_ctx* c, const T* Z, const T* params, double jitter, hipStream_t s, int mode = 0) {
     const int Mp = c->Mp, M = c->M;
-    const int64_t nzs = (int64_t)M * c->D;
+    const int64_t nzs = (int64_t)M * c->Dr;
     if (mode == 2 && c->prefact_valid && jitter == c->prefact_jitter) {
       hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 1, c->flag + 16, params + poff(c, 8),
-                         c->ard ? c->D : 0);
+                         (c->ard ? c->Dr : 0) + c->np);
       // the factorisation stays valid for further calls with the same inputs (a predictive evaluation between two steps): every reuse
       // compares again, and any fresh factorisation below invalidates it first
       LAUNCHCHK("factorize (reuse)");
@@ -623,7 +683,9 @@ template <typename T, typename TS> struct Impl {
     if (mode != 1) HIPCHK(hipMemsetAsync(c->flag + 16, 0, sizeof(int), s));     // this stream's own factorisation: nothing reused, no mismatch to report
     dim3 g2((Mp + 255) / 256, Mp);
     const int64_t nz = (int64_t)M * c->D;
-    if (c->ard) {      // the scaled inducing inputs z_d / ls_d in the solve precision; ls = 1 in the hyper-parameter block
+    if (c->per) {      // the embedded inducing inputs and their phases in the solve precision
+      per_prep<TS>(c, Z, params, c->hyp, Q(c->Zs), Q(c->Zph), s);
+    } else if (c->ard) {      // the scaled inducing inputs z_d / ls_d in the solve precision; ls = 1 in the hyper-parameter block
       hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp);
       hipLaunchKernelGGL((scale_z_kernel<T, TS>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), Q(c->Zs));
     } else {
@@ -653,7 +715,7 @@ template <typename T, typename TS> struct Impl {
     c->fact_pending = 1;
     if (mode == 1) {
       hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 0, (int*)nullptr, params + poff(c, 8),
-                         c->ard ? c->D : 0);
+                         (c->ard ? c->Dr : 0) + c->np);
       c->prefact_valid = 1; c->prefact_jitter = jitter;
     }
     LAUNCHCHK("factorize");
@@ -661,7 +723,12 @@ template <typename T, typename TS> struct Impl {
   }
 
   static int knm(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, T* out, int64_t ldo, hipStream_t s) {
-    if (c->ard) {
+    if (c->per) {
+      per_prep<T>(c, Z, params, c->hyp, P(c->Zp), nullptr, s);
+      Z = (const T*)P(c->Zp);
+      if (int rc = per_rows(c, X, n, params, s)) return rc;
+      X = (const T*)c->Xe;
+    } else if (c->ard) {
       const int64_t nz = (int64_t)c->M * c->D;
       hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp);
       hipLaunchKernelGGL((scale_z_kernel<T, T>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), P(c->Zp));
@@ -676,7 +743,7 @@ template <typename T, typename TS> struct Impl {
     const int64_t cap = 256 * 64;          // swept on MI355X: 2048 blocks 0.60-0.65 of HBM peak, 16384 0.67-0.79
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    if (c->ard)
+    if (ard_fwd(c))
       hipLaunchKernelGGL((knm_kernel<T, T, true, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
     else
       hipLaunchKernelGGL((knm_kernel<T, T, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, Z, c->M, c->D, c->kind, c->hyp, out, ldo);
@@ -817,7 +884,7 @@ template <typename T, typename TS> struct Impl {
     if (blocks < 1) blocks = 1;
     if constexpr (sizeof(TS) == 8) {
       if (c->kind == 0 && vpr <= 256) {
-        if (c->ard) {
+        if (ard_fwd(c)) {
           if (c->D <= 2) hipLaunchKernelGGL((knm_rbf_f64_kernel<T, 2, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D,
                                             c->hyp, (double*)Q(c->Knm), (int64_t)c->Mp);
           else hipLaunchKernelGGL((knm_rbf_f64_kernel<T, GDRF_DMAX, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M,
@@ -833,7 +900,7 @@ template <typename T, typename TS> struct Impl {
         return 0;
       }
     }
-    if (c->ard)
+    if (ard_fwd(c))
       hipLaunchKernelGGL((knm_kernel<TS, T, false, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const TS*)Q(c->Zs), c->M, c->D, c->kind,
                          c->hyp, Q(c->Knm), (int64_t)c->Mp);
     else
@@ -913,6 +980,11 @@ template <typename T, typename TS> struct Impl {
     const T* U = params + poff(c, 3);
     const T* phi_unc = params + poff(c, 4);
     const T* Sunc = params + poff(c, 5);
+    const T* Xr = X;             // periodic contexts: the raw rows (the period sums of the backward); X becomes their embedding
+    if (c->per && X && (mask & (SL_FORWARD | SL_BACKWARD))) {
+      if ((rc = per_rows(c, X, n, params, s))) return rc;
+      X = (const T*)c->Xe;
+    }
     if (c->unwhitened && !(mask & SL_TRANSFORMS)) U = (const T*)c->Uw;
     if (mask & SL_TRANSFORMS) {
       ScopedTimer tm(c, 2, s);
@@ -1158,7 +1230,23 @@ template <typename T, typename TS> struct Impl {
       ScopedTimer tm(c, 8, s);
       const int64_t nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
       if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
-      if (c->ard) {
+      if (c->per) {
+        if (c->learn_z) {
+          BwdKnmProb<TS, T, true, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X,
+                                                (const TS*)Q(c->Zs), c->hyp, c->dpart, c->zpart, c->apart, Xr, (const TS*)Q(c->Zph)};
+          hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, true, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
+          hipLaunchKernelGGL(reduce_parts_kernel<double>, dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, s, (const double*)c->zpart, rtiles,
+                             (int64_t)M * c->D, redd + 8);
+        } else {
+          BwdKnmProb<TS, T, false, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X,
+                                                 (const TS*)Q(c->Zs), c->hyp, c->dpart, nullptr, c->apart, Xr, (const TS*)Q(c->Zph)};
+          if (sizeof(TS) == 8)
+            hipLaunchKernelGGL((gemm_nt_kernel_v160<TS, BwdKnmProb<TS, T, false, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
+          else hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, false, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
+        }
+        // the coordinate sums, then the period sums: red_d[8 + M D ..)
+        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D + c->Dr, redd + 8 + (int64_t)M * c->D);
+      } else if (c->ard) {
         if (c->learn_z) {
           BwdKnmProb<TS, T, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
                                           c->hyp, c->dpart, c->zpart, c->apart};
@@ -1432,7 +1520,11 @@ template <typename T, typename TS> struct Impl {
     // YT = Linv^T P^T ; S' = Linv^T Y
     if ((rc = mm_nt<TS>(c, Q(c->LinvT), 0, Q(c->t2), 0, Q(c->t0), 0, TS(1), 1, s))) return rc;
     if ((rc = mm_nt<TS>(c, Q(c->LinvT), 0, Q(c->t0), 0, Q(c->t1), 0, TS(1), 1, s))) return rc;
-    if (c->ard) {          // K_uu sums of d / d log ls_d -> dsmall[3..3+D)
+    if (c->per) {          // K_uu coordinate and period sums -> dsmall[9..9+D+Dr) (dsmall[8] is the ll_const scratch)
+      hipLaunchKernelGGL((kuu_bar_reduce_kernel<TS, true, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D,
+                         c->kind, c->hyp, c->dpart, c->apart, (const TS*)Q(c->Zph));
+      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, (int64_t)M, c->D + c->Dr, c->dsmall + 9);
+    } else if (c->ard) {          // K_uu sums of d / d log ls_d -> dsmall[3..3+D)
       hipLaunchKernelGGL((kuu_bar_reduce_kernel<TS, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind,
                          c->hyp, c->dpart, c->apart);
       hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, (int64_t)M, c->D, c->dsmall + 3);
@@ -1441,7 +1533,10 @@ template <typename T, typename TS> struct Impl {
                          c->hyp, c->dpart);
     }
     hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)M, 3, c->dsmall);
-    if (c->learn_z && c->ard)
+    if (c->learn_z && c->per)
+      hipLaunchKernelGGL((grad_z_kernel<TS, T, true, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind,
+                         c->hyp, redd + 8, -1.0 / n_global, grads + poff(c, 7), Z);
+    else if (c->learn_z && c->ard)
       hipLaunchKernelGGL((grad_z_kernel<TS, T, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind, c->hyp,
                          redd + 8, -1.0 / n_global, grads + poff(c, 7), Z);
     else if (c->learn_z)
@@ -1456,7 +1551,10 @@ template <typename T, typename TS> struct Impl {
     }
     hipLaunchKernelGGL(grad_small_kernel<T>, dim3(1), dim3(256), 0, s, M, Mp, K, V, c->hyp, redd, c->dsmall, ubar, phib, P(c->phi),
                        c->alpha_dev, c->lgam_const, ll_const, n_global, grads, grads + poff(c, 3), grads + poff(c, 4), c->flag, out_d);
-    if (c->ard)
+    if (c->per)
+      hipLaunchKernelGGL(grad_per_kernel<T>, dim3(1), dim3(64), 0, s, c->Dr, c->ard, c->np, (const double*)redd + 8 + (int64_t)M * c->D,
+                         (const double*)c->dsmall + 9, n_global, grads, grads + poff(c, 8), grads + poff(c, 10));
+    else if (c->ard)
       hipLaunchKernelGGL(grad_ard_kernel<T>, dim3(1), dim3(64), 0, s, c->D, (const double*)redd + 8 + (int64_t)M * c->D, (const double*)c->dsmall + 3,
                          n_global, grads, grads + poff(c, 8));
     if (c->mean_count)
@@ -1489,6 +1587,10 @@ template <typename T, typename TS> struct Impl {
       LAUNCHCHK("predict (loc, var)");
       return 0;
     }
+    if (c->per) {
+      if (int rc = per_rows(c, X, n, params, s)) return rc;
+      X = (const T*)c->Xe;
+    }
     if (mode >= 2) hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + poff(c, 4), K, V, P(c->phi));
     if (c->rows_form == 1) {
       // form 1: the any-K row kernel without Phi in LDS gives f_loc / topic_probs; for word_probs and perplexity it writes topic_probs of
@@ -1496,7 +1598,7 @@ template <typename T, typename TS> struct Impl {
       hipLaunchKernelGGL((predict_coeff_kernel<TS, T>), dim3((M + 127) / 128, K), dim3(128), 0, s, (const TS*)Q(c->Linv), U, M, Mp, K, Q(c->Cf));
       const size_t lds = 128 + (size_t)M * c->D * sizeof(TS);
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D solve-precision elements exceed the LDS budget (150 KB)");
-      auto kfn = c->ard ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
+      auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       auto rows = [&](const T* Xc, int64_t m, int md, T* o, int64_t ldo) {
         int64_t blocks = (m + 127) / 128; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
@@ -1536,7 +1638,7 @@ template <typename T, typename TS> struct Impl {
 #define GDRF_PM(DDv, NBv, ARDv) { if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)predict_mfma_kernel<TS, T, DDv, NBv, ARDv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
                             hipLaunchKernelGGL((predict_mfma_kernel<TS, T, DDv, NBv, ARDv>), dim3((unsigned)blocks), dim3(256), lds, s, X, n, (const TS*)Q(c->Zs), M, M4, c->D, c->kind, \
                                                c->hyp, (const TS*)Q(c->CfT), K, V, (const T*)P(c->phi), ws, mode, out, ldo, c->dpart); }
-        if (c->ard) {
+        if (ard_fwd(c)) {
           if (DDt == 2) { if (NB == 1) GDRF_PM(2, 1, true) else GDRF_PM(2, 2, true) } else { if (NB == 1) GDRF_PM(GDRF_DMAX, 1, true) else GDRF_PM(GDRF_DMAX, 2, true) }
         } else {
           if (DDt == 2) { if (NB == 1) GDRF_PM(2, 1, false) else GDRF_PM(2, 2, false) } else { if (NB == 1) GDRF_PM(GDRF_DMAX, 1, false) else GDRF_PM(GDRF_DMAX, 2, false) }
@@ -1553,7 +1655,7 @@ template <typename T, typename TS> struct Impl {
     if (K > GDRF_KMAX) {
       const size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)128 * (V + 1)) * sizeof(TS);
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V + 128*(V+1) solve-precision elements exceed the LDS budget (150 KB)");
-      auto kfn = c->ard ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
+      auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
       if (lds > 48 * 1024)
         HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,
@@ -1563,7 +1665,7 @@ template <typename T, typename TS> struct Impl {
       int in_lds = 1;
       if (lds > 64 * 1024) { in_lds = 0; lds -= (size_t)K * M * sizeof(TS); }
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V solve-precision elements exceed the LDS budget (150 KB)");
-      auto kfn = c->ard ? predict_rows_kernel<TS, T, true> : predict_rows_kernel<TS, T>;
+      auto kfn = ard_fwd(c) ? predict_rows_kernel<TS, T, true> : predict_rows_kernel<TS, T>;
       if (lds > 48 * 1024)
         HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,

@@ -15,6 +15,8 @@ namespace gdrf {
 // hyper-parameter block kept on the device (double): filled by prep_hyper
 // sc: ARD contexts only (gdrf_set_ard): the per-dimension coordinate scales 1 / ls_d; the isotropic forms then run with ls = 1
 struct Hyper { double ls, var, noise, inv_ls2, alpha; double sc[GDRF_DMAX]; };     // alpha: RationalQuadratic scale_mixture (parameter slot 3)
+// tp: periodic contexts only (gdrf_set_period_count): the angular frequencies 2 pi / period_d of the raw input axes
+struct HyperPer : Hyper { double tp[GDRF_DMAX]; };
 
 template <typename T>
 __global__ void prep_hyper_kernel(const T* __restrict__ params, Hyper* h) {
@@ -40,6 +42,38 @@ template <typename T, typename TO>
 __global__ void scale_z_kernel(int64_t nz, int D, const T* __restrict__ Z, const T* __restrict__ log_ls, TO* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < nz) out[i] = (TO)((double)Z[i] * exp(-(double)log_ls[i % D]));
+}
+
+// Periodic (pyro.contrib.gp.kernels.Periodic: variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / p_d) / ls_d^2)) is the RBF kernel at ls = 1 on
+// the embedded coordinates e(x) = (cos(t_d x_d) / ls_d, sin(t_d x_d) / ls_d), t_d = 2 pi / p_d: |e_d(x) - e_d(z)|^2 = 4 sin^2(t_d (x_d - z_d) / 2) / ls_d^2.
+// A context of Dr raw axes runs every covariance form on D = 2 Dr embedded coordinates.  log_ls / log_p: ls_step / p_step = 0 for one
+// shared value, 1 for one per axis.  The scales sc are 1 (the embedding carries 1 / ls_d): the ARD instantiations give the per-coordinate sums.
+template <typename T>
+__global__ void prep_hyper_per_kernel(const T* __restrict__ params, const T* __restrict__ log_ls, int ls_step, const T* __restrict__ log_p,
+                                      int p_step, int Dr, HyperPer* h) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    h->ls = 1.0; h->var = exp((double)params[1]); h->noise = exp((double)params[2]); h->inv_ls2 = 1.0; h->alpha = exp((double)params[3]);
+    for (int d = 0; d < GDRF_DMAX; ++d) {
+      h->sc[d] = d < 2 * Dr ? 1.0 : 0.0;
+      h->tp[d] = d < Dr ? 6.283185307179586477 * exp(-(double)log_p[d * p_step]) : 0.0;
+    }
+  }
+}
+// out[i][2d], out[i][2d + 1] = cos(t_d x_id) / ls_d, sin(t_d x_id) / ls_d in the output precision (computed in double); ph[i][d] = t_d x_id
+// when ph is given.  One thread per (row, raw axis).
+template <typename T, typename TO>
+__global__ void embed_per_kernel(int64_t n, int Dr, const T* __restrict__ X, const T* __restrict__ log_ls, int ls_step, const T* __restrict__ log_p,
+                                 int p_step, TO* __restrict__ out, TO* __restrict__ ph) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * Dr) return;
+  const int d = (int)(i % Dr);
+  const double t = 6.283185307179586477 * exp(-(double)log_p[d * p_step]), il = exp(-(double)log_ls[d * ls_step]);
+  const double a = t * (double)X[i];
+  double sn, cs;
+  sincos(a, &sn, &cs);
+  out[2 * i] = (TO)(cs * il);
+  out[2 * i + 1] = (TO)(sn * il);
+  if (ph) ph[i] = (TO)a;
 }
 
 // the values a factorisation depends on - the first four parameters (log lengthscale, variance, noise, scale mixture), the inducing inputs and,
@@ -716,13 +750,17 @@ __global__ void phi_tril_kernel(const T* __restrict__ Q, int Mp, T* __restrict__
 // sum_{ij} Kuu_bar * K0,  sum_{ij} Kuu_bar * dK0/dlog(ls)  and  sum_{ij} Kuu_bar * dK0/dlog(alpha), Kuu_bar = (S' + S'^T)/2 ;
 // one partial triple per block.  ARD (Z = the scaled inducing inputs, ls = 1): also the D sums
 // sum_j Kuu_bar * dK0/dlog(ls_d) = sum_j Kuu_bar * dk/dr2 * (-2) (z_id - z_jd)^2 into apart[D * i + d]
-template <typename T, bool ARD = false>
+// PER (periodic contexts, ARD set: Z = the embedded inducing inputs, ph = their phases t_d z_d): also the D / 2 sums of d / d log p_d,
+// sum_j Kuu_bar * dk/dr2 * (-2) (ph_id - ph_jd) (s_id c_jd - c_id s_jd), behind the D coordinate sums: apart stride D + D / 2
+template <typename T, bool ARD = false, bool PER = false>
 __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restrict__ Z, int M, int Mp, int D, int kind,
-                                      const Hyper* __restrict__ h, double* __restrict__ part, double* __restrict__ apart = nullptr) {
+                                      const Hyper* __restrict__ h, double* __restrict__ part, double* __restrict__ apart = nullptr,
+                                      const T* __restrict__ ph = nullptr) {
   __shared__ double scratch[16];
   const int i = blockIdx.x;
   double s1 = 0, s2 = 0, s3 = 0;
   double sd[ARD ? GDRF_DMAX : 1] = {};
+  double pd[PER ? GDRF_DMAX / 2 : 1] = {};
   const T var = (T)h->var, ils2 = (T)h->inv_ls2, al = (T)h->alpha;
   for (int j = threadIdx.x; j < M; j += blockDim.x) {
     const T kb = T(0.5) * (Sp[(int64_t)i * Mp + j] + Sp[(int64_t)j * Mp + i]);
@@ -734,6 +772,12 @@ __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restr
     if constexpr (ARD) {
       const T w = T(-2) * kb * dcov_dr2_from_k<T>(kind, k0, r2, al);
       for (int d = 0; d < D; ++d) { const T t = Z[(int64_t)i * D + d] - Z[(int64_t)j * D + d]; sd[d] += (double)(w * t * t); }
+      if constexpr (PER) {
+        for (int d = 0; d < D / 2; ++d) {
+          const T* zi = Z + (int64_t)i * D + 2 * d; const T* zj = Z + (int64_t)j * D + 2 * d;
+          pd[d] += (double)(w * (ph[(int64_t)i * (D / 2) + d] - ph[(int64_t)j * (D / 2) + d]) * (zi[1] * zj[0] - zi[0] * zj[1]));
+        }
+      }
     }
   }
   s1 = block_sum(s1, scratch);
@@ -741,9 +785,16 @@ __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restr
   s3 = block_sum(s3, scratch);
   if (threadIdx.x == 0) { part[3 * i] = s1; part[3 * i + 1] = s2; part[3 * i + 2] = s3; }
   if constexpr (ARD) {
+    const int as = PER ? D + D / 2 : D;
     for (int d = 0; d < D; ++d) {
       const double v = block_sum(sd[d], scratch);
-      if (threadIdx.x == 0) apart[(int64_t)D * i + d] = v;
+      if (threadIdx.x == 0) apart[(int64_t)as * i + d] = v;
+    }
+    if constexpr (PER) {
+      for (int d = 0; d < D / 2; ++d) {
+        const double v = block_sum(pd[d], scratch);
+        if (threadIdx.x == 0) apart[(int64_t)as * i + D + d] = v;
+      }
     }
   }
 }
@@ -812,7 +863,9 @@ __global__ void grad_unwhitened_kernel(const T* __restrict__ Sbar, const T* __re
 // g = -1/N * Zbar * z (1 - z).  One block per inducing point.
 // ARD: Z and G are in the scaled coordinates z_d / ls_d (ls = 1), d r2 / d z_d carries one more factor 1 / ls_d = sc[d], and the
 // sigmoid Jacobian takes the unscaled inputs Zr.
-template <typename T, typename TP, bool ARD = false>
+// PER (periodic contexts, ARD set): Z and G are in the D = 2 Dr embedded coordinates (c, s) = (cos(t z), sin(t z)) / ls, whose
+// derivatives in the raw input z are (-t s, t c): zbar_d = t_d (s-coordinate gradient * c - c-coordinate gradient * s); Zr = raw inputs (M, Dr).
+template <typename T, typename TP, bool ARD = false, bool PER = false>
 __global__ void grad_z_kernel(const T* __restrict__ Sp, const T* __restrict__ Z, int M, int Mp, int D, int kind,
                               const Hyper* __restrict__ h, const double* __restrict__ G, double neg_inv_n, TP* __restrict__ g,
                               const TP* __restrict__ Zr = nullptr) {
@@ -827,6 +880,20 @@ __global__ void grad_z_kernel(const T* __restrict__ Sp, const T* __restrict__ Z,
     const T r2 = sqdist<T>(Z + (int64_t)i * D, Z + (int64_t)j * D, D) * ils2;
     const T w = kb * dcov_dr2_from_k<T>(kind, cov_from_r2<T>(kind, r2, var, al), r2, al);
     for (int d = 0; d < D; ++d) hs[d] += (double)(w * (Z[(int64_t)i * D + d] - Z[(int64_t)j * D + d]));
+  }
+  if constexpr (PER) {
+    double eb[GDRF_DMAX];          // d r2-side gradient in the embedded coordinates
+    for (int d = 0; d < D; ++d) eb[d] = 2.0 * (G[(int64_t)i * D + d] + 2.0 * block_sum(hs[d], scratch));
+    if (threadIdx.x == 0) {
+      const HyperPer* hp = static_cast<const HyperPer*>(h);
+      for (int d = 0; d < D / 2; ++d) {
+        const double c = (double)Z[(int64_t)i * D + 2 * d], sn = (double)Z[(int64_t)i * D + 2 * d + 1];
+        const double z = (double)Zr[(int64_t)i * (D / 2) + d];
+        const double zbar = hp->tp[d] * (eb[2 * d + 1] * c - eb[2 * d] * sn);
+        g[(int64_t)i * (D / 2) + d] = (TP)(neg_inv_n * zbar * z * (1.0 - z));
+      }
+    }
+    return;
   }
   for (int d = 0; d < D; ++d) {
     const double hsum = block_sum(hs[d], scratch);

@@ -682,7 +682,10 @@ template <typename T> struct BwdWbarTProb : NTXcdPairMap, NTPlainA<T> {
 // ARD: Z holds the scaled inducing inputs, ls = 1, the rows are scaled by 1 / ls_d as they are loaded, and the lengthscale sum splits
 // into the D sums  sum Kbar * dk/dr2 * (-2) (x_d - z_d)^2  (= d / d log ls_d; their total is the isotropic sum), one partial per
 // workgroup in apart[D * block + d].  Every other sum is the isotropic one in the scaled coordinates.
-template <typename T, typename TN, bool LZ = false, bool ARD = false> struct BwdKnmProb : NTXcdRowMap, NTNoExtra {
+// PER (periodic contexts, with ARD): X and Z are the embedded coordinates (D = 2 Dr, ls = 1), Xr the raw rows (nrows, Dr) and Zph the
+// inducing phases t_d z_d; also the Dr sums  sum Kbar * dk/dr2 * (-2) (t_d x_d - t_d z_d) (s_x c_z - c_x s_z)  (= d / d log p_d) behind the
+// D coordinate sums: apart stride D + Dr.
+template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER = false> struct BwdKnmProb : NTXcdRowMap, NTNoExtra {
   using V = typename Vec16<T>::type;
   static constexpr int MIN_WGS = (sizeof(T) == 8 && !LZ) ? 3 : 2;   // f64: three workgroups per CU hide each other's epilogues
   static constexpr int TRI = 2;            // Kbar[n][col] = sum_{k >= col} Wbar[n][k] LinvT[col][k]
@@ -696,10 +699,12 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
   double* part;                    // [gridDim.x][3]: sum Kbar*K, sum Kbar*dK/dlog(ls), sum Kbar*dK/dlog(alpha)
   double* zpart;                   // LZ: [row tiles][M][D]
   double* apart = nullptr;         // ARD: [gridDim.x][D]
+  const TN* Xr = nullptr; const T* Zph = nullptr;   // PER
   struct ACtx { const TN* p[NTCfg<T>::VPT]; };
   struct ECtxIso { T s1, s2, s3; T zs[LZ ? NTCfg<T>::NB : 1][LZ ? GDRF_DMAX : 1]; int n0; };
   struct ECtxArd : ECtxIso { T sd[GDRF_DMAX]; };             // the per-axis sums exist in the ARD instantiations only
-  using ECtx = std::conditional_t<ARD, ECtxArd, ECtxIso>;
+  struct ECtxPer : ECtxArd { T pd[GDRF_DMAX / 2]; };
+  using ECtx = std::conditional_t<PER, ECtxPer, std::conditional_t<ARD, ECtxArd, ECtxIso>>;
   __device__ __forceinline__ int col_tiles() const { return (Mp + NTCfg<T>::CW - 1) / NTCfg<T>::CW; }
   __device__ __forceinline__ bool loop_cols() const { return false; }
   __device__ __forceinline__ int a_reuse() const { return 1; }
@@ -716,6 +721,10 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
     if constexpr (ARD) {
 #pragma unroll
       for (int d = 0; d < GDRF_DMAX; ++d) e.sd[d] = 0;
+    }
+    if constexpr (PER) {
+#pragma unroll
+      for (int d = 0; d < GDRF_DMAX / 2; ++d) e.pd[d] = 0;
     }
     if constexpr (LZ) {
 #pragma unroll
@@ -747,7 +756,7 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
   template <int KD, int DD, int NR>
   __device__ __forceinline__ void strip_math(const KT2 (&kv)[NR], const T* __restrict__ trow, int tstride, const TN (&x)[NR][DD],
                                              const T (&zc)[2][DD], const bool (&rok)[NR], const bool (&cok)[2],
-                                             T ils2, T al, ECtx& e, const T (&xsc)[DD]) const {
+                                             T ils2, T al, ECtx& e, const T (&xsc)[DD], const T (&px)[NR], const T (&pz)[2]) const {
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
       const KT2 kb = *reinterpret_cast<const KT2*>(trow + 4 * i * tstride);
@@ -764,6 +773,7 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
           const T w = T(-2) * kbar * dcov_dr2_from_k<T>(KD, kvv, r2, al);
 #pragma unroll
           for (int d = 0; d < DD; ++d) { const T t = (d < D ? (T)x[i][d] * xsc[d] : T(0)) - zc[j][d]; e.sd[d] += w * t * t; }
+          if constexpr (PER) e.pd[0] += w * (px[i] - pz[j]) * ((T)x[i][1] * zc[j][0] - (T)x[i][0] * zc[j][1]);   // DD = 2: one raw axis
         } else {
           e.s2 += kbar * dcov_dlogls_from_k<T>(KD, kvv, r2, al);
         }
@@ -802,6 +812,12 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
 #pragma unroll
       for (int d = 0; d < DD; ++d) { const T v = Z[nz * D + (d < D ? d : 0)]; zc[j][d] = d < D ? v : T(0); }
     }
+    T pz[2] = {T(0), T(0)}, tp0 = T(0);
+    if constexpr (PER) {
+      tp0 = (T)static_cast<const HyperPer*>(h)->tp[0];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) pz[j] = Zph[cok[j] ? nc + j : 0];
+    }
     const T* __restrict__ Kt = Knm + m0 * Mp;              // uniform bases of this row tile
     const TN* __restrict__ Xt = X + m0 * D;
     const int rmax = (int)((nrows - m0 < GDRF_TILE ? nrows - m0 : GDRF_TILE) - 1);   // last valid row of the tile (m0 < nrows)
@@ -812,7 +828,7 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
     for (int a = 0; a < 4; ++a) {
 #pragma unroll
       for (int hb = 0; hb < 4 / NR; ++hb) {
-        KT2 kv[NR]; TN x[NR][DD]; bool rok[NR];
+        KT2 kv[NR]; TN x[NR][DD]; bool rok[NR]; T px[NR];
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
           const int rl = r0 + a * 16 + 4 * (hb * NR + i);
@@ -821,6 +837,8 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
           kv[i] = *reinterpret_cast<const KT2*>(Kt + (rc * (unsigned)Mp + (unsigned)ncl));
 #pragma unroll
           for (int d = 0; d < DD; ++d) x[i][d] = Xt[rc * (unsigned)D + (unsigned)(d < D ? d : 0)];
+          if constexpr (PER) px[i] = tp0 * (T)Xr[m0 + rc];
+          else px[i] = T(0);
         }
         if (hb == 0) {
 #pragma unroll
@@ -831,11 +849,11 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
         }
         const T* trow = tile + (lg + 4 * hb * NR) * TS_ + 2 * lr;   // slot i: row lg + 4 * (hb * NR + i) of the strip
         switch (kind) {
-          case 0: strip_math<0, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
-          case 1: strip_math<1, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
-          case 2: strip_math<2, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
-          case 3: strip_math<3, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
-          default: strip_math<4, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc); break;
+          case 0: strip_math<0, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc, px, pz); break;
+          case 1: strip_math<1, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc, px, pz); break;
+          case 2: strip_math<2, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc, px, pz); break;
+          case 3: strip_math<3, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc, px, pz); break;
+          default: strip_math<4, DD, NR>(kv, trow, TS_, x, zc, rok, cok, ils2, al, e, xsc, px, pz); break;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);                  // one batch at a time
@@ -859,6 +877,15 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
 #pragma unroll
       for (int d = 0; d < GDRF_DMAX; ++d) z[b][d] = (n < M && d < D) ? Z[(int64_t)n * D + d] : T(0);
     }
+    T pz[PER ? 4 : 1][GDRF_DMAX / 2];
+    if constexpr (PER) {
+#pragma unroll
+      for (int b = 0; b < NTCfg<T>::NB; ++b) {
+        const int n = n0 + nt_acc_col<T>(wc, b, lane);
+#pragma unroll
+        for (int d = 0; d < GDRF_DMAX / 2; ++d) pz[b][d] = (n < M && d < D / 2) ? Zph[(int64_t)n * (D / 2) + d] : T(0);
+      }
+    }
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -868,6 +895,12 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
         T x[GDRF_DMAX];
 #pragma unroll
         for (int d = 0; d < GDRF_DMAX; ++d) x[d] = (d < D) ? (ARD ? (T)X[m * D + d] * (T)h->sc[d] : (T)X[m * D + d]) : T(0);
+        T px[GDRF_DMAX / 2];
+        if constexpr (PER) {
+#pragma unroll
+          for (int d = 0; d < GDRF_DMAX / 2; ++d)
+            px[d] = d < D / 2 ? (T)static_cast<const HyperPer*>(h)->tp[d] * (T)Xr[m * (D / 2) + d] : T(0);
+        }
 #pragma unroll
         for (int b = 0; b < NTCfg<T>::NB; ++b) {
           const int n = n0 + nt_acc_col<T>(wc, b, lane);
@@ -882,6 +915,11 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
             const T w = T(-2) * acc[a][b][r] * dcov_dr2_from_k<T>(kind, kv, r2, al);
 #pragma unroll
             for (int d = 0; d < GDRF_DMAX; ++d) if (d < D) { const T t = x[d] - z[b][d]; e.sd[d] += w * t * t; }
+            if constexpr (PER) {
+#pragma unroll
+              for (int d = 0; d < GDRF_DMAX / 2; ++d)
+                if (d < D / 2) e.pd[d] += w * (px[d] - pz[b][d]) * (x[2 * d + 1] * z[b][2 * d] - x[2 * d] * z[b][2 * d + 1]);
+            }
           } else {
             e.s2 += acc[a][b][r] * dcov_dlogls_from_k<T>(kind, kv, r2, al);
           }
@@ -907,9 +945,16 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false> struct Bwd
     const double c3 = block_sum((double)e.s3, scratch);
     if (threadIdx.x == 0) { part[3 * (int64_t)blockIdx.x] = a; part[3 * (int64_t)blockIdx.x + 1] = b; part[3 * (int64_t)blockIdx.x + 2] = c3; }
     if constexpr (ARD) {
+      const int as = PER ? D + D / 2 : D;
       for (int d = 0; d < D; ++d) {
         const double v = block_sum((double)e.sd[d], scratch);
-        if (threadIdx.x == 0) apart[(int64_t)D * blockIdx.x + d] = v;
+        if (threadIdx.x == 0) apart[(int64_t)as * blockIdx.x + d] = v;
+      }
+      if constexpr (PER) {
+        for (int d = 0; d < D / 2; ++d) {
+          const double v = block_sum((double)e.pd[d], scratch);
+          if (threadIdx.x == 0) apart[(int64_t)as * blockIdx.x + D + d] = v;
+        }
       }
     }
     if constexpr (LZ) {
@@ -1626,6 +1671,25 @@ __global__ void grad_ard_kernel(int D, const double* __restrict__ red_ard, const
   const int d = threadIdx.x;
   if (d == 0) g_hyper[0] = T(0);
   if (d < D) g_ard[d] = (T)((-1.0 / n_global) * (red_ard[d] + kuu_ard[d]));
+}
+
+// periodic contexts, behind grad_small_kernel: red / kuu = the 2 Dr embedded-coordinate sums, then the Dr sums of d / d log p_d (K_nm
+// part all-reduced with the payload, K_uu part).  The lengthscale gradient folds the two coordinates of an axis (ls_ard: one per axis, the
+// ARD segment g_ard; else all axes into slot 0 of g_hyper); the period one folds all axes when np = 1.
+template <typename T>
+__global__ void grad_per_kernel(int Dr, int ls_ard, int np, const double* __restrict__ red, const double* __restrict__ kuu, double n_global,
+                                T* __restrict__ g_hyper, T* __restrict__ g_ard, T* __restrict__ g_per) {
+  if (threadIdx.x != 0) return;
+  const double f = -1.0 / n_global;
+  double lt = 0, pt = 0;
+  for (int d = 0; d < Dr; ++d) {
+    const double l = red[2 * d] + kuu[2 * d] + red[2 * d + 1] + kuu[2 * d + 1], p = red[2 * Dr + d] + kuu[2 * Dr + d];
+    if (ls_ard) g_ard[d] = (T)(f * l);
+    if (np > 1) g_per[d] = (T)(f * p);
+    lt += l; pt += p;
+  }
+  g_hyper[0] = ls_ard ? T(0) : (T)(f * lt);
+  if (np == 1) g_per[0] = (T)(f * pt);
 }
 
 // trainable mean_function parameters (gdrf_set_mean_params): the caller's reduced sums of d elbo / d theta -> d loss / d theta, the scaling

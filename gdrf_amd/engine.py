@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 
-KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "rationalquadratic": 4}
+KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "rationalquadratic": 4, "periodic": 5}
 OPT_MODES = {"adam": 0, "adamw": 1, "clippedadam": 2}
 # update rules of gdrf_optim_step (include/gdrf_hip.h)
 OPT_RULES = {"adam": 0, "adamw": 1, "clippedadam": 2, "adamax": 3, "rmsprop": 4, "adagrad": 5, "adadelta": 6, "asgd": 7, "rprop": 8,
@@ -36,12 +36,13 @@ class Engine:
     """One device context for fixed (n_cap, M, K, V, D, dtype, kernel)."""
 
     opt_extra: Optional[torch.Tensor] = None     # third optimizer state vector (RMSprop with momentum and centered), on demand
+    period_count = 0                             # log-periods of a Periodic kernel's context (1 or D), 0 for the other kernels
 
     def __init__(self, n_cap: int, M: int, K: int, V: int, D: int, *, dtype=torch.float32, kernel: str = "rbf",
                  device="cuda:0", jitter: float = 1e-8, maxjitter: int = 15, process_group="auto", pure_fp32: bool = False,
                  store_t="auto", mfma_mode: str = "auto", learn_inducing: bool = False, whiten: bool = True,
                  hyper_backward: str = "auto", allreduce_fn=None, ard: bool = False, mean_params: Optional[Dict[str, tuple]] = None,
-                 rows_form: str = "auto"):
+                 rows_form: str = "auto", period_count: int = 1):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.GdrfHipError("gdrf_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
@@ -99,6 +100,12 @@ class Engine:
         self.ard = bool(ard)
         if self.ard:
             _lib.check(self.lib.gdrf_set_ard(self.ctx, 1), "gdrf_set_ard")
+        # Periodic kernel (gdrf_set_period_count): "log_period" is a segment of 1 or D log-periods
+        self.period_count = int(period_count) if kernel == "periodic" else 0
+        if kernel == "periodic":
+            if self.period_count not in (1, self.D):
+                raise ValueError(f"period_count must be 1 or D = {self.D}")
+            _lib.check(self.lib.gdrf_set_period_count(self.ctx, self.period_count), "gdrf_set_period_count")
         lay = (C.c_int64 * 7)()
         _lib.check(self.lib.gdrf_param_layout(self.ctx, lay), "gdrf_param_layout")
         zl = (C.c_int64 * 2)()
@@ -109,6 +116,10 @@ class Engine:
             al = (C.c_int64 * 2)()
             _lib.check(self.lib.gdrf_ard_layout(self.ctx, al), "gdrf_ard_layout")
             self.layout["log_lengthscale"] = al[0]
+        if self.period_count:
+            pl = (C.c_int64 * 2)()
+            _lib.check(self.lib.gdrf_periodic_layout(self.ctx, pl), "gdrf_periodic_layout")
+            self.layout["log_period"] = pl[0]
         # trainable mean_function parameters (gdrf_set_mean_params): {name: shape} in order, one segment of the parameter vector; their
         # sums of d elbo / d theta are written by the host into the last doubles of red_d (_write_mean_grads)
         self.mean_shapes = {str(k): torch.Size(v) for k, v in (mean_params or {}).items()}
@@ -200,6 +211,8 @@ class Engine:
         K, M, V = self.K, self.M, self.V
         if name == "log_lengthscale" and self.ard:
             return buf[o:o + self.D].view(self.D)
+        if name == "log_period":
+            return buf[o:o + 1].view(()) if self.period_count == 1 else buf[o:o + self.D].view(self.D)
         if name in ("log_lengthscale", "log_variance", "log_noise", "log_scale_mixture"):
             return buf[o:o + 1].view(())
         if name == "u_loc":
@@ -223,6 +236,7 @@ class Engine:
         """PARAM_NAMES plus the blocks only some configurations learn (RationalQuadratic's scale_mixture, inducing inputs, the
         mean_function's parameters)."""
         extra = (("log_scale_mixture",) if self.kernel == "rationalquadratic" else ()) + \
+                (("log_period",) if self.period_count else ()) + \
                 (("inducing_unc",) if self.learn_inducing else ()) + tuple(self.mean_shapes)
         return self.PARAM_NAMES + extra
 

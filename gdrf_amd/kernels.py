@@ -81,5 +81,30 @@ class RationalQuadratic(Kernel):
             raise ValueError("scale_mixture must be positive")
 
 
+class Periodic(Kernel):
+    """pyro.contrib.gp.kernels.Periodic: variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / period_d) / lengthscale_d^2).  ``period`` is
+    positive and learnable, one element or ``input_dim`` elements (one per input axis), in the scaled units the model sees (the unit
+    cube of its ``world``).  Up to two input dimensions (the device evaluates it on two embedded coordinates per axis)."""
+    name = "periodic"
+    kernel_id = 5
+
+    def __init__(self, input_dim: int, variance=None, lengthscale=None, period=None, active_dims=None):
+        super().__init__(input_dim, variance=variance, lengthscale=lengthscale, active_dims=active_dims)
+        t = torch.as_tensor(1.0 if period is None else period, dtype=torch.float64).detach().cpu()
+        if t.dim() <= 1 and t.numel() == 1:
+            t = t.reshape(())
+        elif t.dim() == 1 and t.numel() == self.input_dim:
+            t = t.clone()
+        else:
+            raise ValueError(f"period must have 1 or input_dim = {self.input_dim} elements along one axis, got shape {tuple(t.shape)}")
+        if not bool((t > 0).all()):
+            raise ValueError("period must be positive")
+        self.period = t
+
+    def __repr__(self):
+        p = self.period.tolist() if self.period.dim() == 1 else float(self.period)
+        return super().__repr__()[:-1] + f", period={p})"
+
+
 KERNEL_DICT = {"rbf": RBF, "matern32": Matern32, "matern52": Matern52, "exponential": Exponential,
                "rationalquadratic": RationalQuadratic}

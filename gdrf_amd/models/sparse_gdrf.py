@@ -26,6 +26,7 @@ _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convent
     "u_scale_tril_unc": "u_scale_tril_unconstrained",
     "inducing_unc": "_inducing_points_unconstrained",          # only when fixed_inducing_points=False
     "log_scale_mixture": "_kernel.scale_mixture_unconstrained",  # only with the RationalQuadratic kernel
+    "log_period": "_kernel.period_unconstrained",                # only with the Periodic kernel
 }
 MEAN_PREFIX = "_mean_function."      # + the name from named_parameters(): a trainable parameter of a torch.nn.Module mean_function
 
@@ -123,13 +124,18 @@ class ModelSnapshot:
     def restore(self, device: Optional[str] = None, mean_function: Callable = None, link_function: Callable = None):
         """A ``SparseMultinomialGDRF`` on ``device`` (default: the device the snapshot was taken on) holding these parameters.  A
         ``torch.nn.Module`` mean_function receives the stored ``_mean_function.*`` values; without one those entries are not used."""
-        from ..kernels import KERNEL_DICT
+        from ..kernels import KERNEL_DICT, Periodic
         m = self.meta
         if self._model is not None and device is None and mean_function is None and link_function is None:
             return self._model
         ls = self._state[_PARAM_KEYS["log_lengthscale"]]
         # an ARD checkpoint stores (D,) log-lengthscales: rebuild an ARD kernel (the values come from load_state_dict below)
-        kern = KERNEL_DICT[m["kernel"]](input_dim=int(m["D"]), lengthscale=torch.ones(int(m["D"])) if ls.dim() == 1 else 1.0, variance=1.0)
+        lsk = torch.ones(int(m["D"])) if ls.dim() == 1 else 1.0
+        if m["kernel"] == Periodic.name:          # the period's shape, () or (D,), from the checkpoint as well
+            per = self._state[_PARAM_KEYS["log_period"]]
+            kern = Periodic(input_dim=int(m["D"]), lengthscale=lsk, variance=1.0, period=torch.ones(int(m["D"])) if per.dim() == 1 else 1.0)
+        else:
+            kern = KERNEL_DICT[m["kernel"]](input_dim=int(m["D"]), lengthscale=lsk, variance=1.0)
         dtype = getattr(torch, m["dtype"])
         model = SparseMultinomialGDRF(
             num_observation_categories=int(m["V"]), num_topic_categories=int(m["K"]), world=[tuple(w) for w in m["world"]],
@@ -213,6 +219,8 @@ class SparseMultinomialGDRF:
         self._randomize_metric, self._randomize_iters = randomize_metric, int(randomize_iters)
         if not isinstance(kernel, Kernel):
             raise TypeError("kernel must be a gdrf_amd.kernels.RBF or Matern52")
+        if kernel.name == "periodic" and kernel.input_dim > 2:
+            raise ValueError(f"the Periodic kernel supports at most 2 input dimensions, got input_dim = {kernel.input_dim}")
         self._V = int(num_observation_categories)
         self._K = int(num_topic_categories)
         self._world = [(float(a), float(b)) for a, b in world]
@@ -277,7 +285,8 @@ class SparseMultinomialGDRF:
                      jitter=self._jitter, maxjitter=self._maxjitter, pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode,
                      learn_inducing=not self._fixed_inducing_points, whiten=self._whiten, hyper_backward=self._hyper_backward,
                      ard=self._kernel.ard, mean_params={n: tuple(p.shape) for n, p in self._mean_params},
-                     rows_form=self._rows_form)
+                     rows_form=self._rows_form,
+                     period_count=self._kernel.period.numel() if self._kernel.name == "periodic" else 1)
         new.set_inducing_points(self._inducing_points)
         new.set_dirichlet(self._dirichlet_param)
         new.link_function = self._link_function
@@ -302,6 +311,8 @@ class SparseMultinomialGDRF:
                 eng.view("log_lengthscale").fill_(float(self._kernel.lengthscale.log()))
             eng.view("log_variance").fill_(float(self._kernel.variance.log()))
             eng.view("log_noise").fill_(float(torch.tensor(self._init_noise, dtype=torch.float64).log()))
+            if self._kernel.name == "periodic":
+                eng.view("log_period").copy_(self._kernel.period.log().reshape(eng.view("log_period").shape))
             if self._kernel.name == "rationalquadratic":
                 eng.view("log_scale_mixture").fill_(float(self._kernel.scale_mixture.log()))
             eng.view("u_loc").zero_()
@@ -501,6 +512,13 @@ class SparseMultinomialGDRF:
     @property
     def kernel_lengthscale(self):
         return self._engine.view("log_lengthscale").exp().detach().cpu().numpy()
+
+    @property
+    def kernel_period(self):
+        """The Periodic kernel's period: a 0-d or (D,) array."""
+        if self._kernel.name != "periodic":
+            raise AttributeError("kernel_period: the model's kernel is not Periodic")
+        return self._engine.view("log_period").exp().detach().cpu().numpy()
 
     @property
     def kernel_variance(self):

@@ -9,7 +9,7 @@
  * gdrf_last_error()); pointers named *_dev are borrowed device pointers that the caller keeps
  * alive until the stream has been synchronised; `stream` is a hipStream_t passed as void*;
  * no exceptions cross the ABI; one host thread per context.  kernel_id: 0 RBF, 1 Matern52, 2 Matern32, 3 Exponential,
- * 4 RationalQuadratic.
+ * 4 RationalQuadratic, 5 Periodic (D <= 2, gdrf_set_period_count).
  * dtype fixes the element type of every "void*" real array below:
  *   GDRF_F32 (0)      float arrays.  The K-fold contractions are f32 GEMMs evaluated on the matrix cores in the arithmetic
  *                     gdrf_set_mfma_mode() selects (native f32 MFMA, or split operands on the 16-bit matrix path with f32
@@ -29,7 +29,7 @@ extern "C" {
 typedef struct gdrf_ctx gdrf_ctx;
 
 enum { GDRF_F32 = 0, GDRF_F64 = 1, GDRF_F32_PURE = 2 };
-enum { GDRF_RBF = 0, GDRF_MATERN52 = 1, GDRF_MATERN32 = 2, GDRF_EXPONENTIAL = 3, GDRF_RATIONALQUADRATIC = 4 };
+enum { GDRF_RBF = 0, GDRF_MATERN52 = 1, GDRF_MATERN32 = 2, GDRF_EXPONENTIAL = 3, GDRF_RATIONALQUADRATIC = 4, GDRF_PERIODIC = 5 };
 enum { GDRF_ADAM = 0, GDRF_ADAMW = 1, GDRF_CLIPPED_ADAM = 2 };
 enum { GDRF_PRED_LOC = 0, GDRF_PRED_TOPIC_PROBS = 1, GDRF_PRED_WORD_PROBS = 2, GDRF_PRED_PERPLEXITY = 3, GDRF_PRED_LOC_VAR = 4 };
 
@@ -115,6 +115,16 @@ int gdrf_inducing_layout(const gdrf_ctx* ctx, int64_t out[2]);
  * never called it. */
 int gdrf_set_ard(gdrf_ctx* ctx, int on);
 int gdrf_ard_layout(const gdrf_ctx* ctx, int64_t out[2]);
+/* Periodic kernel (kernel_id GDRF_PERIODIC, D <= 2): pyro.contrib.gp.kernels.Periodic,
+ * k(x, z) = variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / period_d) / lengthscale_d^2).  It is evaluated as the RBF kernel at lengthscale 1 on
+ * the embedded coordinates (cos(t_d x_d), sin(t_d x_d)) / lengthscale_d, t_d = 2 pi / period_d.  The flat parameter vector grows by a segment
+ * of log-periods (gdrf_periodic_layout -> {offset, count}; {offset of the would-be segment, 0} in other contexts), right behind the ARD
+ * segment when there is one.  Slot 0 holds the log-lengthscale unless gdrf_set_ard(1) gives one per axis.  gdrf_set_period_count sets
+ * count = 1 (one shared period, the default) or D; call it before reading gdrf_param_layout.  red_d then carries, at 8 + M*2D, 2D
+ * embedded-coordinate sums and D sums of d / d log period_d (all-reduced with the rest), and the learnable-inducing-input sums at 8 are
+ * (M, 2D) in the embedded coordinates.  The opt-in gdrf_set_hyper_backward(1) falls back to the f64 form. */
+int gdrf_set_period_count(gdrf_ctx* ctx, int count);
+int gdrf_periodic_layout(const gdrf_ctx* ctx, int64_t out[2]);
 /* Trainable mean_function parameters (gdrf/models/abstract_gdrf.py:33-48: the mean_function is an attribute of a gp.Parameterized, so the
  * parameters of a torch.nn.Module mean - registered by pyro.module - or a PyroModule mean's own PyroParams land in the param store and
  * SVI.step trains them with the optimizer of every other parameter, gdrf/train_script.py:365-371,467).  The library never evaluates the
@@ -141,7 +151,7 @@ void gdrf_ctx_destroy(gdrf_ctx* ctx);
  * kernels.isotropic.RationalQuadratic: variance * (1 + r2 / (2 scale_mixture))^(-scale_mixture)); the other kernels
  * ignore it and its gradient is 0. */
 int gdrf_param_layout(const gdrf_ctx* ctx, int64_t out[7]);
-/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}; total_d = 8 + M*D (+ D in ARD contexts)
+/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}; total_d = 8 + M*D (+ D in ARD contexts; 8 + M*2D + 3D in periodic ones)
  * (+ the count of gdrf_set_mean_params, the last doubles). */
 int gdrf_red_layout(const gdrf_ctx* ctx, int64_t out[6]);
 /* The step's ONE collective ("one ncclAllReduce(sum) per step over a flat buffer"): gdrf_payload_pack copies the
