@@ -33,6 +33,8 @@ SIGNATURES = {
     "gdrf_ard_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_set_period_count": (_int, [_vp, _int]),
     "gdrf_periodic_layout": (_int, [_vp, C.POINTER(_i64)]),
+    "gdrf_set_product": (_int, [_vp, _int, C.POINTER(C.c_int)]),
+    "gdrf_product_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_set_mean_params": (_int, [_vp, _i64]),
     "gdrf_mean_param_layout": (_int, [_vp, C.POINTER(_i64)]),
     "gdrf_ctx_destroy": (None, [_vp]),

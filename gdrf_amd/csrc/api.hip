@@ -94,6 +94,10 @@ struct gdrf_ctx {
   // Periodic kernel (kernel_id GDRF_PERIODIC): D = 2 Dr embedded coordinates per raw input axis pair (kernels_mm.h: prep_hyper_per_kernel), np
   // log-periods (1 or Dr; 0 in other contexts), the embedded rows of the current call (Xe, xe_cap rows), the inducing phases t_d z_d (Zph)
   int per, Dr, np; void *Xe, *Zph; int64_t xe_cap;
+  // Product kernel (kernel_id GDRF_PRODUCT, gdrf_set_product): a periodic context whose embedded coordinates come from a table of nf factors
+  // {kind, axis count, lengthscale count, period count, axes[4]}; nls / nper: elements of its log-lengthscale and log-period segments (the
+  // nf log-variances come first).  npair: the pair coordinates of a periodic or product context (Dr in a periodic one).
+  int prod, nf, pfac[GDRF_DMAX][8], nls, nper, npair;
   int64_t mean_count;         // trainable mean_function parameters (gdrf_set_mean_params): elements of their segment, 0 = none
   double* opt_part; int64_t opt_part_cap;   // gdrf_optim_step: per-workgroup sums of squares of the clip_norm pass, allocated on first use
   int rows_form;              // gdrf_set_rows_form: 0 the LDS row forms, 1 the vocabulary-streamed form (rows_vstream.h)
@@ -131,18 +135,22 @@ static int64_t poff(const gdrf_ctx* c, int which) {
   const int64_t o_S = round_up(o_phi + (int64_t)c->K * c->V, 4);
   const int64_t o_Z = round_up(o_S + (int64_t)c->K * c->M * c->M, 4);          // unconstrained inducing inputs (M, D)
   const int64_t o_ard = round_up(o_Z + (int64_t)c->M * c->Dr, 4);              // ARD contexts only: the D log-lengthscales
-  const int64_t o_per = o_ard + (c->ard ? c->Dr : 0);                          // periodic contexts only: the np log-periods, right behind them
-  const int64_t o_mean = (c->ard || c->per) ? round_up(o_per + c->np, 4) : o_ard;   // contexts with gdrf_set_mean_params only: mean_function parameters
+  // periodic contexts only: the np log-periods, right behind them.  Product contexts: the nf factor log-variances at o_ard, then the nls
+  // log-lengthscales (o_pls), then the nper log-periods (o_per)
+  const int64_t o_pls = o_ard + c->nf;
+  const int64_t o_per = c->prod ? o_pls + c->nls : o_ard + (c->ard ? c->Dr : 0);
+  const int64_t o_mean = c->prod ? round_up(o_per + c->nper, 4)
+                                 : (c->ard || c->per) ? round_up(o_per + c->np, 4) : o_ard;   // contexts with gdrf_set_mean_params only: mean_function parameters
   const int64_t total = c->mean_count ? round_up(o_mean + c->mean_count, 4) : o_mean;
   switch (which) { case 0: return 0; case 1: return 1; case 2: return 2; case 3: return o_uloc; case 4: return o_phi;
                    case 5: return o_S; case 7: return o_Z; case 8: return o_ard; case 9: return o_mean; case 10: return o_per;
-                   default: return total; }
+                   case 11: return o_pls; default: return total; }
 }
 // doubles of red_d: 8 scalars, the (M, D) inducing-input sums, in ARD contexts the D sums of d / d log ls_d over the rows, then the
 // caller's sums of d elbo / d theta of the mean_function parameters (gdrf_set_mean_params)
-// periodic contexts: D (= 2 Dr) embedded-coordinate sums in place of the ARD ones, then the Dr sums of d / d log p_d
+// periodic and product contexts: D embedded-coordinate sums in place of the ARD ones, then the npair sums of d / d log p
 static int64_t red_nd(const gdrf_ctx* c) {
-  return 8 + (int64_t)c->M * c->D + ((c->ard || c->per) ? c->D : 0) + (c->per ? c->Dr : 0) + c->mean_count;
+  return 8 + (int64_t)c->M * c->D + ((c->ard || c->per) ? c->D : 0) + (c->per ? c->npair : 0) + c->mean_count;
 }
 static int64_t red_mean_off(const gdrf_ctx* c) { return red_nd(c) - c->mean_count; }
 static int64_t roff(const gdrf_ctx* c, int which) {
@@ -164,6 +172,52 @@ int gdrf_red_layout(const gdrf_ctx* c, int64_t out[6]) {
 int gdrf_inducing_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 7); out[1] = (int64_t)c->M * c->Dr; return 0; }
 int gdrf_ard_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 8); out[1] = c->ard ? c->Dr : 0; return 0; }
 int gdrf_periodic_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 10); out[1] = c->np; return 0; }
+int gdrf_product_layout(const gdrf_ctx* c, int64_t out[6]) {
+  out[0] = poff(c, 8); out[1] = c->nf; out[2] = poff(c, 11); out[3] = c->nls; out[4] = poff(c, 10); out[5] = c->nper;
+  return 0;
+}
+// the parameters a factorisation depends on beyond slots 0-3 and Z, contiguous from poff(c, 8): the ARD log-lengthscales and the log-periods
+// of a periodic context, the three segments of a product one
+static int snap_extra(const gdrf_ctx* c) { return c->prod ? c->nf + c->nls + c->nper : (c->ard ? c->Dr : 0) + c->np; }
+// embedded coordinates the context's buffers hold: a product context's table may change until its first step
+static int dcap(const gdrf_ctx* c) { return c->prod ? GDRF_DMAX : c->D; }
+// The embedded-coordinate table (kernels_mm.h: CoordTab) with absolute parameter indices.  A periodic context is one Periodic factor over all
+// its raw axes; a product context lists the sources of its Periodic factors (pairs), then those of its RBF factors, each in factor order.
+static CoordTab coord_tab(const gdrf_ctx* c) {
+  CoordTab t{};
+  t.dr = c->Dr;
+  if (!c->prod) {
+    t.D = 2 * c->Dr; t.npair = t.nsrc = c->Dr; t.nvar = 1; t.var[0] = 1;
+    for (int d = 0; d < c->Dr; ++d) {
+      t.ax[d] = d;
+      t.ls[d] = c->ard ? poff(c, 8) + d : 0;
+      t.per[d] = poff(c, 10) + (c->np > 1 ? d : 0);
+    }
+    return t;
+  }
+  int64_t lsb[GDRF_DMAX], pb[GDRF_DMAX], ol = poff(c, 11), op = poff(c, 10);
+  for (int f = 0; f < c->nf; ++f) {
+    lsb[f] = ol; ol += c->pfac[f][2];
+    pb[f] = op; op += c->pfac[f][3];
+    t.var[f] = poff(c, 8) + f;
+  }
+  t.nvar = c->nf;
+  int j = 0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int f = 0; f < c->nf; ++f) {
+      const int* fa = c->pfac[f];
+      if ((fa[0] == GDRF_PERIODIC) != (pass == 0)) continue;
+      for (int k = 0; k < fa[1]; ++k, ++j) {
+        t.ax[j] = fa[4 + k];
+        t.ls[j] = lsb[f] + (fa[2] > 1 ? k : 0);
+        if (pass == 0) t.per[j] = pb[f] + (fa[3] > 1 ? k : 0);
+      }
+      if (pass == 0) t.npair = j;
+    }
+  t.nsrc = j;
+  t.D = 2 * t.npair + (t.nsrc - t.npair);
+  return t;
+}
 // the covariance forms of the forward and predictive paths: ARD scales on the rows (a periodic context's embedding carries its own)
 static bool ard_fwd(const gdrf_ctx* c) { return c->ard && !c->per; }
 int gdrf_mean_param_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 9); out[1] = c->mean_count; return 0; }
@@ -240,14 +294,22 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   if (K > GDRF_TILE) return fail(-1, "gdrf_ctx_create", "num_topic_categories > 128 not supported (loc = W U^T runs as one 128-wide column tile)");
   if (D > GDRF_DMAX) return fail(-1, "gdrf_ctx_create", "more than 4 input dimensions not supported");
   if (dtype != GDRF_F32 && dtype != GDRF_F64 && dtype != GDRF_F32_PURE) return fail(-1, "gdrf_ctx_create", "dtype");
-  if (kernel_id < GDRF_RBF || kernel_id > GDRF_PERIODIC) return fail(-1, "gdrf_ctx_create", "kernel_id");
+  if (kernel_id < GDRF_RBF || kernel_id > GDRF_PRODUCT) return fail(-1, "gdrf_ctx_create", "kernel_id");
   if (kernel_id == GDRF_PERIODIC && 2 * D > GDRF_DMAX) return fail(-1, "gdrf_ctx_create", "the Periodic kernel supports at most 2 input dimensions");
   const int Dr = D;
   if (kernel_id == GDRF_PERIODIC) D = 2 * D;       // the embedded coordinates (cos, sin) of every raw axis
+  if (kernel_id == GDRF_PRODUCT) D = GDRF_DMAX;    // buffers for any table; the default table is one RBF factor over every axis
   HIPCHK(hipSetDevice(device));
   gdrf_ctx* c = new gdrf_ctx();
   c->dev = device; c->M = M; c->Mp = (int)round_up(M, GDRF_MPAD); c->K = K; c->V = V; c->D = D; c->Dr = Dr;
-  c->per = kernel_id == GDRF_PERIODIC; c->np = c->per ? 1 : 0; c->Xe = c->Zph = nullptr; c->xe_cap = 0;
+  c->per = kernel_id == GDRF_PERIODIC || kernel_id == GDRF_PRODUCT; c->np = kernel_id == GDRF_PERIODIC ? 1 : 0; c->Xe = c->Zph = nullptr; c->xe_cap = 0;
+  c->prod = kernel_id == GDRF_PRODUCT; c->nf = c->nls = c->nper = 0; c->npair = kernel_id == GDRF_PERIODIC ? Dr : 0;
+  memset(c->pfac, 0, sizeof(c->pfac));
+  if (c->prod) {
+    c->nf = 1; c->nls = 1; c->D = Dr;
+    c->pfac[0][0] = GDRF_RBF; c->pfac[0][1] = Dr; c->pfac[0][2] = 1;
+    for (int d = 0; d < Dr; ++d) c->pfac[0][4 + d] = d;
+  }
   c->dtype = dtype; c->kind = c->per ? GDRF_RBF : kernel_id; c->ncap = n_cap; c->ldk = round_up(n_cap, 4);   // periodic: the RBF forms, embedded
   c->esz = dtype == GDRF_F64 ? 8 : 4;
   c->ssz = dtype == GDRF_F32_PURE ? 4 : 8;
@@ -271,7 +333,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   AL(c->Kuu, mms) AL(c->Lw, mms) AL(c->Lo, mms)
   c->mmslab_bytes = 8 * mms;
   c->prefact_valid = 0; c->prefact_jitter = 0;
-  AL(c->snap, (size_t)(4 + (size_t)c->M * c->D + GDRF_DMAX) * c->esz)
+  AL(c->snap, (size_t)(4 + (size_t)c->M * D + (c->prod ? 3 : 1) * GDRF_DMAX) * c->esz)
   AL(c->mmslab, c->mmslab_bytes) AL(c->L, mms) AL(c->LT, mms) AL(c->Linv, mms) AL(c->LinvT, mms)
   AL(c->Dinv, (size_t)(c->Mp / 32) * 1024 * c->ssz)
   AL(c->t0, mms) AL(c->t1, mms) AL(c->t2, mms) AL(c->GTs, mms)
@@ -312,9 +374,10 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   AL(c->alpha_dev, (size_t)K * V * sizeof(double))
   AL(c->hyp, sizeof(HyperPer)) AL(c->hyp_probe, sizeof(HyperPer)) AL(c->flag, 128)
   if (c->per) {
-    // apart: D coordinate sums and Dr period sums per backward workgroup or per inducing point
-    AL(c->Xe, (size_t)n_cap * D * c->esz) AL(c->Zp, (size_t)c->Mp * D * c->esz) AL(c->Zph, (size_t)c->Mp * Dr * c->ssz)
-    AL(c->apart, (size_t)c->dpart_len * (D + Dr) * sizeof(double))
+    // apart: D coordinate sums and npair period sums per backward workgroup or per inducing point
+    const int npc = c->prod ? GDRF_DMAX / 2 : Dr;
+    AL(c->Xe, (size_t)n_cap * D * c->esz) AL(c->Zp, (size_t)c->Mp * D * c->esz) AL(c->Zph, (size_t)c->Mp * npc * c->ssz)
+    AL(c->apart, (size_t)c->dpart_len * (D + npc) * sizeof(double))
     c->xe_cap = n_cap;
   }
   AL(c->ssc, (size_t)SplitLay{K}.nfloats() * sizeof(float)) AL(c->smx, (size_t)SplitLay{K}.nmax() * sizeof(unsigned))
@@ -443,7 +506,7 @@ int gdrf_set_learn_inducing(gdrf_ctx* c, int on) {
   HIPCHK(hipSetDevice(c->dev));
   if (on && !c->zpart) {
     void* p = nullptr;
-    const size_t bytes = (size_t)((c->ncap + GDRF_TILE - 1) / GDRF_TILE) * c->M * c->D * sizeof(double);
+    const size_t bytes = (size_t)((c->ncap + GDRF_TILE - 1) / GDRF_TILE) * c->M * dcap(c) * sizeof(double);
     hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(zpart)", hipGetErrorString(e));
     c->zpart = (double*)p; c->allocs.push_back(p);
@@ -453,6 +516,7 @@ int gdrf_set_learn_inducing(gdrf_ctx* c, int on) {
 }
 int gdrf_set_ard(gdrf_ctx* c, int on) {
   if (on != 0 && on != 1) return fail(-1, "gdrf_set_ard", "on must be 0 or 1");
+  if (c->prod) return fail(-1, "gdrf_set_ard", "a product context takes its lengthscale counts from gdrf_set_product");
   HIPCHK(hipSetDevice(c->dev));
   if (on && !c->Zp) {
     // apart: D per backward workgroup (at most dpart_len / 3 of them, gdrf_step_local checks) or per inducing point (M < dpart_len)
@@ -470,10 +534,40 @@ int gdrf_set_ard(gdrf_ctx* c, int on) {
   return 0;
 }
 int gdrf_set_period_count(gdrf_ctx* c, int count) {
-  if (!c->per) return fail(-1, "gdrf_set_period_count", "not a periodic context (kernel_id GDRF_PERIODIC)");
+  if (!c->per || c->prod) return fail(-1, "gdrf_set_period_count", "not a periodic context (kernel_id GDRF_PERIODIC)");
   if (count != 1 && count != c->Dr) return fail(-1, "gdrf_set_period_count", "count must be 1 or the number of input dimensions");
   if (c->g_loc) return fail(-1, "gdrf_set_period_count", "call it before the first gdrf_step_local2");
   c->np = count;
+  c->prefact_valid = 0;
+  return 0;
+}
+int gdrf_set_product(gdrf_ctx* c, int nfactors, const int* table) {
+  if (!c->prod) return fail(-1, "gdrf_set_product", "not a product context (kernel_id GDRF_PRODUCT)");
+  if (c->g_loc) return fail(-1, "gdrf_set_product", "call it before the first gdrf_step_local2");
+  if (nfactors < 1 || nfactors > GDRF_DMAX || !table) return fail(-1, "gdrf_set_product", "1 to 4 factors");
+  int coords = 0, nls = 0, nper = 0, npair = 0;
+  for (int f = 0; f < nfactors; ++f) {
+    const int* fa = table + 8 * f;
+    const int kind = fa[0], na = fa[1];
+    if (kind != GDRF_RBF && kind != GDRF_PERIODIC) return fail(-1, "gdrf_set_product", "a factor's kind must be GDRF_RBF or GDRF_PERIODIC");
+    if (na < 1 || na > GDRF_DMAX) return fail(-1, "gdrf_set_product", "a factor reads 1 to 4 axes");
+    for (int k = 0; k < na; ++k) {
+      if (fa[4 + k] < 0 || fa[4 + k] >= c->Dr) return fail(-1, "gdrf_set_product", "an active axis is not < D");
+      for (int q = 0; q < k; ++q)
+        if (fa[4 + q] == fa[4 + k]) return fail(-1, "gdrf_set_product", "a factor lists an axis twice");
+    }
+    if (fa[2] != 1 && fa[2] != na) return fail(-1, "gdrf_set_product", "a factor's lengthscale count must be 1 or its axis count");
+    if (kind == GDRF_RBF && fa[3] != 0) return fail(-1, "gdrf_set_product", "an RBF factor has no period");
+    if (kind == GDRF_PERIODIC && fa[3] != 1 && fa[3] != na)
+      return fail(-1, "gdrf_set_product", "a Periodic factor's period count must be 1 or its axis count");
+    coords += kind == GDRF_PERIODIC ? 2 * na : na;
+    npair += kind == GDRF_PERIODIC ? na : 0;
+    nls += fa[2]; nper += fa[3];
+  }
+  if (coords > GDRF_DMAX) return fail(-1, "gdrf_set_product", "more than 4 embedded coordinates (an RBF axis takes 1, a Periodic axis 2)");
+  for (int f = 0; f < GDRF_DMAX; ++f)
+    for (int k = 0; k < 8; ++k) c->pfac[f][k] = f < nfactors ? table[8 * f + k] : 0;
+  c->nf = nfactors; c->nls = nls; c->nper = nper; c->npair = npair; c->D = coords;
   c->prefact_valid = 0;
   return 0;
 }
@@ -604,19 +698,17 @@ template <typename T, typename TS> struct Impl {
   // nlev (<= 8) Cholesky attempts in ONE launch, in the N-side precision (what the reference's fp32
   // torch.linalg.cholesky would see): K_uu built once, one workgroup per cumulative jitter; flags in c->flag[8..8+nlev)
   // (slot 0 is the solve factorisation's, so a probe may run on another stream beside gdrf_factorize)
-  // periodic contexts: the hyper-parameter block h and the embedded inducing inputs zout (M, 2 Dr) in precision TO, with their phases
-  // t_d z_d (M, Dr) when ph is given
+  // periodic and product contexts: the hyper-parameter block h and the embedded inducing inputs zout (M, D) in precision TO, with the
+  // phases of their pairs (M, npair) when ph is given
   template <typename TO>
   static void per_prep(gdrf_ctx* c, const T* Z, const T* params, Hyper* h, void* zout, void* ph, hipStream_t s) {
-    const T* lls = c->ard ? params + poff(c, 8) : params;
-    const T* lp = params + poff(c, 10);
-    const int ls_step = c->ard ? 1 : 0, p_step = c->np > 1 ? 1 : 0;
-    const int64_t nz = (int64_t)c->M * c->Dr;
-    hipLaunchKernelGGL(prep_hyper_per_kernel<T>, dim3(1), dim3(64), 0, s, params, lls, ls_step, lp, p_step, c->Dr, (HyperPer*)h);
-    hipLaunchKernelGGL((embed_per_kernel<T, TO>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, (int64_t)c->M, c->Dr, Z, lls, ls_step, lp,
-                       p_step, (TO*)zout, (TO*)ph);
+    const CoordTab tb = coord_tab(c);
+    const int64_t nz = (int64_t)c->M * tb.nsrc;
+    hipLaunchKernelGGL(prep_hyper_per_kernel<T>, dim3(1), dim3(64), 0, s, params, tb, (HyperPer*)h);
+    hipLaunchKernelGGL((embed_per_kernel<T, TO>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, (int64_t)c->M, tb, Z, params, (TO*)zout,
+                       (TO*)ph);
   }
-  // periodic contexts: the embedded rows (n, 2 Dr) of this call into c->Xe.  More rows than it holds (gdrf_knm, gdrf_predict) grow it; the
+  // periodic and product contexts: the embedded rows (n, D) of this call into c->Xe.  More rows than it holds (gdrf_knm, gdrf_predict) grow it; the
   // old buffer stays allocated until gdrf_ctx_destroy, since work queued before may still read it.
   static int per_rows(gdrf_ctx* c, const T* X, int64_t n, const T* params, hipStream_t s) {
     if (n > c->xe_cap) {
@@ -625,10 +717,10 @@ template <typename T, typename TS> struct Impl {
       if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(embedded rows)", hipGetErrorString(e));
       c->allocs.push_back(p); c->Xe = p; c->xe_cap = n;
     }
-    const int64_t nx = n * c->Dr;
+    const CoordTab tb = coord_tab(c);
+    const int64_t nx = n * tb.nsrc;
     if (nx > 0)
-      hipLaunchKernelGGL((embed_per_kernel<T, T>), dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, n, c->Dr, X,
-                         c->ard ? params + poff(c, 8) : params, c->ard ? 1 : 0, params + poff(c, 10), c->np > 1 ? 1 : 0, (T*)c->Xe, (T*)nullptr);
+      hipLaunchKernelGGL((embed_per_kernel<T, T>), dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, n, tb, X, params, (T*)c->Xe, (T*)nullptr);
     LAUNCHCHK("embed rows (periodic)");
     return 0;
   }
@@ -673,7 +765,7 @@ template <typename T, typename TS> struct Impl {
     const int64_t nzs = (int64_t)M * c->Dr;
     if (mode == 2 && c->prefact_valid && jitter == c->prefact_jitter) {
       hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 1, c->flag + 16, params + poff(c, 8),
-                         (c->ard ? c->Dr : 0) + c->np);
+                         snap_extra(c));
       // the factorisation stays valid for further calls with the same inputs (a predictive evaluation between two steps): every reuse
       // compares again, and any fresh factorisation below invalidates it first
       LAUNCHCHK("factorize (reuse)");
@@ -715,7 +807,7 @@ template <typename T, typename TS> struct Impl {
     c->fact_pending = 1;
     if (mode == 1) {
       hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 0, (int*)nullptr, params + poff(c, 8),
-                         (c->ard ? c->Dr : 0) + c->np);
+                         snap_extra(c));
       c->prefact_valid = 1; c->prefact_jitter = jitter;
     }
     LAUNCHCHK("factorize");
@@ -1245,7 +1337,7 @@ template <typename T, typename TS> struct Impl {
           else hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, false, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
         }
         // the coordinate sums, then the period sums: red_d[8 + M D ..)
-        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D + c->Dr, redd + 8 + (int64_t)M * c->D);
+        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D + c->npair, redd + 8 + (int64_t)M * c->D);
       } else if (c->ard) {
         if (c->learn_z) {
           BwdKnmProb<TS, T, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
@@ -1520,10 +1612,10 @@ template <typename T, typename TS> struct Impl {
     // YT = Linv^T P^T ; S' = Linv^T Y
     if ((rc = mm_nt<TS>(c, Q(c->LinvT), 0, Q(c->t2), 0, Q(c->t0), 0, TS(1), 1, s))) return rc;
     if ((rc = mm_nt<TS>(c, Q(c->LinvT), 0, Q(c->t0), 0, Q(c->t1), 0, TS(1), 1, s))) return rc;
-    if (c->per) {          // K_uu coordinate and period sums -> dsmall[9..9+D+Dr) (dsmall[8] is the ll_const scratch)
+    if (c->per) {          // K_uu coordinate and period sums -> dsmall[9..9+D+npair) (dsmall[8] is the ll_const scratch)
       hipLaunchKernelGGL((kuu_bar_reduce_kernel<TS, true, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D,
                          c->kind, c->hyp, c->dpart, c->apart, (const TS*)Q(c->Zph));
-      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, (int64_t)M, c->D + c->Dr, c->dsmall + 9);
+      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, (int64_t)M, c->D + c->npair, c->dsmall + 9);
     } else if (c->ard) {          // K_uu sums of d / d log ls_d -> dsmall[3..3+D)
       hipLaunchKernelGGL((kuu_bar_reduce_kernel<TS, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind,
                          c->hyp, c->dpart, c->apart);
@@ -1552,8 +1644,8 @@ template <typename T, typename TS> struct Impl {
     hipLaunchKernelGGL(grad_small_kernel<T>, dim3(1), dim3(256), 0, s, M, Mp, K, V, c->hyp, redd, c->dsmall, ubar, phib, P(c->phi),
                        c->alpha_dev, c->lgam_const, ll_const, n_global, grads, grads + poff(c, 3), grads + poff(c, 4), c->flag, out_d);
     if (c->per)
-      hipLaunchKernelGGL(grad_per_kernel<T>, dim3(1), dim3(64), 0, s, c->Dr, c->ard, c->np, (const double*)redd + 8 + (int64_t)M * c->D,
-                         (const double*)c->dsmall + 9, n_global, grads, grads + poff(c, 8), grads + poff(c, 10));
+      hipLaunchKernelGGL(grad_per_kernel<T>, dim3(1), dim3(64), 0, s, coord_tab(c), (const double*)redd + 8 + (int64_t)M * c->D,
+                         (const double*)c->dsmall + 9, n_global, grads);
     else if (c->ard)
       hipLaunchKernelGGL(grad_ard_kernel<T>, dim3(1), dim3(64), 0, s, c->D, (const double*)redd + 8 + (int64_t)M * c->D, (const double*)c->dsmall + 3,
                          n_global, grads, grads + poff(c, 8));

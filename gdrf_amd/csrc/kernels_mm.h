@@ -15,8 +15,21 @@ namespace gdrf {
 // hyper-parameter block kept on the device (double): filled by prep_hyper
 // sc: ARD contexts only (gdrf_set_ard): the per-dimension coordinate scales 1 / ls_d; the isotropic forms then run with ls = 1
 struct Hyper { double ls, var, noise, inv_ls2, alpha; double sc[GDRF_DMAX]; };     // alpha: RationalQuadratic scale_mixture (parameter slot 3)
-// tp: periodic contexts only (gdrf_set_period_count): the angular frequencies 2 pi / period_d of the raw input axes
-struct HyperPer : Hyper { double tp[GDRF_DMAX]; };
+// Periodic and product contexts (kernel_id GDRF_PERIODIC, GDRF_PRODUCT): tp = the angular frequencies 2 pi / period of the npair pair
+// coordinates, il = 1 / ls of every embedded coordinate, cax = its raw axis, pax = the raw axis of each pair, dr = the raw axes of a row
+struct HyperPer : Hyper {
+  double tp[GDRF_DMAX]; double il[GDRF_DMAX];
+  int npair, dr; int pax[GDRF_DMAX / 2]; int cax[GDRF_DMAX];
+};
+// The embedded-coordinate table of a periodic or product context (api.hip: coord_tab).  A source is one raw axis of one factor: a Periodic
+// factor's axis is a pair source (two coordinates, cos and sin), an RBF factor's a linear one.  Pair sources come first: pair j owns the
+// coordinates 2 j, 2 j + 1, linear source j >= npair the coordinate npair + j.  ax / ls / per: the source's raw axis, the parameter-vector
+// index of its log-lengthscale and (pairs) of its log-period; var: the indices of the nvar factor log-variances (their sum is log variance).
+struct CoordTab {
+  int D, npair, nsrc, dr, nvar;
+  int ax[GDRF_DMAX];
+  int64_t ls[GDRF_DMAX], per[GDRF_DMAX / 2], var[GDRF_DMAX];
+};
 
 template <typename T>
 __global__ void prep_hyper_kernel(const T* __restrict__ params, Hyper* h) {
@@ -46,34 +59,50 @@ __global__ void scale_z_kernel(int64_t nz, int D, const T* __restrict__ Z, const
 
 // Periodic (pyro.contrib.gp.kernels.Periodic: variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / p_d) / ls_d^2)) is the RBF kernel at ls = 1 on
 // the embedded coordinates e(x) = (cos(t_d x_d) / ls_d, sin(t_d x_d) / ls_d), t_d = 2 pi / p_d: |e_d(x) - e_d(z)|^2 = 4 sin^2(t_d (x_d - z_d) / 2) / ls_d^2.
-// A context of Dr raw axes runs every covariance form on D = 2 Dr embedded coordinates.  log_ls / log_p: ls_step / p_step = 0 for one
-// shared value, 1 for one per axis.  The scales sc are 1 (the embedding carries 1 / ls_d): the ARD instantiations give the per-coordinate sums.
+// An RBF factor adds the linear coordinate x_d / ls_d, and a product of such factors is prod(variances) * exp(-|e(x) - e(z)|^2 / 2): the RBF
+// kernel at ls = 1 on the concatenated coordinates of the table tb.  Every covariance form then runs on D = tb.D embedded coordinates.  The
+// scales sc are 1 (the embedding carries 1 / ls): the ARD instantiations give the per-coordinate sums.
 template <typename T>
-__global__ void prep_hyper_per_kernel(const T* __restrict__ params, const T* __restrict__ log_ls, int ls_step, const T* __restrict__ log_p,
-                                      int p_step, int Dr, HyperPer* h) {
+__global__ void prep_hyper_per_kernel(const T* __restrict__ params, CoordTab tb, HyperPer* h) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    h->ls = 1.0; h->var = exp((double)params[1]); h->noise = exp((double)params[2]); h->inv_ls2 = 1.0; h->alpha = exp((double)params[3]);
+    double lv = 0;
+    for (int f = 0; f < tb.nvar; ++f) lv += (double)params[tb.var[f]];
+    h->ls = 1.0; h->var = exp(lv); h->noise = exp((double)params[2]); h->inv_ls2 = 1.0; h->alpha = exp((double)params[3]);
+    h->npair = tb.npair; h->dr = tb.dr;
     for (int d = 0; d < GDRF_DMAX; ++d) {
-      h->sc[d] = d < 2 * Dr ? 1.0 : 0.0;
-      h->tp[d] = d < Dr ? 6.283185307179586477 * exp(-(double)log_p[d * p_step]) : 0.0;
+      h->sc[d] = d < tb.D ? 1.0 : 0.0;
+      h->tp[d] = d < tb.npair ? 6.283185307179586477 * exp(-(double)params[tb.per[d]]) : 0.0;
+      h->il[d] = 0.0; h->cax[d] = 0;
+    }
+    for (int d = 0; d < GDRF_DMAX / 2; ++d) h->pax[d] = d < tb.npair ? tb.ax[d] : 0;
+    for (int j = 0; j < tb.nsrc; ++j) {
+      const double il = exp(-(double)params[tb.ls[j]]);
+      const int c0 = j < tb.npair ? 2 * j : tb.npair + j, nc = j < tb.npair ? 2 : 1;
+      for (int k = 0; k < nc; ++k) { h->il[c0 + k] = il; h->cax[c0 + k] = tb.ax[j]; }
     }
   }
 }
-// out[i][2d], out[i][2d + 1] = cos(t_d x_id) / ls_d, sin(t_d x_id) / ls_d in the output precision (computed in double); ph[i][d] = t_d x_id
-// when ph is given.  One thread per (row, raw axis).
+// The embedded rows: for a pair source j, out[i][2j], out[i][2j + 1] = cos(t x) / ls, sin(t x) / ls and, when ph is given, ph[i][j] = t x;
+// for a linear source out[i][npair + j] = x / ls; x = X[i][ax_j].  Output precision, computed in double.  One thread per (row, source).
 template <typename T, typename TO>
-__global__ void embed_per_kernel(int64_t n, int Dr, const T* __restrict__ X, const T* __restrict__ log_ls, int ls_step, const T* __restrict__ log_p,
-                                 int p_step, TO* __restrict__ out, TO* __restrict__ ph) {
+__global__ void embed_per_kernel(int64_t n, CoordTab tb, const T* __restrict__ X, const T* __restrict__ params, TO* __restrict__ out,
+                                 TO* __restrict__ ph) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * Dr) return;
-  const int d = (int)(i % Dr);
-  const double t = 6.283185307179586477 * exp(-(double)log_p[d * p_step]), il = exp(-(double)log_ls[d * ls_step]);
-  const double a = t * (double)X[i];
-  double sn, cs;
-  sincos(a, &sn, &cs);
-  out[2 * i] = (TO)(cs * il);
-  out[2 * i + 1] = (TO)(sn * il);
-  if (ph) ph[i] = (TO)a;
+  if (i >= n * tb.nsrc) return;
+  const int64_t r = i / tb.nsrc;
+  const int j = (int)(i - r * tb.nsrc);
+  const double il = exp(-(double)params[tb.ls[j]]), x = (double)X[r * tb.dr + tb.ax[j]];
+  if (j < tb.npair) {
+    const double t = 6.283185307179586477 * exp(-(double)params[tb.per[j]]);
+    const double a = t * x;
+    double sn, cs;
+    sincos(a, &sn, &cs);
+    out[r * tb.D + 2 * j] = (TO)(cs * il);
+    out[r * tb.D + 2 * j + 1] = (TO)(sn * il);
+    if (ph) ph[r * tb.npair + j] = (TO)a;
+  } else {
+    out[r * tb.D + tb.npair + j] = (TO)(x * il);
+  }
 }
 
 // the values a factorisation depends on - the first four parameters (log lengthscale, variance, noise, scale mixture), the inducing inputs and,
@@ -750,8 +779,9 @@ __global__ void phi_tril_kernel(const T* __restrict__ Q, int Mp, T* __restrict__
 // sum_{ij} Kuu_bar * K0,  sum_{ij} Kuu_bar * dK0/dlog(ls)  and  sum_{ij} Kuu_bar * dK0/dlog(alpha), Kuu_bar = (S' + S'^T)/2 ;
 // one partial triple per block.  ARD (Z = the scaled inducing inputs, ls = 1): also the D sums
 // sum_j Kuu_bar * dK0/dlog(ls_d) = sum_j Kuu_bar * dk/dr2 * (-2) (z_id - z_jd)^2 into apart[D * i + d]
-// PER (periodic contexts, ARD set: Z = the embedded inducing inputs, ph = their phases t_d z_d): also the D / 2 sums of d / d log p_d,
-// sum_j Kuu_bar * dk/dr2 * (-2) (ph_id - ph_jd) (s_id c_jd - c_id s_jd), behind the D coordinate sums: apart stride D + D / 2
+// PER (periodic and product contexts, ARD set: Z = the embedded inducing inputs, ph = the phases t_p z_p of their npair pairs): also the
+// npair sums of d / d log p_p, sum_j Kuu_bar * dk/dr2 * (-2) (ph_ip - ph_jp) (s_ip c_jp - c_ip s_jp), behind the D coordinate sums: apart
+// stride D + npair
 template <typename T, bool ARD = false, bool PER = false>
 __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restrict__ Z, int M, int Mp, int D, int kind,
                                       const Hyper* __restrict__ h, double* __restrict__ part, double* __restrict__ apart = nullptr,
@@ -762,6 +792,7 @@ __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restr
   double sd[ARD ? GDRF_DMAX : 1] = {};
   double pd[PER ? GDRF_DMAX / 2 : 1] = {};
   const T var = (T)h->var, ils2 = (T)h->inv_ls2, al = (T)h->alpha;
+  const int npr = PER ? static_cast<const HyperPer*>(h)->npair : 0;
   for (int j = threadIdx.x; j < M; j += blockDim.x) {
     const T kb = T(0.5) * (Sp[(int64_t)i * Mp + j] + Sp[(int64_t)j * Mp + i]);
     const T r2 = sqdist<T>(Z + (int64_t)i * D, Z + (int64_t)j * D, D) * ils2;
@@ -773,9 +804,9 @@ __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restr
       const T w = T(-2) * kb * dcov_dr2_from_k<T>(kind, k0, r2, al);
       for (int d = 0; d < D; ++d) { const T t = Z[(int64_t)i * D + d] - Z[(int64_t)j * D + d]; sd[d] += (double)(w * t * t); }
       if constexpr (PER) {
-        for (int d = 0; d < D / 2; ++d) {
+        for (int d = 0; d < npr; ++d) {
           const T* zi = Z + (int64_t)i * D + 2 * d; const T* zj = Z + (int64_t)j * D + 2 * d;
-          pd[d] += (double)(w * (ph[(int64_t)i * (D / 2) + d] - ph[(int64_t)j * (D / 2) + d]) * (zi[1] * zj[0] - zi[0] * zj[1]));
+          pd[d] += (double)(w * (ph[(int64_t)i * npr + d] - ph[(int64_t)j * npr + d]) * (zi[1] * zj[0] - zi[0] * zj[1]));
         }
       }
     }
@@ -785,13 +816,13 @@ __global__ void kuu_bar_reduce_kernel(const T* __restrict__ Sp, const T* __restr
   s3 = block_sum(s3, scratch);
   if (threadIdx.x == 0) { part[3 * i] = s1; part[3 * i + 1] = s2; part[3 * i + 2] = s3; }
   if constexpr (ARD) {
-    const int as = PER ? D + D / 2 : D;
+    const int as = D + npr;
     for (int d = 0; d < D; ++d) {
       const double v = block_sum(sd[d], scratch);
       if (threadIdx.x == 0) apart[(int64_t)as * i + d] = v;
     }
     if constexpr (PER) {
-      for (int d = 0; d < D / 2; ++d) {
+      for (int d = 0; d < npr; ++d) {
         const double v = block_sum(pd[d], scratch);
         if (threadIdx.x == 0) apart[(int64_t)as * i + D + d] = v;
       }
@@ -863,8 +894,9 @@ __global__ void grad_unwhitened_kernel(const T* __restrict__ Sbar, const T* __re
 // g = -1/N * Zbar * z (1 - z).  One block per inducing point.
 // ARD: Z and G are in the scaled coordinates z_d / ls_d (ls = 1), d r2 / d z_d carries one more factor 1 / ls_d = sc[d], and the
 // sigmoid Jacobian takes the unscaled inputs Zr.
-// PER (periodic contexts, ARD set): Z and G are in the D = 2 Dr embedded coordinates (c, s) = (cos(t z), sin(t z)) / ls, whose
-// derivatives in the raw input z are (-t s, t c): zbar_d = t_d (s-coordinate gradient * c - c-coordinate gradient * s); Zr = raw inputs (M, Dr).
+// PER (periodic and product contexts, ARD set): Z and G are in the D embedded coordinates.  A pair (c, s) = (cos(t z), sin(t z)) / ls has the
+// derivatives (-t s, t c) in its raw input z: it adds t (s-coordinate gradient * c - c-coordinate gradient * s) to its axis; a linear
+// coordinate z / ls adds its gradient / ls.  Zr = raw inputs (M, dr); an axis no coordinate reads gets 0.
 template <typename T, typename TP, bool ARD = false, bool PER = false>
 __global__ void grad_z_kernel(const T* __restrict__ Sp, const T* __restrict__ Z, int M, int Mp, int D, int kind,
                               const Hyper* __restrict__ h, const double* __restrict__ G, double neg_inv_n, TP* __restrict__ g,
@@ -886,11 +918,16 @@ __global__ void grad_z_kernel(const T* __restrict__ Sp, const T* __restrict__ Z,
     for (int d = 0; d < D; ++d) eb[d] = 2.0 * (G[(int64_t)i * D + d] + 2.0 * block_sum(hs[d], scratch));
     if (threadIdx.x == 0) {
       const HyperPer* hp = static_cast<const HyperPer*>(h);
-      for (int d = 0; d < D / 2; ++d) {
+      const int npr = hp->npair, dr = hp->dr;
+      double zbar[GDRF_DMAX] = {};
+      for (int d = 0; d < npr; ++d) {
         const double c = (double)Z[(int64_t)i * D + 2 * d], sn = (double)Z[(int64_t)i * D + 2 * d + 1];
-        const double z = (double)Zr[(int64_t)i * (D / 2) + d];
-        const double zbar = hp->tp[d] * (eb[2 * d + 1] * c - eb[2 * d] * sn);
-        g[(int64_t)i * (D / 2) + d] = (TP)(neg_inv_n * zbar * z * (1.0 - z));
+        zbar[hp->pax[d]] += hp->tp[d] * (eb[2 * d + 1] * c - eb[2 * d] * sn);
+      }
+      for (int d = 2 * npr; d < D; ++d) zbar[hp->cax[d]] += eb[d] * hp->il[d];
+      for (int a = 0; a < dr; ++a) {
+        const double z = (double)Zr[(int64_t)i * dr + a];
+        g[(int64_t)i * dr + a] = (TP)(neg_inv_n * zbar[a] * z * (1.0 - z));
       }
     }
     return;

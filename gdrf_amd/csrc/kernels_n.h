@@ -682,9 +682,9 @@ template <typename T> struct BwdWbarTProb : NTXcdPairMap, NTPlainA<T> {
 // ARD: Z holds the scaled inducing inputs, ls = 1, the rows are scaled by 1 / ls_d as they are loaded, and the lengthscale sum splits
 // into the D sums  sum Kbar * dk/dr2 * (-2) (x_d - z_d)^2  (= d / d log ls_d; their total is the isotropic sum), one partial per
 // workgroup in apart[D * block + d].  Every other sum is the isotropic one in the scaled coordinates.
-// PER (periodic contexts, with ARD): X and Z are the embedded coordinates (D = 2 Dr, ls = 1), Xr the raw rows (nrows, Dr) and Zph the
-// inducing phases t_d z_d; also the Dr sums  sum Kbar * dk/dr2 * (-2) (t_d x_d - t_d z_d) (s_x c_z - c_x s_z)  (= d / d log p_d) behind the
-// D coordinate sums: apart stride D + Dr.
+// PER (periodic and product contexts, with ARD): X and Z are the D embedded coordinates (ls = 1; pairs first, HyperPer), Xr the raw rows
+// (nrows, dr) and Zph the inducing phases t_p z_p of the npair pairs; also the npair sums  sum Kbar * dk/dr2 * (-2) (t_p x_p - t_p z_p)
+// (s_x c_z - c_x s_z)  (= d / d log p_p; x_p = the raw axis pax_p of the row) behind the D coordinate sums: apart stride D + npair.
 template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER = false> struct BwdKnmProb : NTXcdRowMap, NTNoExtra {
   using V = typename Vec16<T>::type;
   static constexpr int MIN_WGS = (sizeof(T) == 8 && !LZ) ? 3 : 2;   // f64: three workgroups per CU hide each other's epilogues
@@ -773,7 +773,7 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER =
           const T w = T(-2) * kbar * dcov_dr2_from_k<T>(KD, kvv, r2, al);
 #pragma unroll
           for (int d = 0; d < DD; ++d) { const T t = (d < D ? (T)x[i][d] * xsc[d] : T(0)) - zc[j][d]; e.sd[d] += w * t * t; }
-          if constexpr (PER) e.pd[0] += w * (px[i] - pz[j]) * ((T)x[i][1] * zc[j][0] - (T)x[i][0] * zc[j][1]);   // DD = 2: one raw axis
+          if constexpr (PER) e.pd[0] += w * (px[i] - pz[j]) * ((T)x[i][1] * zc[j][0] - (T)x[i][0] * zc[j][1]);   // DD = 2: at most one pair
         } else {
           e.s2 += kbar * dcov_dlogls_from_k<T>(KD, kvv, r2, al);
         }
@@ -813,10 +813,15 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER =
       for (int d = 0; d < DD; ++d) { const T v = Z[nz * D + (d < D ? d : 0)]; zc[j][d] = d < D ? v : T(0); }
     }
     T pz[2] = {T(0), T(0)}, tp0 = T(0);
-    if constexpr (PER) {
-      tp0 = (T)static_cast<const HyperPer*>(h)->tp[0];
+    unsigned xr_s = 0;
+    const TN* __restrict__ Xrt = Xr;
+    if constexpr (PER) {           // one pair or none (a product of two linear coordinates: tp0 = 0, its sum is never written)
+      const HyperPer* hp = static_cast<const HyperPer*>(h);
+      tp0 = (T)hp->tp[0];
+      xr_s = (unsigned)hp->dr;
+      Xrt = Xr + m0 * hp->dr + hp->pax[0];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) pz[j] = Zph[cok[j] ? nc + j : 0];
+      for (int j = 0; j < 2; ++j) pz[j] = hp->npair ? Zph[cok[j] ? nc + j : 0] : T(0);
     }
     const T* __restrict__ Kt = Knm + m0 * Mp;              // uniform bases of this row tile
     const TN* __restrict__ Xt = X + m0 * D;
@@ -837,7 +842,7 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER =
           kv[i] = *reinterpret_cast<const KT2*>(Kt + (rc * (unsigned)Mp + (unsigned)ncl));
 #pragma unroll
           for (int d = 0; d < DD; ++d) x[i][d] = Xt[rc * (unsigned)D + (unsigned)(d < D ? d : 0)];
-          if constexpr (PER) px[i] = tp0 * (T)Xr[m0 + rc];
+          if constexpr (PER) px[i] = tp0 * (T)Xrt[rc * xr_s];
           else px[i] = T(0);
         }
         if (hb == 0) {
@@ -878,12 +883,13 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER =
       for (int d = 0; d < GDRF_DMAX; ++d) z[b][d] = (n < M && d < D) ? Z[(int64_t)n * D + d] : T(0);
     }
     T pz[PER ? 4 : 1][GDRF_DMAX / 2];
+    const int npr = PER ? static_cast<const HyperPer*>(h)->npair : 0;
     if constexpr (PER) {
 #pragma unroll
       for (int b = 0; b < NTCfg<T>::NB; ++b) {
         const int n = n0 + nt_acc_col<T>(wc, b, lane);
 #pragma unroll
-        for (int d = 0; d < GDRF_DMAX / 2; ++d) pz[b][d] = (n < M && d < D / 2) ? Zph[(int64_t)n * (D / 2) + d] : T(0);
+        for (int d = 0; d < GDRF_DMAX / 2; ++d) pz[b][d] = (n < M && d < npr) ? Zph[(int64_t)n * npr + d] : T(0);
       }
     }
 #pragma unroll
@@ -898,8 +904,10 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER =
         T px[GDRF_DMAX / 2];
         if constexpr (PER) {
 #pragma unroll
-          for (int d = 0; d < GDRF_DMAX / 2; ++d)
-            px[d] = d < D / 2 ? (T)static_cast<const HyperPer*>(h)->tp[d] * (T)Xr[m * (D / 2) + d] : T(0);
+          for (int d = 0; d < GDRF_DMAX / 2; ++d) {
+            const HyperPer* hp = static_cast<const HyperPer*>(h);
+            px[d] = d < npr ? (T)hp->tp[d] * (T)Xr[m * hp->dr + hp->pax[d]] : T(0);
+          }
         }
 #pragma unroll
         for (int b = 0; b < NTCfg<T>::NB; ++b) {
@@ -918,7 +926,7 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER =
             if constexpr (PER) {
 #pragma unroll
               for (int d = 0; d < GDRF_DMAX / 2; ++d)
-                if (d < D / 2) e.pd[d] += w * (px[d] - pz[b][d]) * (x[2 * d + 1] * z[b][2 * d] - x[2 * d] * z[b][2 * d + 1]);
+                if (d < npr) e.pd[d] += w * (px[d] - pz[b][d]) * (x[2 * d + 1] * z[b][2 * d] - x[2 * d] * z[b][2 * d + 1]);
             }
           } else {
             e.s2 += acc[a][b][r] * dcov_dlogls_from_k<T>(kind, kv, r2, al);
@@ -945,13 +953,14 @@ template <typename T, typename TN, bool LZ = false, bool ARD = false, bool PER =
     const double c3 = block_sum((double)e.s3, scratch);
     if (threadIdx.x == 0) { part[3 * (int64_t)blockIdx.x] = a; part[3 * (int64_t)blockIdx.x + 1] = b; part[3 * (int64_t)blockIdx.x + 2] = c3; }
     if constexpr (ARD) {
-      const int as = PER ? D + D / 2 : D;
+      const int npr = PER ? static_cast<const HyperPer*>(h)->npair : 0;
+      const int as = D + npr;
       for (int d = 0; d < D; ++d) {
         const double v = block_sum((double)e.sd[d], scratch);
         if (threadIdx.x == 0) apart[(int64_t)as * blockIdx.x + d] = v;
       }
       if constexpr (PER) {
-        for (int d = 0; d < D / 2; ++d) {
+        for (int d = 0; d < npr; ++d) {
           const double v = block_sum((double)e.pd[d], scratch);
           if (threadIdx.x == 0) apart[(int64_t)as * blockIdx.x + D + d] = v;
         }
@@ -1673,23 +1682,45 @@ __global__ void grad_ard_kernel(int D, const double* __restrict__ red_ard, const
   if (d < D) g_ard[d] = (T)((-1.0 / n_global) * (red_ard[d] + kuu_ard[d]));
 }
 
-// periodic contexts, behind grad_small_kernel: red / kuu = the 2 Dr embedded-coordinate sums, then the Dr sums of d / d log p_d (K_nm
-// part all-reduced with the payload, K_uu part).  The lengthscale gradient folds the two coordinates of an axis (ls_ard: one per axis, the
-// ARD segment g_ard; else all axes into slot 0 of g_hyper); the period one folds all axes when np = 1.
+// periodic and product contexts, behind grad_small_kernel: red / kuu = the D embedded-coordinate sums, then the npair sums of d / d log p
+// (K_nm part all-reduced with the payload, K_uu part).  By the table tb: a source's lengthscale sum is the sum over its coordinates (two for
+// a pair), and every log-lengthscale or log-period parameter receives the sum over the sources that read it, in source order.  Slot 0 is 0
+// unless a source reads it.  grad_small_kernel wrote d / d log(total variance) into slot 1: every factor log-variance receives it, and slot 1
+// is 0 unless it is one of them.  g = the gradient vector (the table holds absolute indices).
 template <typename T>
-__global__ void grad_per_kernel(int Dr, int ls_ard, int np, const double* __restrict__ red, const double* __restrict__ kuu, double n_global,
-                                T* __restrict__ g_hyper, T* __restrict__ g_ard, T* __restrict__ g_per) {
+__global__ void grad_per_kernel(CoordTab tb, const double* __restrict__ red, const double* __restrict__ kuu, double n_global, T* __restrict__ g) {
   if (threadIdx.x != 0) return;
   const double f = -1.0 / n_global;
-  double lt = 0, pt = 0;
-  for (int d = 0; d < Dr; ++d) {
-    const double l = red[2 * d] + kuu[2 * d] + red[2 * d + 1] + kuu[2 * d + 1], p = red[2 * Dr + d] + kuu[2 * Dr + d];
-    if (ls_ard) g_ard[d] = (T)(f * l);
-    if (np > 1) g_per[d] = (T)(f * p);
-    lt += l; pt += p;
+  const int np = tb.npair;
+  double l[GDRF_DMAX], p[GDRF_DMAX / 2];
+  for (int j = 0; j < tb.nsrc; ++j) {
+    const int c = j < np ? 2 * j : np + j;
+    l[j] = j < np ? red[c] + kuu[c] + red[c + 1] + kuu[c + 1] : red[c] + kuu[c];
   }
-  g_hyper[0] = ls_ard ? T(0) : (T)(f * lt);
-  if (np == 1) g_per[0] = (T)(f * pt);
+  for (int j = 0; j < np; ++j) p[j] = red[tb.D + j] + kuu[tb.D + j];
+  bool slot0 = false;
+  for (int j = 0; j < tb.nsrc; ++j) {
+    bool first = true;
+    for (int k = 0; k < j; ++k) first = first && tb.ls[k] != tb.ls[j];
+    slot0 = slot0 || tb.ls[j] == 0;
+    if (!first) continue;
+    double t = 0;
+    for (int k = j; k < tb.nsrc; ++k) if (tb.ls[k] == tb.ls[j]) t += l[k];
+    g[tb.ls[j]] = (T)(f * t);
+  }
+  if (!slot0) g[0] = T(0);
+  for (int j = 0; j < np; ++j) {
+    bool first = true;
+    for (int k = 0; k < j; ++k) first = first && tb.per[k] != tb.per[j];
+    if (!first) continue;
+    double t = 0;
+    for (int k = j; k < np; ++k) if (tb.per[k] == tb.per[j]) t += p[k];
+    g[tb.per[j]] = (T)(f * t);
+  }
+  const T gv = g[1];
+  bool slot1 = false;
+  for (int k = 0; k < tb.nvar; ++k) { g[tb.var[k]] = gv; slot1 = slot1 || tb.var[k] == 1; }
+  if (!slot1) g[1] = T(0);
 }
 
 // trainable mean_function parameters (gdrf_set_mean_params): the caller's reduced sums of d elbo / d theta -> d loss / d theta, the scaling

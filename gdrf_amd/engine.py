@@ -17,7 +17,9 @@ import torch
 
 from . import _lib
 
-KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "rationalquadratic": 4, "periodic": 5}
+KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "rationalquadratic": 4, "periodic": 5, "product": 6}
+# factor kinds of a product context's table (gdrf_set_product)
+PRODUCT_KINDS = {"rbf": 0, "periodic": 5}
 OPT_MODES = {"adam": 0, "adamw": 1, "clippedadam": 2}
 # update rules of gdrf_optim_step (include/gdrf_hip.h)
 OPT_RULES = {"adam": 0, "adamw": 1, "clippedadam": 2, "adamax": 3, "rmsprop": 4, "adagrad": 5, "adadelta": 6, "asgd": 7, "rprop": 8,
@@ -37,12 +39,14 @@ class Engine:
 
     opt_extra: Optional[torch.Tensor] = None     # third optimizer state vector (RMSprop with momentum and centered), on demand
     period_count = 0                             # log-periods of a Periodic kernel's context (1 or D), 0 for the other kernels
+    product = None                               # a product context's factor table (Engine(kernel="product", product=...)), else None
+    _prod_views: Dict[str, tuple] = {}           # its parameter views: {name: (offset, shape)}
 
     def __init__(self, n_cap: int, M: int, K: int, V: int, D: int, *, dtype=torch.float32, kernel: str = "rbf",
                  device="cuda:0", jitter: float = 1e-8, maxjitter: int = 15, process_group="auto", pure_fp32: bool = False,
                  store_t="auto", mfma_mode: str = "auto", learn_inducing: bool = False, whiten: bool = True,
                  hyper_backward: str = "auto", allreduce_fn=None, ard: bool = False, mean_params: Optional[Dict[str, tuple]] = None,
-                 rows_form: str = "auto", period_count: int = 1):
+                 rows_form: str = "auto", period_count: int = 1, product=None):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.GdrfHipError("gdrf_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
@@ -106,6 +110,13 @@ class Engine:
             if self.period_count not in (1, self.D):
                 raise ValueError(f"period_count must be 1 or D = {self.D}")
             _lib.check(self.lib.gdrf_set_period_count(self.ctx, self.period_count), "gdrf_set_period_count")
+        # Product kernel (gdrf_set_product): ``product`` lists the leaf factors as dicts {"name": pyro path ("kern0", "kern0.kern1"; "" for
+        # a lone kernel on a subset of the axes), "kind": "rbf" | "periodic", "active_dims", "lengthscales": 1 or len(active_dims),
+        # "periods": 0 for RBF, 1 or len(active_dims)}.  Each factor's parameters are views "<name>.log_variance", "<name>.log_lengthscale",
+        # "<name>.log_period" ("log_variance", ... for the name "") into the three segments of gdrf_product_layout.
+        self._prod_views: Dict[str, tuple] = {}
+        if kernel == "product":
+            self._set_product(product)
         lay = (C.c_int64 * 7)()
         _lib.check(self.lib.gdrf_param_layout(self.ctx, lay), "gdrf_param_layout")
         zl = (C.c_int64 * 2)()
@@ -168,6 +179,35 @@ class Engine:
         self._mean_vjp = None
         self._adjoints: Dict[str, torch.Tensor] = {}      # host copies of the row adjoints the mean's vector-Jacobian product reads
 
+    def _set_product(self, product):
+        table = [dict(f) for f in (product or ())]
+        if not table:
+            raise ValueError("Engine(kernel='product') needs a factor table (product=[...])")
+        arr = (C.c_int * (8 * len(table)))()
+        for f, fac in enumerate(table):
+            if fac["kind"] not in PRODUCT_KINDS:
+                raise ValueError(f"product factor kind must be 'rbf' or 'periodic', got {fac['kind']!r}")
+            dims = [int(d) for d in fac["active_dims"]]
+            row = [PRODUCT_KINDS[fac["kind"]], len(dims), int(fac["lengthscales"]), int(fac.get("periods", 0))] + dims + [0] * (4 - len(dims))
+            if len(row) != 8:
+                raise ValueError("a product factor reads at most 4 axes")
+            for k, v in enumerate(row):
+                arr[8 * f + k] = v
+        _lib.check(self.lib.gdrf_set_product(self.ctx, len(table), arr), "gdrf_set_product")
+        pl = (C.c_int64 * 6)()
+        _lib.check(self.lib.gdrf_product_layout(self.ctx, pl), "gdrf_product_layout")
+        ol, op = pl[2], pl[4]
+        for f, fac in enumerate(table):
+            pre = fac["name"] + "." if fac["name"] else ""
+            nl, npr = int(fac["lengthscales"]), int(fac.get("periods", 0))
+            self._prod_views[pre + "log_variance"] = (pl[0] + f, ())
+            self._prod_views[pre + "log_lengthscale"] = (ol, () if nl == 1 else (nl,))
+            ol += nl
+            if npr:
+                self._prod_views[pre + "log_period"] = (op, () if npr == 1 else (npr,))
+                op += npr
+        self.product = table
+
     def set_allreduce(self, fn):
         """Register the step's collective behind the C ABI (gdrf_set_allreduce): ``fn(buf_ptr, count, is_double, stream_ptr)`` sums the flat
         payload in place over the caller's ranks and returns 0 / None; None unregisters (back to torch.distributed, or one rank)."""
@@ -207,6 +247,11 @@ class Engine:
         buf = self.params if buf is None else buf
         if name in self.mean_shapes:
             return self._mean_view(name, buf)
+        if name in self._prod_views:
+            o, shape = self._prod_views[name]
+            return buf[o:o + math.prod(shape)].view(shape)
+        if self.product is not None and name in ("log_lengthscale", "log_variance", "log_period", "log_scale_mixture"):
+            raise KeyError(f"{name}: a product context's kernel parameters are {tuple(self._prod_views)}")
         o = self.layout[name]
         K, M, V = self.K, self.M, self.V
         if name == "log_lengthscale" and self.ard:
@@ -238,6 +283,8 @@ class Engine:
         extra = (("log_scale_mixture",) if self.kernel == "rationalquadratic" else ()) + \
                 (("log_period",) if self.period_count else ()) + \
                 (("inducing_unc",) if self.learn_inducing else ()) + tuple(self.mean_shapes)
+        if self.product is not None:          # the factors' segments in place of slots 0 and 1
+            return tuple(self._prod_views) + self.PARAM_NAMES[2:] + extra
         return self.PARAM_NAMES + extra
 
     def named_views(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:

@@ -6,16 +6,33 @@ kernels' (gdrf_amd/csrc/common.h::cov_from_r2; pyro semantics restated in SURVEY
 """
 from __future__ import annotations
 
+import numbers
+
 import torch
+
+
+def _active_dims(input_dim: int, active_dims):
+    """pyro 1.8 Kernel.__init__: None means the first ``input_dim`` axes; otherwise ``input_dim == len(active_dims)``."""
+    if active_dims is None:
+        return list(range(int(input_dim))), False
+    dims = [int(d) for d in active_dims]
+    if len(dims) != int(input_dim):
+        raise ValueError("Input size and the length of active dimensionals should be equal.")
+    if any(d < 0 for d in dims) or len(set(dims)) != len(dims):
+        raise ValueError(f"active_dims must be distinct non-negative axes, got {dims}")
+    return dims, True
 
 
 class Kernel:
     name = None
     kernel_id = None
+    subset_dims = False          # True for the kinds that may read a proper subset of the input axes (RBF, Periodic)
 
     def __init__(self, input_dim: int, variance=None, lengthscale=None, active_dims=None):
-        if active_dims is not None and list(active_dims) != list(range(input_dim)):
-            raise NotImplementedError("active_dims other than all input dimensions")
+        self.active_dims, self.explicit_active_dims = _active_dims(input_dim, active_dims)
+        if self.active_dims != list(range(int(input_dim))) and not self.subset_dims:
+            raise NotImplementedError(f"{type(self).__name__} with active_dims other than all input dimensions: only RBF and Periodic "
+                                      "take a subset of the axes")
         self.input_dim = int(input_dim)
         self.variance = torch.as_tensor(1.0 if variance is None else variance, dtype=torch.float64).detach().cpu().reshape(())
         self.lengthscale = self._lengthscale(lengthscale, self.input_dim)
@@ -50,6 +67,7 @@ class Kernel:
 class RBF(Kernel):
     name = "rbf"
     kernel_id = 0
+    subset_dims = True
 
 
 class Matern52(Kernel):
@@ -84,9 +102,11 @@ class RationalQuadratic(Kernel):
 class Periodic(Kernel):
     """pyro.contrib.gp.kernels.Periodic: variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / period_d) / lengthscale_d^2).  ``period`` is
     positive and learnable, one element or ``input_dim`` elements (one per input axis), in the scaled units the model sees (the unit
-    cube of its ``world``).  Up to two input dimensions (the device evaluates it on two embedded coordinates per axis)."""
+    cube of its ``world``).  The device evaluates it on two embedded coordinates per axis, at most 4: a kernel over all the world's
+    axes takes up to two; with ``active_dims`` or in a Product it shares the 4 with the other factors."""
     name = "periodic"
     kernel_id = 5
+    subset_dims = True
 
     def __init__(self, input_dim: int, variance=None, lengthscale=None, period=None, active_dims=None):
         super().__init__(input_dim, variance=variance, lengthscale=lengthscale, active_dims=active_dims)
@@ -104,6 +124,55 @@ class Periodic(Kernel):
     def __repr__(self):
         p = self.period.tolist() if self.period.dim() == 1 else float(self.period)
         return super().__repr__()[:-1] + f", period={p})"
+
+
+class Product(Kernel):
+    """pyro.contrib.gp.kernels.Product(kern0, kern1): kern0(X, Z) * kern1(X, Z), each factor reading its own ``active_dims`` of the
+    inputs.  As in pyro 1.8's Combination, ``active_dims`` is the sorted union of the factors' and ``input_dim`` its length.  The factors
+    are RBF, Periodic or Product kernels and keep their own learnable parameters (the product's variance is the product of theirs).  The
+    device evaluates it on the factors' embedded coordinates (one per RBF axis, two per Periodic axis, at most 4 in all)."""
+    name = "product"
+    kernel_id = 6
+
+    def __init__(self, kern0, kern1):
+        for k in (kern0, kern1):
+            if isinstance(k, numbers.Number) or (isinstance(k, torch.Tensor) and k.dim() == 0):
+                raise NotImplementedError("Product with a constant factor is not supported: scale a factor's variance instead")
+            if not isinstance(k, (RBF, Periodic, Product)):
+                raise NotImplementedError(f"Product factors must be RBF, Periodic or Product kernels, got {type(k).__name__}")
+        self.kern0, self.kern1 = kern0, kern1
+        self.active_dims = sorted(set(kern0.active_dims) | set(kern1.active_dims))
+        self.input_dim = len(self.active_dims)
+        self.explicit_active_dims = True
+
+    @property
+    def ard(self) -> bool:
+        return False
+
+    def factors(self, prefix: str = ""):
+        """The leaf factors in pyro's module order: [(path, kernel)], path like "kern0.kern1"."""
+        out = []
+        for attr in ("kern0", "kern1"):
+            k, path = getattr(self, attr), prefix + attr
+            out += k.factors(path + ".") if isinstance(k, Product) else [(path, k)]
+        return out
+
+    def __repr__(self):
+        return f"Product({self.kern0!r}, {self.kern1!r})"
+
+
+class Sum(Kernel):
+    """pyro.contrib.gp.kernels.Sum: not supported (a sum of kernels is no product of embedded RBF factors)."""
+    name = "sum"
+
+    def __init__(self, kern0, kern1):
+        raise NotImplementedError("Sum of kernels is not supported; Product of RBF and Periodic factors is")
+
+
+def embedded_coordinates(kernel) -> int:
+    """The embedded coordinates the device evaluates ``kernel`` on: one per RBF axis, two per Periodic axis."""
+    leaves = kernel.factors() if isinstance(kernel, Product) else [("", kernel)]
+    return sum((2 if k.name == "periodic" else 1) * k.input_dim for _, k in leaves)
 
 
 KERNEL_DICT = {"rbf": RBF, "matern32": Matern32, "matern52": Matern52, "exponential": Exponential,

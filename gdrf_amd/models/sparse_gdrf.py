@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..engine import Engine
-from ..kernels import Kernel
+from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
     "log_lengthscale": "_kernel.lengthscale_unconstrained",
@@ -28,6 +28,57 @@ _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convent
     "log_scale_mixture": "_kernel.scale_mixture_unconstrained",  # only with the RationalQuadratic kernel
     "log_period": "_kernel.period_unconstrained",                # only with the Periodic kernel
 }
+_FACTOR_KEYS = {"log_variance": "variance", "log_lengthscale": "lengthscale", "log_period": "period"}
+
+
+def state_key(name: str) -> str:
+    """The state-dict name of an engine parameter: pyro's module path plus "_unconstrained".  A product factor's parameters
+    ("kern0.log_variance", "kern0.kern1.log_period") become "_kernel.kern0.variance_unconstrained", ..."""
+    if name in _PARAM_KEYS:
+        return _PARAM_KEYS[name]
+    path, _, leaf = name.rpartition(".")
+    if path.startswith("kern") and leaf in _FACTOR_KEYS:
+        return f"_kernel.{path}.{_FACTOR_KEYS[leaf]}_unconstrained"
+    return name
+
+
+def product_table(kernel: Kernel, n_dims: int):
+    """The factor table a kernel runs with on a product context (Engine(kernel="product", product=...)), or None when it runs as its own
+    kind: a Product, or a lone RBF / Periodic whose explicit active_dims are not all of the world's axes (a one-factor product)."""
+    if isinstance(kernel, Product):
+        leaves = kernel.factors()
+    elif kernel.name in ("rbf", "periodic") and kernel.explicit_active_dims and kernel.active_dims != list(range(n_dims)):
+        leaves = [("", kernel)]
+    else:
+        return None
+    return [dict(name=path, kind=k.name, active_dims=list(k.active_dims), lengthscales=k.lengthscale.numel(),
+                 periods=k.period.numel() if k.name == "periodic" else 0) for path, k in leaves]
+
+
+def kernel_spec(kernel: Kernel) -> dict:
+    """The structure of a kernel as plain values (a checkpoint's meta): kinds, active_dims and parameter counts, no values."""
+    if isinstance(kernel, Product):
+        return dict(kind="product", kern0=kernel_spec(kernel.kern0), kern1=kernel_spec(kernel.kern1))
+    spec = dict(kind=kernel.name, input_dim=kernel.input_dim, lengthscales=kernel.lengthscale.numel(),
+                active_dims=list(kernel.active_dims) if kernel.explicit_active_dims else None)
+    if kernel.name == "periodic":
+        spec["periods"] = kernel.period.numel()
+    return spec
+
+
+def kernel_from_spec(spec: dict) -> Kernel:
+    """A kernel of the structure ``spec`` (kernel_spec) with placeholder values of the right shapes (load_state_dict fills them)."""
+    from ..kernels import KERNEL_DICT, Periodic
+    if spec["kind"] == "product":
+        return Product(kernel_from_spec(spec["kern0"]), kernel_from_spec(spec["kern1"]))
+    n, nl = int(spec["input_dim"]), int(spec["lengthscales"])
+    kw = dict(input_dim=n, lengthscale=torch.ones(nl) if nl > 1 else 1.0, variance=1.0, active_dims=spec.get("active_dims"))
+    if spec["kind"] == Periodic.name:
+        npr = int(spec["periods"])
+        return Periodic(period=torch.ones(npr) if npr > 1 else 1.0, **kw)
+    return KERNEL_DICT[spec["kind"]](**kw)
+
+
 MEAN_PREFIX = "_mean_function."      # + the name from named_parameters(): a trainable parameter of a torch.nn.Module mean_function
 
 
@@ -128,14 +179,18 @@ class ModelSnapshot:
         m = self.meta
         if self._model is not None and device is None and mean_function is None and link_function is None:
             return self._model
-        ls = self._state[_PARAM_KEYS["log_lengthscale"]]
-        # an ARD checkpoint stores (D,) log-lengthscales: rebuild an ARD kernel (the values come from load_state_dict below)
-        lsk = torch.ones(int(m["D"])) if ls.dim() == 1 else 1.0
-        if m["kernel"] == Periodic.name:          # the period's shape, () or (D,), from the checkpoint as well
-            per = self._state[_PARAM_KEYS["log_period"]]
-            kern = Periodic(input_dim=int(m["D"]), lengthscale=lsk, variance=1.0, period=torch.ones(int(m["D"])) if per.dim() == 1 else 1.0)
+        if m.get("kernel_spec") is not None:      # a product, or a kernel on a subset of the axes: rebuilt from its structure
+            kern = kernel_from_spec(m["kernel_spec"])
         else:
-            kern = KERNEL_DICT[m["kernel"]](input_dim=int(m["D"]), lengthscale=lsk, variance=1.0)
+            ls = self._state[_PARAM_KEYS["log_lengthscale"]]
+            # an ARD checkpoint stores (D,) log-lengthscales: rebuild an ARD kernel (the values come from load_state_dict below)
+            lsk = torch.ones(int(m["D"])) if ls.dim() == 1 else 1.0
+            if m["kernel"] == Periodic.name:          # the period's shape, () or (D,), from the checkpoint as well
+                per = self._state[_PARAM_KEYS["log_period"]]
+                kern = Periodic(input_dim=int(m["D"]), lengthscale=lsk, variance=1.0,
+                                period=torch.ones(int(m["D"])) if per.dim() == 1 else 1.0)
+            else:
+                kern = KERNEL_DICT[m["kernel"]](input_dim=int(m["D"]), lengthscale=lsk, variance=1.0)
         dtype = getattr(torch, m["dtype"])
         model = SparseMultinomialGDRF(
             num_observation_categories=int(m["V"]), num_topic_categories=int(m["K"]), world=[tuple(w) for w in m["world"]],
@@ -145,7 +200,7 @@ class ModelSnapshot:
             whiten=bool(m["whiten"]), jitter=float(m["jitter"]), maxjitter=int(m["maxjitter"]), dtype=dtype,
             pure_fp32=bool(m["pure_fp32"]), mfma_mode=m["mfma_mode"], seed=int(m["seed"]), guide_rescale=bool(m["guide_rescale"]),
             rows_form=m.get("rows_form", "auto"))
-        keys = {_PARAM_KEYS.get(n, n) for n in model._param_names()}
+        keys = {state_key(n) for n in model._param_names()}
         model.load_state_dict({k: v.to(dtype) for k, v in self._state.items() if k in keys or not k.startswith(MEAN_PREFIX)})
         if device is None and mean_function is None and link_function is None:
             self._model = model
@@ -219,8 +274,16 @@ class SparseMultinomialGDRF:
         self._randomize_metric, self._randomize_iters = randomize_metric, int(randomize_iters)
         if not isinstance(kernel, Kernel):
             raise TypeError("kernel must be a gdrf_amd.kernels.RBF or Matern52")
-        if kernel.name == "periodic" and kernel.input_dim > 2:
+        self._product = product_table(kernel, len(world))
+        if self._product is None and kernel.name == "periodic" and kernel.input_dim > 2:
             raise ValueError(f"the Periodic kernel supports at most 2 input dimensions, got input_dim = {kernel.input_dim}")
+        if self._product is not None:
+            bad = [d for d in kernel.active_dims if d >= len(world)]
+            if bad:
+                raise ValueError(f"kernel active_dims {bad} are not axes of the {len(world)}-dimensional world")
+            if embedded_coordinates(kernel) > 4:
+                raise ValueError(f"the kernel needs {embedded_coordinates(kernel)} embedded coordinates (one per RBF axis, two per Periodic "
+                                 "axis); at most 4 are supported")
         self._V = int(num_observation_categories)
         self._K = int(num_topic_categories)
         self._world = [(float(a), float(b)) for a, b in world]
@@ -238,7 +301,7 @@ class SparseMultinomialGDRF:
             raise ValueError("rows_form must be 'auto' or 'streamed'")
         self._rows_form = rows_form          # Engine(rows_form=...): "auto" (LDS row forms) | "streamed" (any V, csrc/rows_vstream.h)
         self._kernel = kernel
-        if kernel.input_dim != self._n_dims:
+        if self._product is None and kernel.input_dim != self._n_dims:
             raise ValueError("kernel.input_dim does not match the world's dimensionality")
         self._lower = torch.tensor([b[0] for b in self._world], dtype=torch.float64)
         self._upper = torch.tensor([b[1] for b in self._world], dtype=torch.float64)
@@ -281,12 +344,13 @@ class SparseMultinomialGDRF:
         e = self._engine
         if e is not None and n <= e.n_cap:
             return e
-        new = Engine(n, self.M, self._K, self._V, self.D, dtype=self.dtype, kernel=self._kernel.name, device=self.device,
+        new = Engine(n, self.M, self._K, self._V, self.D, dtype=self.dtype, kernel="product" if self._product else self._kernel.name,
+                     device=self.device, product=self._product,
                      jitter=self._jitter, maxjitter=self._maxjitter, pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode,
                      learn_inducing=not self._fixed_inducing_points, whiten=self._whiten, hyper_backward=self._hyper_backward,
-                     ard=self._kernel.ard, mean_params={n: tuple(p.shape) for n, p in self._mean_params},
+                     ard=self._kernel.ard and not self._product, mean_params={n: tuple(p.shape) for n, p in self._mean_params},
                      rows_form=self._rows_form,
-                     period_count=self._kernel.period.numel() if self._kernel.name == "periodic" else 1)
+                     period_count=self._kernel.period.numel() if self._kernel.name == "periodic" and not self._product else 1)
         new.set_inducing_points(self._inducing_points)
         new.set_dirichlet(self._dirichlet_param)
         new.link_function = self._link_function
@@ -305,13 +369,22 @@ class SparseMultinomialGDRF:
     def _init_params(self, eng: Engine):
         """sparse_gdrf.py:96-122 and abstract_gdrf.py:57-84."""
         with torch.no_grad():
-            if self._kernel.ard:
+            if self._product:
+                leaves = self._kernel.factors() if isinstance(self._kernel, Product) else [("", self._kernel)]
+                for path, k in leaves:
+                    pre = path + "." if path else ""
+                    eng.view(pre + "log_variance").fill_(float(k.variance.log()))
+                    eng.view(pre + "log_lengthscale").copy_(k.lengthscale.log().reshape(eng.view(pre + "log_lengthscale").shape))
+                    if k.name == "periodic":
+                        eng.view(pre + "log_period").copy_(k.period.log().reshape(eng.view(pre + "log_period").shape))
+            elif self._kernel.ard:
                 eng.view("log_lengthscale").copy_(self._kernel.lengthscale.log())
             else:
                 eng.view("log_lengthscale").fill_(float(self._kernel.lengthscale.log()))
-            eng.view("log_variance").fill_(float(self._kernel.variance.log()))
+            if not self._product:
+                eng.view("log_variance").fill_(float(self._kernel.variance.log()))
             eng.view("log_noise").fill_(float(torch.tensor(self._init_noise, dtype=torch.float64).log()))
-            if self._kernel.name == "periodic":
+            if self._kernel.name == "periodic" and not self._product:
                 eng.view("log_period").copy_(self._kernel.period.log().reshape(eng.view("log_period").shape))
             if self._kernel.name == "rationalquadratic":
                 eng.view("log_scale_mixture").fill_(float(self._kernel.scale_mixture.log()))
@@ -511,17 +584,34 @@ class SparseMultinomialGDRF:
 
     @property
     def kernel_lengthscale(self):
+        if "log_lengthscale" not in self._engine.param_names:
+            raise AttributeError("kernel_lengthscale: the model's kernel is a Product; its factors' values are in kernel_parameters")
         return self._engine.view("log_lengthscale").exp().detach().cpu().numpy()
+
+    @property
+    def kernel_parameters(self) -> Dict[str, object]:
+        """The kernel's constrained parameter values by pyro name, relative to the kernel: {"variance": ..., "lengthscale": ...} for a
+        lone kernel, {"kern0.variance": ..., "kern1.period": ...} for a Product.  0-d or 1-d arrays."""
+        out = {}
+        for n in self._param_names():
+            key = state_key(n)
+            if key.startswith("_kernel.") and key.endswith("_unconstrained"):
+                out[key[len("_kernel."):-len("_unconstrained")]] = self._engine.view(n).exp().detach().cpu().numpy()
+        return out
 
     @property
     def kernel_period(self):
         """The Periodic kernel's period: a 0-d or (D,) array."""
         if self._kernel.name != "periodic":
             raise AttributeError("kernel_period: the model's kernel is not Periodic")
+        if "log_period" not in self._engine.param_names:
+            raise AttributeError("kernel_period: the model's kernel is a Product; its factors' values are in kernel_parameters")
         return self._engine.view("log_period").exp().detach().cpu().numpy()
 
     @property
     def kernel_variance(self):
+        if "log_variance" not in self._engine.param_names:
+            raise AttributeError("kernel_variance: the model's kernel is a Product; its factors' values are in kernel_parameters")
         return self._engine.view("log_variance").exp().detach().cpu().numpy()
 
     @property
@@ -540,14 +630,17 @@ class SparseMultinomialGDRF:
     def artifacts(self, xs, ws, all: bool = False):
         """gdrf/models/sparse_gdrf.py:146-158: the kernel variance and lengthscale (a (D,) array for an ARD kernel), plus the inducing
         inputs when they are learnable."""
-        ret = {"kernel variance": self.kernel_variance, "kernel lengthscale": self.kernel_lengthscale}
+        if isinstance(self._kernel, Product):      # the reference's _get("_kernel.lengthscale") has no such parameter to read
+            ret = {f"kernel {k}": v for k, v in self.kernel_parameters.items()}
+        else:
+            ret = {"kernel variance": self.kernel_variance, "kernel lengthscale": self.kernel_lengthscale}
         if not self._fixed_inducing_points:
             ret["inducing_points"] = self.inducing_points.detach().cpu().numpy()
         return ret
 
     # ------------------------------------------------------------------ state (train_script.py:338-363,490-506)
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {_PARAM_KEYS.get(n, n): self._engine.view(n).detach().clone() for n in self._param_names()}
+        return {state_key(n): self._engine.view(n).detach().clone() for n in self._param_names()}
 
     def _param_names(self):
         return tuple(self._engine.param_names)
@@ -560,7 +653,7 @@ class SparseMultinomialGDRF:
                 raise RuntimeError(f"unexpected keys: {unexpected}")
         missing = []
         for n in self._param_names():
-            key = _PARAM_KEYS.get(n, n)
+            key = state_key(n)
             if key not in state:
                 missing.append(key)
                 continue
@@ -590,5 +683,6 @@ class SparseMultinomialGDRF:
                     jitter=self._jitter, maxjitter=self._maxjitter, dirichlet_param=self._dirichlet_param.detach().cpu().clone(),
                     inducing_points=self._engine.Z.detach().cpu().clone(), dtype=str(self.dtype).replace("torch.", ""),
                     device=str(self.device), pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode, seed=self.rng_seed,
-                    guide_rescale=self._guide_rescale, rows_form=self._rows_form)
+                    guide_rescale=self._guide_rescale, rows_form=self._rows_form,
+                    kernel_spec=kernel_spec(self._kernel) if self._product else None)
         return ModelSnapshot(self.state_dict(), meta)

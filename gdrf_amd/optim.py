@@ -21,8 +21,8 @@ CLIP_KEYS = ("clip_norm", "clip_value")
 def param_store_name(name: str) -> str:
     """The name pyro's param store gives an engine parameter, as an ``optim_args`` / ``clip_args`` callable receives it: the
     state-dict name without its ``_unconstrained`` suffix ("u_loc", "_kernel.lengthscale", "_mean_function.w")."""
-    from .models.sparse_gdrf import _PARAM_KEYS
-    key = _PARAM_KEYS.get(name, name)
+    from .models.sparse_gdrf import state_key
+    key = state_key(name)
     return key[:-len("_unconstrained")] if key.endswith("_unconstrained") else key
 
 

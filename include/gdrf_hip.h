@@ -9,7 +9,7 @@
  * gdrf_last_error()); pointers named *_dev are borrowed device pointers that the caller keeps
  * alive until the stream has been synchronised; `stream` is a hipStream_t passed as void*;
  * no exceptions cross the ABI; one host thread per context.  kernel_id: 0 RBF, 1 Matern52, 2 Matern32, 3 Exponential,
- * 4 RationalQuadratic, 5 Periodic (D <= 2, gdrf_set_period_count).
+ * 4 RationalQuadratic, 5 Periodic (D <= 2, gdrf_set_period_count), 6 a product of RBF and Periodic factors (gdrf_set_product).
  * dtype fixes the element type of every "void*" real array below:
  *   GDRF_F32 (0)      float arrays.  The K-fold contractions are f32 GEMMs evaluated on the matrix cores in the arithmetic
  *                     gdrf_set_mfma_mode() selects (native f32 MFMA, or split operands on the 16-bit matrix path with f32
@@ -29,7 +29,8 @@ extern "C" {
 typedef struct gdrf_ctx gdrf_ctx;
 
 enum { GDRF_F32 = 0, GDRF_F64 = 1, GDRF_F32_PURE = 2 };
-enum { GDRF_RBF = 0, GDRF_MATERN52 = 1, GDRF_MATERN32 = 2, GDRF_EXPONENTIAL = 3, GDRF_RATIONALQUADRATIC = 4, GDRF_PERIODIC = 5 };
+enum { GDRF_RBF = 0, GDRF_MATERN52 = 1, GDRF_MATERN32 = 2, GDRF_EXPONENTIAL = 3, GDRF_RATIONALQUADRATIC = 4, GDRF_PERIODIC = 5,
+       GDRF_PRODUCT = 6 };
 enum { GDRF_ADAM = 0, GDRF_ADAMW = 1, GDRF_CLIPPED_ADAM = 2 };
 enum { GDRF_PRED_LOC = 0, GDRF_PRED_TOPIC_PROBS = 1, GDRF_PRED_WORD_PROBS = 2, GDRF_PRED_PERPLEXITY = 3, GDRF_PRED_LOC_VAR = 4 };
 
@@ -125,6 +126,19 @@ int gdrf_ard_layout(const gdrf_ctx* ctx, int64_t out[2]);
  * (M, 2D) in the embedded coordinates.  The opt-in gdrf_set_hyper_backward(1) falls back to the f64 form. */
 int gdrf_set_period_count(gdrf_ctx* ctx, int count);
 int gdrf_periodic_layout(const gdrf_ctx* ctx, int64_t out[2]);
+/* Product kernel (kernel_id GDRF_PRODUCT; D = the raw input axes): pyro.contrib.gp.kernels.Product of RBF and Periodic factors, each over
+ * its own active axes, k = prod_f variance_f * k_f(x[axes_f], z[axes_f]).  It is evaluated as the RBF kernel at lengthscale 1 on the
+ * concatenated embedded coordinates: (cos(t x_a), sin(t x_a)) / lengthscale for an axis a of a Periodic factor, x_a / lengthscale for one
+ * of an RBF factor; at most 4 of them.  gdrf_set_product sets the table before the first step: nfactors (1-4) rows of 8 ints
+ * {kind (GDRF_RBF or GDRF_PERIODIC), axis count, lengthscale count (1 or the axis count), period count (0 for RBF; 1 or the axis count),
+ * axes[4] (each < D, the unused ones 0)}; a table with an axis >= D or more than 4 coordinates returns -1 (gdrf_last_error).  Until it is
+ * called the table is one RBF factor over every axis.  The parameter vector then holds three segments (gdrf_product_layout -> {offset,
+ * count} of the nfactors log-variances, of the log-lengthscales and of the log-periods, each in factor order; counts 0 in other contexts);
+ * slots 0 and 1 are not read and receive a zero gradient, and every factor log-variance receives the gradient of the total log-variance.
+ * red_d carries, at 8 + M*D', D' embedded-coordinate sums and one sum per Periodic axis, D' = the table's coordinate count; the
+ * learnable-inducing-input sums at 8 are (M, D') in the embedded coordinates.  gdrf_set_hyper_backward(1) falls back to the f64 form. */
+int gdrf_set_product(gdrf_ctx* ctx, int nfactors, const int* table);
+int gdrf_product_layout(const gdrf_ctx* ctx, int64_t out[6]);
 /* Trainable mean_function parameters (gdrf/models/abstract_gdrf.py:33-48: the mean_function is an attribute of a gp.Parameterized, so the
  * parameters of a torch.nn.Module mean - registered by pyro.module - or a PyroModule mean's own PyroParams land in the param store and
  * SVI.step trains them with the optimizer of every other parameter, gdrf/train_script.py:365-371,467).  The library never evaluates the
@@ -151,7 +165,7 @@ void gdrf_ctx_destroy(gdrf_ctx* ctx);
  * kernels.isotropic.RationalQuadratic: variance * (1 + r2 / (2 scale_mixture))^(-scale_mixture)); the other kernels
  * ignore it and its gradient is 0. */
 int gdrf_param_layout(const gdrf_ctx* ctx, int64_t out[7]);
-/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}; total_d = 8 + M*D (+ D in ARD contexts; 8 + M*2D + 3D in periodic ones)
+/* Per-step all-reduce payload: out = {off_ubar, off_phibar, off_A, off_GT, total_T, total_d}; total_d = 8 + M*D (+ D in ARD contexts; 8 + M*2D + 3D in periodic ones; see gdrf_set_product for product ones)
  * (+ the count of gdrf_set_mean_params, the last doubles). */
 int gdrf_red_layout(const gdrf_ctx* ctx, int64_t out[6]);
 /* The step's ONE collective ("one ncclAllReduce(sum) per step over a flat buffer"): gdrf_payload_pack copies the
