@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the GDRF SVI ELBO hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: launched by torch.distributed.run, one rank per GPU over RCCL)
 
 A "step" is one full ``SVI.step(xs, ws)`` of ``SparseMultinomialGDRF`` (jitter-retry Cholesky,
@@ -10,9 +10,12 @@ workload: N = 1e6 synthetic 2-D observations, V = 50 taxa, K = 10 topics, M = 51
 (32 x 16 grid), RBF kernel, fp32.  With N GPUs the 1e6 observations are sharded over the ranks
 (strong scaling: the total work is fixed).  Inputs are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line.  ``value`` comes from a timed region that runs with the library's per-kernel event timing OFF;
-per-kernel times are collected in a second, untimed pass of the same steps.  ``roofline`` is the dominant kernel of the
-step, priced on the matrix pipe it EXECUTES on (the f32 contractions are issued as split fp16 / bf16 products:
+Rank 0 prints ONE JSON line.  ``value`` comes from a timed region that runs with the library's per-kernel event timing OFF.
+A plain run does no more than that line needs: set-up, warm-up, the timed steps, ``--dump-outputs`` if given.
+
+``--full`` adds, after the timed steps, what takes runs of its own: per-kernel times (``kernel_ms_per_step``) from a second,
+untimed pass of the same steps, the ``perplexity`` of the model that pass leaves, and the keys below.  ``roofline`` is the
+dominant kernel of the step, priced on the matrix pipe it EXECUTES on (the f32 contractions are issued as split fp16 / bf16 products:
 ``achieved`` counts the issued MFMA flops, ``peak`` is that pipe's dense peak, the f32-equivalent view is an extra key);
 ``roofline.traffic`` is that kernel's HBM bytes per launch from the rocprofv3 PMC passes of the same command, read from
 ``profiles/<round>/pmc_hbm.json`` (tools/profile_round.sh).  ``roofline_knm`` is the K_nm kernel the metric names
@@ -60,6 +63,9 @@ def parse(argv=None):
     ap.add_argument("--kernel", default="rbf")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--jitter", type=float, default=1e-6)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure per-kernel times, the perplexity, the rooflines and the CPU baseline "
+                         "(--cpu-baseline-n, --cpu-baseline-steps, --kernel-pass-steps and --knm-iters shape this part alone)")
     ap.add_argument("--cpu-baseline-n", type=int, nargs="+", default=[25000, 50000, 100000],
                     help="rows of the CPU-baseline samples (0 = skip); BASELINE.md section 3: three sizes, linearity checked")
     ap.add_argument("--cpu-baseline-steps", type=int, default=5)
@@ -201,6 +207,118 @@ def cpu_baseline(args, M_points):
     }
 
 
+def full_measurements(args, svi, model, eng, xs, ws, N, world, rank, barrier, steps_per_s):
+    """What ``--full`` measures beyond the headline, after the timed steps: per-kernel times from a second, untimed pass of the
+    same steps, the perplexity, the standalone K_nm kernel, the dominant kernel's roofline and the CPU baseline.  Runs on every
+    rank (the second pass all-reduces); returns the extra keys of the result line on rank 0 and {} on the others."""
+    device, dtype = xs.device, xs.dtype
+    M, D = model.M, xs.shape[1]
+    # ---- second pass (untimed): per-kernel times from HIP events recorded on the launch streams inside the library
+    kp = max(1, args.kernel_pass_steps)
+    eng.set_timing(True)
+    for _ in range(kp):
+        svi.step(xs=xs, ws=ws, subsample=False)
+    barrier()
+    timing = eng.get_timing()
+    eng.set_timing(False)
+    perplexity = float(model.perplexity(xs, ws).item()) if world == 1 else None
+
+    # ---- standalone K_nm kernel (HBM roofline), same shard
+    knm_out = torch.empty(xs.shape[0], M, dtype=dtype, device=device)
+    for _ in range(5):                       # untimed: the first launches after the step loop run 10-15 % slow
+        eng.knm_into(xs, knm_out)
+    eng.set_timing(True)
+    for _ in range(args.knm_iters):
+        eng.knm_into(xs, knm_out)
+    torch.cuda.synchronize(device)
+    t_knm = eng.get_timing()["k_nm"]
+    eng.set_timing(False)
+    del knm_out
+
+    if rank != 0:
+        return {}
+    esz = 4 if dtype == torch.float32 else 8
+    ssz = 4 if eng.pure_fp32 else 8                      # solve precision (K_nm of the step, W = K_nm L^-T, its backward)
+    n_loc = xs.shape[0]
+    K = args.topics
+    Mp = (M + 31) // 32 * 32
+    ms = {k: (v["ms"] / v["count"] if v["count"] else 0.0) for k, v in timing.items()}
+    per_step = {k: v["ms"] / kp for k, v in timing.items()}
+    flops = {  # useful flops per launch (triangular/symmetric halves skipped, nothing counted twice)
+        "fwd_w": 1.0 * n_loc * M * M, "loc": 2.0 * n_loc * M * K, "fwd_t": 1.0 * n_loc * M * M * K,
+        "bwd_wbar": (1.0 if eng.stores_t else 2.0) * n_loc * M * M * K,   # triangular T_k S_k^T vs dense W B_k
+        "bwd_knm": 1.0 * n_loc * M * M, "tn_sym": 1.0 * n_loc * M * M * K, "tn_gt": 2.0 * n_loc * M * M,
+    }
+    # whole 128-wide tiles are computed: executed / useful MFMA work of the triangular and symmetric products
+    tile_factor = {"fwd_t": 1.25, "tn_sym": 1.25, "fwd_w": 1.25, "bwd_knm": 1.25}
+    if eng.mfma_mode == "f16x3":
+        tile_factor["tn_sym"] = 1.25         # tn_topics_w2_kernel multiplies whole 128 x 64 tiles (20 of them at M = 512: 160 of 256 blocks for 128 needed)
+        tile_factor["fwd_t"] = 1.125         # fwd_t_split_q4_kernel: the triangle at 64-column granularity per wave
+    dom = max(flops, key=lambda k: per_step[k])
+    dom_t = ms[dom] * 1e-3
+    f32_equiv = flops[dom] / dom_t / 1e12 if dom_t > 0 else 0.0
+    split = eng.mfma_mode in SPLIT_PRODUCTS and dom in ("fwd_t", "bwd_wbar", "tn_sym", "tn_gt")
+    if dom in ("fwd_w", "bwd_knm") and not eng.pure_fp32:
+        pipe, peak, nprod = "f64", PEAK_F64_MFMA_TFLOPS, 1
+    elif split:
+        pipe, peak, nprod = ("bf16" if eng.mfma_mode == "bf16x6" else "f16"), PEAK_16BIT_MFMA_TFLOPS, SPLIT_PRODUCTS[eng.mfma_mode]
+    else:
+        pipe, peak, nprod = ("f32" if dtype == torch.float32 else "f64"), (PEAK_F32_MFMA_TFLOPS if dtype == torch.float32 else PEAK_F64_MFMA_TFLOPS), 1
+    issued = nprod * f32_equiv        # MFMA flops the algorithm needs on this pipe per second (products per multiply-add x useful f32 flops), TFLOP/s
+    issued_tiles = tile_factor.get(dom, 1.0) * issued      # including the work above the diagonal that whole tiles execute
+    f16 = eng.mfma_mode == "f16x3"
+    kname = {"fwd_t": "fwd_t_split_q4_kernel" if f16 else "fwd_t_split_cc_kernel",
+             "bwd_wbar": "bwd_wbar_f16_k64_kernel" if f16 else "bwd_wbar_split_kernel",
+             "tn_sym": "tn_topics_w2_kernel" if f16 else "gemm_tn_split_kernel<A_k>",
+             "tn_gt": "gemm_tn_split_kernel<GT>"}[dom] if split else (
+        f"gemm_nt<{dom}>" if not dom.startswith("tn") else f"gemm_tn<{dom}>")
+    # HBM bytes per launch of the dominant kernel from the PMC passes of this command (tools/profile_round.sh -> pmc_hbm.json)
+    traffic, traffic_note = None, "no profiles/%s/pmc_hbm.json" % PROFILE_ROUND
+    try:
+        pm = json.load(open(os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_hbm.json")))
+        ent = pm["kernels"].get(dom)
+        if pm.get("csrc_sha") != csrc_sha():
+            traffic_note = "profiles/%s/pmc_hbm.json was collected on other kernel sources (csrc_sha differs): stale, not reported" % PROFILE_ROUND
+        elif ent and pm.get("mfma_mode") == eng.mfma_mode and pm.get("N") == N and world == 1:
+            traffic = ent["traffic_bytes"]
+            traffic_note = pm.get("note", "")
+        else:
+            traffic_note = "pmc_hbm.json was collected for another configuration"
+    except Exception:
+        pass
+    knm_bytes = n_loc * M * esz + n_loc * D * esz + M * D * esz
+    knm_t = t_knm["ms"] / max(t_knm["count"], 1) * 1e-3
+    knm_gbs = knm_bytes / knm_t / 1e9 if knm_t > 0 else 0.0
+    knm_step_bytes = n_loc * Mp * ssz + n_loc * D * esz + M * D * ssz      # the step's own launch: solve precision, padded rows
+    knm_step_t = ms["k_nm"] * 1e-3
+    knm_step_gbs = knm_step_bytes / knm_step_t / 1e9 if knm_step_t > 0 else 0.0
+    extra = {
+        "roofline": {"bound": "mfma", "kernel": kname, "pipe": pipe,
+                     "achieved": issued, "peak": peak, "unit": "TFLOP/s", "frac": issued / peak, "traffic": traffic,
+                     "traffic_note": traffic_note,
+                     "algorithmic_flops_per_launch": flops[dom], "issued_flops_per_launch": tile_factor.get(dom, 1.0) * nprod * flops[dom],
+                     "products_per_f32_mac": nprod, "tile_granularity_factor": tile_factor.get(dom, 1.0),
+                     "frac_including_whole_tile_overcompute": issued_tiles / peak, "avg_ms": ms[dom],
+                     "f32_equivalent_tflops": f32_equiv, "f32_mfma_peak": PEAK_F32_MFMA_TFLOPS,
+                     "note": "achieved = USEFUL MFMA flops per second on the pipe the kernel runs on (algorithmic f32 flops x products per "
+                             "multiply-add; work above the diagonal that whole tiles execute is NOT counted - frac_including_whole_tile_overcompute "
+                             "has it); f32_equivalent_tflops = algorithmic f32 flops / time"},
+        "roofline_knm": {"bound": "hbm", "kernel": "knm_kernel<f32> (standalone, the metric's K_nm kernel)", "achieved": knm_gbs,
+                         "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": knm_gbs / PEAK_HBM_GBS, "traffic": knm_bytes,
+                         "traffic_note": "WRITE_SIZE of this kernel equals its algorithmic bytes (profiles/%s/pmc_hbm.json, k_nm_f32)" % PROFILE_ROUND,
+                         "bytes_per_launch": knm_bytes, "avg_ms": knm_t * 1e3,
+                         "in_step": {"kernel": ("knm_rbf_f64_kernel" if (ssz == 8 and args.kernel == "rbf") else f"knm_kernel<f{8 * ssz}>")
+                                               + " (the launch inside the step: solve precision, feeds W = K_nm L^-T)",
+                                     "achieved": knm_step_gbs, "peak": PEAK_HBM_GBS, "frac": knm_step_gbs / PEAK_HBM_GBS,
+                                     "bytes_per_launch": knm_step_bytes, "avg_ms": ms["k_nm"]}},
+        "kernel_ms_per_step": per_step, "kernel_pass_steps": kp, "perplexity": perplexity,
+    }
+    if world == 1 and args.cpu_baseline_n and min(args.cpu_baseline_n) > 0:
+        extra["cpu_baseline"] = cpu_baseline(args, M)
+        extra["gpu_over_cpu"] = steps_per_s / extra["cpu_baseline"]["value"]
+    return extra
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", 0))
@@ -275,89 +393,16 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    # ---- what the last timed step returned, taken before the passes below move the parameters on (replicated on every rank)
+    # ---- what the last timed step returned, taken before --full's passes move the parameters on (replicated on every rank)
     outputs = None
     if args.dump_outputs and rank == 0:
         outputs = {"loss": np.float64(loss)}
         outputs.update({k: v.cpu().numpy() for k, v in model.state_dict().items()})
-    # ---- second pass (untimed): per-kernel times from HIP events recorded on the launch streams inside the library
-    kp = max(1, args.kernel_pass_steps)
-    eng.set_timing(True)
-    for _ in range(kp):
-        svi.step(xs=xs, ws=ws, subsample=False)
-    barrier()
-    timing = eng.get_timing()
-    eng.set_timing(False)
-    perplexity = float(model.perplexity(xs, ws).item()) if world == 1 else None
-
-    # ---- standalone K_nm kernel (HBM roofline), same shard
-    knm_out = torch.empty(xs.shape[0], M, dtype=dtype, device=device)
-    for _ in range(5):                       # untimed: the first launches after the step loop run 10-15 % slow
-        eng.knm_into(xs, knm_out)
-    eng.set_timing(True)
-    for _ in range(args.knm_iters):
-        eng.knm_into(xs, knm_out)
-    torch.cuda.synchronize(device)
-    t_knm = eng.get_timing()["k_nm"]
-    eng.set_timing(False)
-    del knm_out
+    extra = full_measurements(args, svi, model, eng, xs, ws, N, world, rank, barrier, args.steps / dt) if args.full else {}
 
     if rank == 0:
-        esz = 4 if dtype == torch.float32 else 8
-        ssz = 4 if eng.pure_fp32 else 8                      # solve precision (K_nm of the step, W = K_nm L^-T, its backward)
         n_loc = xs.shape[0]
         K = args.topics
-        Mp = (M + 31) // 32 * 32
-        ms = {k: (v["ms"] / v["count"] if v["count"] else 0.0) for k, v in timing.items()}
-        per_step = {k: v["ms"] / kp for k, v in timing.items()}
-        flops = {  # useful flops per launch (triangular/symmetric halves skipped, nothing counted twice)
-            "fwd_w": 1.0 * n_loc * M * M, "loc": 2.0 * n_loc * M * K, "fwd_t": 1.0 * n_loc * M * M * K,
-            "bwd_wbar": (1.0 if eng.stores_t else 2.0) * n_loc * M * M * K,   # triangular T_k S_k^T vs dense W B_k
-            "bwd_knm": 1.0 * n_loc * M * M, "tn_sym": 1.0 * n_loc * M * M * K, "tn_gt": 2.0 * n_loc * M * M,
-        }
-        # whole 128-wide tiles are computed: executed / useful MFMA work of the triangular and symmetric products
-        tile_factor = {"fwd_t": 1.25, "tn_sym": 1.25, "fwd_w": 1.25, "bwd_knm": 1.25}
-        if eng.mfma_mode == "f16x3":
-            tile_factor["tn_sym"] = 1.25         # tn_topics_w2_kernel multiplies whole 128 x 64 tiles (20 of them at M = 512: 160 of 256 blocks for 128 needed)
-            tile_factor["fwd_t"] = 1.125         # fwd_t_split_q4_kernel: the triangle at 64-column granularity per wave
-        dom = max(flops, key=lambda k: per_step[k])
-        dom_t = ms[dom] * 1e-3
-        f32_equiv = flops[dom] / dom_t / 1e12 if dom_t > 0 else 0.0
-        split = eng.mfma_mode in SPLIT_PRODUCTS and dom in ("fwd_t", "bwd_wbar", "tn_sym", "tn_gt")
-        if dom in ("fwd_w", "bwd_knm") and not eng.pure_fp32:
-            pipe, peak, nprod = "f64", PEAK_F64_MFMA_TFLOPS, 1
-        elif split:
-            pipe, peak, nprod = ("bf16" if eng.mfma_mode == "bf16x6" else "f16"), PEAK_16BIT_MFMA_TFLOPS, SPLIT_PRODUCTS[eng.mfma_mode]
-        else:
-            pipe, peak, nprod = ("f32" if dtype == torch.float32 else "f64"), (PEAK_F32_MFMA_TFLOPS if dtype == torch.float32 else PEAK_F64_MFMA_TFLOPS), 1
-        issued = nprod * f32_equiv        # MFMA flops the algorithm needs on this pipe per second (products per multiply-add x useful f32 flops), TFLOP/s
-        issued_tiles = tile_factor.get(dom, 1.0) * issued      # including the work above the diagonal that whole tiles execute
-        f16 = eng.mfma_mode == "f16x3"
-        kname = {"fwd_t": "fwd_t_split_q4_kernel" if f16 else "fwd_t_split_cc_kernel",
-                 "bwd_wbar": "bwd_wbar_f16_k64_kernel" if f16 else "bwd_wbar_split_kernel",
-                 "tn_sym": "tn_topics_w2_kernel" if f16 else "gemm_tn_split_kernel<A_k>",
-                 "tn_gt": "gemm_tn_split_kernel<GT>"}[dom] if split else (
-            f"gemm_nt<{dom}>" if not dom.startswith("tn") else f"gemm_tn<{dom}>")
-        # HBM bytes per launch of the dominant kernel from the PMC passes of this command (tools/profile_round.sh -> pmc_hbm.json)
-        traffic, traffic_note = None, "no profiles/%s/pmc_hbm.json" % PROFILE_ROUND
-        try:
-            pm = json.load(open(os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_hbm.json")))
-            ent = pm["kernels"].get(dom)
-            if pm.get("csrc_sha") != csrc_sha():
-                traffic_note = "profiles/%s/pmc_hbm.json was collected on other kernel sources (csrc_sha differs): stale, not reported" % PROFILE_ROUND
-            elif ent and pm.get("mfma_mode") == eng.mfma_mode and pm.get("N") == N and world == 1:
-                traffic = ent["traffic_bytes"]
-                traffic_note = pm.get("note", "")
-            else:
-                traffic_note = "pmc_hbm.json was collected for another configuration"
-        except Exception:
-            pass
-        knm_bytes = n_loc * M * esz + n_loc * D * esz + M * D * esz
-        knm_t = t_knm["ms"] / max(t_knm["count"], 1) * 1e-3
-        knm_gbs = knm_bytes / knm_t / 1e9 if knm_t > 0 else 0.0
-        knm_step_bytes = n_loc * Mp * ssz + n_loc * D * esz + M * D * ssz      # the step's own launch: solve precision, padded rows
-        knm_step_t = ms["k_nm"] * 1e-3
-        knm_step_gbs = knm_step_bytes / knm_step_t / 1e9 if knm_step_t > 0 else 0.0
         survey_flops = 3 * (2.0 * N * M * M * K) + 3 * (2.0 * N * M * M) + 2 * (2.0 * N * M * K) + 2 * (2.0 * N * K * args.vocab)
         out = {
             "metric": "ELBO steps/sec (+ achieved HBM GB/s on K_nm) at N=1e6,M=512,K=10,V=50",
@@ -369,31 +414,10 @@ def main():
                                    f"Adam lr=1e-3, Trace_ELBO, 1 particle, jitter={args.jitter}, observations sharded over ranks",
                        "N": N, "M": M, "K": K, "V": args.vocab, "D": D, "rows_per_rank": n_loc,
                        "jitter_level": eng.last_jitter_level, "stores_T": eng.stores_t, "mfma_mode": eng.mfma_mode},
-            "roofline": {"bound": "mfma", "kernel": kname, "pipe": pipe,
-                         "achieved": issued, "peak": peak, "unit": "TFLOP/s", "frac": issued / peak, "traffic": traffic,
-                         "traffic_note": traffic_note,
-                         "algorithmic_flops_per_launch": flops[dom], "issued_flops_per_launch": tile_factor.get(dom, 1.0) * nprod * flops[dom],
-                         "products_per_f32_mac": nprod, "tile_granularity_factor": tile_factor.get(dom, 1.0),
-                         "frac_including_whole_tile_overcompute": issued_tiles / peak, "avg_ms": ms[dom],
-                         "f32_equivalent_tflops": f32_equiv, "f32_mfma_peak": PEAK_F32_MFMA_TFLOPS,
-                         "note": "achieved = USEFUL MFMA flops per second on the pipe the kernel runs on (algorithmic f32 flops x products per "
-                                 "multiply-add; work above the diagonal that whole tiles execute is NOT counted - frac_including_whole_tile_overcompute "
-                                 "has it); f32_equivalent_tflops = algorithmic f32 flops / time"},
-            "roofline_knm": {"bound": "hbm", "kernel": "knm_kernel<f32> (standalone, the metric's K_nm kernel)", "achieved": knm_gbs,
-                             "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": knm_gbs / PEAK_HBM_GBS, "traffic": knm_bytes,
-                             "traffic_note": "WRITE_SIZE of this kernel equals its algorithmic bytes (profiles/%s/pmc_hbm.json, k_nm_f32)" % PROFILE_ROUND,
-                             "bytes_per_launch": knm_bytes, "avg_ms": knm_t * 1e3,
-                             "in_step": {"kernel": ("knm_rbf_f64_kernel" if (ssz == 8 and args.kernel == "rbf") else f"knm_kernel<f{8 * ssz}>")
-                                                   + " (the launch inside the step: solve precision, feeds W = K_nm L^-T)",
-                                         "achieved": knm_step_gbs, "peak": PEAK_HBM_GBS, "frac": knm_step_gbs / PEAK_HBM_GBS,
-                                         "bytes_per_launch": knm_step_bytes, "avg_ms": ms["k_nm"]}},
             "step_f32_equivalent_tflops": survey_flops / world / (dt / args.steps) / 1e12,
-            "kernel_ms_per_step": per_step, "kernel_pass_steps": kp,
-            "final_loss": loss, "perplexity": perplexity,
+            "final_loss": loss,
         }
-        if world == 1 and args.cpu_baseline_n and min(args.cpu_baseline_n) > 0:
-            out["cpu_baseline"] = cpu_baseline(args, M)
-            out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+        out.update(extra)
         if outputs is not None:
             dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))

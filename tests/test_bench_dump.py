@@ -52,3 +52,8 @@ def test_large_outputs_are_sampled_within_the_budget_the_same_way_every_time(tmp
         s = a[k].astype(np.float64)
         assert s.ndim == 1 and 1000 < s.size < big.size, (k, s.size)
         assert (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < big.size and np.array_equal(s, np.round(s)), k
+
+
+def test_full_is_off_by_default():
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full", "--steps", "3"]).full is True

@@ -37,3 +37,17 @@ def test_dump_outputs_holds_the_last_timed_step_and_repeats_exactly(tmp_path):
         assert other.keys() == a.keys()
         for k in a:
             assert other[k].dtype == a[k].dtype and np.array_equal(other[k], a[k]), k
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_prints_the_headline_without_the_full_measurements():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "1", "--steps", "2",
+                        "--rows", "30000", "--n-points", "8", "8"], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 2
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3 and d["metric"].startswith("ELBO steps/sec")
+    assert not {"roofline", "roofline_knm", "kernel_ms_per_step", "kernel_pass_steps", "perplexity", "cpu_baseline",
+                "gpu_over_cpu"} & set(d)

@@ -370,8 +370,8 @@ def test_bench_multi_rank_path_on_one_gpu_matches_a_single_rank(tmp_path):
     contract's keys, and - the noise being keyed by the global row - end on the single-rank run's loss."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--rows", "30000", "--n-points", "8", "8", "--steps", "3", "--warmup", "1", "--cpu-baseline-n", "0", "--knm-iters", "2",
-              "--kernel-pass-steps", "1"]
+    common = ["--full", "--rows", "30000", "--n-points", "8", "8", "--steps", "3", "--warmup", "1", "--cpu-baseline-n", "0",
+              "--knm-iters", "2", "--kernel-pass-steps", "1"]
     env = dict(os.environ, GDRF_BENCH_ONE_GPU="1", GDRF_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = 31000 + (os.getpid() % 2000)
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",

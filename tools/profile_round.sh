@@ -3,11 +3,11 @@
 set -e
 R=$PWD; O=$R/gpurun_out/${1:-prof_round}; rm -rf $O; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-timeout -k 10 560 python3 $R/bench.py > $O/bench_default_run.log 2>$O/bench_default_run.err
+timeout -k 10 560 python3 $R/bench.py --full > $O/bench_default_run.log 2>$O/bench_default_run.err
 echo "default run done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 5 --warmup 1 --cpu-baseline-n 0 > $O/bench_under_trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 5 --warmup 1 --cpu-baseline-n 0 > $O/bench_under_trace.log 2>&1
 echo "trace done"
-P="--steps 1 --warmup 1 --knm-iters 3 --kernel-pass-steps 1 --cpu-baseline-n 0"
+P="--full --steps 1 --warmup 1 --knm-iters 3 --kernel-pass-steps 1 --cpu-baseline-n 0"
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/w -- python3 $R/bench.py $P > $O/pmc_w.log 2>&1
 echo "write pmc done"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/f -- python3 $R/bench.py $P > $O/pmc_f.log 2>&1
