@@ -68,6 +68,7 @@ SIGNATURES = {
     "gdrf_ws_copy": (_int, [_vp, _int, _vp, _i64, _vp]),
     "gdrf_set_timing": (_int, [_vp, _int]),
     "gdrf_get_timing": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_i64), _int]),
+    "gdrf_last_forms": (_int, [_vp, C.POINTER(_int), _int]),
 }
 
 

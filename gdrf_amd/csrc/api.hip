@@ -109,6 +109,7 @@ struct gdrf_ctx {
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> tev;   // (slot, (start, stop)) pending
   std::vector<hipEvent_t> ev_pool;
   double t_ms[GDRF_NSLOTS]; int64_t t_cnt[GDRF_NSLOTS];
+  int forms[GDRF_NFORMS];     // gdrf_last_forms: the form each shape-dispatched stage launched last (host bookkeeping, GDRF_FORM_* of gdrf_hip.h)
 };
 
 struct ScopedTimer {
@@ -321,6 +322,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   c->mean_count = 0;
   c->rows_form = 0; c->vs_tmp = c->vs_part = c->vs_cpart = c->vs_rs = nullptr; c->vs_gcap = 0; c->phibar_part = nullptr;
   for (int i = 0; i < GDRF_NSLOTS; ++i) { c->t_ms[i] = 0; c->t_cnt[i] = 0; }
+  memset(c->forms, 0, sizeof(c->forms));
   const size_t mm = (size_t)c->Mp * c->Mp * c->esz, mms = (size_t)c->Mp * c->Mp * c->ssz;
   auto A = [&](void** p, size_t bytes) -> int {
     hipError_t e = hipMalloc(p, bytes ? bytes : 16);
@@ -591,6 +593,11 @@ int gdrf_set_rows_form(gdrf_ctx* c, int form) {
   return 0;
 }
 int gdrf_get_rows_form(const gdrf_ctx* c) { return c->rows_form; }
+int gdrf_last_forms(const gdrf_ctx* c, int* out, int n) {
+  if (!c || (n > 0 && !out)) return fail(-1, "gdrf_last_forms", "null argument");
+  for (int i = 0; i < n; ++i) out[i] = i < GDRF_NFORMS ? c->forms[i] : 0;
+  return 0;
+}
 
 // the LDS row forms' Phi-bar partials, [erows_grid_cap][K*V]: allocated on the first launch that writes them
 static int phibar_part_ensure(gdrf_ctx* c) {
@@ -868,6 +875,7 @@ template <typename T, typename TS> struct Impl {
       // topics per group: as many lower-triangular S^T piece panels (NP x ~0.6 Mp^2 halfwords each) as fit in 2 MB
       const double panel = 0.625 * 2.0 * SP::NP * (double)Mp * Mp;
       const int KG = std::max(1, std::min(K, (int)(2.0 * 1024 * 1024 / panel)));
+      c->forms[GDRF_FORM_FWD_T] = SP::NP == 2 ? 2 : 3; c->forms[GDRF_FORM_FWD_T_KG] = KG;
       // two row tiles per 512-thread workgroup (two phase-shifted wave groups, LDS-DMA staging): 6 operand images
       const int64_t pairs = (rtiles + 1) / 2;
       const int rt8 = (int)((pairs + 7) / 8);
@@ -934,8 +942,9 @@ template <typename T, typename TS> struct Impl {
             const int nkb = Mp / 64;
             int nslice = 1;
             if (pairs * nct_ <= 32 && nkb >= 2) nslice = std::min(nkb, 8);
-            if ((size_t)nslice * n * Mp * sizeof(float) > (size_t)c->nsplit_cap * (K + 1) * Mp * Mp * sizeof(float)) nslice = 1;   // the TN slab buffer is idle now
+            if ((size_t)nslice * round_up(n, 256) * Mp > (size_t)c->nsplit_cap * (K + 1) * Mp * Mp) nslice = 1;   // the TN slab buffer is idle now
             if (nslice > 1) { a.slab = (float*)c->slab; a.slab_stride = (int64_t)round_up(n, 256) * Mp; a.nslice = nslice; }
+            c->forms[GDRF_FORM_WBAR] = 6; c->forms[GDRF_FORM_WBAR_NSLICE] = nslice;
             HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_f16_k64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
             hipLaunchKernelGGL(bwd_wbar_f16_k64_kernel, dim3((unsigned)round_up(pairs * nct_, 8), (unsigned)nslice), dim3(512), lds64, s, a);
             if (nslice > 1) {
@@ -947,16 +956,19 @@ template <typename T, typename TS> struct Impl {
         } else if (lds_cc <= 160 * 1024) {
           HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_cc_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cc));
           hipLaunchKernelGGL((bwd_wbar_split_cc_kernel<SP>), dim3((unsigned)round_up(pairs * nct_, 8)), dim3(512), lds_cc, s, a);
+          c->forms[GDRF_FORM_WBAR] = 5; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
         } else {
           const size_t lds = std::max<size_t>(2 * grp, 8 * 32 * 68 * sizeof(float));      // the epilogue's transposition tiles
           HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_kernel<SP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
           hipLaunchKernelGGL((bwd_wbar_split_kernel<SP, 2>), dim3((unsigned)round_up(pairs * nct_, 8)), dim3(512), lds, s, a);
+          c->forms[GDRF_FORM_WBAR] = 4; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
         }
       } else {
         if (grp > 160 * 1024) return fail(-1, "wbar_split", "too many topics for the LDS scale table");
         const size_t lds = std::max<size_t>(grp, 4 * 32 * 68 * sizeof(float));
         HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_kernel<SP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((bwd_wbar_split_kernel<SP, 1>), dim3((unsigned)round_up(rtiles * nct_, 8)), dim3(256), lds, s, a);
+        c->forms[GDRF_FORM_WBAR] = 3; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
       }
       LAUNCHCHK("wbar_split");
       return 0;
@@ -1124,6 +1136,7 @@ template <typename T, typename TS> struct Impl {
         if (ulds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)loc_rows_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ulds));
         const int64_t blocks = std::min<int64_t>((n + 31) / 32, 256 * 8);
         hipLaunchKernelGGL(loc_rows_kernel<T>, dim3((unsigned)blocks), dim3(256), ulds, c->side, (const T*)P(c->W), n, Mp, K, (const T*)P(c->Upad), P(c->loc), ldk);
+        c->forms[GDRF_FORM_LOC] = 1;
       } else {
         bool wide = false;
         if constexpr (sizeof(T) == 8) {
@@ -1137,6 +1150,7 @@ template <typename T, typename TS> struct Impl {
           LocProb<T> p{{}, {}, {}, P(c->W), n, Mp, K, P(c->Upad), P(c->loc), ldk};
           hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T>>), dim3((unsigned)rtiles), dim3(256), C::LDS_BYTES, c->side, p);
         }
+        c->forms[GDRF_FORM_LOC] = wide ? 3 : 2;
       }
     }
     HIPCHK(hipEventRecord(c->ev_loc, c->side));
@@ -1167,6 +1181,7 @@ template <typename T, typename TS> struct Impl {
       ScopedTimer tm(c, 5, s);
       FwdTProb<T> p{{K}, {}, {}, P(c->W), n, Mp, P(c->ST), P(c->tt), ldk, P(c->Tst), c->t_bs, c->t_ts};
       hipLaunchKernelGGL((gemm_nt_kernel<T, FwdTProb<T>>), dim3((unsigned)(8 * K * ((rtiles + 7) / 8))), dim3(256), C::LDS_BYTES, s, p);
+      c->forms[GDRF_FORM_FWD_T] = 1; c->forms[GDRF_FORM_FWD_T_KG] = 0;
     }
     LAUNCHCHK("forward");
     HIPCHK(hipStreamWaitEvent(s, c->ev_loc, 0));
@@ -1176,6 +1191,7 @@ template <typename T, typename TS> struct Impl {
     if ((mask & SL_ROWS) && c->rows_form == 1) {
       ScopedTimer tm(c, 6, s);
       if (int rc = rows_streamed(c, ws, eps, n, redT, redd, s)) return rc;
+      c->forms[GDRF_FORM_ROWS] = 3; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
     } else if (mask & SL_ROWS) {
       ScopedTimer tm(c, 6, s);
       if (int rc = phibar_part_ensure(c)) return rc;
@@ -1183,6 +1199,7 @@ template <typename T, typename TS> struct Impl {
       // register-resident operands; K <= 32, V <= 64 and 32-bit offsets.  The one-thread-per-row kernel serves the other sizes
       if (K <= 32 && V <= 64 && rows_mfma_offsets_fit<T>(K, nct<TS>(c), ldk, n)) {
         const int nkt = K <= 16 ? 1 : 2, nvt = V <= 32 ? 2 : 4;
+        c->forms[GDRF_FORM_ROWS] = 1; c->forms[GDRF_FORM_ROWS_KT] = nkt; c->forms[GDRF_FORM_ROWS_VT] = nvt;
         const size_t lds = rows_mfma_lds<T>(K, V, nkt, nvt, 4);
         const int64_t groups = (n + 15) / 16;
         egrid = (int)std::min<int64_t>((groups + 3) / 4, c->erows_grid_cap);
@@ -1206,6 +1223,7 @@ template <typename T, typename TS> struct Impl {
                                            "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB); "
                                            "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit");
       const void* kfn = kreg ? (const void*)elbo_rows_kernel<T, true> : (const void*)elbo_rows_kernel<T, false>;
+      c->forms[GDRF_FORM_ROWS] = 2; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       int64_t nblk = (n + RB - 1) / RB;
       egrid = (int)std::min<int64_t>(nblk, c->erows_grid_cap);
@@ -1242,6 +1260,7 @@ template <typename T, typename TS> struct Impl {
       const int64_t rpb = ubar_rows_per_block(n), nb = (n + rpb - 1) / rpb;
       if (nb > c->ubar_blocks_cap) return fail(-1, "gdrf_step_local", "ubar partial buffer too small");
       const int kq = K <= 16 ? (K + 3) / 4 : 4;
+      c->forms[GDRF_FORM_UBAR_Q4] = kq;
 #define GDRF_UBAR(Q4) hipLaunchKernelGGL((ubar_part_kernel<T, Q4>), dim3((unsigned)nb, (Mp + 255) / 256), dim3(256), 0, ss, P(c->W), n, Mp, K, P(c->locbar), \
                                           ldk, rpb, P(c->ubar_part))
       if (kq == 1) GDRF_UBAR(1); else if (kq == 2) GDRF_UBAR(2); else if (kq == 3) GDRF_UBAR(3); else GDRF_UBAR(4);
@@ -1260,6 +1279,7 @@ template <typename T, typename TS> struct Impl {
         if (lds > 48 * 1024)
           HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_kernel<T, BwdWbarTProb<T>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((gemm_nt_kernel<T, BwdWbarTProb<T>>), grid, dim3(256), lds, s, p);
+        c->forms[GDRF_FORM_WBAR] = 2; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
       } else if (c->split) {
         if ((rc = (c->split == 2 ? wbar_split<SplitF16>(c, n, U, rtiles, s) : wbar_split<SplitBf16>(c, n, U, rtiles, s)))) return rc;
         split_scales(c, SPLIT_SC_WBAR, s);           // max |Wbar| came out of the epilogue: scale of the G^T contraction's operand
@@ -1268,6 +1288,7 @@ template <typename T, typename TS> struct Impl {
         if (lds > 48 * 1024)
           HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_kernel<T, BwdWbarProb<T>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((gemm_nt_kernel<T, BwdWbarProb<T>>), grid, dim3(256), lds, s, p);
+        c->forms[GDRF_FORM_WBAR] = 1; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
       }
     }
     // Wbar is ready: G^T = W^T Wbar and ubar = locbar W go to the side stream, where they fill the last-round tails of
@@ -1282,6 +1303,7 @@ template <typename T, typename TS> struct Impl {
       T* slab_gt = P(c->slab) + (int64_t)c->nsplit_cap * K * mm;           // the (K+1)-th batch region of the slab buffer
       TNArgs<T> b{P(c->W), Mp, P(c->Wbar), Mp, nullptr, 0, n, rps, Mp, 0, slab_gt, 1, ns};
       { ScopedTimer tm(c, 10, ss);
+        c->forms[GDRF_FORM_GT] = c->split ? 2 : 1;
         if (c->split) {
           const int ib = SplitLay{K}.wbar();
           if ((rc = (c->split == 2 ? tn_split<SplitF16>(c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, (float*)slab_gt, 1, ns, c->nt * c->nt, ib, 0, ss)
@@ -1316,10 +1338,12 @@ template <typename T, typename TS> struct Impl {
         LAUNCHCHK("hyper_tn");
         HIPCHK(hipEventRecord(c->ev_join, c->side));           // the join event now also covers these
         hyper_done = true;
+        c->forms[GDRF_FORM_HYPER] = 2;
       }
     }
     if (!hyper_done) {
       ScopedTimer tm(c, 8, s);
+      c->forms[GDRF_FORM_HYPER] = 1;
       const int64_t nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
       if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
       if (c->per) {
@@ -1386,9 +1410,11 @@ template <typename T, typename TS> struct Impl {
             const int ntl = tnt_ntiles(Mp), kgroups = (K + TNT_KT - 1) / TNT_KT;
             TNTopicsArgs ta{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbar, ldk, n, rpst, Mp,
                             (float*)c->slab, K, nst, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
-            // The one-wave forms run every stage of their 10-topic groups whatever K: with more than 40 % of the topic slots empty (K <= 5, K = 11 .. 12)
+            // The one-wave forms run every stage of their 10-topic groups whatever K: with more than 40 % of the topic slots empty (K <= 5, K = 11)
             // the two-wave form, which walks the topic pairs that exist, is the faster one.
+            c->forms[GDRF_FORM_AK_KGROUPS] = kgroups;
             if (10 * K >= 6 * kgroups * TNT_KT) {      // one-wave-per-SIMD form (gemm_tn_topics1.h): 128 rows per wave
+              c->forms[GDRF_FORM_AK] = 4;
               int ns1 = c->nsplit_cap < 64 ? c->nsplit_cap : 64;                            // 8 k splits: every XCD owns whole splits
               while (ns1 > 8 && (n + ns1 - 1) / ns1 < 8 * TN1_CH) ns1 -= 8;                 // at least 8 chunks per split
               if (ns1 >= 8) ns1 &= ~7;
@@ -1409,6 +1435,7 @@ template <typename T, typename TS> struct Impl {
               LAUNCHCHK("tn_topics_w2");
               red_ns = ns1; red_qd = 32;
             } else {
+              c->forms[GDRF_FORM_AK] = 3;
               HIPCHK(hipFuncSetAttribute((const void*)tn_topics_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tnt_lds_bytes()));
               hipLaunchKernelGGL(tn_topics_f16_kernel, dim3((unsigned)(ntl * kgroups * nst)), dim3(512), tnt_lds_bytes(), s, ta);
               LAUNCHCHK("tn_topics");
@@ -1416,10 +1443,12 @@ template <typename T, typename TS> struct Impl {
             }
           }
         } else if (c->split) {
+          c->forms[GDRF_FORM_AK] = 2; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
           const int ib = SplitLay{K}.v(0), ntl = c->nt * (c->nt + 1) / 2;
           if ((rc = (c->split == 2 ? tn_split<SplitF16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s)
                                    : tn_split<SplitBf16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s)))) return rc;
         } else {
+          c->forms[GDRF_FORM_AK] = 1; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
           hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * (c->nt + 1) / 2 * K * ns)), dim3(256), TNCfg<T>::LDS_BYTES, s, a);
         } }
       { ScopedTimer tm(c, 11, s);

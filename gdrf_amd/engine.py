@@ -350,6 +350,25 @@ class Engine:
         _lib.check(self.lib.gdrf_get_timing(self.ctx, ms, cnt, n), "gdrf_get_timing")
         return {name: dict(ms=ms[i], count=cnt[i]) for i, name in enumerate(self.TIMING_SLOTS)}
 
+    # gdrf_last_forms slots (include/gdrf_hip.h) and the names of their codes; the slots without names are counts
+    FORM_SLOTS = ("wbar", "wbar_nslice", "a_k", "a_k_kgroups", "fwd_t", "fwd_t_kg", "loc", "ubar_q4", "rows", "rows_kt", "rows_vt", "gt",
+                  "hyper")
+    FORM_NAMES = dict(wbar=("gemm_nt", "gemm_nt_t", "split<1>", "split<2>", "split_cc", "k64"), a_k=("gemm_tn", "tn_split", "tn_topics", "w2"),
+                      fwd_t=("gemm_nt", "q4", "cc"), loc=("rows", "gemm_nt", "gemm_nt_wide"), rows=("mfma", "thread", "streamed"),
+                      gt=("gemm_tn", "tn_split"), hyper=("f64", "tn"))
+
+    def last_forms(self) -> Dict[str, object]:
+        """The kernel form each stage that the library picks from K, Mp or n launched in the most recent call that ran it
+        (gdrf_last_forms): names for the form slots, counts for the others; stages that have not run yet are left out."""
+        n = len(self.FORM_SLOTS)
+        arr = (C.c_int * n)()
+        _lib.check(self.lib.gdrf_last_forms(self.ctx, arr, n), "gdrf_last_forms")
+        out = {}
+        for slot, v in zip(self.FORM_SLOTS, arr):
+            if v:
+                out[slot] = self.FORM_NAMES[slot][v - 1] if slot in self.FORM_NAMES else v
+        return out
+
     # ---- primitives ------------------------------------------------------------------------------
     def _chk_rows(self, xs: torch.Tensor, ws: Optional[torch.Tensor] = None):
         if xs.device != self.device or xs.dtype != self.dtype or not xs.is_contiguous() or xs.dim() != 2 or xs.shape[1] != self.D:

@@ -323,6 +323,25 @@ int gdrf_ws_copy(gdrf_ctx* ctx, int which, void* dst_dev, int64_t nelem, void* s
 int gdrf_set_timing(gdrf_ctx* ctx, int enable);
 int gdrf_get_timing(gdrf_ctx* ctx, double* ms_out, int64_t* count_out, int nslots);
 
+/* The kernel form each stage that the host picks from K, Mp or n launched in the most recent call that ran it (host bookkeeping,
+ * no synchronisation; 0 = not run yet in this context).  out[i] = slot i for i < n (slots past GDRF_NFORMS read 0):
+ *   GDRF_FORM_WBAR         Wbar: 1 gemm_nt (dense B_k), 2 gemm_nt on the stored T_k, 3 bwd_wbar_split<SP,1>, 4 bwd_wbar_split<SP,2>,
+ *                          5 bwd_wbar_split_cc, 6 bwd_wbar_f16_k64
+ *   GDRF_FORM_WBAR_NSLICE  reduction slices of the k64 form (> 1: partial sums in slabs, then wbar_slab_sum); 1 for the others
+ *   GDRF_FORM_AK           A_k: 1 gemm_tn, 2 gemm_tn_split, 3 tn_topics_f16 (two waves per SIMD), 4 tn_topics_w2 (one wave per SIMD)
+ *   GDRF_FORM_AK_KGROUPS   10-topic groups of forms 3 and 4 (0 for the others)
+ *   GDRF_FORM_FWD_T        tt: 1 gemm_nt, 2 fwd_t_split_q4, 3 fwd_t_split_cc
+ *   GDRF_FORM_FWD_T_KG     topics per L2 group of forms 2 and 3 (0 for gemm_nt)
+ *   GDRF_FORM_LOC          loc = W U^T: 1 loc_rows, 2 gemm_nt, 3 gemm_nt with two column tiles (f64, K > 64)
+ *   GDRF_FORM_UBAR_Q4      topic quads per pass of ubar_part
+ *   GDRF_FORM_ROWS         row terms: 1 elbo_rows_mfma, 2 elbo_rows (one thread per row), 3 vocabulary-streamed
+ *   GDRF_FORM_ROWS_KT, _VT 16-topic and 16-word tiles of elbo_rows_mfma (0 for the others)
+ *   GDRF_FORM_GT           G^T = W^T Wbar: 1 gemm_tn, 2 gemm_tn_split
+ *   GDRF_FORM_HYPER        K_nm parts of the hyper-parameter gradients: 1 the backward GEMM (form 0 of gdrf_set_hyper_backward), 2 Hd (form 1) */
+enum { GDRF_FORM_WBAR = 0, GDRF_FORM_WBAR_NSLICE, GDRF_FORM_AK, GDRF_FORM_AK_KGROUPS, GDRF_FORM_FWD_T, GDRF_FORM_FWD_T_KG, GDRF_FORM_LOC,
+       GDRF_FORM_UBAR_Q4, GDRF_FORM_ROWS, GDRF_FORM_ROWS_KT, GDRF_FORM_ROWS_VT, GDRF_FORM_GT, GDRF_FORM_HYPER, GDRF_NFORMS };
+int gdrf_last_forms(const gdrf_ctx* ctx, int* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
