@@ -130,22 +130,24 @@ struct ScopedTimer {
 const char* gdrf_last_error(void) { return g_err.c_str(); }
 int gdrf_version(void) { return 1; }
 
-static int64_t poff(const gdrf_ctx* c, int which) {
-  // flat parameter layout; every segment starts on a multiple of 4 elements
-  const int64_t o_uloc = 4, o_phi = round_up(o_uloc + (int64_t)c->K * c->M, 4);
-  const int64_t o_S = round_up(o_phi + (int64_t)c->K * c->V, 4);
-  const int64_t o_Z = round_up(o_S + (int64_t)c->K * c->M * c->M, 4);          // unconstrained inducing inputs (M, D)
-  const int64_t o_ard = round_up(o_Z + (int64_t)c->M * c->Dr, 4);              // ARD contexts only: the D log-lengthscales
-  // periodic contexts only: the np log-periods, right behind them.  Product contexts: the nf factor log-variances at o_ard, then the nls
-  // log-lengthscales (o_pls), then the nper log-periods (o_per)
-  const int64_t o_pls = o_ard + c->nf;
-  const int64_t o_per = c->prod ? o_pls + c->nls : o_ard + (c->ard ? c->Dr : 0);
-  const int64_t o_mean = c->prod ? round_up(o_per + c->nper, 4)
-                                 : (c->ard || c->per) ? round_up(o_per + c->np, 4) : o_ard;   // contexts with gdrf_set_mean_params only: mean_function parameters
-  const int64_t total = c->mean_count ? round_up(o_mean + c->mean_count, 4) : o_mean;
-  switch (which) { case 0: return 0; case 1: return 1; case 2: return 2; case 3: return o_uloc; case 4: return o_phi;
-                   case 5: return o_S; case 7: return o_Z; case 8: return o_ard; case 9: return o_mean; case 10: return o_per;
-                   case 11: return o_pls; default: return total; }
+// Flat parameter layout: three scalars at 0, 1, 2, then the segments below, each starting on a multiple of 4 elements.  Setters change it
+// after creation (ard, nf, nls, nper, np, mean_count), so it is computed on demand.
+struct ParamLay { int64_t uloc, phi, S, Z, ard, pls, per, mean, total; };
+static ParamLay param_lay(const gdrf_ctx* c) {
+  ParamLay l;
+  l.uloc = 4;
+  l.phi = round_up(l.uloc + (int64_t)c->K * c->M, 4);
+  l.S = round_up(l.phi + (int64_t)c->K * c->V, 4);
+  l.Z = round_up(l.S + (int64_t)c->K * c->M * c->M, 4);          // unconstrained inducing inputs (M, D)
+  l.ard = round_up(l.Z + (int64_t)c->M * c->Dr, 4);              // ARD contexts only: the D log-lengthscales
+  // periodic contexts only: the np log-periods, right behind them.  Product contexts: the nf factor log-variances at ard, then the nls
+  // log-lengthscales (pls), then the nper log-periods (per)
+  l.pls = l.ard + c->nf;
+  l.per = c->prod ? l.pls + c->nls : l.ard + (c->ard ? c->Dr : 0);
+  l.mean = c->prod ? round_up(l.per + c->nper, 4)
+                   : (c->ard || c->per) ? round_up(l.per + c->np, 4) : l.ard;   // contexts with gdrf_set_mean_params only: mean_function parameters
+  l.total = c->mean_count ? round_up(l.mean + c->mean_count, 4) : l.mean;
+  return l;
 }
 // doubles of red_d: 8 scalars, the (M, D) inducing-input sums, in ARD contexts the D sums of d / d log ls_d over the rows, then the
 // caller's sums of d elbo / d theta of the mean_function parameters (gdrf_set_mean_params)
@@ -154,31 +156,44 @@ static int64_t red_nd(const gdrf_ctx* c) {
   return 8 + (int64_t)c->M * c->D + ((c->ard || c->per) ? c->D : 0) + (c->per ? c->npair : 0) + c->mean_count;
 }
 static int64_t red_mean_off(const gdrf_ctx* c) { return red_nd(c) - c->mean_count; }
-static int64_t roff(const gdrf_ctx* c, int which) {
+// layout of red_T: ubar (K, Mp), phibar (K, V), A_k (K, Mp, Mp), G^T (Mp, Mp), then the tail
+struct RedLay { int64_t ubar, phibar, A, GT, tail, total; };
+static RedLay red_lay(const gdrf_ctx* c) {
   const int64_t mm = (int64_t)c->Mp * c->Mp;
-  const int64_t o_ubar = 0, o_phib = round_up((int64_t)c->K * c->Mp, 4), o_A = round_up(o_phib + (int64_t)c->K * c->V, 4);
-  const int64_t o_GT = o_A + c->K * mm, o_tail = o_GT + mm;
+  RedLay l;
+  l.ubar = 0;
+  l.phibar = round_up((int64_t)c->K * c->Mp, 4);
+  l.A = round_up(l.phibar + (int64_t)c->K * c->V, 4);
+  l.GT = l.A + c->K * mm;
+  l.tail = l.GT + mm;
   // tail: the doubles of red_d for the step's single all-reduce (gdrf_payload_pack): as they are in f64 contexts, four float
   // pieces each in f32 ones
-  const int64_t nd = red_nd(c), total = o_tail + round_up(c->esz == 8 ? nd : 4 * nd, 4);
-  switch (which) { case 0: return o_ubar; case 1: return o_phib; case 2: return o_A; case 3: return o_GT; case 5: return o_tail; default: return total; }
+  const int64_t nd = red_nd(c);
+  l.total = l.tail + round_up(c->esz == 8 ? nd : 4 * nd, 4);
+  return l;
 }
 
-int gdrf_param_layout(const gdrf_ctx* c, int64_t out[7]) { for (int i = 0; i < 7; ++i) out[i] = poff(c, i); return 0; }
+int gdrf_param_layout(const gdrf_ctx* c, int64_t out[7]) {
+  const ParamLay l = param_lay(c);
+  out[0] = 0; out[1] = 1; out[2] = 2; out[3] = l.uloc; out[4] = l.phi; out[5] = l.S; out[6] = l.total;
+  return 0;
+}
 int gdrf_red_layout(const gdrf_ctx* c, int64_t out[6]) {
-  for (int i = 0; i < 5; ++i) out[i] = roff(c, i);
-  out[5] = red_nd(c);          // 8 scalars, then the (M, D) inducing-input sums (learnable inducing points), then the ARD sums, then the mean segment
+  const RedLay l = red_lay(c);
+  out[0] = l.ubar; out[1] = l.phibar; out[2] = l.A; out[3] = l.GT; out[4] = l.total;
+  out[5] = red_nd(c);          // the doubles of red_d, in the order red_nd lists them
   return 0;
 }
-int gdrf_inducing_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 7); out[1] = (int64_t)c->M * c->Dr; return 0; }
-int gdrf_ard_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 8); out[1] = c->ard ? c->Dr : 0; return 0; }
-int gdrf_periodic_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 10); out[1] = c->np; return 0; }
+int gdrf_inducing_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = param_lay(c).Z; out[1] = (int64_t)c->M * c->Dr; return 0; }
+int gdrf_ard_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = param_lay(c).ard; out[1] = c->ard ? c->Dr : 0; return 0; }
+int gdrf_periodic_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = param_lay(c).per; out[1] = c->np; return 0; }
 int gdrf_product_layout(const gdrf_ctx* c, int64_t out[6]) {
-  out[0] = poff(c, 8); out[1] = c->nf; out[2] = poff(c, 11); out[3] = c->nls; out[4] = poff(c, 10); out[5] = c->nper;
+  const ParamLay l = param_lay(c);
+  out[0] = l.ard; out[1] = c->nf; out[2] = l.pls; out[3] = c->nls; out[4] = l.per; out[5] = c->nper;
   return 0;
 }
-// the parameters a factorisation depends on beyond slots 0-3 and Z, contiguous from poff(c, 8): the ARD log-lengthscales and the log-periods
-// of a periodic context, the three segments of a product one
+// the parameters a factorisation depends on beyond slots 0-3 and Z, contiguous from the ard offset: the ARD log-lengthscales and the
+// log-periods of a periodic context, the three segments of a product one
 static int snap_extra(const gdrf_ctx* c) { return c->prod ? c->nf + c->nls + c->nper : (c->ard ? c->Dr : 0) + c->np; }
 // embedded coordinates the context's buffers hold: a product context's table may change until its first step
 static int dcap(const gdrf_ctx* c) { return c->prod ? GDRF_DMAX : c->D; }
@@ -186,21 +201,22 @@ static int dcap(const gdrf_ctx* c) { return c->prod ? GDRF_DMAX : c->D; }
 // its raw axes; a product context lists the sources of its Periodic factors (pairs), then those of its RBF factors, each in factor order.
 static CoordTab coord_tab(const gdrf_ctx* c) {
   CoordTab t{};
+  const ParamLay pl = param_lay(c);
   t.dr = c->Dr;
   if (!c->prod) {
     t.D = 2 * c->Dr; t.npair = t.nsrc = c->Dr; t.nvar = 1; t.var[0] = 1;
     for (int d = 0; d < c->Dr; ++d) {
       t.ax[d] = d;
-      t.ls[d] = c->ard ? poff(c, 8) + d : 0;
-      t.per[d] = poff(c, 10) + (c->np > 1 ? d : 0);
+      t.ls[d] = c->ard ? pl.ard + d : 0;
+      t.per[d] = pl.per + (c->np > 1 ? d : 0);
     }
     return t;
   }
-  int64_t lsb[GDRF_DMAX], pb[GDRF_DMAX], ol = poff(c, 11), op = poff(c, 10);
+  int64_t lsb[GDRF_DMAX], pb[GDRF_DMAX], ol = pl.pls, op = pl.per;
   for (int f = 0; f < c->nf; ++f) {
     lsb[f] = ol; ol += c->pfac[f][2];
     pb[f] = op; op += c->pfac[f][3];
-    t.var[f] = poff(c, 8) + f;
+    t.var[f] = pl.ard + f;
   }
   t.nvar = c->nf;
   int j = 0;
@@ -221,7 +237,7 @@ static CoordTab coord_tab(const gdrf_ctx* c) {
 }
 // the covariance forms of the forward and predictive paths: ARD scales on the rows (a periodic context's embedding carries its own)
 static bool ard_fwd(const gdrf_ctx* c) { return c->ard && !c->per; }
-int gdrf_mean_param_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = poff(c, 9); out[1] = c->mean_count; return 0; }
+int gdrf_mean_param_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = param_lay(c).mean; out[1] = c->mean_count; return 0; }
 
 // row blocks of the ubar partial kernel: ~1024 workgroups, multiples of its 256-row staging step
 static int64_t ubar_rows_per_block(int64_t n) { return std::max<int64_t>(256, round_up((n + 1023) / 1024, 256)); }
@@ -286,6 +302,19 @@ static int tn_topics_nsplit(const gdrf_ctx* c, int64_t n) {
   return best;
 }
 
+// Device memory the context owns until gdrf_ctx_destroy.  A block that a later call replaces (Wh, Xe, opt_part) stays owned as well: queued
+// work may still read it.  `what` labels the error of a failed allocation.
+template <typename P>
+static int ctx_alloc(gdrf_ctx* c, P** p, size_t bytes, const char* what, bool zero = false) {
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess) return fail(-(int)e - 1000, what, hipGetErrorString(e));
+  c->allocs.push_back(q);
+  if (zero) HIPCHK(hipMemset(q, 0, bytes));
+  *p = (P*)q;
+  return 0;
+}
+
 int gdrf_ctx_create(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, int V, int D, int dtype, int kernel_id) {
   return gdrf_ctx_create_ex(out, device, n_cap, M, K, V, D, dtype, kernel_id, GDRF_STORE_T_OFF);
 }
@@ -301,11 +330,10 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   if (kernel_id == GDRF_PERIODIC) D = 2 * D;       // the embedded coordinates (cos, sin) of every raw axis
   if (kernel_id == GDRF_PRODUCT) D = GDRF_DMAX;    // buffers for any table; the default table is one RBF factor over every axis
   HIPCHK(hipSetDevice(device));
-  gdrf_ctx* c = new gdrf_ctx();
+  gdrf_ctx* c = new gdrf_ctx();       // value-initialised (no user-provided constructor): every member not set below is zero / null / empty
   c->dev = device; c->M = M; c->Mp = (int)round_up(M, GDRF_MPAD); c->K = K; c->V = V; c->D = D; c->Dr = Dr;
-  c->per = kernel_id == GDRF_PERIODIC || kernel_id == GDRF_PRODUCT; c->np = kernel_id == GDRF_PERIODIC ? 1 : 0; c->Xe = c->Zph = nullptr; c->xe_cap = 0;
-  c->prod = kernel_id == GDRF_PRODUCT; c->nf = c->nls = c->nper = 0; c->npair = kernel_id == GDRF_PERIODIC ? Dr : 0;
-  memset(c->pfac, 0, sizeof(c->pfac));
+  c->per = kernel_id == GDRF_PERIODIC || kernel_id == GDRF_PRODUCT; c->np = kernel_id == GDRF_PERIODIC ? 1 : 0;
+  c->prod = kernel_id == GDRF_PRODUCT; c->npair = kernel_id == GDRF_PERIODIC ? Dr : 0;
   if (c->prod) {
     c->nf = 1; c->nls = 1; c->D = Dr;
     c->pfac[0][0] = GDRF_RBF; c->pfac[0][1] = Dr; c->pfac[0][2] = 1;
@@ -315,26 +343,11 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   c->esz = dtype == GDRF_F64 ? 8 : 4;
   c->ssz = dtype == GDRF_F32_PURE ? 4 : 8;
   c->nt = (c->Mp + GDRF_TILE - 1) / GDRF_TILE;
-  c->lgam_const = 0; c->alpha_dev = nullptr; c->timing = 0;
-  c->pK = c->pL = nullptr; c->Tst = nullptr; c->side = nullptr; c->Bh = c->STh = c->Wh = nullptr; c->split = 0; c->wh_pieces = 0; c->ssc = nullptr; c->smx = nullptr;
-  c->ev_fork = c->ev_loc = c->ev_fork2 = c->ev_join = c->ev_fact0 = c->ev_fact = nullptr; c->fact_pending = 0; c->learn_z = 0; c->zpart = nullptr; c->ard = 0; c->Zp = nullptr; c->apart = nullptr; c->unwhitened = 0; c->mean = nullptr; c->mean_sk = c->mean_sn = 0;
-  c->allreduce = nullptr; c->allreduce_user = nullptr; c->hyper_tn = 0; c->hpart = nullptr; c->dKh = nullptr; c->uS = c->uSb = c->uSc = c->uU = c->uUb = c->Uw = nullptr; c->g_loc = nullptr; c->mean_g = nullptr; c->mean_g_sk = c->mean_g_sn = 0; c->opt_part = nullptr; c->opt_part_cap = 0;
-  c->mean_count = 0;
-  c->rows_form = 0; c->vs_tmp = c->vs_part = c->vs_cpart = c->vs_rs = nullptr; c->vs_gcap = 0; c->phibar_part = nullptr;
-  for (int i = 0; i < GDRF_NSLOTS; ++i) { c->t_ms[i] = 0; c->t_cnt[i] = 0; }
-  memset(c->forms, 0, sizeof(c->forms));
   const size_t mm = (size_t)c->Mp * c->Mp * c->esz, mms = (size_t)c->Mp * c->Mp * c->ssz;
-  auto A = [&](void** p, size_t bytes) -> int {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc", hipGetErrorString(e));
-    c->allocs.push_back(*p);
-    return 0;
-  };
-  int rc = 0;
-#define AL(ptr, bytes) if ((rc = A((void**)&(ptr), (bytes)))) { gdrf_ctx_destroy(c); return rc; }
+  auto A = [&](auto** p, size_t bytes) { return ctx_alloc(c, p, bytes ? bytes : 16, "hipMalloc"); };
+#define AL(ptr, bytes) if (int rc = A(&(ptr), (bytes))) { gdrf_ctx_destroy(c); return rc; }
   AL(c->Kuu, mms) AL(c->Lw, mms) AL(c->Lo, mms)
   c->mmslab_bytes = 8 * mms;
-  c->prefact_valid = 0; c->prefact_jitter = 0;
   AL(c->snap, (size_t)(4 + (size_t)c->M * D + (c->prod ? 3 : 1) * GDRF_DMAX) * c->esz)
   AL(c->mmslab, c->mmslab_bytes) AL(c->L, mms) AL(c->LT, mms) AL(c->Linv, mms) AL(c->LinvT, mms)
   AL(c->Dinv, (size_t)(c->Mp / 32) * 1024 * c->ssz)
@@ -464,10 +477,8 @@ int gdrf_set_mfma_mode(gdrf_ctx* c, int mode) {
   HIPCHK(hipSetDevice(c->dev));
   const int np = mode == 1 ? 3 : (mode == 2 ? 2 : 0);
   if (np > c->wh_pieces) {            // 16-bit pieces of W: np x n_cap x Mp halfwords, allocated on first use
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, (size_t)np * c->ncap * c->Mp * 2);
-    if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(Wh)", hipGetErrorString(e));
-    c->Wh = p; c->wh_pieces = np; c->allocs.push_back(p);          // a smaller earlier block stays owned by the context until destroy
+    if (int rc = ctx_alloc(c, &c->Wh, (size_t)np * c->ncap * c->Mp * 2, "hipMalloc(Wh)")) return rc;
+    c->wh_pieces = np;
   }
   c->split = mode;
   return 0;
@@ -492,13 +503,8 @@ int gdrf_set_whiten(gdrf_ctx* c, int whiten) {
     const size_t kmm = (size_t)c->K * c->Mp * c->Mp * c->ssz, kv = (size_t)c->K * c->Mp * c->ssz;
     void** ps[] = {&c->uS, &c->uSb, &c->uSc, &c->uU, &c->uUb, &c->Uw};
     const size_t sz[] = {kmm, kmm, kmm, kv, kv, (size_t)c->K * c->M * c->esz};
-    for (int i = 0; i < 6; ++i) {
-      void* p = nullptr;
-      hipError_t e = hipMalloc(&p, sz[i]);
-      if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(unwhitened scratch)", hipGetErrorString(e));
-      HIPCHK(hipMemset(p, 0, sz[i]));
-      *ps[i] = p; c->allocs.push_back(p);
-    }
+    for (int i = 0; i < 6; ++i)
+      if (int rc = ctx_alloc(c, ps[i], sz[i], "hipMalloc(unwhitened scratch)", true)) return rc;
   }
   c->unwhitened = !whiten;
   return 0;
@@ -507,11 +513,8 @@ int gdrf_set_learn_inducing(gdrf_ctx* c, int on) {
   if (on != 0 && on != 1) return fail(-1, "gdrf_set_learn_inducing", "on must be 0 or 1");
   HIPCHK(hipSetDevice(c->dev));
   if (on && !c->zpart) {
-    void* p = nullptr;
     const size_t bytes = (size_t)((c->ncap + GDRF_TILE - 1) / GDRF_TILE) * c->M * dcap(c) * sizeof(double);
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(zpart)", hipGetErrorString(e));
-    c->zpart = (double*)p; c->allocs.push_back(p);
+    if (int rc = ctx_alloc(c, &c->zpart, bytes, "hipMalloc(zpart)")) return rc;
   }
   c->learn_z = on;
   return 0;
@@ -522,14 +525,8 @@ int gdrf_set_ard(gdrf_ctx* c, int on) {
   HIPCHK(hipSetDevice(c->dev));
   if (on && !c->Zp) {
     // apart: D per backward workgroup (at most dpart_len / 3 of them, gdrf_step_local checks) or per inducing point (M < dpart_len)
-    const size_t sz[] = {(size_t)c->Mp * c->D * c->esz, (size_t)c->dpart_len * c->D * sizeof(double)};
-    void** ps[] = {&c->Zp, (void**)&c->apart};
-    for (int i = 0; i < 2; ++i) {
-      void* p = nullptr;
-      hipError_t e = hipMalloc(&p, sz[i]);
-      if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(ARD scratch)", hipGetErrorString(e));
-      *ps[i] = p; c->allocs.push_back(p);
-    }
+    if (int rc = ctx_alloc(c, &c->Zp, (size_t)c->Mp * c->D * c->esz, "hipMalloc(ARD scratch)")) return rc;
+    if (int rc = ctx_alloc(c, &c->apart, (size_t)c->dpart_len * c->D * sizeof(double), "hipMalloc(ARD scratch)")) return rc;
   }
   c->ard = on;
   c->prefact_valid = 0;
@@ -602,11 +599,7 @@ int gdrf_last_forms(const gdrf_ctx* c, int* out, int n) {
 // the LDS row forms' Phi-bar partials, [erows_grid_cap][K*V]: allocated on the first launch that writes them
 static int phibar_part_ensure(gdrf_ctx* c) {
   if (c->phibar_part) return 0;
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, (size_t)c->erows_grid_cap * c->K * c->V * c->esz);
-  if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(phibar_part)", hipGetErrorString(e));
-  c->phibar_part = p; c->allocs.push_back(p);
-  return 0;
+  return ctx_alloc(c, &c->phibar_part, (size_t)c->erows_grid_cap * c->K * c->V * c->esz, "hipMalloc(phibar_part)");
 }
 // form 1 scratch on first use.  The grid of the streamed kernels is capped so that its Phi-bar slots take at most
 // max(256 MiB, 16 K V elements), never 1024 K V: vs_gcap = min(1024, max(16, 256 MiB / (K V esz)), ceil(n_cap / 64))
@@ -616,13 +609,9 @@ static int vs_ensure(gdrf_ctx* c) {
   c->vs_gcap = std::min<int64_t>({(int64_t)1024, std::max<int64_t>(16, (int64_t)((size_t)256 << 20) / (int64_t)kv), (c->ncap + 63) / 64});
   void** ps[] = {&c->vs_tmp, &c->vs_cpart, &c->vs_rs, &c->vs_part};
   const size_t sz[] = {(size_t)c->K * c->ldk * c->esz, (size_t)c->vs_gcap * c->K * c->esz, (size_t)2 * c->K * c->esz, (size_t)c->vs_gcap * kv};
-  for (int i = 0; i < 4; ++i) {
-    if (*ps[i]) continue;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, sz[i]);
-    if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(streamed row form scratch)", hipGetErrorString(e));
-    *ps[i] = p; c->allocs.push_back(p);
-  }
+  for (int i = 0; i < 4; ++i)
+    if (!*ps[i])
+      if (int rc = ctx_alloc(c, ps[i], sz[i], "hipMalloc(streamed row form scratch)")) return rc;
   return 0;
 }
 int gdrf_ws_elem_size(gdrf_ctx* c, int which) { void* p; int64_t n; int e; return ws_lookup(c, which, &p, &n, &e) ? -1 : e; }
@@ -661,6 +650,23 @@ int gdrf_ws_copy(gdrf_ctx* c, int which, void* dst, int64_t nelem, void* stream)
   if ((rc = join_fact(c, (hipStream_t)stream))) return rc;
   HIPCHK(hipMemcpyAsync(dst, p, (size_t)nelem * e, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
+}
+
+// A launch with `lds` bytes of dynamic LDS: more than the 48 KB default needs the kernel's limit raised first
+template <typename... KA, typename... A>
+static int launch_lds(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+  return 0;
+}
+
+// fn<SP>(...) of Impl for the context's split mode: 2 = f16x3 (SplitF16), 1 = bf16x6 (SplitBf16)
+#define BY_SPLIT(c, fn, ...) ((c)->split == 2 ? fn<SplitF16>(__VA_ARGS__) : fn<SplitBf16>(__VA_ARGS__))
+
+// the LDS row forms of the two-point and link steps hold the (K, V) word-topic matrix and its gradient in LDS
+#define GDRF_STREAMED_HINT "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit"
+static int rows_lds_fail(const char* fn) {
+  return fail(-1, fn, "num_topic_categories x num_observation_categories too large for the row kernel's LDS; " GDRF_STREAMED_HINT);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -702,27 +708,37 @@ template <typename T, typename TS> struct Impl {
     return 0;
   }
 
-  // nlev (<= 8) Cholesky attempts in ONE launch, in the N-side precision (what the reference's fp32
-  // torch.linalg.cholesky would see): K_uu built once, one workgroup per cumulative jitter; flags in c->flag[8..8+nlev)
-  // (slot 0 is the solve factorisation's, so a probe may run on another stream beside gdrf_factorize)
-  // periodic and product contexts: the hyper-parameter block h and the embedded inducing inputs zout (M, D) in precision TO, with the
-  // phases of their pairs (M, npair) when ph is given
+  // What the covariance kernels read, refreshed from the parameters: the hyper-parameter block h, and the inducing inputs in precision TO,
+  // which are returned.  Periodic and product contexts: the embedded inducing inputs (M, D) in zout, with the phases of their pairs
+  // (M, npair) when ph is given.  ARD contexts: the scaled inducing inputs z_d / ls_d in zout; ls = 1 in the hyper-parameter block.
+  // Otherwise Z itself, or with `copy` its cast into zout.
   template <typename TO>
-  static void per_prep(gdrf_ctx* c, const T* Z, const T* params, Hyper* h, void* zout, void* ph, hipStream_t s) {
-    const CoordTab tb = coord_tab(c);
-    const int64_t nz = (int64_t)c->M * tb.nsrc;
-    hipLaunchKernelGGL(prep_hyper_per_kernel<T>, dim3(1), dim3(64), 0, s, params, tb, (HyperPer*)h);
-    hipLaunchKernelGGL((embed_per_kernel<T, TO>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, (int64_t)c->M, tb, Z, params, (TO*)zout,
-                       (TO*)ph);
+  static const TO* cov_inputs(gdrf_ctx* c, const T* Z, const T* params, Hyper* h, TO* zout, TO* ph, bool copy, hipStream_t s) {
+    const int64_t nz = (int64_t)c->M * c->D;
+    if (c->per) {
+      const CoordTab tb = coord_tab(c);
+      const int64_t nzr = (int64_t)c->M * tb.nsrc;
+      hipLaunchKernelGGL(prep_hyper_per_kernel<T>, dim3(1), dim3(64), 0, s, params, tb, (HyperPer*)h);
+      hipLaunchKernelGGL((embed_per_kernel<T, TO>), dim3((unsigned)((nzr + 255) / 256)), dim3(256), 0, s, (int64_t)c->M, tb, Z, params, zout, ph);
+    } else if (c->ard) {
+      const T* ls = params + param_lay(c).ard;
+      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, ls, c->D, h);
+      hipLaunchKernelGGL((scale_z_kernel<T, TO>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, ls, zout);
+    } else {
+      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, h);
+      if constexpr (std::is_same<T, TO>::value) {
+        if (!copy) return Z;
+      }
+      hipLaunchKernelGGL((cast_kernel<T, TO>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, Z, zout);
+    }
+    return zout;
   }
   // periodic and product contexts: the embedded rows (n, D) of this call into c->Xe.  More rows than it holds (gdrf_knm, gdrf_predict) grow it; the
   // old buffer stays allocated until gdrf_ctx_destroy, since work queued before may still read it.
   static int per_rows(gdrf_ctx* c, const T* X, int64_t n, const T* params, hipStream_t s) {
     if (n > c->xe_cap) {
-      void* p = nullptr;
-      hipError_t e = hipMalloc(&p, (size_t)n * c->D * c->esz);
-      if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(embedded rows)", hipGetErrorString(e));
-      c->allocs.push_back(p); c->Xe = p; c->xe_cap = n;
+      if (int rc = ctx_alloc(c, &c->Xe, (size_t)n * c->D * c->esz, "hipMalloc(embedded rows)")) return rc;
+      c->xe_cap = n;
     }
     const CoordTab tb = coord_tab(c);
     const int64_t nx = n * tb.nsrc;
@@ -731,30 +747,22 @@ template <typename T, typename TS> struct Impl {
     LAUNCHCHK("embed rows (periodic)");
     return 0;
   }
+  // nlev (<= 8) Cholesky attempts in ONE launch, in the N-side precision (what the reference's fp32
+  // torch.linalg.cholesky would see): K_uu built once, one workgroup per cumulative jitter; flags in c->flag[8..8+nlev)
+  // (slot 0 is the solve factorisation's, so a probe may run on another stream beside gdrf_factorize)
   static int probe(gdrf_ctx* c, const T* Z, const T* params, const double* jitters, int nlev, hipStream_t s) {
     const int Mp = c->Mp, M = c->M;
     ScopedTimer tm(c, 0, s);
     HIPCHK(hipMemsetAsync(c->flag + 8, 0, 32, s));
     dim3 g2((Mp + 255) / 256, Mp);
-    if (c->per) {
-      per_prep<T>(c, Z, params, c->hyp_probe, P(c->Zp), nullptr, s);
-      Z = (const T*)P(c->Zp);
-    } else if (c->ard) {
-      const int64_t nz = (int64_t)M * c->D;
-      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp_probe);
-      hipLaunchKernelGGL((scale_z_kernel<T, T>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), P(c->Zp));
-      Z = (const T*)P(c->Zp);
-    } else {
-      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp_probe);
-    }
+    Z = cov_inputs<T>(c, Z, params, c->hyp_probe, P(c->Zp), nullptr, false, s);
     hipLaunchKernelGGL(kuu_kernel<T>, g2, dim3(256), 0, s, Z, M, Mp, c->D, c->kind, c->hyp_probe, 0.0, P(c->pK));
     JitterLevels jl;
     for (int l = 0; l < 8; ++l) jl.v[l] = l < nlev ? jitters[l] : 0.0;
     dim3 g3((Mp + 255) / 256, Mp, nlev);
     hipLaunchKernelGGL(level_copies_kernel<T>, g3, dim3(256), 0, s, (const T*)P(c->pK), M, Mp, jl, P(c->pL));
-    if (chol_lds_bytes<T>(M) > 48 * 1024)
-      HIPCHK(hipFuncSetAttribute((const void*)chol_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chol_lds_bytes<T>(M)));
-    hipLaunchKernelGGL(chol_kernel<T>, dim3(nlev), dim3(1024), chol_lds_bytes<T>(M), s, P(c->pL), M, Mp, c->flag + 8, (int64_t)Mp * Mp);
+    if (int rc = launch_lds(chol_kernel<T>, dim3(nlev), dim3(1024), chol_lds_bytes<T>(M), s, P(c->pL), M, Mp, c->flag + 8, (int64_t)Mp * Mp))
+      return rc;
     LAUNCHCHK("probe");
     return 0;
   }
@@ -771,7 +779,7 @@ template <typename T, typename TS> struct Impl {
     const int Mp = c->Mp, M = c->M;
     const int64_t nzs = (int64_t)M * c->Dr;
     if (mode == 2 && c->prefact_valid && jitter == c->prefact_jitter) {
-      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 1, c->flag + 16, params + poff(c, 8),
+      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 1, c->flag + 16, params + param_lay(c).ard,
                          snap_extra(c));
       // the factorisation stays valid for further calls with the same inputs (a predictive evaluation between two steps): every reuse
       // compares again, and any fresh factorisation below invalidates it first
@@ -781,16 +789,7 @@ template <typename T, typename TS> struct Impl {
     c->prefact_valid = 0;
     if (mode != 1) HIPCHK(hipMemsetAsync(c->flag + 16, 0, sizeof(int), s));     // this stream's own factorisation: nothing reused, no mismatch to report
     dim3 g2((Mp + 255) / 256, Mp);
-    const int64_t nz = (int64_t)M * c->D;
-    if (c->per) {      // the embedded inducing inputs and their phases in the solve precision
-      per_prep<TS>(c, Z, params, c->hyp, Q(c->Zs), Q(c->Zph), s);
-    } else if (c->ard) {      // the scaled inducing inputs z_d / ls_d in the solve precision; ls = 1 in the hyper-parameter block
-      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp);
-      hipLaunchKernelGGL((scale_z_kernel<T, TS>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), Q(c->Zs));
-    } else {
-      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp);
-      hipLaunchKernelGGL((cast_kernel<T, TS>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, Z, Q(c->Zs));
-    }
+    cov_inputs<TS>(c, Z, params, c->hyp, Q(c->Zs), Q(c->Zph), true, s);      // the inducing inputs (and phases) in the solve precision: c->Zs, c->Zph
     HIPCHK(hipEventRecord(c->ev_fact0, s));
     hipStream_t f = c->side;
     HIPCHK(hipStreamWaitEvent(f, c->ev_fact0, 0));
@@ -813,7 +812,7 @@ template <typename T, typename TS> struct Impl {
     HIPCHK(hipEventRecord(c->ev_fact, f));
     c->fact_pending = 1;
     if (mode == 1) {
-      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 0, (int*)nullptr, params + poff(c, 8),
+      hipLaunchKernelGGL(fact_snapshot_kernel<T>, dim3(1), dim3(256), 0, s, params, Z, nzs, P(c->snap), 0, (int*)nullptr, params + param_lay(c).ard,
                          snap_extra(c));
       c->prefact_valid = 1; c->prefact_jitter = jitter;
     }
@@ -822,18 +821,10 @@ template <typename T, typename TS> struct Impl {
   }
 
   static int knm(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, T* out, int64_t ldo, hipStream_t s) {
+    Z = cov_inputs<T>(c, Z, params, c->hyp, P(c->Zp), nullptr, false, s);
     if (c->per) {
-      per_prep<T>(c, Z, params, c->hyp, P(c->Zp), nullptr, s);
-      Z = (const T*)P(c->Zp);
       if (int rc = per_rows(c, X, n, params, s)) return rc;
       X = (const T*)c->Xe;
-    } else if (c->ard) {
-      const int64_t nz = (int64_t)c->M * c->D;
-      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + poff(c, 8), c->D, c->hyp);
-      hipLaunchKernelGGL((scale_z_kernel<T, T>), dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, c->D, Z, params + poff(c, 8), P(c->Zp));
-      Z = (const T*)P(c->Zp);
-    } else {
-      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, c->hyp);
     }
     ScopedTimer tm(c, 1, s);
     const int VE = Vec16<T>::N;
@@ -988,18 +979,12 @@ template <typename T, typename TS> struct Impl {
     if (blocks < 1) blocks = 1;
     if constexpr (sizeof(TS) == 8) {
       if (c->kind == 0 && vpr <= 256) {
-        if (ard_fwd(c)) {
-          if (c->D <= 2) hipLaunchKernelGGL((knm_rbf_f64_kernel<T, 2, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D,
-                                            c->hyp, (double*)Q(c->Knm), (int64_t)c->Mp);
-          else hipLaunchKernelGGL((knm_rbf_f64_kernel<T, GDRF_DMAX, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M,
-                                  c->D, c->hyp, (double*)Q(c->Knm), (int64_t)c->Mp);
-          LAUNCHCHK("knm_solve");
-          return 0;
-        }
-        if (c->D <= 2) hipLaunchKernelGGL((knm_rbf_f64_kernel<T, 2>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D, c->hyp,
-                                          (double*)Q(c->Knm), (int64_t)c->Mp);
-        else hipLaunchKernelGGL((knm_rbf_f64_kernel<T, GDRF_DMAX>), dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D, c->hyp,
-                                (double*)Q(c->Knm), (int64_t)c->Mp);
+        auto go = [&](auto kern) {
+          hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, X, n, (const double*)Q(c->Zs), c->M, c->D, c->hyp, (double*)Q(c->Knm),
+                             (int64_t)c->Mp);
+        };
+        if (ard_fwd(c)) { if (c->D <= 2) go(knm_rbf_f64_kernel<T, 2, true, true>); else go(knm_rbf_f64_kernel<T, GDRF_DMAX, true, true>); }
+        else { if (c->D <= 2) go(knm_rbf_f64_kernel<T, 2>); else go(knm_rbf_f64_kernel<T, GDRF_DMAX>); }
         LAUNCHCHK("knm_solve");
         return 0;
       }
@@ -1029,17 +1014,25 @@ template <typename T, typename TS> struct Impl {
     return 0;
   }
 
+  // the tail of the per-row ELBO stage: `grid` workgroups' Phi-bar partials -> the phibar block of red_T; with their four scalars -> red_d[0..4)
+  static void phibar_reduce(gdrf_ctx* c, const T* parts, int64_t grid, T* redT, hipStream_t s) {
+    const int64_t kv = (int64_t)c->K * c->V;
+    hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((unsigned)((kv + 255) / 256)), dim3(256), 0, s, parts, grid, kv, redT + red_lay(c).phibar);
+  }
+  static void rows_reduce(gdrf_ctx* c, const T* parts, int64_t grid, T* redT, double* redd, hipStream_t s) {
+    hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, grid, 4, redd);
+    phibar_reduce(c, parts, grid, redT, s);
+  }
+
   // ---- the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_vstream.h) ----
   static int vs_grid(const gdrf_ctx* c, int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, c->vs_gcap)); }
   template <int MODE>
   static int vs_launch(gdrf_ctx* c, int64_t n, int grid, const T* src, int64_t sk, int64_t sn, const int32_t* ws, T* dst, int64_t dld,
                        double* dpart, int dacc, hipStream_t s) {
     const size_t lds = vs_lds<T>(c->K);
-    auto go = [&](auto kern) -> int {
-      if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, n, c->K, c->V, src, sk, sn, ws, (const T*)P(c->phi), (const T*)c->vs_rs, dst, dld,
-                         dpart, dacc, (T*)c->vs_part, (T*)c->vs_cpart);
-      return 0;
+    auto go = [&](auto kern) {
+      return launch_lds(kern, dim3(grid), dim3(256), lds, s, n, c->K, c->V, src, sk, sn, ws, (const T*)P(c->phi), (const T*)c->vs_rs, dst, dld, dpart, dacc,
+                        (T*)c->vs_part, (T*)c->vs_cpart);
     };
     int rc;
     if constexpr (MODE == VS_SOFTMAX || MODE == VS_LINK) rc = c->K <= 32 ? go(rows_vstream_kernel<T, MODE, 8>) : go(rows_vstream_kernel<T, MODE, 32>);
@@ -1066,10 +1059,23 @@ template <typename T, typename TS> struct Impl {
     if (int rc = vs_launch<VS_SOFTMAX>(c, n, G, P(c->mu), c->ldk, 1, ws, (T*)c->vs_tmp, c->ldk, c->dpart, 0, s)) return rc;
     vs_link_phase(c, 2, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), nullptr, 0, 0, (const T*)c->vs_tmp, c->ldk, s);
     LAUNCHCHK("elbo_rows (streamed)");
-    hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
-    hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, (const T*)c->vs_part, (int64_t)G,
-                       (int64_t)K * V, redT + roff(c, 1));
+    rows_reduce(c, (const T*)c->vs_part, G, redT, redd, s);
     return 0;
+  }
+
+  // The backward through K_nm (kernels_n.h: BwdKnmProb) on `nb` workgroups: the three hyper-parameter partials per workgroup into c->dpart, with
+  // LZ the inducing-input partials (c->zpart), with ARD the per-axis ones (c->apart), with PER the period ones behind them.
+  template <bool LZ, bool ARD, bool PER>
+  static void bwd_knm(gdrf_ctx* c, const T* X, const T* Xr, int64_t n, int64_t nb, hipStream_t s) {
+    using Prob = BwdKnmProb<TS, T, LZ, ARD, PER>;
+    Prob p{{}, {}, P(c->Wbar), n, c->M, c->Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs), c->hyp, c->dpart,
+           LZ ? c->zpart : nullptr, ARD ? c->apart : nullptr, PER ? Xr : nullptr, PER ? (const TS*)Q(c->Zph) : nullptr};
+    // capped at 160 registers where the LDS-transposed f64 epilogue runs: two of its waves then share a SIMD with one wave of
+    // G^T's TN contraction on the side stream (192 registers), which fills this kernel's stalls instead of queueing behind it
+    if constexpr (!LZ) {
+      if (sizeof(TS) == 8) { hipLaunchKernelGGL((gemm_nt_kernel_v160<TS, Prob>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p); return; }
+    }
+    hipLaunchKernelGGL((gemm_nt_kernel<TS, Prob>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
   }
 
   // parts of one evaluation: the parameter transforms, the forward over the rows (K_nm, W, loc, tt), the per-row terms, the backward
@@ -1081,9 +1087,11 @@ template <typename T, typename TS> struct Impl {
     const int Mp = c->Mp, M = c->M, K = c->K, V = c->V;
     const int64_t mm = (int64_t)Mp * Mp, ldk = c->ldk;
     int rc;
-    const T* U = params + poff(c, 3);
-    const T* phi_unc = params + poff(c, 4);
-    const T* Sunc = params + poff(c, 5);
+    const ParamLay pl = param_lay(c);
+    const RedLay rl = red_lay(c);
+    const T* U = params + pl.uloc;
+    const T* phi_unc = params + pl.phi;
+    const T* Sunc = params + pl.S;
     const T* Xr = X;             // periodic contexts: the raw rows (the period sums of the backward); X becomes their embedding
     if (c->per && X && (mask & (SL_FORWARD | SL_BACKWARD))) {
       if ((rc = per_rows(c, X, n, params, s))) return rc;
@@ -1133,9 +1141,9 @@ template <typename T, typename TS> struct Impl {
       ScopedTimer tm(c, 4, c->side);
       const size_t ulds = (size_t)K * Mp * sizeof(T);
       if (K <= LOC_KMAX && Mp % (16 * Vec16<T>::N) == 0 && ulds <= 150 * 1024) {
-        if (ulds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)loc_rows_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ulds));
         const int64_t blocks = std::min<int64_t>((n + 31) / 32, 256 * 8);
-        hipLaunchKernelGGL(loc_rows_kernel<T>, dim3((unsigned)blocks), dim3(256), ulds, c->side, (const T*)P(c->W), n, Mp, K, (const T*)P(c->Upad), P(c->loc), ldk);
+        if ((rc = launch_lds(loc_rows_kernel<T>, dim3((unsigned)blocks), dim3(256), ulds, c->side, (const T*)P(c->W), n, Mp, K, (const T*)P(c->Upad),
+                             P(c->loc), ldk))) return rc;
         c->forms[GDRF_FORM_LOC] = 1;
       } else {
         bool wide = false;
@@ -1159,24 +1167,17 @@ template <typename T, typename TS> struct Impl {
         // pieces of dK_nm / d log(lengthscale) for the backward's Hd = dK^T Wbar; on the side stream behind loc: the main stream does not wait for it
         const int vpr = Mp / 8, rpp = 256 / vpr;
         const int64_t blocks = std::min<int64_t>((n + rpp - 1) / rpp, 256 * 16);
-        if (!c->dKh) {
-          void* pw = nullptr;
-          hipError_t e = hipMalloc(&pw, (size_t)2 * c->ncap * Mp * 2);
-          if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(dKh)", hipGetErrorString(e));
-          c->dKh = pw; c->allocs.push_back(pw);
-        }
+        if (!c->dKh && (rc = ctx_alloc(c, &c->dKh, (size_t)2 * c->ncap * Mp * 2, "hipMalloc(dKh)"))) return rc;
         _Float16* dkh = (_Float16*)c->dKh;
         const float* dsc = (const float*)c->ssc + SplitLay{K}.dk();
-        if (c->D <= 2) hipLaunchKernelGGL((dk_pieces_kernel<T, 2>), dim3((unsigned)blocks), dim3(256), 0, c->side, X, n, (const double*)c->Zs, M, c->D, c->kind, c->hyp, dkh,
-                                          (int64_t)c->ncap * Mp, Mp, dsc);
-        else hipLaunchKernelGGL((dk_pieces_kernel<T, GDRF_DMAX>), dim3((unsigned)blocks), dim3(256), 0, c->side, X, n, (const double*)c->Zs, M, c->D, c->kind, c->hyp, dkh,
-                                (int64_t)c->ncap * Mp, Mp, dsc);
+        hipLaunchKernelGGL((c->D <= 2 ? dk_pieces_kernel<T, 2> : dk_pieces_kernel<T, GDRF_DMAX>), dim3((unsigned)blocks), dim3(256), 0, c->side, X, n,
+                           (const double*)c->Zs, M, c->D, c->kind, c->hyp, dkh, (int64_t)c->ncap * Mp, Mp, dsc);
         LAUNCHCHK("dk_pieces");
       }
     }
     // (2) tt_kn = ||S_k^T w_n||^2
     if (c->split) {
-      if ((rc = (c->split == 2 ? fwd_t_split<SplitF16>(c, n, rtiles, s) : fwd_t_split<SplitBf16>(c, n, rtiles, s)))) return rc;
+      if ((rc = BY_SPLIT(c, fwd_t_split, c, n, rtiles, s))) return rc;
     } else {
       ScopedTimer tm(c, 5, s);
       FwdTProb<T> p{{K}, {}, {}, P(c->W), n, Mp, P(c->ST), P(c->tt), ldk, P(c->Tst), c->t_bs, c->t_ts};
@@ -1195,6 +1196,10 @@ template <typename T, typename TS> struct Impl {
     } else if (mask & SL_ROWS) {
       ScopedTimer tm(c, 6, s);
       if (int rc = phibar_part_ensure(c)) return rc;
+      auto rows = [&](auto kern, int threads, size_t lds) {         // the LDS row forms take the same arguments
+        return launch_lds(kern, dim3(egrid), dim3(threads), lds, s, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt), eps, ldk, n, ws, P(c->phi),
+                          (const T*)c->mean, c->mean_sk, c->mean_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart, P(c->phibar_part));
+      };
       // matrix-core form (rows_mfma.h): 16 rows per wave, the three K x V products of a row block as 16x16x4 matrix instructions on
       // register-resident operands; K <= 32, V <= 64 and 32-bit offsets.  The one-thread-per-row kernel serves the other sizes
       if (K <= 32 && V <= 64 && rows_mfma_offsets_fit<T>(K, nct<TS>(c), ldk, n)) {
@@ -1203,40 +1208,25 @@ template <typename T, typename TS> struct Impl {
         const size_t lds = rows_mfma_lds<T>(K, V, nkt, nvt, 4);
         const int64_t groups = (n + 15) / 16;
         egrid = (int)std::min<int64_t>((groups + 3) / 4, c->erows_grid_cap);
-#define GDRF_RM(KT, VT) { if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)elbo_rows_mfma_kernel<T, KT, VT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                          hipLaunchKernelGGL((elbo_rows_mfma_kernel<T, KT, VT>), dim3(egrid), dim3(256), lds, s, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt), eps, ldk, n, ws, \
-                                             P(c->phi), (const T*)c->mean, c->mean_sk, c->mean_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart, P(c->phibar_part)); }
-        if (nkt == 1) { if (nvt == 2) GDRF_RM(1, 2) else GDRF_RM(1, 4) } else { if (nvt == 2) GDRF_RM(2, 2) else GDRF_RM(2, 4) }
-#undef GDRF_RM
+        if ((rc = rows(nkt == 1 ? (nvt == 2 ? elbo_rows_mfma_kernel<T, 1, 2> : elbo_rows_mfma_kernel<T, 1, 4>)
+                                : (nvt == 2 ? elbo_rows_mfma_kernel<T, 2, 2> : elbo_rows_mfma_kernel<T, 2, 4>), 256, lds))) return rc;
         LAUNCHCHK("elbo_rows (mfma)");
-        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)egrid, 4, redd);
-        hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * V + 255) / 256), dim3(256), 0, s, P(c->phibar_part), (int64_t)egrid,
-                           (int64_t)K * V, redT + roff(c, 1));
       } else {
-      const bool kreg = K <= GDRF_KMAX;
-      auto lds_for = [&](int rb) { return 128 + ((size_t)2 * K * V + (size_t)rb * (K + 1) * (kreg ? 1 : 2) + (size_t)rb * (V + 1)) * sizeof(T); };
-      int RB = 128;
-      while (RB > 32 && lds_for(RB) > 150 * 1024) RB >>= 1;
-      const size_t lds = lds_for(RB);
-      if (lds > 150 * 1024)
-        return fail(-1, "gdrf_step_local", "num_topic_categories x num_observation_categories too large: the row kernel keeps the "
-                                           "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB); "
-                                           "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit");
-      const void* kfn = kreg ? (const void*)elbo_rows_kernel<T, true> : (const void*)elbo_rows_kernel<T, false>;
-      c->forms[GDRF_FORM_ROWS] = 2; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
-      if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      int64_t nblk = (n + RB - 1) / RB;
-      egrid = (int)std::min<int64_t>(nblk, c->erows_grid_cap);
-#define GDRF_ROWS_ARGS n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt), eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk, c->mean_sn, \
-                       P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart, P(c->phibar_part)
-      if (kreg) hipLaunchKernelGGL((elbo_rows_kernel<T, true>), dim3(egrid), dim3(RB), lds, s, GDRF_ROWS_ARGS);
-      else hipLaunchKernelGGL((elbo_rows_kernel<T, false>), dim3(egrid), dim3(RB), lds, s, GDRF_ROWS_ARGS);
-#undef GDRF_ROWS_ARGS
-      LAUNCHCHK("elbo_rows");
-      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)egrid, 4, redd);
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * V + 255) / 256), dim3(256), 0, s, P(c->phibar_part), (int64_t)egrid,
-                         (int64_t)K * V, redT + roff(c, 1));
+        const bool kreg = K <= GDRF_KMAX;
+        auto lds_for = [&](int rb) { return 128 + ((size_t)2 * K * V + (size_t)rb * (K + 1) * (kreg ? 1 : 2) + (size_t)rb * (V + 1)) * sizeof(T); };
+        int RB = 128;
+        while (RB > 32 && lds_for(RB) > 150 * 1024) RB >>= 1;
+        const size_t lds = lds_for(RB);
+        if (lds > 150 * 1024)
+          return fail(-1, "gdrf_step_local", "num_topic_categories x num_observation_categories too large: the row kernel keeps the "
+                                             "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB); "
+                                             GDRF_STREAMED_HINT);
+        c->forms[GDRF_FORM_ROWS] = 2; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
+        egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
+        if ((rc = rows(kreg ? elbo_rows_kernel<T, true> : elbo_rows_kernel<T, false>, RB, lds))) return rc;
+        LAUNCHCHK("elbo_rows");
       }
+      rows_reduce(c, P(c->phibar_part), egrid, redT, redd, s);
     }
     if (!(mask & SL_BACKWARD)) return 0;
     if constexpr (std::is_same<T, float>::value) {
@@ -1261,12 +1251,9 @@ template <typename T, typename TS> struct Impl {
       if (nb > c->ubar_blocks_cap) return fail(-1, "gdrf_step_local", "ubar partial buffer too small");
       const int kq = K <= 16 ? (K + 3) / 4 : 4;
       c->forms[GDRF_FORM_UBAR_Q4] = kq;
-#define GDRF_UBAR(Q4) hipLaunchKernelGGL((ubar_part_kernel<T, Q4>), dim3((unsigned)nb, (Mp + 255) / 256), dim3(256), 0, ss, P(c->W), n, Mp, K, P(c->locbar), \
-                                          ldk, rpb, P(c->ubar_part))
-      if (kq == 1) GDRF_UBAR(1); else if (kq == 2) GDRF_UBAR(2); else if (kq == 3) GDRF_UBAR(3); else GDRF_UBAR(4);
-#undef GDRF_UBAR
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * Mp + 255) / 256), dim3(256), 0, ss, P(c->ubar_part), nb, (int64_t)K * Mp,
-                         redT + roff(c, 0));
+      hipLaunchKernelGGL((kq == 1 ? ubar_part_kernel<T, 1> : kq == 2 ? ubar_part_kernel<T, 2> : kq == 3 ? ubar_part_kernel<T, 3> : ubar_part_kernel<T, 4>),
+                         dim3((unsigned)nb, (Mp + 255) / 256), dim3(256), 0, ss, P(c->W), n, Mp, K, P(c->locbar), ldk, rpb, P(c->ubar_part));
+      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * Mp + 255) / 256), dim3(256), 0, ss, P(c->ubar_part), nb, (int64_t)K * Mp, redT + rl.ubar);
     }
     // (3) Wbar
     {
@@ -1276,18 +1263,14 @@ template <typename T, typename TS> struct Impl {
       if (c->Tst) {
         BwdWbarTProb<T> p{{}, {}, P(c->Tst), c->t_bs, c->t_ts, P(c->W), n, M, Mp, K, P(c->S), P(c->vbar), P(c->locbar), ldk,
                           P(c->asum), U, P(c->Wbar)};
-        if (lds > 48 * 1024)
-          HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_kernel<T, BwdWbarTProb<T>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BwdWbarTProb<T>>), grid, dim3(256), lds, s, p);
+        if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarTProb<T>>, grid, dim3(256), lds, s, p))) return rc;
         c->forms[GDRF_FORM_WBAR] = 2; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
       } else if (c->split) {
-        if ((rc = (c->split == 2 ? wbar_split<SplitF16>(c, n, U, rtiles, s) : wbar_split<SplitBf16>(c, n, U, rtiles, s)))) return rc;
+        if ((rc = BY_SPLIT(c, wbar_split, c, n, U, rtiles, s))) return rc;
         split_scales(c, SPLIT_SC_WBAR, s);           // max |Wbar| came out of the epilogue: scale of the G^T contraction's operand
       } else {
         BwdWbarProb<T> p{{}, {}, P(c->W), n, M, Mp, K, P(c->Bm), P(c->vbar), P(c->locbar), ldk, P(c->asum), U, P(c->Wbar)};
-        if (lds > 48 * 1024)
-          HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_kernel<T, BwdWbarProb<T>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((gemm_nt_kernel<T, BwdWbarProb<T>>), grid, dim3(256), lds, s, p);
+        if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarProb<T>>, grid, dim3(256), lds, s, p))) return rc;
         c->forms[GDRF_FORM_WBAR] = 1; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
       }
     }
@@ -1306,14 +1289,13 @@ template <typename T, typename TS> struct Impl {
         c->forms[GDRF_FORM_GT] = c->split ? 2 : 1;
         if (c->split) {
           const int ib = SplitLay{K}.wbar();
-          if ((rc = (c->split == 2 ? tn_split<SplitF16>(c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, (float*)slab_gt, 1, ns, c->nt * c->nt, ib, 0, ss)
-                                   : tn_split<SplitBf16>(c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, (float*)slab_gt, 1, ns, c->nt * c->nt, ib, 0, ss)))) return rc;
+          if ((rc = BY_SPLIT(c, tn_split, c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, (float*)slab_gt, 1, ns, c->nt * c->nt, ib, 0, ss))) return rc;
         } else {
           hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * c->nt * ns)), dim3(256), TNCfg<T>::LDS_BYTES, ss, b);
         } }
       { ScopedTimer tm(c, 11, ss);
         dim3 gr1((Mp + 255) / 256, Mp, 1);
-        hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr1, dim3(256), 0, ss, (const T*)slab_gt, ns, 1, Mp, 0, redT + roff(c, 3)); }
+        hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr1, dim3(256), 0, ss, (const T*)slab_gt, ns, 1, Mp, 0, redT + rl.GT); }
     }
     HIPCHK(hipEventRecord(c->ev_join, c->side));
     // (4) kernel hyper-parameter partials through K_nm
@@ -1346,50 +1328,16 @@ template <typename T, typename TS> struct Impl {
       c->forms[GDRF_FORM_HYPER] = 1;
       const int64_t nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
       if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
-      if (c->per) {
-        if (c->learn_z) {
-          BwdKnmProb<TS, T, true, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X,
-                                                (const TS*)Q(c->Zs), c->hyp, c->dpart, c->zpart, c->apart, Xr, (const TS*)Q(c->Zph)};
-          hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, true, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-          hipLaunchKernelGGL(reduce_parts_kernel<double>, dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, s, (const double*)c->zpart, rtiles,
-                             (int64_t)M * c->D, redd + 8);
-        } else {
-          BwdKnmProb<TS, T, false, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X,
-                                                 (const TS*)Q(c->Zs), c->hyp, c->dpart, nullptr, c->apart, Xr, (const TS*)Q(c->Zph)};
-          if (sizeof(TS) == 8)
-            hipLaunchKernelGGL((gemm_nt_kernel_v160<TS, BwdKnmProb<TS, T, false, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-          else hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, false, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-        }
-        // the coordinate sums, then the period sums: red_d[8 + M D ..)
-        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D + c->npair, redd + 8 + (int64_t)M * c->D);
-      } else if (c->ard) {
-        if (c->learn_z) {
-          BwdKnmProb<TS, T, true, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
-                                          c->hyp, c->dpart, c->zpart, c->apart};
-          hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, true, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-          hipLaunchKernelGGL(reduce_parts_kernel<double>, dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, s, (const double*)c->zpart, rtiles,
-                             (int64_t)M * c->D, redd + 8);
-        } else {
-          BwdKnmProb<TS, T, false, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
-                                           c->hyp, c->dpart, nullptr, c->apart};
-          if (sizeof(TS) == 8) hipLaunchKernelGGL((gemm_nt_kernel_v160<TS, BwdKnmProb<TS, T, false, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-          else hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, false, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-        }
-        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D, redd + 8 + (int64_t)M * c->D);   // the ARD tail
-      } else if (c->learn_z) {
-        BwdKnmProb<TS, T, true> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs),
-                                  c->hyp, c->dpart, c->zpart};
-        hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T, true>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
+      if (c->per) { if (c->learn_z) bwd_knm<true, true, true>(c, X, Xr, n, nb, s); else bwd_knm<false, true, true>(c, X, Xr, n, nb, s); }
+      else if (c->ard) { if (c->learn_z) bwd_knm<true, true, false>(c, X, Xr, n, nb, s); else bwd_knm<false, true, false>(c, X, Xr, n, nb, s); }
+      else if (c->learn_z) bwd_knm<true, false, false>(c, X, Xr, n, nb, s);
+      else bwd_knm<false, false, false>(c, X, Xr, n, nb, s);
+      if (c->learn_z)
         hipLaunchKernelGGL(reduce_parts_kernel<double>, dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, s, (const double*)c->zpart, rtiles,
                            (int64_t)M * c->D, redd + 8);
-      } else {
-        BwdKnmProb<TS, T> p{{}, {}, P(c->Wbar), n, M, Mp, c->D, c->kind, (const TS*)Q(c->LinvT), (const TS*)Q(c->Knm), X, (const TS*)Q(c->Zs), c->hyp,
-                            c->dpart, nullptr};
-        // capped at 160 registers where the LDS-transposed f64 epilogue runs: two of its waves then share a SIMD with one wave of
-        // G^T's TN contraction on the side stream (192 registers), which fills this kernel's stalls instead of queueing behind it
-        if (sizeof(TS) == 8) hipLaunchKernelGGL((gemm_nt_kernel_v160<TS, BwdKnmProb<TS, T>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-        else hipLaunchKernelGGL((gemm_nt_kernel<TS, BwdKnmProb<TS, T>>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
-      }
+      // red_d[8 + M D ..): the ARD tail; periodic and product contexts: the coordinate sums, then the period sums
+      if (c->per || c->ard)
+        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D + (c->per ? c->npair : 0), redd + 8 + (int64_t)M * c->D);
       hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, nb, 3, redd + 4);      // red_d[4..6]
     }
     LAUNCHCHK("backward");
@@ -1445,15 +1393,15 @@ template <typename T, typename TS> struct Impl {
         } else if (c->split) {
           c->forms[GDRF_FORM_AK] = 2; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
           const int ib = SplitLay{K}.v(0), ntl = c->nt * (c->nt + 1) / 2;
-          if ((rc = (c->split == 2 ? tn_split<SplitF16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s)
-                                   : tn_split<SplitBf16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s)))) return rc;
+          // bf16x6 (f16x3 took the branch above)
+          if ((rc = tn_split<SplitBf16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s))) return rc;
         } else {
           c->forms[GDRF_FORM_AK] = 1; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
           hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * (c->nt + 1) / 2 * K * ns)), dim3(256), TNCfg<T>::LDS_BYTES, s, a);
         } }
       { ScopedTimer tm(c, 11, s);
         dim3 gr((Mp + 255) / 256, Mp, K);
-        hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr, dim3(256), 0, s, P(c->slab), red_ns, K, Mp, 1, redT + roff(c, 2), red_qd); }
+        hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr, dim3(256), 0, s, P(c->slab), red_ns, K, Mp, 1, redT + rl.A, red_qd); }
     }
     HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
     LAUNCHCHK("reductions");
@@ -1468,18 +1416,15 @@ template <typename T, typename TS> struct Impl {
                          T* redT, double* redd, hipStream_t s) {
     const int K = c->K, V = c->V;
     const int64_t ldk = c->ldk, kn = (int64_t)K * ldk, nq = (int64_t)((c->Mp + 63) / 64) * ldk;
-    const int64_t nT = roff(c, 4), nd = red_nd(c);
+    const RedLay rl = red_lay(c);
+    const int64_t nT = rl.total, nd = red_nd(c);
     int rc;
     if (!c->g_loc) {
       void** ps[] = {&c->g_loc, &c->g_tt, &c->g_qpart, &c->g_vbar, &c->g_locbar, &c->g_asum, &c->g_redT, (void**)&c->g_redd};
       const size_t sz[] = {(size_t)kn * c->esz, (size_t)kn * c->esz, (size_t)nq * c->esz, (size_t)kn * c->esz, (size_t)kn * c->esz,
                            (size_t)ldk * c->esz, (size_t)nT * c->esz, (size_t)nd * sizeof(double)};
-      for (int i = 0; i < 8; ++i) {
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, sz[i]);
-        if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(two-point scratch)", hipGetErrorString(e));
-        *ps[i] = p; c->allocs.push_back(p);
-      }
+      for (int i = 0; i < 8; ++i)
+        if ((rc = ctx_alloc(c, ps[i], sz[i], "hipMalloc(two-point scratch)"))) return rc;
     }
     if ((rc = step_local(c, Xg, ws, eps, n, Z, params, redT, redd, s, SL_TRANSFORMS | SL_FORWARD))) return rc;
     HIPCHK(hipMemcpyAsync(c->g_loc, c->loc, (size_t)kn * c->esz, hipMemcpyDeviceToDevice, s));
@@ -1501,26 +1446,20 @@ template <typename T, typename TS> struct Impl {
                          c->mean_sk, c->mean_sn, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum),
                          (T*)c->g_vbar, (T*)c->g_locbar, (T*)c->g_asum, P(c->mu), c->dpart);
       LAUNCHCHK("elbo_rows2 (streamed)");
-      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, (const T*)c->vs_part, (int64_t)G,
-                         (int64_t)K * V, redT + roff(c, 1));
+      rows_reduce(c, (const T*)c->vs_part, G, redT, redd, s);
     } else {
       ScopedTimer tm(c, 6, s);
       const int RB = 64;
       const size_t lds = 128 + ((size_t)2 * K * V + (size_t)2 * RB * (K + 1) + (size_t)RB * (V + 1)) * sizeof(T);
-      if (lds > 150 * 1024) return fail(-1, "gdrf_step_local2", "num_topic_categories x num_observation_categories too large for the row kernel's LDS; "
-                                                                "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit");
+      if (lds > 150 * 1024) return rows_lds_fail("gdrf_step_local2");
       if ((rc = phibar_part_ensure(c))) return rc;
-      if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)elbo_rows2_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const int egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
-      hipLaunchKernelGGL(elbo_rows2_kernel<T>, dim3(egrid), dim3(RB), lds, s, n, K, V, c->hyp, nct<TS>(c), P(c->qpart), P(c->loc), P(c->tt),
-                         (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk,
-                         c->mean_sn, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum),
-                         (T*)c->g_vbar, (T*)c->g_locbar, (T*)c->g_asum, P(c->mu), c->dpart, P(c->phibar_part));
+      if ((rc = launch_lds(elbo_rows2_kernel<T>, dim3(egrid), dim3(RB), lds, s, n, K, V, c->hyp, nct<TS>(c), P(c->qpart), P(c->loc), P(c->tt),
+                           (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk,
+                           c->mean_sn, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum),
+                           (T*)c->g_vbar, (T*)c->g_locbar, (T*)c->g_asum, P(c->mu), c->dpart, P(c->phibar_part)))) return rc;
       LAUNCHCHK("elbo_rows2");
-      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)egrid, 4, redd);
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * V + 255) / 256), dim3(256), 0, s, P(c->phibar_part), (int64_t)egrid,
-                         (int64_t)K * V, redT + roff(c, 1));
+      rows_reduce(c, P(c->phibar_part), egrid, redT, redd, s);
     }
     // backward through the model-side predictive (the buffers hold its W), payload aside
     if ((rc = step_local(c, Xm, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD))) return rc;
@@ -1536,8 +1475,8 @@ template <typename T, typename TS> struct Impl {
     auto add = [&](int64_t off, int64_t len) {
       hipLaunchKernelGGL(add_into_kernel<T>, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, len, (const T*)c->g_redT + off, redT + off);
     };
-    add(roff(c, 0), roff(c, 1) - roff(c, 0));
-    add(roff(c, 2), roff(c, 5) - roff(c, 2));
+    add(rl.ubar, rl.phibar - rl.ubar);
+    add(rl.A, rl.tail - rl.A);
     const int64_t ndk = nd - 4 - c->mean_count;      // the mean segment is the caller's to write (gdrf_set_mean_params)
     hipLaunchKernelGGL(add_into_kernel<double>, dim3((unsigned)((ndk + 255) / 256)), dim3(256), 0, s, ndk, (const double*)c->g_redd + 4, redd + 4);
     LAUNCHCHK("step_local2");
@@ -1568,28 +1507,23 @@ template <typename T, typename TS> struct Impl {
       T* rs = (T*)c->vs_rs;
       hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, rs);
       if ((rc = vs_launch<VS_LINK>(c, n, G, ext, ext_ld, 1, ws, P(c->locbar), ldk, c->dpart, 0, s))) return rc;
-      T* phib = redT + roff(c, 1);
-      const unsigned gkv = (unsigned)(((int64_t)K * V + 255) / 256);
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3(gkv), dim3(256), 0, s, (const T*)c->vs_part, (int64_t)G, (int64_t)K * V, phib);
+      phibar_reduce(c, (const T*)c->vs_part, G, redT, s);
       hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K + 255) / 256), dim3(256), 0, s, (const T*)c->vs_cpart, (int64_t)G, (int64_t)K, rs + K);
-      hipLaunchKernelGGL(vs_sub_rows_kernel<T>, dim3(gkv), dim3(256), 0, s, K, V, (const T*)(rs + K), phib);
+      hipLaunchKernelGGL(vs_sub_rows_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, K, V, (const T*)(rs + K),
+                         redT + red_lay(c).phibar);
       LAUNCHCHK("elbo_rows_link (streamed)");
       return 0;
     }
     const int RB = 64;
     const size_t lds = 128 + ((size_t)2 * K * V + (size_t)RB * (K + 1) + (size_t)RB * (V + 1)) * sizeof(T);
-    if (lds > 150 * 1024) return fail(-1, "gdrf_step_local_link", "num_topic_categories x num_observation_categories too large for the row kernel's LDS; "
-                                                                  "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit");
+    if (lds > 150 * 1024) return rows_lds_fail("gdrf_step_local_link");
     if ((rc = phibar_part_ensure(c))) return rc;
-    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)elbo_rows_link_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
-    hipLaunchKernelGGL(elbo_rows_link_kernel<T>, dim3(egrid), dim3(RB), lds, s, phase, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt),
-                       eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk, c->mean_sn, ext, ext_ld, P(c->q), P(c->vbar), P(c->locbar),
-                       P(c->asum), P(c->mu), c->dpart, P(c->phibar_part));
+    if ((rc = launch_lds(elbo_rows_link_kernel<T>, dim3(egrid), dim3(RB), lds, s, phase, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt),
+                         eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk, c->mean_sn, ext, ext_ld, P(c->q), P(c->vbar), P(c->locbar),
+                         P(c->asum), P(c->mu), c->dpart, P(c->phibar_part)))) return rc;
     LAUNCHCHK("elbo_rows_link");
-    if (phase == 1)
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * V + 255) / 256), dim3(256), 0, s, P(c->phibar_part), (int64_t)egrid, (int64_t)K * V,
-                         redT + roff(c, 1));
+    if (phase == 1) phibar_reduce(c, P(c->phibar_part), egrid, redT, s);
     if (phase == 2) {
       hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)egrid, 4, redd);
       return step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD);
@@ -1602,10 +1536,12 @@ template <typename T, typename TS> struct Impl {
     const int Mp = c->Mp, M = c->M, K = c->K, V = c->V;
     const int64_t mm = (int64_t)Mp * Mp;
     int rc;
-    const T* ubar = redT + roff(c, 0);
-    const T* phib = redT + roff(c, 1);
-    const T* Ak = redT + roff(c, 2);
-    const T* GT = redT + roff(c, 3);
+    const ParamLay pl = param_lay(c);
+    const RedLay rl = red_lay(c);
+    const T* ubar = redT + rl.ubar;
+    const T* phib = redT + rl.phibar;
+    const T* Ak = redT + rl.A;
+    const T* GT = redT + rl.GT;
     if ((rc = join_fact(c, s))) return rc;
     ScopedTimer tm(c, 13, s);
     dim3 g2((Mp + 255) / 256, Mp);
@@ -1617,7 +1553,7 @@ template <typename T, typename TS> struct Impl {
       HIPCHK(hipEventRecord(c->ev_fork, s));
       HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
       if ((rc = mm_nt<T>(c, Ak, mm, P(c->ST), mm, P(c->Sbar), mm, T(2), K, c->side))) return rc;
-      hipLaunchKernelGGL(grad_s_kernel<T>, g3, dim3(256), 0, c->side, P(c->Sbar), P(c->S), M, Mp, -1.0 / n_global, grads + poff(c, 5));
+      hipLaunchKernelGGL(grad_s_kernel<T>, g3, dim3(256), 0, c->side, P(c->Sbar), P(c->S), M, Mp, -1.0 / n_global, grads + pl.S);
       HIPCHK(hipEventRecord(c->ev_join, c->side));
     }
     // Cholesky / inverse backward in the solve precision
@@ -1656,34 +1592,34 @@ template <typename T, typename TS> struct Impl {
     hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)M, 3, c->dsmall);
     if (c->learn_z && c->per)
       hipLaunchKernelGGL((grad_z_kernel<TS, T, true, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind,
-                         c->hyp, redd + 8, -1.0 / n_global, grads + poff(c, 7), Z);
+                         c->hyp, redd + 8, -1.0 / n_global, grads + pl.Z, Z);
     else if (c->learn_z && c->ard)
       hipLaunchKernelGGL((grad_z_kernel<TS, T, true>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind, c->hyp,
-                         redd + 8, -1.0 / n_global, grads + poff(c, 7), Z);
+                         redd + 8, -1.0 / n_global, grads + pl.Z, Z);
     else if (c->learn_z)
       hipLaunchKernelGGL((grad_z_kernel<TS, T>), dim3(M), dim3(256), 0, s, (const TS*)Q(c->t1), (const TS*)Q(c->Zs), M, Mp, c->D, c->kind, c->hyp,
-                         redd + 8, -1.0 / n_global, grads + poff(c, 7));
+                         redd + 8, -1.0 / n_global, grads + pl.Z);
     // Sbar_k = 2 A_k S_k (N-side precision: well conditioned)
     if (sbar_aside) {
       HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
     } else {
       if ((rc = mm_nt<T>(c, Ak, mm, P(c->ST), mm, P(c->Sbar), mm, T(2), K, s))) return rc;
-      hipLaunchKernelGGL(grad_s_kernel<T>, g3, dim3(256), 0, s, P(c->Sbar), P(c->S), M, Mp, -1.0 / n_global, grads + poff(c, 5));
+      hipLaunchKernelGGL(grad_s_kernel<T>, g3, dim3(256), 0, s, P(c->Sbar), P(c->S), M, Mp, -1.0 / n_global, grads + pl.S);
     }
     hipLaunchKernelGGL(grad_small_kernel<T>, dim3(1), dim3(256), 0, s, M, Mp, K, V, c->hyp, redd, c->dsmall, ubar, phib, P(c->phi),
-                       c->alpha_dev, c->lgam_const, ll_const, n_global, grads, grads + poff(c, 3), grads + poff(c, 4), c->flag, out_d);
+                       c->alpha_dev, c->lgam_const, ll_const, n_global, grads, grads + pl.uloc, grads + pl.phi, c->flag, out_d);
     if (c->per)
       hipLaunchKernelGGL(grad_per_kernel<T>, dim3(1), dim3(64), 0, s, coord_tab(c), (const double*)redd + 8 + (int64_t)M * c->D,
                          (const double*)c->dsmall + 9, n_global, grads);
     else if (c->ard)
       hipLaunchKernelGGL(grad_ard_kernel<T>, dim3(1), dim3(64), 0, s, c->D, (const double*)redd + 8 + (int64_t)M * c->D, (const double*)c->dsmall + 3,
-                         n_global, grads, grads + poff(c, 8));
+                         n_global, grads, grads + pl.ard);
     if (c->mean_count)
       hipLaunchKernelGGL(grad_mean_kernel<T>, dim3((unsigned)((c->mean_count + 255) / 256)), dim3(256), 0, s, c->mean_count,
-                         (const double*)redd + red_mean_off(c), n_global, grads + poff(c, 9));
+                         (const double*)redd + red_mean_off(c), n_global, grads + pl.mean);
     if (c->unwhitened)       // overwrite the u_loc / u_scale_tril blocks with the gradients chained through L^-T
-      hipLaunchKernelGGL((grad_unwhitened_kernel<TS, T>), g3, dim3(256), 0, s, (const TS*)Q(c->uSc), (const TS*)Q(c->uUb), params + poff(c, 5), K, M,
-                         Mp, -1.0 / n_global, grads + poff(c, 5), grads + poff(c, 3));
+      hipLaunchKernelGGL((grad_unwhitened_kernel<TS, T>), g3, dim3(256), 0, s, (const TS*)Q(c->uSc), (const TS*)Q(c->uUb), params + pl.S, K, M,
+                         Mp, -1.0 / n_global, grads + pl.S, grads + pl.uloc);
     LAUNCHCHK("step_finish");
     return 0;
   }
@@ -1691,7 +1627,7 @@ template <typename T, typename TS> struct Impl {
   static int predict(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, int mode,
                      T* out, double* out_d, hipStream_t s) {
     const int Mp = c->Mp, M = c->M, K = c->K, V = c->V;
-    const T* U = params + poff(c, 3);
+    const T* U = params + param_lay(c).uloc;
     if (int rcj = join_fact(c, s)) return rcj;
     if (c->unwhitened) {       // loc = K_nm L^-T (L^-1 u)
       hipLaunchKernelGGL((lower_matvec_kernel<TS, T>), dim3((M + 127) / 128, K), dim3(128), 0, s, (const TS*)Q(c->Linv), U, M, Mp, Q(c->uU),
@@ -1712,7 +1648,7 @@ template <typename T, typename TS> struct Impl {
       if (int rc = per_rows(c, X, n, params, s)) return rc;
       X = (const T*)c->Xe;
     }
-    if (mode >= 2) hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + poff(c, 4), K, V, P(c->phi));
+    if (mode >= 2) hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + param_lay(c).phi, K, V, P(c->phi));
     if (c->rows_form == 1) {
       // form 1: the any-K row kernel without Phi in LDS gives f_loc / topic_probs; for word_probs and perplexity it writes topic_probs of
       // up to n_cap rows at a time into the form's scratch and the streamed product over Phi tiles (rows_vstream.h) finishes them
@@ -1756,15 +1692,16 @@ template <typename T, typename TS> struct Impl {
         const int64_t groups = (n + 15) / 16;
         int64_t blocks = (groups + 3) / 4; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
         const int64_t ldo = mode == 0 ? n : (mode == 1 ? K : V);
-#define GDRF_PM(DDv, NBv, ARDv) { if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)predict_mfma_kernel<TS, T, DDv, NBv, ARDv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                            hipLaunchKernelGGL((predict_mfma_kernel<TS, T, DDv, NBv, ARDv>), dim3((unsigned)blocks), dim3(256), lds, s, X, n, (const TS*)Q(c->Zs), M, M4, c->D, c->kind, \
-                                               c->hyp, (const TS*)Q(c->CfT), K, V, (const T*)P(c->phi), ws, mode, out, ldo, c->dpart); }
-        if (ard_fwd(c)) {
-          if (DDt == 2) { if (NB == 1) GDRF_PM(2, 1, true) else GDRF_PM(2, 2, true) } else { if (NB == 1) GDRF_PM(GDRF_DMAX, 1, true) else GDRF_PM(GDRF_DMAX, 2, true) }
-        } else {
-          if (DDt == 2) { if (NB == 1) GDRF_PM(2, 1, false) else GDRF_PM(2, 2, false) } else { if (NB == 1) GDRF_PM(GDRF_DMAX, 1, false) else GDRF_PM(GDRF_DMAX, 2, false) }
-        }
-#undef GDRF_PM
+        auto go = [&](auto kern) {
+          return launch_lds(kern, dim3((unsigned)blocks), dim3(256), lds, s, X, n, (const TS*)Q(c->Zs), M, M4, c->D, c->kind, c->hyp, (const TS*)Q(c->CfT), K, V,
+                            (const T*)P(c->phi), ws, mode, out, ldo, c->dpart);
+        };
+        constexpr int DM = GDRF_DMAX;
+        const int rc = ard_fwd(c) ? (DDt == 2 ? (NB == 1 ? go(predict_mfma_kernel<TS, T, 2, 1, true>) : go(predict_mfma_kernel<TS, T, 2, 2, true>))
+                                              : (NB == 1 ? go(predict_mfma_kernel<TS, T, DM, 1, true>) : go(predict_mfma_kernel<TS, T, DM, 2, true>)))
+                                  : (DDt == 2 ? (NB == 1 ? go(predict_mfma_kernel<TS, T, 2, 1, false>) : go(predict_mfma_kernel<TS, T, 2, 2, false>))
+                                              : (NB == 1 ? go(predict_mfma_kernel<TS, T, DM, 1, false>) : go(predict_mfma_kernel<TS, T, DM, 2, false>)));
+        if (rc) return rc;
         if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, blocks, 2, out_d);
         LAUNCHCHK("predict (mfma)");
         return 0;
@@ -1777,20 +1714,16 @@ template <typename T, typename TS> struct Impl {
       const size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)128 * (V + 1)) * sizeof(TS);
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V + 128*(V+1) solve-precision elements exceed the LDS budget (150 KB)");
       auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
-      if (lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,
-                         c->hyp, (const TS*)Q(c->Cf), K, V, (const T*)P(c->phi), ws, mode, out, ldo, c->dpart);
+      if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
+                              (const T*)P(c->phi), ws, mode, out, ldo, c->dpart)) return rc;
     } else {
       size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)K * M) * sizeof(TS);
       int in_lds = 1;
       if (lds > 64 * 1024) { in_lds = 0; lds -= (size_t)K * M * sizeof(TS); }
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V solve-precision elements exceed the LDS budget (150 KB)");
       auto kfn = ard_fwd(c) ? predict_rows_kernel<TS, T, true> : predict_rows_kernel<TS, T>;
-      if (lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind,
-                         c->hyp, (const TS*)Q(c->Cf), K, V, (const T*)P(c->phi), ws, mode, out, ldo, c->dpart, in_lds);
+      if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
+                              (const T*)P(c->phi), ws, mode, out, ldo, c->dpart, in_lds)) return rc;
     }
     if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, blocks, 2, out_d);
     LAUNCHCHK("predict");
@@ -1820,16 +1753,16 @@ int gdrf_fill_eps(gdrf_ctx* c, uint64_t seed, uint32_t step, int64_t n_offset, i
 int gdrf_payload_pack(gdrf_ctx* c, void* redT, const double* redd, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
   const int nd = (int)red_nd(c);
-  if (c->esz == 8) hipLaunchKernelGGL(payload_pack_kernel<double>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, redd, nd, (double*)redT + roff(c, 5));
-  else hipLaunchKernelGGL(payload_pack_kernel<float>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, redd, nd, (float*)redT + roff(c, 5));
+  if (c->esz == 8) hipLaunchKernelGGL(payload_pack_kernel<double>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, redd, nd, (double*)redT + red_lay(c).tail);
+  else hipLaunchKernelGGL(payload_pack_kernel<float>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, redd, nd, (float*)redT + red_lay(c).tail);
   LAUNCHCHK("payload_pack");
   return 0;
 }
 int gdrf_payload_unpack(gdrf_ctx* c, const void* redT, double* redd, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
   const int nd = (int)red_nd(c);
-  if (c->esz == 8) hipLaunchKernelGGL(payload_unpack_kernel<double>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const double*)redT + roff(c, 5), nd, redd);
-  else hipLaunchKernelGGL(payload_unpack_kernel<float>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)redT + roff(c, 5), nd, redd);
+  if (c->esz == 8) hipLaunchKernelGGL(payload_unpack_kernel<double>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const double*)redT + red_lay(c).tail, nd, redd);
+  else hipLaunchKernelGGL(payload_unpack_kernel<float>, dim3((nd + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)redT + red_lay(c).tail, nd, redd);
   LAUNCHCHK("payload_unpack");
   return 0;
 }
@@ -1842,7 +1775,7 @@ int gdrf_set_allreduce(gdrf_ctx* c, gdrf_allreduce_fn fn, void* user) {
 int gdrf_payload_allreduce(gdrf_ctx* c, void* redT, double* redd, void* stream) {
   if (!c->allreduce) return 0;
   if (int rc = gdrf_payload_pack(c, redT, redd, stream)) return rc;
-  const int rc = c->allreduce(redT, roff(c, 4), c->esz == 8 ? 1 : 0, stream, c->allreduce_user);
+  const int rc = c->allreduce(redT, red_lay(c).total, c->esz == 8 ? 1 : 0, stream, c->allreduce_user);
   if (rc) return fail(-2, "gdrf_payload_allreduce", "the registered all-reduce function reported an error");
   return gdrf_payload_unpack(c, redT, redd, stream);
 }
@@ -1953,7 +1886,7 @@ int gdrf_adam(gdrf_ctx* c, int mode, void* params, const void* grads, void* m, v
               double eps, double wd, double clip, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
   hipStream_t s = (hipStream_t)stream;
-  const int64_t n = poff(c, 6);
+  const int64_t n = param_lay(c).total;
   const double bc1 = 1.0 - std::pow(b1, (double)t), bc2 = 1.0 - std::pow(b2, (double)t);
   dim3 grid((unsigned)((n + 255) / 256));
   ScopedTimer tm(c, 14, s);
@@ -1973,7 +1906,7 @@ int gdrf_optim_step(gdrf_ctx* c, int rule, const gdrf_opt_seg* segs, int nseg, v
   if (rule < GDRF_ADAM || rule > GDRF_ADAGRAD_RMSPROP) return fail(-1, "gdrf_optim_step", "unknown rule");
   if (nseg < 0 || (nseg > 0 && !segs)) return fail(-1, "gdrf_optim_step", "segment table");
   if (!params || !grads || !s1 || !s2) return fail(-1, "gdrf_optim_step", "params, grads, s1 and s2 are required");
-  const int64_t total = poff(c, 6);
+  const int64_t total = param_lay(c).total;
   // every segment inside the vector, no two overlapping (an element is updated at most once)
   std::vector<std::pair<int64_t, int64_t>> iv;
   int64_t npart = 0;
@@ -1991,12 +1924,9 @@ int gdrf_optim_step(gdrf_ctx* c, int rule, const gdrf_opt_seg* segs, int nseg, v
   for (size_t k = 1; k < iv.size(); ++k)
     if (iv[k - 1].first + iv[k - 1].second > iv[k].first) return fail(-1, "gdrf_optim_step", "segments overlap");
   if (npart > c->opt_part_cap) {                 // first use (the partials of all segments of a call fit; chunks reuse the buffer)
-    void* pw = nullptr;
     const int64_t cap = total / OPT_NRM + nseg + 1;
-    hipError_t e = hipMalloc(&pw, (size_t)cap * sizeof(double));
-    if (e != hipSuccess) return fail(-(int)e - 1000, "hipMalloc(opt_part)", hipGetErrorString(e));
-    c->allocs.push_back(pw);
-    c->opt_part = (double*)pw; c->opt_part_cap = cap;
+    if (int rc = ctx_alloc(c, &c->opt_part, (size_t)cap * sizeof(double), "hipMalloc(opt_part)")) return rc;
+    c->opt_part_cap = cap;
   }
   hipStream_t s = (hipStream_t)stream;
   ScopedTimer tm(c, 14, s);
