@@ -25,6 +25,7 @@ SIGNATURES = {
     "gdrf_get_hyper_backward": (_int, [_vp]),
     "gdrf_set_rows_form": (_int, [_vp, _int]),
     "gdrf_get_rows_form": (_int, [_vp]),
+    "gdrf_bind_counts_csr": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "gdrf_set_whiten": (_int, [_vp, _int]),
     "gdrf_set_mean": (_int, [_vp, _vp, _i64, _i64]),
     "gdrf_set_learn_inducing": (_int, [_vp, _int]),

@@ -11,6 +11,7 @@
 #include "predict.h"
 #include "rows_mfma.h"
 #include "rows_vstream.h"
+#include "rows_csr.h"
 #include "hyper_tn.h"
 #include "optim.h"
 
@@ -103,6 +104,14 @@ struct gdrf_ctx {
   int rows_form;              // gdrf_set_rows_form: 0 the LDS row forms, 1 the vocabulary-streamed form (rows_vstream.h)
   void *vs_tmp, *vs_part, *vs_cpart, *vs_rs;   // form 1, allocated on first use: (K, ldk) mubar / topic_probs, Phi-bar slots [vs_gcap][K*V],
   int64_t vs_gcap;                             // link-constant slots [vs_gcap][K], row sums of Phi and their reduced constants [2][K]
+  // the sparse row form (rows_csr.h): the CSR count matrix bound with gdrf_bind_counts_csr (borrowed pointers; csr_crow = null: none) ...
+  const int64_t *csr_crow, *csr_ccol, *csr_cperm; const int32_t *csr_col, *csr_val; int64_t csr_n, csr_nnz;
+  int csr_fresh;                               // the binding's entry rows and segment table are still to be built
+  // ... its scratch of fixed size, allocated on first use: Phi^T (V, Kp), theta (n_cap, K), the link constant per row (n_cap) and per
+  // workgroup [1024][K], one Phi-bar slot (K, V) ...
+  void *csr_phiT, *csr_thN, *csr_cn, *csr_cpart, *csr_slot;
+  // ... and the arrays that grow with nnz: pbar and the row of every entry, the column segments' table and partial sums
+  void *csr_pb, *csr_parts; int32_t *csr_erow, *csr_segcol; int64_t *csr_segoff; int64_t csr_cap;
   std::vector<void*> allocs;
   // optional per-kernel HIP-event timing (gdrf_set_timing): events recorded on the launch stream
   int timing;
@@ -603,7 +612,10 @@ static int phibar_part_ensure(gdrf_ctx* c) {
 }
 // form 1 scratch on first use.  The grid of the streamed kernels is capped so that its Phi-bar slots take at most
 // max(256 MiB, 16 K V elements), never 1024 K V: vs_gcap = min(1024, max(16, 256 MiB / (K V esz)), ceil(n_cap / 64))
-static int vs_ensure(gdrf_ctx* c) {
+static int csr_ensure(gdrf_ctx* c);
+// (`counts`: the call reads counts; with a bound CSR matrix it then takes the sparse form's scratch instead)
+static int vs_ensure(gdrf_ctx* c, bool counts = true) {
+  if (c->csr_crow && counts) return csr_ensure(c);
   if (c->vs_part) return 0;
   const size_t kv = (size_t)c->K * c->V * c->esz;
   c->vs_gcap = std::min<int64_t>({(int64_t)1024, std::max<int64_t>(16, (int64_t)((size_t)256 << 20) / (int64_t)kv), (c->ncap + 63) / 64});
@@ -612,6 +624,60 @@ static int vs_ensure(gdrf_ctx* c) {
   for (int i = 0; i < 4; ++i)
     if (!*ps[i])
       if (int rc = ctx_alloc(c, ps[i], sz[i], "hipMalloc(streamed row form scratch)")) return rc;
+  return 0;
+}
+// the sparse row form's scratch that does not depend on nnz, on first use; a context that never binds a CSR matrix holds none of it.  The
+// (K, ldk) array and the row sums are the streamed form's (vs_ensure allocates whichever of its own are still missing).
+static int csr_ensure(gdrf_ctx* c) {
+  if (c->csr_slot) return 0;
+  const size_t kv = (size_t)c->K * c->V * c->esz;
+  void** ps[] = {&c->vs_tmp, &c->vs_rs, &c->csr_phiT, &c->csr_thN, &c->csr_cn, &c->csr_cpart, &c->csr_slot};
+  const size_t sz[] = {(size_t)c->K * c->ldk * c->esz, (size_t)2 * c->K * c->esz, (size_t)c->V * round_up(c->K, 16) * c->esz,
+                       (size_t)c->ncap * c->K * c->esz, (size_t)c->ncap * c->esz, (size_t)1024 * c->K * c->esz, kv};
+  for (int i = 0; i < 7; ++i)
+    if (!*ps[i])
+      if (int rc = ctx_alloc(c, ps[i], sz[i], "hipMalloc(sparse row form scratch)")) return rc;
+  return 0;
+}
+// the arrays of the sparse row form that grow with nnz (in steps of a quarter, so that mini-batches of varying size settle quickly).  The
+// blocks they replace are released: hipFree waits for the work that may still read them.
+static int csr_grow(gdrf_ctx* c, int64_t nnz) {
+  if (c->csr_pb && nnz <= c->csr_cap) return 0;
+  const int64_t cap = std::max<int64_t>(nnz + nnz / 4, 1024), nseg = c->V + cap / CSR_SEG + 1;
+  void** ps[] = {&c->csr_pb, (void**)&c->csr_erow, (void**)&c->csr_segcol, (void**)&c->csr_segoff, &c->csr_parts};
+  const size_t sz[] = {(size_t)cap * c->esz, (size_t)cap * sizeof(int32_t), (size_t)nseg * sizeof(int32_t), (size_t)(c->V + 1) * sizeof(int64_t),
+                       (size_t)nseg * c->K * c->esz};
+  for (int i = 0; i < 5; ++i) {
+    if (*ps[i]) {
+      c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), *ps[i]), c->allocs.end());
+      HIPCHK(hipFree(*ps[i]));
+      *ps[i] = nullptr;
+    }
+    if (int rc = ctx_alloc(c, ps[i], sz[i], "hipMalloc(sparse row form scratch)")) return rc;
+  }
+  c->csr_cap = cap;
+  c->csr_fresh = 1;
+  return 0;
+}
+int gdrf_bind_counts_csr(gdrf_ctx* c, const int64_t* crow, const int32_t* col, const int32_t* val, int64_t n, int64_t nnz, const int64_t* ccol,
+                         const int64_t* cperm) {
+  if (!c) return fail(-1, "gdrf_bind_counts_csr", "null context");
+  if (!crow) {
+    c->csr_crow = c->csr_ccol = c->csr_cperm = nullptr; c->csr_col = c->csr_val = nullptr; c->csr_n = c->csr_nnz = 0;
+    return 0;
+  }
+  if (n < 1 || nnz < 0) return fail(-1, "gdrf_bind_counts_csr", "n must be >= 1 and nnz >= 0");
+  if (nnz > 0 && (!col || !val)) return fail(-1, "gdrf_bind_counts_csr", "col_dev and val_dev are required when nnz > 0");
+  if ((ccol == nullptr) != (cperm == nullptr) && nnz > 0) return fail(-1, "gdrf_bind_counts_csr", "ccol_dev and cperm_dev come together");
+  c->csr_crow = crow; c->csr_col = col; c->csr_val = val; c->csr_n = n; c->csr_nnz = nnz; c->csr_ccol = ccol; c->csr_cperm = cperm;
+  c->csr_fresh = 1;
+  return 0;
+}
+// With a bound CSR matrix the calls that read counts take ws_dev = NULL and the bound matrix's row count
+static int counts_check(const gdrf_ctx* c, const int32_t* ws, int64_t n, const char* fn) {
+  if (!c->csr_crow) return 0;
+  if (ws) return fail(-1, fn, "a CSR count matrix is bound (gdrf_bind_counts_csr): ws_dev must be NULL");
+  if (n != c->csr_n) return fail(-1, fn, "n differs from the row count of the bound CSR count matrix");
   return 0;
 }
 int gdrf_ws_elem_size(gdrf_ctx* c, int which) { void* p; int64_t n; int e; return ws_lookup(c, which, &p, &n, &e) ? -1 : e; }
@@ -1019,16 +1085,80 @@ template <typename T, typename TS> struct Impl {
     const int64_t kv = (int64_t)c->K * c->V;
     hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((unsigned)((kv + 255) / 256)), dim3(256), 0, s, parts, grid, kv, redT + red_lay(c).phibar);
   }
-  static void rows_reduce(gdrf_ctx* c, const T* parts, int64_t grid, T* redT, double* redd, hipStream_t s) {
+  static void rows_reduce(gdrf_ctx* c, const T* parts, int64_t grid, T* redT, double* redd, hipStream_t s, int64_t nparts = -1) {
     hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, grid, 4, redd);
-    phibar_reduce(c, parts, grid, redT, s);
+    phibar_reduce(c, parts, nparts < 0 ? grid : nparts, redT, s);
   }
 
   // ---- the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_vstream.h) ----
-  static int vs_grid(const gdrf_ctx* c, int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, c->vs_gcap)); }
+  // (with a bound CSR matrix the Phi-bar slots do not bound the grid: up to 1024 workgroups)
+  static int vs_grid(const gdrf_ctx* c, int64_t n, bool counts = true) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, c->csr_crow && counts ? 1024 : c->vs_gcap));
+  }
+  // where the streamed call sites find the Phi-bar partials and the link constants: the streamed kernel's `grid` slots, or the sparse form's one
+  static const T* vs_parts(const gdrf_ctx* c) { return (const T*)(c->csr_crow ? c->csr_slot : c->vs_part); }
+  static int64_t vs_nparts(const gdrf_ctx* c, int64_t grid) { return c->csr_crow ? 1 : grid; }
+  static const T* vs_cparts(const gdrf_ctx* c) { return (const T*)(c->csr_crow ? c->csr_cpart : c->vs_cpart); }
+
+  // ---- the sparse row form (rows_csr.h): rows [row_off, row_off + n) of the bound CSR matrix in place of rows_vstream_kernel ----
+  template <int MODE>
+  static int csr_launch(gdrf_ctx* c, int64_t n, int grid, const T* src, int64_t sk, int64_t sn, int64_t row_off, T* dst, int64_t dld,
+                        double* dpart, int dacc, hipStream_t s, bool new_phi) {
+    constexpr bool ELBO = MODE == VS_SOFTMAX || MODE == VS_LINK;
+    const int K = c->K, V = c->V, LG = K <= 8 ? 8 : 16, Kp = (int)round_up(K, LG);
+    const int64_t nnz = c->csr_nnz;
+    if (row_off < 0 || row_off + n > c->csr_n) return fail(-1, "rows_csr", "rows outside the bound CSR count matrix");
+    if (ELBO && nnz > 0 && !c->csr_ccol) return fail(-1, "rows_csr", "a step needs the column grouping (ccol_dev, cperm_dev) of the bound CSR count matrix");
+    if (int rc = csr_ensure(c)) return rc;
+    if (ELBO) {
+      if (int rc = csr_grow(c, nnz)) return rc;
+      if (c->csr_fresh) {            // once per binding: the row of every entry, the column segments
+        hipLaunchKernelGGL(csr_entry_rows_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 15) / 16, 4096))), dim3(256), 0, s, c->csr_crow, n,
+                           nnz, c->csr_erow);
+        if (nnz > 0) hipLaunchKernelGGL(csr_segscan_kernel, dim3(1), dim3(1024), 0, s, c->csr_ccol, V, c->csr_segoff, c->csr_segcol);
+        c->csr_fresh = 0;
+      }
+    }
+    const int64_t nt = (int64_t)V * Kp;
+    if (new_phi) {                   // Phi^T of this call's Phi; the later pieces of a gdrf_predict call reuse it
+      hipLaunchKernelGGL(csr_transpose_phi_kernel<T>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, (const T*)P(c->phi), K, Kp, V, (T*)c->csr_phiT);
+    }
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, n, K, Kp, V, nnz, src, sk, sn, c->csr_crow + row_off, c->csr_col, c->csr_val,
+                         (const T*)c->csr_phiT, (const T*)c->vs_rs, dst, dld, dpart, dacc, (T*)c->csr_thN, (T*)c->csr_pb, (T*)c->csr_cn);
+    };
+    if (K <= 8) go(rows_csr_kernel<T, MODE, 8, 1>);
+    else if (K <= 32) go(rows_csr_kernel<T, MODE, 16, 2>);
+    else go(rows_csr_kernel<T, MODE, 16, 8>);
+    if constexpr (MODE == VS_LINK)
+      hipLaunchKernelGGL(csr_link_const_kernel<T>, dim3(grid), dim3(128), 0, s, n, K, (const T*)c->csr_thN, (const T*)c->csr_cn, (T*)c->csr_cpart);
+    if constexpr (ELBO) {
+      if (nnz > 0) {
+        const int64_t nseg = V + nnz / CSR_SEG + 1;         // an upper bound of the table's length; the kernel reads the length itself
+        auto seg = [&](auto kern) {
+          hipLaunchKernelGGL(kern, dim3((unsigned)((nseg * LG + 255) / 256)), dim3(256), 0, s, K, V, nnz, n, c->csr_ccol, c->csr_cperm,
+                             (const int64_t*)c->csr_segoff, (const int32_t*)c->csr_segcol, (const int32_t*)c->csr_erow, (const T*)c->csr_pb,
+                             (const T*)c->csr_thN, (T*)c->csr_parts);
+        };
+        if (K <= 8) seg(csr_phibar_seg_kernel<T, 8, 1>);
+        else if (K <= 32) seg(csr_phibar_seg_kernel<T, 16, 2>);
+        else seg(csr_phibar_seg_kernel<T, 16, 8>);
+        hipLaunchKernelGGL(csr_phibar_combine_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, K, V,
+                           (const int64_t*)c->csr_segoff, (const T*)c->csr_parts, (T*)c->csr_slot);
+      } else {
+        HIPCHK(hipMemsetAsync(c->csr_slot, 0, (size_t)K * V * c->esz, s));
+      }
+    }
+    LAUNCHCHK("rows_csr");
+    return 0;
+  }
+
   template <int MODE>
   static int vs_launch(gdrf_ctx* c, int64_t n, int grid, const T* src, int64_t sk, int64_t sn, const int32_t* ws, T* dst, int64_t dld,
-                       double* dpart, int dacc, hipStream_t s) {
+                       double* dpart, int dacc, hipStream_t s, int64_t row_off = 0) {
+    if constexpr (MODE != VS_WORDP) {
+      if (c->csr_crow) return csr_launch<MODE>(c, n, grid, src, sk, sn, row_off, dst, dld, dpart, dacc, s, row_off == 0);
+    }
     const size_t lds = vs_lds<T>(c->K);
     auto go = [&](auto kern) {
       return launch_lds(kern, dim3(grid), dim3(256), lds, s, n, c->K, c->V, src, sk, sn, ws, (const T*)P(c->phi), (const T*)c->vs_rs, dst, dld, dpart, dacc,
@@ -1059,7 +1189,7 @@ template <typename T, typename TS> struct Impl {
     if (int rc = vs_launch<VS_SOFTMAX>(c, n, G, P(c->mu), c->ldk, 1, ws, (T*)c->vs_tmp, c->ldk, c->dpart, 0, s)) return rc;
     vs_link_phase(c, 2, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), nullptr, 0, 0, (const T*)c->vs_tmp, c->ldk, s);
     LAUNCHCHK("elbo_rows (streamed)");
-    rows_reduce(c, (const T*)c->vs_part, G, redT, redd, s);
+    rows_reduce(c, vs_parts(c), G, redT, redd, s, vs_nparts(c, G));
     return 0;
   }
 
@@ -1189,7 +1319,7 @@ template <typename T, typename TS> struct Impl {
     }
     // per-row ELBO terms and row-local backward
     int egrid;
-    if ((mask & SL_ROWS) && c->rows_form == 1) {
+    if ((mask & SL_ROWS) && (c->rows_form == 1 || c->csr_crow)) {
       ScopedTimer tm(c, 6, s);
       if (int rc = rows_streamed(c, ws, eps, n, redT, redd, s)) return rc;
       c->forms[GDRF_FORM_ROWS] = 3; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
@@ -1431,7 +1561,7 @@ template <typename T, typename TS> struct Impl {
     HIPCHK(hipMemcpyAsync(c->g_tt, c->tt, (size_t)kn * c->esz, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->g_qpart, c->qpart, (size_t)nq * c->esz, hipMemcpyDeviceToDevice, s));
     if ((rc = step_local(c, Xm, ws, eps, n, Z, params, redT, redd, s, SL_FORWARD))) return rc;
-    if (c->rows_form == 1) {
+    if (c->rows_form == 1 || c->csr_crow) {
       // form 1: the guide-side mu (link phase 0 on the guide's arrays; its q is rewritten below), the streamed likelihood -> mubar, the
       // two-point sites (V-free)
       ScopedTimer tm(c, 6, s);
@@ -1446,7 +1576,7 @@ template <typename T, typename TS> struct Impl {
                          c->mean_sk, c->mean_sn, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum),
                          (T*)c->g_vbar, (T*)c->g_locbar, (T*)c->g_asum, P(c->mu), c->dpart);
       LAUNCHCHK("elbo_rows2 (streamed)");
-      rows_reduce(c, (const T*)c->vs_part, G, redT, redd, s);
+      rows_reduce(c, vs_parts(c), G, redT, redd, s, vs_nparts(c, G));
     } else {
       ScopedTimer tm(c, 6, s);
       const int RB = 64;
@@ -1492,7 +1622,7 @@ template <typename T, typename TS> struct Impl {
     const int64_t ldk = c->ldk;
     int rc;
     if (phase == 0 && (rc = step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_TRANSFORMS | SL_FORWARD))) return rc;
-    if (c->rows_form == 1) {
+    if (c->rows_form == 1 || c->csr_crow) {
       // form 1: phases 0 and 2 are V-free; phase 1 is the streamed likelihood on ext = theta, thetabar -> locbar, its Phi-bar's constant
       // part subtracted after the reduction
       if ((rc = vs_ensure(c))) return rc;
@@ -1507,8 +1637,8 @@ template <typename T, typename TS> struct Impl {
       T* rs = (T*)c->vs_rs;
       hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, rs);
       if ((rc = vs_launch<VS_LINK>(c, n, G, ext, ext_ld, 1, ws, P(c->locbar), ldk, c->dpart, 0, s))) return rc;
-      phibar_reduce(c, (const T*)c->vs_part, G, redT, s);
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K + 255) / 256), dim3(256), 0, s, (const T*)c->vs_cpart, (int64_t)G, (int64_t)K, rs + K);
+      phibar_reduce(c, vs_parts(c), vs_nparts(c, G), redT, s);
+      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K + 255) / 256), dim3(256), 0, s, vs_cparts(c), (int64_t)G, (int64_t)K, rs + K);
       hipLaunchKernelGGL(vs_sub_rows_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, K, V, (const T*)(rs + K),
                          redT + red_lay(c).phibar);
       LAUNCHCHK("elbo_rows_link (streamed)");
@@ -1649,7 +1779,7 @@ template <typename T, typename TS> struct Impl {
       X = (const T*)c->Xe;
     }
     if (mode >= 2) hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + param_lay(c).phi, K, V, P(c->phi));
-    if (c->rows_form == 1) {
+    if (c->rows_form == 1 || (mode == 3 && c->csr_crow)) {
       // form 1: the any-K row kernel without Phi in LDS gives f_loc / topic_probs; for word_probs and perplexity it writes topic_probs of
       // up to n_cap rows at a time into the form's scratch and the streamed product over Phi tiles (rows_vstream.h) finishes them
       hipLaunchKernelGGL((predict_coeff_kernel<TS, T>), dim3((M + 127) / 128, K), dim3(128), 0, s, (const TS*)Q(c->Linv), U, M, Mp, K, Q(c->Cf));
@@ -1667,14 +1797,14 @@ template <typename T, typename TS> struct Impl {
         LAUNCHCHK("predict (streamed form)");
         return 0;
       }
-      if (int rc = vs_ensure(c)) return rc;
-      const int G = vs_grid(c, std::min<int64_t>(n, c->ncap));
+      if (int rc = vs_ensure(c, mode == 3)) return rc;
+      const int G = vs_grid(c, std::min<int64_t>(n, c->ncap), mode == 3);
       for (int64_t off = 0; off < n; off += c->ncap) {
         const int64_t m = std::min<int64_t>(c->ncap, n - off);
         rows(X + off * c->D, m, 1, (T*)c->vs_tmp, K);
         int rc;
         if (mode == 2) rc = vs_launch<VS_WORDP>(c, m, G, (const T*)c->vs_tmp, 1, K, nullptr, out + off * V, V, nullptr, 0, s);
-        else rc = vs_launch<VS_PERP>(c, m, G, (const T*)c->vs_tmp, 1, K, ws + off * V, nullptr, 0, c->dpart, off > 0, s);
+        else rc = vs_launch<VS_PERP>(c, m, G, (const T*)c->vs_tmp, 1, K, ws ? ws + off * V : nullptr, nullptr, 0, c->dpart, off > 0, s, off);
         if (rc) return rc;
       }
       if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 2, out_d);
@@ -1783,8 +1913,14 @@ int gdrf_payload_allreduce(gdrf_ctx* c, void* redT, double* redd, void* stream) 
 int gdrf_ll_const_dev(gdrf_ctx* c, const int32_t* ws, int64_t n, double* out_dev, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
   hipStream_t s = (hipStream_t)stream;
+  if (int rc = counts_check(c, ws, n, "gdrf_ll_const")) return rc;
   int64_t blocks = (n + 255) / 256; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(ll_const_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ws, n, c->V, c->llpart);
+  if (c->csr_crow) {
+    blocks = std::max<int64_t>(1, std::min<int64_t>((n + 15) / 16, 2048));
+    hipLaunchKernelGGL(ll_const_csr_kernel, dim3((unsigned)blocks), dim3(256), 0, s, c->csr_crow, c->csr_val, n, c->csr_nnz, c->llpart);
+  } else {
+    hipLaunchKernelGGL(ll_const_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ws, n, c->V, c->llpart);
+  }
   hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->llpart, blocks, 1, out_dev);
   LAUNCHCHK("ll_const");
   return 0;
@@ -1852,6 +1988,7 @@ int gdrf_step_local(gdrf_ctx* c, const void* X, const int32_t* ws, const void* e
                     void* redT, double* redd, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
   if (n < 1 || n > c->ncap) return fail(-1, "gdrf_step_local", "n_local outside [1, n_cap]");
+  if (int rc = counts_check(c, ws, n, "gdrf_step_local")) return rc;
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, step_local, c, (const T*)X, ws, (const T*)eps, n, (const T*)Z, (const T*)params, (T*)redT, redd, s);
 }
@@ -1861,6 +1998,7 @@ int gdrf_step_local_link(gdrf_ctx* c, const void* X, const int32_t* ws, const vo
   HIPCHK(hipSetDevice(c->dev));
   if (n < 1 || n > c->ncap) return fail(-1, "gdrf_step_local_link", "n_local outside [1, n_cap]");
   if (phase < 0 || phase > 2) return fail(-1, "gdrf_step_local_link", "phase must be 0, 1 or 2");
+  if (int rc = counts_check(c, ws, n, "gdrf_step_local_link")) return rc;
   if (phase > 0 && (!ext || ext_ld < n)) return fail(-1, "gdrf_step_local_link", "phases 1 and 2 take a (K, ext_ld >= n) array");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, step_local_link, c, (const T*)X, ws, (const T*)eps, n, (const T*)Z, (const T*)params, (T*)redT, redd, s, phase, (const T*)ext, ext_ld);
@@ -1871,6 +2009,7 @@ int gdrf_step_local2(gdrf_ctx* c, const void* X_model, const void* X_guide, cons
   HIPCHK(hipSetDevice(c->dev));
   if (n < 1 || n > c->ncap) return fail(-1, "gdrf_step_local2", "n_local outside [1, n_cap]");
   if (c->Tst) return fail(-1, "gdrf_step_local2", "needs the dense Wbar form (GDRF_STORE_T_OFF)");
+  if (int rc = counts_check(c, ws, n, "gdrf_step_local2")) return rc;
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, step_local2, c, (const T*)X_model, (const T*)X_guide, ws, (const T*)eps, n, (const T*)Z, (const T*)params, (T*)redT, redd, s);
 }
@@ -1965,7 +2104,9 @@ int gdrf_predict(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const voi
   HIPCHK(hipSetDevice(c->dev));
   if (mode < 0 || mode > 4) return fail(-1, "gdrf_predict", "mode");
   if (n < 1) return fail(-1, "gdrf_predict", "n must be >= 1");
-  if (mode == 3 && !ws) return fail(-1, "gdrf_predict", "perplexity needs ws");
+  if (mode == 3 && !ws && !c->csr_crow) return fail(-1, "gdrf_predict", "perplexity needs ws");
+  if (mode == 3)
+    if (int rc = counts_check(c, ws, n, "gdrf_predict")) return rc;
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, mode, (T*)out, out_d, s);
 }

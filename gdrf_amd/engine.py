@@ -16,6 +16,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
+from .data import check_counts, is_sparse_counts
 
 KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "rationalquadratic": 4, "periodic": 5, "product": 6}
 # factor kinds of a product context's table (gdrf_set_product)
@@ -169,6 +170,8 @@ class Engine:
         self.opt_step = 0
         self.last_jitter_level = 0
         self._ll_cache = None
+        self._csr_cache = None                       # (tensor, _version, the device arrays bound for it): one CSR count matrix at a time
+        self._csr_bound = False
         self._guess_level: Optional[int] = None      # jitter level of the previous step: this step starts on it speculatively
         self._probe_stream = torch.cuda.Stream(device=self.device)
         self.speculate = True
@@ -373,9 +376,39 @@ class Engine:
     def _chk_rows(self, xs: torch.Tensor, ws: Optional[torch.Tensor] = None):
         if xs.device != self.device or xs.dtype != self.dtype or not xs.is_contiguous() or xs.dim() != 2 or xs.shape[1] != self.D:
             raise ValueError(f"xs must be a contiguous ({'n'},{self.D}) {self.dtype} tensor on {self.device}")
-        if ws is not None:
+        if ws is not None and is_sparse_counts(ws):
+            check_counts(ws, xs.shape[0], self.V, self.device)
+        elif ws is not None:
             if ws.device != self.device or ws.dtype != torch.int32 or not ws.is_contiguous() or ws.shape != (xs.shape[0], self.V):
                 raise ValueError(f"ws must be a contiguous (n,{self.V}) int32 tensor on {self.device}")
+
+    def _counts_ptr(self, ws: Optional[torch.Tensor]):
+        """What the library takes as ``ws_dev``: the address of a dense count matrix (any binding cleared), or None with the CSR tensor
+        ``ws`` bound (gdrf_bind_counts_csr).  The int64 / int32 index arrays and the column grouping - CSR positions in (column, row) order
+        by a stable sort of the column indices, and their column pointers - are built once per tensor object and ``_version``, as
+        ``_ll_cache`` does for the data constant."""
+        if ws is None or not is_sparse_counts(ws):
+            if self._csr_bound:
+                _lib.check(self.lib.gdrf_bind_counts_csr(self.ctx, None, None, None, 0, 0, None, None), "gdrf_bind_counts_csr")
+                self._csr_bound = False
+            return None if ws is None else ws.data_ptr()
+        c = self._csr_cache
+        if c is None or c[0] is not ws or c[1] != ws._version:
+            crow = ws.crow_indices().to(torch.int64).contiguous()
+            col = ws.col_indices().to(torch.int32).contiguous()
+            val = ws.values().contiguous()
+            order = torch.sort(col, stable=True)
+            cperm = order.indices.to(torch.int64).contiguous()
+            # ccol[v] = the number of entries with a column < v (no host read: a mini-batch step stays asynchronous)
+            ccol = torch.searchsorted(order.values, torch.arange(self.V + 1, dtype=torch.int32, device=self.device)).to(torch.int64).contiguous()
+            c = self._csr_cache = (ws, ws._version, (crow, col, val, ccol, cperm))
+            self._csr_bound = False
+        if not self._csr_bound:
+            crow, col, val, ccol, cperm = c[2]
+            _lib.check(self.lib.gdrf_bind_counts_csr(self.ctx, crow.data_ptr(), col.data_ptr(), val.data_ptr(), ws.shape[0], col.numel(),
+                                                     ccol.data_ptr(), cperm.data_ptr()), "gdrf_bind_counts_csr")
+            self._csr_bound = True
+        return None
 
     def knm(self, xs: torch.Tensor) -> torch.Tensor:
         """K_nm = k(xs, Z) (n, M) row-major: the HBM-roofline kernel."""
@@ -403,7 +436,9 @@ class Engine:
         if c is not None and c[0] is ws and c[1] == ws._version:
             return c[2]
         out = torch.empty(1, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.gdrf_ll_const_dev(self.ctx, ws.data_ptr(), ws.shape[0], out.data_ptr(), _stream_ptr(self.device)),
+        if is_sparse_counts(ws):
+            check_counts(ws, None, self.V, self.device)
+        _lib.check(self.lib.gdrf_ll_const_dev(self.ctx, self._counts_ptr(ws), ws.shape[0], out.data_ptr(), _stream_ptr(self.device)),
                    "gdrf_ll_const_dev")
         self._ll_cache = (ws, ws._version, out)
         return out
@@ -566,11 +601,11 @@ class Engine:
                     raise NotImplementedError("a custom link_function together with a non-unit world's doubly scaled guide (quirk Q3)")
                 self._step_local_link(xs, ws, eps[p], n, s)
             elif xg is None:
-                _lib.check(self.lib.gdrf_step_local(self.ctx, xs.data_ptr(), ws.data_ptr(), eps[p].data_ptr(), n, self.Z.data_ptr(),
+                _lib.check(self.lib.gdrf_step_local(self.ctx, xs.data_ptr(), self._counts_ptr(ws), eps[p].data_ptr(), n, self.Z.data_ptr(),
                                                     self.params.data_ptr(), self.red_T.data_ptr(), self.red_d.data_ptr(), s),
                            "gdrf_step_local")
             else:
-                _lib.check(self.lib.gdrf_step_local2(self.ctx, xs.data_ptr(), xg.data_ptr(), ws.data_ptr(), eps[p].data_ptr(), n,
+                _lib.check(self.lib.gdrf_step_local2(self.ctx, xs.data_ptr(), xg.data_ptr(), self._counts_ptr(ws), eps[p].data_ptr(), n,
                                                      self.Z.data_ptr(), self.params.data_ptr(), self.red_T.data_ptr(),
                                                      self.red_d.data_ptr(), s), "gdrf_step_local2")
             if self.mean_count:
@@ -633,7 +668,7 @@ class Engine:
     def _step_local_link(self, xs, ws, eps_p, n: int, s: int):
         """gdrf_step_local with the link and its Jacobian evaluated here: theta = link(mu) and mubar = J^T thetabar by autograd
         (sparse_gdrf.py:361: `topic_probs = self._link_function(mu).transpose(-2, -1)`)."""
-        args = (self.ctx, xs.data_ptr(), ws.data_ptr(), eps_p.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(),
+        args = (self.ctx, xs.data_ptr(), self._counts_ptr(ws), eps_p.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(),
                 self.red_T.data_ptr(), self.red_d.data_ptr(), s)
         _lib.check(self.lib.gdrf_step_local_link(*args, 0, None, 0), "gdrf_step_local_link(0)")
         mu = self.workspace("mu", n).requires_grad_(True)                      # (K, n)
@@ -741,7 +776,7 @@ class Engine:
             elif mode == 4:          # (f_loc, f_var) of gp.util.conditional(full_cov=False): sparse_gdrf.py:277-319
                 out = torch.empty(2, self.K, n, dtype=self.dtype, device=self.device)
             _lib.check(self.lib.gdrf_predict(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(),
-                                             ws.data_ptr() if ws is not None else None, mode,
+                                             self._counts_ptr(ws) if mode == 3 else None, mode,
                                              out.data_ptr() if out is not None else None, self.out_d.data_ptr(),
                                              _stream_ptr(self.device)), "gdrf_predict")
             return self.out_d[:2].clone() if mode == 3 else out

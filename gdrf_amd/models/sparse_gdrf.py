@@ -14,6 +14,7 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
+from ..data import check_counts, csr_to, is_sparse_counts
 from ..engine import Engine
 from ..kernels import Kernel, Product, embedded_coordinates
 
@@ -29,6 +30,7 @@ _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convent
     "log_period": "_kernel.period_unconstrained",                # only with the Periodic kernel
 }
 _FACTOR_KEYS = {"log_variance": "variance", "log_lengthscale": "lengthscale", "log_period": "period"}
+
 
 
 def state_key(name: str) -> str:
@@ -337,6 +339,9 @@ class SparseMultinomialGDRF:
         self._randomize_wt = bool(randomize_wt_matrix)
         self._gen = gen
         xs = kwargs.get("xs")
+        ws0 = kwargs.get("ws")
+        if ws0 is not None and is_sparse_counts(ws0):      # a sparse count matrix: validated here, before the device is touched
+            check_counts(ws0, int(xs.shape[0]) if xs is not None else None, self._V)
         self._engine_for(int(xs.shape[0]) if xs is not None else 1)
 
     # ------------------------------------------------------------------ engine / parameters
@@ -454,7 +459,12 @@ class SparseMultinomialGDRF:
         xs_s = xs if unit else self.scale(xs)
         xs_s = xs_s.to(self.dtype).contiguous()
         ws_d = None
-        if ws is not None:
+        if ws is not None and is_sparse_counts(ws):
+            # a torch.sparse_csr count matrix goes through as it is (csrc/rows_csr.h); moving a tensor that already lives on the device
+            # returns the same object, so the engine's per-tensor caches hold
+            check_counts(ws, xs_s.shape[0], self._V)
+            ws_d = csr_to(ws, xs_s.device)
+        elif ws is not None:
             ws_d = torch.as_tensor(ws).to(device=self.device, dtype=torch.int32).contiguous()
             if ws_d.shape != (xs_s.shape[0], self._V):
                 raise ValueError(f"ws must have shape ({xs_s.shape[0]}, {self._V})")
@@ -572,6 +582,14 @@ class SparseMultinomialGDRF:
     def perplexity(self, x, w) -> torch.Tensor:
         """exp(-sum w log p / sum w): abstract_gdrf.py:137-139, as a 0-d tensor (train_script.py:469-472 calls .item())."""
         if self._link_function is not None:                  # abstract_gdrf.py:137-139, literally
+            if is_sparse_counts(w):                          # sum w log p over the stored entries: the counts are never densified
+                check_counts(w, None, self._V)
+                wd = csr_to(w, self.device)
+                crow, val = wd.crow_indices(), wd.values()
+                row = torch.repeat_interleave(torch.arange(wd.shape[0], device=self.device), crow[1:] - crow[:-1], output_size=val.numel())
+                lp = self.word_probs(x)[row, wd.col_indices().long()].log()
+                keep = val != 0                               # a stored zero is an absent entry
+                return ((val[keep] * lp[keep]).sum() / -val.sum()).exp()
             wd = torch.as_tensor(w).to(self.device)
             return ((wd * self.word_probs(x).log()).sum() / -wd.sum()).exp()
         xs_s, ws_d = self._prepare_inputs(x, w)

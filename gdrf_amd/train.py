@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import poutine
-from .data import normalise_index
+from .data import check_counts, csr_rows, csr_to, is_sparse_counts, normalise_index, to_csr
 from .infer import OBJECTIVE_DICT, SVI
 from .kernels import KERNEL_DICT
 from .models import GDRF_MODEL_DICT
@@ -83,14 +83,23 @@ def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Op
           objective_type: str = "graphelbo", objective_num_particles: int = 1, streaming_inference: str = "",
           streaming_weight: float = 0.1, streaming_exp: float = 1.0, streaming_truncate: int = -1, streaming_size: int = 1,
           streaming_subepochs: int = 1, streaming_batch_splits: int = -1, randomize_wt_matrix: bool = False, seed: int = 1,
-          dtype: torch.dtype = torch.float32, perplexity_every: int = 1, rows_form: str = "auto") -> Dict[str, object]:
+          dtype: torch.dtype = torch.float32, perplexity_every: int = 1, rows_form: str = "auto", sparse: bool = False) -> Dict[str, object]:
+    """``ws`` may be a ``torch.sparse_csr`` count matrix (int32 values); ``sparse=True`` converts dense counts (an array, or what ``data``
+    loaded) to one.  Either way the model trains and scores on the stored entries alone (csrc/rows_csr.h)."""
     kernel_ls = kernel_lengthscale_arg(kernel_lengthscale, dimensions)
     if data is not None:
         xs, ws = load_csv(data, dimensions)
     xs_t = torch.as_tensor(xs).float().to(device)
     if xs_t.dim() == 1:
         xs_t = xs_t.unsqueeze(-1)
-    ws_t = torch.as_tensor(ws).int().to(device)
+    if is_sparse_counts(ws):
+        check_counts(ws, None, None)
+        ws_t = csr_to(ws, device)
+    else:
+        ws_t = torch.as_tensor(ws).int().to(device)
+        if sparse:
+            ws_t = to_csr(ws_t)
+    rows = (lambda sel: csr_rows(ws_t, sel)) if is_sparse_counts(ws_t) else (lambda sel: ws_t[sel, ...])
     world = list(zip(xs_t.min(dim=0).values.cpu().numpy().tolist(), xs_t.max(dim=0).values.cpu().numpy().tolist()))
     n_data = len(xs_t)
     streaming = streaming_inference != ""
@@ -125,7 +134,7 @@ def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Op
                 if streaming_truncate > 0:
                     selection = selection + epoch + 1 - n_stream
                 sel = np.atleast_1d(selection)
-                loss = svi.step(xs=xs_t[sel, ...], ws=ws_t[sel, ...], subsample=False)
+                loss = svi.step(xs=xs_t[sel, ...], ws=rows(sel), subsample=False)
         else:
             loss = svi.step(xs=xs_t, ws=ws_t, subsample=False)
         model.eval()

@@ -85,6 +85,22 @@ int gdrf_get_hyper_backward(const gdrf_ctx* ctx);
  * Any other value is an error. */
 int gdrf_set_rows_form(gdrf_ctx* ctx, int form);
 int gdrf_get_rows_form(const gdrf_ctx* ctx);
+/* Sparse counts (csrc/rows_csr.h).  Binds a CSR count matrix of n rows and the context's V columns: crow_dev (n + 1) row pointers with
+ * crow[0] = 0 and crow[n] = nnz, col_dev (nnz) column indices in [0, V), val_dev (nnz) counts; all BORROWED device arrays that must stay
+ * valid and unchanged while bound.  Column indices need not be sorted inside a row; a stored 0 behaves as an absent entry; duplicate
+ * (row, column) entries are not supported.  The column grouping is the caller's to supply: cperm_dev (nnz) lists the CSR positions
+ * 0 .. nnz - 1 sorted by (column, row) - a stable sort of col_dev by value - and ccol_dev (V + 1) are the column pointers into it
+ * (ccol[v] = the number of entries with a column < v).  The steps need it; gdrf_predict mode 3 and the data constant do not (NULL, NULL).
+ * While a matrix is bound, gdrf_step_local, gdrf_step_local2, gdrf_step_local_link, gdrf_predict mode 3, gdrf_ll_const and
+ * gdrf_ll_const_dev must be given ws_dev = NULL and n = the bound row count (anything else is an error) and read the bound matrix; the
+ * per-row stage then runs the decomposition of row form 1 with its one vocabulary kernel replaced by a row pass over the stored entries
+ * and a column pass for Phi-bar, whatever the row form is set to: nnz x K work instead of n x V x K, no dense (n, V) array anywhere.
+ * gdrf_predict streams the bound rows n_cap at a time, so there n may exceed n_cap.  Scratch: Phi^T, an (n_cap, K) array, one (K, V) slot,
+ * allocated on the first such call; and 8 bytes + an element per stored entry plus K elements per column segment (256 entries), grown with
+ * nnz.  Same element type and arithmetic per stored entry as form 1, sums in another order; bit-identical from run to run.
+ * crow_dev = NULL clears the binding: every call then does what it does without one. */
+int gdrf_bind_counts_csr(gdrf_ctx* ctx, const int64_t* crow_dev, const int32_t* col_dev, const int32_t* val_dev, int64_t n, int64_t nnz,
+                         const int64_t* ccol_dev, const int64_t* cperm_dev);
 /* whiten = 0: the unwhitened branch of pyro's gp.util.conditional (gdrf/models/sparse_gdrf.py:30,175-185: the
  * constructor's `whiten` argument): u_loc and u_scale_tril parameterise q(f(Z)) itself, the predictive uses
  * L^-1 u_loc and L^-1 u_scale_tril.  Default 1 (whitened), which is what the reference's train() always runs. */
