@@ -9,6 +9,7 @@
 #include "kernels_mm.h"
 #include "kernels_n.h"
 #include "predict.h"
+#include "predict_mc.h"
 #include "rows_mfma.h"
 #include "rows_vstream.h"
 #include "rows_csr.h"
@@ -1859,6 +1860,33 @@ template <typename T, typename TS> struct Impl {
     LAUNCHCHK("predict");
     return 0;
   }
+
+  // Monte-Carlo integration over q(mu) at new inputs (predict_mc.h): the step's forward as in mode 4 of predict, then one kernel over the
+  // rows that draws (or reads) eps and reduces the samples; mode 2 ends in the per-workgroup partials' sum
+  static int predict_mc(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, int mode, int S, uint64_t seed,
+                        int64_t row_offset, const T* eps, T* out, double* out_d, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    const int LG = K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64, KJ = K <= 64 ? 1 : 2;
+    size_t lds = 0;
+    if (mode == MC_SCORE) {          // the LDS budget of the default row forms
+      lds = mc_score_lds<T>(K, V, LG, KJ);
+      if (128 + lds > 150 * 1024) return rows_lds_fail("gdrf_predict_mc");
+    }
+    if (int rc = step_local(c, X, nullptr, nullptr, n, Z, params, nullptr, nullptr, s, SL_TRANSFORMS | SL_FORWARD | SL_NO_DK)) return rc;
+    const int64_t nblk = (n + 256 / LG - 1) / (256 / LG);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
+    auto go = [&](auto kern) {
+      return launch_lds(kern, dim3(grid), dim3(256), lds, s, mode, n, K, V, S, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c),
+                        (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk, c->mean_sn, eps, seed, row_offset,
+                        (const T*)P(c->phi), ws, out, c->dpart);
+    };
+    const int rc = LG == 8 ? go(predict_mc_kernel<T, 8, 1>) : LG == 16 ? go(predict_mc_kernel<T, 16, 1>) : LG == 32 ? go(predict_mc_kernel<T, 32, 1>)
+                 : KJ == 1 ? go(predict_mc_kernel<T, 64, 1>) : go(predict_mc_kernel<T, 64, 2>);
+    if (rc) return rc;
+    if (mode == MC_SCORE) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)grid, 2, out_d);
+    LAUNCHCHK("predict_mc");
+    return 0;
+  }
 };
 
 
@@ -2109,6 +2137,21 @@ int gdrf_predict(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const voi
     if (int rc = counts_check(c, ws, n, "gdrf_predict")) return rc;
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, mode, (T*)out, out_d, s);
+}
+
+int gdrf_predict_mc(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, const int32_t* ws, int mode, int num_samples,
+                    uint64_t seed, int64_t row_offset, const void* eps, void* out, double* out_d, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (mode < 0 || mode > 3) return fail(-1, "gdrf_predict_mc", "mode");
+  if (n < 1) return fail(-1, "gdrf_predict_mc", "n must be >= 1");
+  if (n > c->ncap) return fail(-1, "gdrf_predict_mc", "needs n <= n_cap");
+  if (num_samples < 1) return fail(-1, "gdrf_predict_mc", "num_samples must be >= 1");
+  if (row_offset < 0) return fail(-1, "gdrf_predict_mc", "row_offset must be >= 0");
+  if (mode == MC_SCORE && c->csr_crow) return fail(-1, "gdrf_predict_mc", "the predictive score reads dense counts: clear the CSR binding");
+  if (mode == MC_SCORE && (!ws || !out_d)) return fail(-1, "gdrf_predict_mc", "the predictive score needs ws and out_d");
+  if (mode != MC_SCORE && !out) return fail(-1, "gdrf_predict_mc", "out is required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, predict_mc, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, mode, num_samples, seed, row_offset, (const T*)eps, (T*)out, out_d, s);
 }
 
 int gdrf_chol_failed(gdrf_ctx* c, int* failed, void* stream) {

@@ -1950,19 +1950,23 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
   const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
   c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
 }
+// the draw of (global row gn, topic k, step): Box-Muller in double on the first two words of the block, rounded to T
 template <typename T>
-__global__ void fill_eps_kernel(uint64_t seed, uint32_t step, int64_t n_offset, int64_t nrows, int K, T* __restrict__ eps, int64_t ldk) {
-  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int k = blockIdx.y;
-  if (n >= nrows) return;
-  const uint64_t gn = (uint64_t)(n + n_offset);
+__device__ __forceinline__ T philox_normal(uint64_t seed, uint64_t gn, int k, uint32_t step) {
   uint32_t c[4] = {(uint32_t)gn, (uint32_t)(gn >> 32), (uint32_t)k, step};
   uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
   for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
   const double u1 = ((double)c[0] + 0.5) * (1.0 / 4294967296.0);
   const double u2 = ((double)c[1] + 0.5) * (1.0 / 4294967296.0);
-  eps[(int64_t)k * ldk + n] = (T)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+  return (T)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+}
+template <typename T>
+__global__ void fill_eps_kernel(uint64_t seed, uint32_t step, int64_t n_offset, int64_t nrows, int K, T* __restrict__ eps, int64_t ldk) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = blockIdx.y;
+  if (n >= nrows) return;
+  eps[(int64_t)k * ldk + n] = philox_normal<T>(seed, (uint64_t)(n + n_offset), k, step);
 }
 
 }  // namespace gdrf

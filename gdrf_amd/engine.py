@@ -35,6 +35,19 @@ def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def check_mc_args(num_samples, K: int, n: int, eps=None, ws=None) -> int:
+    """The argument errors of the Monte-Carlo predictive calls (Engine.predict_mc and the model methods above it), raised before the
+    device is touched: ``num_samples`` >= 1, an injected ``eps`` of shape (num_samples, K, n), dense counts.  Returns num_samples as an int."""
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+    if eps is not None and tuple(eps.shape) != (S, K, n):
+        raise ValueError(f"eps must have shape (num_samples, K, n) = ({S}, {K}, {n}), got {tuple(eps.shape)}")
+    if ws is not None and is_sparse_counts(ws):
+        raise ValueError("the Monte-Carlo predictive score reads dense counts: a sparse (CSR) ws is not supported")
+    return S
+
+
 class Engine:
     """One device context for fixed (n_cap, M, K, V, D, dtype, kernel)."""
 
@@ -781,6 +794,12 @@ class Engine:
                                              _stream_ptr(self.device)), "gdrf_predict")
             return self.out_d[:2].clone() if mode == 3 else out
 
+        return self._speculated(run)
+
+    def _speculated(self, run):
+        """``run()`` under the jitter-level protocol of the predictive calls: start on the previous level (and on the factorisation adam()
+        queued ahead, if its inputs still match) while the array-precision probe that decides the level runs on the second stream; a wrong
+        guess redoes ``run()`` on the right level."""
         guess = self._guess_level if self.speculate else None
         if guess is None:
             self.factorize()
@@ -810,3 +829,42 @@ class Engine:
         self.factorize(None)
         self._guess_level = self.last_jitter_level
         return run()
+
+    def predict_mc(self, xs: torch.Tensor, mode: int, num_samples: int, ws: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                   row_offset: int = 0, eps: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None):
+        """Monte-Carlo integration over the guide's q(mu) at the rows ``xs`` (gdrf_predict_mc, csrc/predict_mc.h): mode 0 theta samples
+        (S, n, K), 1 their mean and variance (2, n, K), 2 {sum_n l_n, sum w} of the predictive score against the dense counts ``ws``, 3 mu
+        samples (S, K, n).  ``eps``: an injected (S, K, n) array; None = Philox draws keyed by ``seed`` with counter (row_offset + row, topic,
+        sample), so rows cut into several calls, each with its ``row_offset``, draw what one call draws.  ``mean``: the mean_function's values
+        on these rows, broadcastable to (K, n).  n <= n_cap.  Same jitter-level protocol as predict()."""
+        if mode not in (0, 1, 2, 3):
+            raise ValueError("predict_mc: mode must be 0 (theta samples), 1 (moments), 2 (predictive score) or 3 (mu samples)")
+        S = check_mc_args(num_samples, self.K, int(xs.shape[0]), eps, ws)
+        if mode == 2 and ws is None:
+            raise ValueError("predict_mc(mode=2) needs ws")
+        self._chk_rows(xs, ws if mode == 2 else None)
+        n = xs.shape[0]
+        if n > self.n_cap:
+            raise ValueError(f"predict_mc needs n <= n_cap ({n} > {self.n_cap})")
+        if eps is not None and (eps.dtype != self.dtype or eps.device != self.device or not eps.is_contiguous()):
+            raise ValueError(f"eps must be a contiguous {self.dtype} tensor on {self.device}")
+        if eps is None and seed is None:
+            raise ValueError("predict_mc needs a seed or an injected eps")
+        seed = 0 if seed is None else int(seed) & (2 ** 64 - 1)
+        self.refresh_inducing()
+        self._set_mean(mean, n)
+
+        def run():
+            out = None
+            if mode != 2:
+                out = torch.empty({0: (S, n, self.K), 1: (2, n, self.K), 3: (S, self.K, n)}[mode], dtype=self.dtype, device=self.device)
+            _lib.check(self.lib.gdrf_predict_mc(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(),
+                                                self._counts_ptr(ws) if mode == 2 else None, mode, S, seed, int(row_offset),
+                                                eps.data_ptr() if eps is not None else None, out.data_ptr() if out is not None else None,
+                                                self.out_d.data_ptr(), _stream_ptr(self.device)), "gdrf_predict_mc")
+            return self.out_d[:2].clone() if mode == 2 else out
+
+        try:
+            return self._speculated(run)
+        finally:
+            self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)

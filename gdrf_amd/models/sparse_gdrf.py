@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..data import check_counts, csr_to, is_sparse_counts
-from ..engine import Engine
+from ..engine import Engine, check_mc_args
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -110,6 +110,11 @@ def validate_dirichlet_param(b: torch.Tensor, K: int, V: int) -> torch.Tensor:
         assert tuple(b.shape) == (K, V), "b should be KxV if 2D"
         return b
     raise ValueError("invalid b parameter- you passed %s" % (b,))
+
+
+# Rows one Monte-Carlo predictive call holds in the engine: like forward(), the call grows the engine to hold its rows, but only up to
+# this many (the engine's workspaces take about 3 M elements per row); more rows are cut into pieces of the engine's n_cap.
+MC_PIECE_ROWS = 65536
 
 
 class ModelSnapshot:
@@ -219,6 +224,18 @@ class ModelSnapshot:
 
     def perplexity(self, x, w):
         return self.restore().perplexity(x, w)
+
+    def sample_topic_probs(self, xs, num_samples, seed=None, eps=None):
+        return self.restore().sample_topic_probs(xs, num_samples, seed=seed, eps=eps)
+
+    def topic_probs_mc(self, xs, num_samples=256, seed=None):
+        return self.restore().topic_probs_mc(xs, num_samples, seed=seed)
+
+    def word_probs_mc(self, xs, num_samples=256, seed=None):
+        return self.restore().word_probs_mc(xs, num_samples, seed=seed)
+
+    def predictive_perplexity(self, x, w, num_samples=64, seed=None):
+        return self.restore().predictive_perplexity(x, w, num_samples, seed=seed)
 
 
 class SparseMultinomialGDRF:
@@ -594,6 +611,70 @@ class SparseMultinomialGDRF:
             return ((wd * self.word_probs(x).log()).sum() / -wd.sum()).exp()
         xs_s, ws_d = self._prepare_inputs(x, w)
         s = self._engine_for(1).predict(xs_s, 3, ws_d)
+        return torch.exp(-s[0] / s[1])
+
+    # ------------------------------------------------------------------ Monte-Carlo predictive path (csrc/predict_mc.h)
+    def _predict_mc(self, xs_s: torch.Tensor, mode: int, S: int, ws_d=None, seed=None, eps=None) -> torch.Tensor:
+        """Engine.predict_mc on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows, each with its row_offset: the draws are keyed by the global row, so
+        the result does not depend on the piece size.  The pieces are joined along the row axis; mode 2's two sums are added."""
+        n = xs_s.shape[0]
+        eng = self._engine_for(min(n, MC_PIECE_ROWS))
+        seed = self.rng_seed if seed is None else int(seed)
+        if eps is not None:
+            eps = torch.as_tensor(eps).to(device=self.device, dtype=self.dtype)
+        mean = self._mean_values(xs_s)
+        if mean is not None:
+            mean = mean.to(device=self.device, dtype=self.dtype)
+            try:
+                mean = mean.expand(self._K, n)
+            except RuntimeError:
+                raise ValueError(f"mean_function returned shape {tuple(mean.shape)}, not broadcastable to ({self._K}, {n})") from None
+        parts = []
+        for a in range(0, n, eng.n_cap):
+            b = min(n, a + eng.n_cap)
+            parts.append(eng.predict_mc(xs_s[a:b], mode, S, ws=None if ws_d is None else ws_d[a:b], seed=seed, row_offset=a,
+                                        eps=None if eps is None else eps[:, :, a:b].contiguous(),
+                                        mean=None if mean is None else mean[:, a:b]))
+        if mode == 2:
+            return torch.stack(parts).sum(0)
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=2 if mode == 3 else 1)
+
+    def sample_topic_probs(self, xs, num_samples, seed=None, eps=None) -> torch.Tensor:
+        """(S, N, K) samples of the topic proportions under the guide's posterior: theta_s = link(mu_s), mu_s = f_loc + mean + f_var eps_s
+        with (f_loc, f_var) = forward(xs) and f_var as the scale, as the guide draws mu (sparse_gdrf.py:403-405).  ``eps``: injected
+        (S, K, N) standard normals; otherwise counter-based Philox draws keyed by ``seed`` (default: the model's rng_seed) and
+        (row, topic, sample).  topic_probs(xs) is the plug-in softmax(f_loc), which ignores f_var."""
+        S = check_mc_args(num_samples, self._K, int(torch.as_tensor(xs).shape[0]), eps)
+        xs_s, _ = self._prepare_inputs(xs)
+        if self._link_function is not None:      # the link with torch on the raw mu samples, as topic_probs applies it to f_loc
+            mu = self._predict_mc(xs_s, 3, S, seed=seed, eps=eps)
+            return torch.stack([self._link_function(mu[s]).T for s in range(S)])
+        return self._predict_mc(xs_s, 0, S, seed=seed, eps=eps)
+
+    def topic_probs_mc(self, xs, num_samples: int = 256, seed=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(mean, var), each (N, K): the posterior-predictive topic proportions E_q[link(mu)] and their variance (divisor S) over
+        ``num_samples`` draws, reduced on the device without storing the samples."""
+        S = check_mc_args(num_samples, self._K, int(torch.as_tensor(xs).shape[0]))
+        if self._link_function is not None:
+            th = self.sample_topic_probs(xs, S, seed=seed)
+            return th.mean(0), th.var(0, unbiased=False)
+        xs_s, _ = self._prepare_inputs(xs)
+        mv = self._predict_mc(xs_s, 1, S, seed=seed)
+        return mv[0], mv[1]
+
+    def word_probs_mc(self, xs, num_samples: int = 256, seed=None) -> torch.Tensor:
+        """(N, V) posterior-predictive word distributions: E_q[theta] Phi (the expectation is linear in theta)."""
+        check_mc_args(num_samples, self._K, 0)
+        return self.topic_probs_mc(xs, num_samples, seed=seed)[0] @ self.word_topic_matrix
+
+    def predictive_perplexity(self, x, w, num_samples: int = 64, seed=None) -> torch.Tensor:
+        """exp(-sum_n l_n / sum w), l_n = log (1/S) sum_s prod_v p[s][n][v]^w[n][v]: the Monte-Carlo predictive density of each row's
+        counts under q(mu) (the Multinomial coefficient left out, as perplexity leaves it out), as a 0-d tensor."""
+        if self._link_function is not None:
+            raise NotImplementedError("predictive_perplexity with a custom link_function: the score kernel fuses the softmax link")
+        S = check_mc_args(num_samples, self._K, 0, ws=w)
+        xs_s, ws_d = self._prepare_inputs(x, w)
+        s = self._predict_mc(xs_s, 2, S, ws_d=ws_d, seed=seed)
         return torch.exp(-s[0] / s[1])
 
     @property

@@ -320,6 +320,26 @@ int gdrf_optim_step(gdrf_ctx* ctx, int rule, const gdrf_opt_seg* segs_host, int 
 int gdrf_predict(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev,
                  const int32_t* ws_dev, int mode, void* out_dev, double* out_d_dev, void* stream);
 
+/* Monte-Carlo integration over the guide's posterior q(mu) at new inputs (csrc/predict_mc.h): the quantities of gdrf_predict are plug-ins
+ * softmax(f_loc); these integrate over mu ~ Normal(f_loc, f_var) as the guide writes it (f_var as the SCALE, gdrf/models/sparse_gdrf.py:403-405):
+ *   mu[s][k][n] = f_loc[k][n] + mean[k][n] + f_var[k][n] eps[s][k][n],  theta[s][n][:] = softmax_k(mu[s][:][n]),  p[s][n][:] = theta[s][n][:] Phi,
+ * (f_loc, f_var) as mode 4 of gdrf_predict gives them (X: the inputs scaled ONCE), mean = the values set with gdrf_set_mean (NULL: zero).
+ * eps_dev: an (S, K, n) array of the context's element type, or NULL for Philox4x32-10 draws keyed by `seed` with counter (row_offset + n, k, s):
+ * sample s of row n is the number gdrf_fill_eps(seed, step = s, n_offset = row_offset) writes, so cutting the rows into several calls, each
+ * with its row_offset, changes no draw.  S = num_samples >= 1.
+ *   GDRF_MC_THETA    out (S, n, K): the theta samples
+ *   GDRF_MC_MOMENTS  out (2, n, K): mean and variance (divisor S) of theta over the samples; no sample is stored
+ *   GDRF_MC_SCORE    out_d_dev[0..1] = {sum_n l_n, sum w}, l_n = logsumexp_s(sum_v w[n][v] log p[s][n][v]) - log S (the Multinomial
+ *                    coefficient left out, as gdrf_predict mode 3 leaves it out); ws_dev (n, V) dense int32 counts (not with a bound CSR
+ *                    matrix); Phi, the counts and theta of a workgroup's rows live in LDS, so K x V is bounded as for the LDS row forms
+ *                    ("too large" otherwise); p is never stored; deterministic sums (per-workgroup partials, no atomics)
+ *   GDRF_MC_MU       out (S, K, n): the mu samples, for a link function the caller evaluates
+ * n <= n_cap.  Runs the step's forward (as mode 4), so it overwrites the same workspaces; every step recomputes them.  Everything but the
+ * two sums of GDRF_MC_SCORE is bit-identical however the rows are batched.  Needs gdrf_factorize(). */
+enum { GDRF_MC_THETA = 0, GDRF_MC_MOMENTS = 1, GDRF_MC_SCORE = 2, GDRF_MC_MU = 3 };
+int gdrf_predict_mc(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const int32_t* ws_dev, int mode,
+                    int num_samples, uint64_t seed, int64_t row_offset, const void* eps_dev, void* out_dev, double* out_d_dev, void* stream);
+
 /* Did the last gdrf_factorize() hit a non-positive pivot?  Synchronises the stream. */
 int gdrf_chol_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
 
