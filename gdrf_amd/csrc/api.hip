@@ -10,6 +10,7 @@
 #include "kernels_n.h"
 #include "predict.h"
 #include "predict_mc.h"
+#include "rows_lds.h"
 #include "rows_mfma.h"
 #include "rows_vstream.h"
 #include "rows_csr.h"
@@ -730,7 +731,6 @@ static int launch_lds(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hi
 // fn<SP>(...) of Impl for the context's split mode: 2 = f16x3 (SplitF16), 1 = bf16x6 (SplitBf16)
 #define BY_SPLIT(c, fn, ...) ((c)->split == 2 ? fn<SplitF16>(__VA_ARGS__) : fn<SplitBf16>(__VA_ARGS__))
 
-// the LDS row forms of the two-point and link steps hold the (K, V) word-topic matrix and its gradient in LDS
 #define GDRF_STREAMED_HINT "the vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1), rows_form=\"streamed\") has no such limit"
 static int rows_lds_fail(const char* fn) {
   return fail(-1, fn, "num_topic_categories x num_observation_categories too large for the row kernel's LDS; " GDRF_STREAMED_HINT);
@@ -1172,23 +1172,27 @@ template <typename T, typename TS> struct Impl {
     LAUNCHCHK("rows_vstream");
     return 0;
   }
-  // the V-free phases 0 / 2 of elbo_rows_link_kernel (no Phi in LDS) on the streamed form's grid
-  static void vs_link_phase(gdrf_ctx* c, int phase, int64_t n, int grid, const T* eps, const int32_t* ws, const T* qpart, const T* loc,
-                            const T* tt, const T* mean, int64_t msk, int64_t msn, const T* ext, int64_t ext_ld, hipStream_t s) {
-    hipLaunchKernelGGL(elbo_rows_link_kernel<T>, dim3(grid), dim3(64), 128, s, phase, n, c->K, c->V, c->hyp, qpart, nct<TS>(c), loc, tt, eps,
-                       c->ldk, n, ws, P(c->phi), mean, msk, msn, ext, ext_ld, P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart,
-                       (T*)nullptr);
+  // the V-free head and tail of the row stage (rows_lds.h) on the streamed form's grid: q and mu from one side's (qpart, loc, tt, mean);
+  // the Normal sites and the row-local backward from mub = mubar (K, mub_ld)
+  static void rows_mu(gdrf_ctx* c, int64_t n, int grid, const T* eps, const T* qpart, const T* loc, const T* tt, const T* mean, int64_t msk,
+                      int64_t msn, hipStream_t s) {
+    hipLaunchKernelGGL(rows_mu_kernel<T>, dim3(grid), dim3(64), 0, s, n, c->K, c->hyp, qpart, nct<TS>(c), loc, tt, eps, c->ldk, n, mean, msk, msn,
+                       P(c->q), P(c->mu));
   }
-  // gdrf_step_local's row terms in form 1: q, mu (link phase 0) ; Phi row sums ; theta = softmax(mu) through the streamed likelihood
-  // -> mubar ; the Normal sites and the row-local backward (link phase 2 with ext = mubar) ; reductions
+  static void rows_sites(gdrf_ctx* c, int64_t n, int grid, const T* eps, const T* mub, int64_t mub_ld, hipStream_t s) {
+    hipLaunchKernelGGL(rows_sites_kernel<T>, dim3(grid), dim3(64), 0, s, n, c->K, c->hyp, (const T*)P(c->qpart), nct<TS>(c), (const T*)P(c->tt), eps,
+                       c->ldk, n, mub, mub_ld, P(c->vbar), P(c->locbar), P(c->asum), c->dpart);
+  }
+  // gdrf_step_local's row terms in form 1: q, mu ; Phi row sums ; theta = softmax(mu) through the streamed likelihood -> mubar ; the
+  // Normal sites and the row-local backward ; reductions
   static int rows_streamed(gdrf_ctx* c, const int32_t* ws, const T* eps, int64_t n, T* redT, double* redd, hipStream_t s) {
     const int K = c->K, V = c->V;
     if (int rc = vs_ensure(c)) return rc;
     const int G = vs_grid(c, n);
-    vs_link_phase(c, 0, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), (const T*)c->mean, c->mean_sk, c->mean_sn, nullptr, 0, s);
+    rows_mu(c, n, G, eps, P(c->qpart), P(c->loc), P(c->tt), (const T*)c->mean, c->mean_sk, c->mean_sn, s);
     hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, (T*)c->vs_rs);
     if (int rc = vs_launch<VS_SOFTMAX>(c, n, G, P(c->mu), c->ldk, 1, ws, (T*)c->vs_tmp, c->ldk, c->dpart, 0, s)) return rc;
-    vs_link_phase(c, 2, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), nullptr, 0, 0, (const T*)c->vs_tmp, c->ldk, s);
+    rows_sites(c, n, G, eps, (const T*)c->vs_tmp, c->ldk, s);
     LAUNCHCHK("elbo_rows (streamed)");
     rows_reduce(c, vs_parts(c), G, redT, redd, s, vs_nparts(c, G));
     return 0;
@@ -1562,35 +1566,20 @@ template <typename T, typename TS> struct Impl {
     HIPCHK(hipMemcpyAsync(c->g_tt, c->tt, (size_t)kn * c->esz, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->g_qpart, c->qpart, (size_t)nq * c->esz, hipMemcpyDeviceToDevice, s));
     if ((rc = step_local(c, Xm, ws, eps, n, Z, params, redT, redd, s, SL_FORWARD))) return rc;
-    if (c->rows_form == 1 || c->csr_crow) {
-      // form 1: the guide-side mu (link phase 0 on the guide's arrays; its q is rewritten below), the streamed likelihood -> mubar, the
-      // two-point sites (V-free)
+    {
+      // the guide-side mu (its q is rewritten below), the streamed or sparse likelihood -> mubar, the two-point sites (V-free)
       ScopedTimer tm(c, 6, s);
       if ((rc = vs_ensure(c))) return rc;
       const int G = vs_grid(c, n);
-      vs_link_phase(c, 0, n, G, eps, ws, (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, (const T*)c->mean_g, c->mean_g_sk,
-                    c->mean_g_sn, nullptr, 0, s);
+      rows_mu(c, n, G, eps, (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, s);
       hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, (T*)c->vs_rs);
       if ((rc = vs_launch<VS_SOFTMAX>(c, n, G, P(c->mu), ldk, 1, ws, (T*)c->vs_tmp, ldk, c->dpart, 0, s))) return rc;
       hipLaunchKernelGGL(elbo_rows2_sites_kernel<T>, dim3(G), dim3(64), 0, s, n, K, c->hyp, nct<TS>(c), P(c->qpart), P(c->loc), P(c->tt),
                          (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, eps, ldk, n, (const T*)c->vs_tmp, (const T*)c->mean,
                          c->mean_sk, c->mean_sn, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum),
                          (T*)c->g_vbar, (T*)c->g_locbar, (T*)c->g_asum, P(c->mu), c->dpart);
-      LAUNCHCHK("elbo_rows2 (streamed)");
-      rows_reduce(c, vs_parts(c), G, redT, redd, s, vs_nparts(c, G));
-    } else {
-      ScopedTimer tm(c, 6, s);
-      const int RB = 64;
-      const size_t lds = 128 + ((size_t)2 * K * V + (size_t)2 * RB * (K + 1) + (size_t)RB * (V + 1)) * sizeof(T);
-      if (lds > 150 * 1024) return rows_lds_fail("gdrf_step_local2");
-      if ((rc = phibar_part_ensure(c))) return rc;
-      const int egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
-      if ((rc = launch_lds(elbo_rows2_kernel<T>, dim3(egrid), dim3(RB), lds, s, n, K, V, c->hyp, nct<TS>(c), P(c->qpart), P(c->loc), P(c->tt),
-                           (const T*)c->g_qpart, (const T*)c->g_loc, (const T*)c->g_tt, eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk,
-                           c->mean_sn, (const T*)c->mean_g, c->mean_g_sk, c->mean_g_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum),
-                           (T*)c->g_vbar, (T*)c->g_locbar, (T*)c->g_asum, P(c->mu), c->dpart, P(c->phibar_part)))) return rc;
       LAUNCHCHK("elbo_rows2");
-      rows_reduce(c, P(c->phibar_part), egrid, redT, redd, s);
+      rows_reduce(c, vs_parts(c), G, redT, redd, s, vs_nparts(c, G));
     }
     // backward through the model-side predictive (the buffers hold its W), payload aside
     if ((rc = step_local(c, Xm, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD))) return rc;
@@ -1614,52 +1603,33 @@ template <typename T, typename TS> struct Impl {
     return 0;
   }
 
-  // one svi.step around a caller-supplied link function, in three calls (kernels_n.h: elbo_rows_link_kernel):
-  //   phase 0: transforms + forward + mu -> workspace 14;  phase 1: ext = theta (K, ext_ld) -> thetabar in workspace 6 (locbar), Phi-bar,
-  //   the log-likelihood sum;  phase 2: ext = mubar (K, ext_ld) -> the Normal sites, the row-local backward and the rest of gdrf_step_local
+  // one svi.step around a caller-supplied link function, in three calls:
+  //   phase 0: transforms + forward + mu (rows_mu_kernel) -> workspace 14;  phase 1: ext = theta (K, ext_ld) through the streamed or sparse
+  //   likelihood -> thetabar in workspace 6 (locbar), Phi-bar (its constant part subtracted after the reduction), the log-likelihood sum;
+  //   phase 2: ext = mubar (K, ext_ld) -> the Normal sites, the row-local backward (rows_sites_kernel) and the rest of gdrf_step_local
   static int step_local_link(gdrf_ctx* c, const T* X, const int32_t* ws, const T* eps, int64_t n, const T* Z, const T* params,
                              T* redT, double* redd, hipStream_t s, int phase, const T* ext, int64_t ext_ld) {
     const int K = c->K, V = c->V;
-    const int64_t ldk = c->ldk;
     int rc;
     if (phase == 0 && (rc = step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_TRANSFORMS | SL_FORWARD))) return rc;
-    if (c->rows_form == 1 || c->csr_crow) {
-      // form 1: phases 0 and 2 are V-free; phase 1 is the streamed likelihood on ext = theta, thetabar -> locbar, its Phi-bar's constant
-      // part subtracted after the reduction
-      if ((rc = vs_ensure(c))) return rc;
-      const int G = vs_grid(c, n);
-      if (phase != 1) {
-        vs_link_phase(c, phase, n, G, eps, ws, P(c->qpart), P(c->loc), P(c->tt), (const T*)c->mean, c->mean_sk, c->mean_sn, ext, ext_ld, s);
-        LAUNCHCHK("elbo_rows_link (streamed)");
-        if (phase == 0) return 0;
-        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
-        return step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD);
-      }
+    if ((rc = vs_ensure(c))) return rc;
+    const int G = vs_grid(c, n);
+    if (phase == 0) {
+      rows_mu(c, n, G, eps, P(c->qpart), P(c->loc), P(c->tt), (const T*)c->mean, c->mean_sk, c->mean_sn, s);
+    } else if (phase == 1) {
       T* rs = (T*)c->vs_rs;
       hipLaunchKernelGGL(vs_rowsum_kernel<T>, dim3(K), dim3(256), 0, s, P(c->phi), K, V, rs);
-      if ((rc = vs_launch<VS_LINK>(c, n, G, ext, ext_ld, 1, ws, P(c->locbar), ldk, c->dpart, 0, s))) return rc;
+      if ((rc = vs_launch<VS_LINK>(c, n, G, ext, ext_ld, 1, ws, P(c->locbar), c->ldk, c->dpart, 0, s))) return rc;
       phibar_reduce(c, vs_parts(c), vs_nparts(c, G), redT, s);
       hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K + 255) / 256), dim3(256), 0, s, vs_cparts(c), (int64_t)G, (int64_t)K, rs + K);
       hipLaunchKernelGGL(vs_sub_rows_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, K, V, (const T*)(rs + K),
                          redT + red_lay(c).phibar);
-      LAUNCHCHK("elbo_rows_link (streamed)");
-      return 0;
+    } else {
+      rows_sites(c, n, G, eps, ext, ext_ld, s);
+      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
     }
-    const int RB = 64;
-    const size_t lds = 128 + ((size_t)2 * K * V + (size_t)RB * (K + 1) + (size_t)RB * (V + 1)) * sizeof(T);
-    if (lds > 150 * 1024) return rows_lds_fail("gdrf_step_local_link");
-    if ((rc = phibar_part_ensure(c))) return rc;
-    const int egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
-    if ((rc = launch_lds(elbo_rows_link_kernel<T>, dim3(egrid), dim3(RB), lds, s, phase, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt),
-                         eps, ldk, n, ws, P(c->phi), (const T*)c->mean, c->mean_sk, c->mean_sn, ext, ext_ld, P(c->q), P(c->vbar), P(c->locbar),
-                         P(c->asum), P(c->mu), c->dpart, P(c->phibar_part)))) return rc;
     LAUNCHCHK("elbo_rows_link");
-    if (phase == 1) phibar_reduce(c, P(c->phibar_part), egrid, redT, s);
-    if (phase == 2) {
-      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)egrid, 4, redd);
-      return step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD);
-    }
-    return 0;
+    return phase == 2 ? step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD) : 0;
   }
 
   static int step_finish(gdrf_ctx* c, const T* Z, const T* params, const T* redT, const double* redd, double n_global,

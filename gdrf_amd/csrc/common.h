@@ -11,6 +11,7 @@
 #define GDRF_FWDW_DEPTH 2      // register prefetch distance (chunks) of the f64 W = K_nm L^-T kernel
 #define GDRF_MPAD 32           // M is padded to a multiple of this in every workspace matrix
 #define GDRF_DMAX 4            // input dimensions supported (index columns of the reference's CSV)
+#define GDRF_KMAX 32           // topics whose per-row values the one-thread-per-row kernels keep in registers
 
 namespace gdrf {
 
@@ -69,6 +70,19 @@ __device__ __forceinline__ double block_sum(double v, double* scratch) {
   double r = 0.0;
   if (threadIdx.x == 0) for (int i = 0; i < nw; ++i) r += scratch[i];
   return r;
+}
+// The row kernels' four scalars per workgroup, dpart[grid][4] = (Normal sites, sum w log p, d/d noise, a sum vbar): block sums of the
+// slots in SLOTS (bit i = slot i), written by thread 0.  The vocabulary kernels own slot 1, the V-free tails the other three.
+enum { DP_SITES = 13, DP_LOGLIK = 2, DP_ALL = 15 };
+template <int SLOTS>
+__device__ __forceinline__ void dpart_store(double* __restrict__ dpart, double* scratch, double s_site, double s_llw, double s_noise, double s_vd) {
+  double b[4] = {s_site, s_llw, s_noise, s_vd};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) if (SLOTS >> i & 1) b[i] = block_sum(b[i], scratch);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) if (SLOTS >> i & 1) dpart[4 * (int64_t)blockIdx.x + i] = b[i];
+  }
 }
 
 template <typename T> __device__ __forceinline__ T t_exp(T x);

@@ -4,7 +4,7 @@
 // Phi-bar; the normaliser sum_v p_v = sum_k theta_k rowsum_k needs no sweep over the words), so visiting the stored entries alone gives the
 // sums of rows_vstream_kernel with nnz x K work instead of n x V x K, and no dense (n, V) array exists anywhere.  The kernels below stand
 // in for rows_vstream_kernel in its three modes that read counts (VS_SOFTMAX, VS_LINK, VS_PERP), on the same buffers with the same
-// meaning; the V-free kernels around it are those of the streamed form.  The arithmetic per stored entry is that of rows_vstream_kernel
+// meaning; the V-free kernels around it are those of the streamed form (rows_lds.h).  The arithmetic per stored entry is that of rows_vstream_kernel
 // (ph = p / sum p, the clamp to [eps, 1 - eps], pbar = w / p inside the clamp range only, the unclamped count sum of the link mode): the
 // two forms differ by summation order only.
 //
@@ -207,8 +207,7 @@ __global__ __launch_bounds__(256) void rows_csr_kernel(
     }
   }
   if constexpr (ELBO) {
-    const double a = block_sum(s_a, scratch);
-    if (tid == 0) dpart[4 * (int64_t)blockIdx.x + 1] = a;
+    dpart_store<DP_LOGLIK>(dpart, scratch, 0, s_a, 0, 0);
   } else {
     const double a = block_sum(s_a, scratch), b = block_sum(s_b, scratch);
     if (tid == 0) {

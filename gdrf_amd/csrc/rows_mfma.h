@@ -4,7 +4,7 @@
 //   v_kn = clamp(variance - q_n, 0) + tt_kn ; mu = loc + v eps (+ mean) ; theta = softmax_k(mu) ; p = theta Phi ;
 //   log-likelihood sum_v w_v log clamp(p_v / sum p) ; both Normal sites ; row-local backward (vbar, locbar) ; Phi-bar.
 //
-// The one-thread-per-row kernel (kernels_n.h: elbo_rows_kernel) spends ~3000 LDS reads per row on the three small products
+// The one-thread-per-row kernel (rows_lds.h: elbo_rows_kernel) spends ~3000 LDS reads per row on the three small products
 // p = theta Phi, thetabar = pbar Phi^T and Phi-bar += theta^T pbar (K x V each), holds 209 registers and runs two waves per SIMD:
 // 0.67 ms at N = 1e6 for 0.45 GB of traffic.  Here the three products are 16x16x4 matrix instructions whose operands never leave the
 // registers: lane (lr, lg) = (lane & 15, lane >> 4) of a wave owns row lr of the wave's 16 rows and, of every 16-wide block of topics or

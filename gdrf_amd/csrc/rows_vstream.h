@@ -1,6 +1,6 @@
 // The vocabulary-streamed row form (gdrf_set_rows_form(ctx, 1)): the per-row terms that touch the vocabulary, for any V.
 //
-// Per row n the likelihood needs (kernels_n.h: elbo_rows_kernel for the arithmetic)
+// Per row n the likelihood needs (rows_lds.h: elbo_rows_kernel for the arithmetic)
 //   p_v = sum_k theta_k phi_kv ;  ph_v = p_v / sum_v p_v clamped to [eps, 1 - eps] ;  sum_v w_v log ph_v ;
 //   pbar_v = w_v / p_v (0 where the clamp is active) ;  thetabar_k = sum_v phi_kv pbar_v ;  Phi-bar_kv += theta_k pbar_v.
 // The LDS forms keep all of Phi (K x V) and its gradient in LDS.  Here a workgroup owns 64 rows at a time and keeps only their theta
@@ -13,8 +13,9 @@
 // One kernel, four uses (MODE):
 //   VS_SOFTMAX  src = mu (K, n): theta = softmax(mu); after the sweep the softmax pull-back around the dominant topic (the same
 //               cancellation-free form as elbo_rows_kernel) -> dst = mubar (K, n).  The V-free remainder (Normal sites, row-local
-//               backward) is phase 2 of elbo_rows_link_kernel (single point) or elbo_rows2_sites_kernel (two points).
-//   VS_LINK     src = theta (K, n) returned by a caller's link -> dst = thetabar_k - cn rowsum_k, as phase 1 of elbo_rows_link_kernel;
+//               backward) is rows_sites_kernel (single point) or elbo_rows2_sites_kernel (two points), rows_lds.h.
+//   VS_LINK     src = theta (K, n) returned by a caller's link, which need not sum to one -> dst = thetabar_k - cn rowsum_k =
+//               sum_v phi_kv w_v / p_v - sum_v w_v / sum_v p_v (sums over the words inside the clamp range), call 1 of gdrf_step_local_link;
 //               the constant part of its Phi-bar (- sum_rows theta_k cn) is known only after the sweep: its per-workgroup sums go to cpart
 //               and are subtracted after the reduction (vs_sub_rows_kernel).
 //   VS_WORDP    src = topic_probs (n, K): dst = p (n, V), gdrf_predict mode 2.
@@ -228,8 +229,7 @@ __global__ __launch_bounds__(256) void rows_vstream_kernel(
     }
   }
   if constexpr (ELBO) {
-    const double a = block_sum(s_a, scratch);
-    if (tid == 0) dpart[4 * (int64_t)blockIdx.x + 1] = a;
+    dpart_store<DP_LOGLIK>(dpart, scratch, 0, s_a, 0, 0);
     if constexpr (MODE == VS_LINK) { if (tid < K) cpart[(int64_t)blockIdx.x * K + tid] = cacc; }
   } else if constexpr (MODE == VS_PERP) {
     const double a = block_sum(s_a, scratch), b = block_sum(s_b, scratch);

@@ -103,7 +103,8 @@ class Engine:
         _lib.check(self.lib.gdrf_set_hyper_backward(self.ctx, 1 if hyper_backward == "tn" else 0), "gdrf_set_hyper_backward")
         self._hyper_backward_request = hyper_backward
         # the per-row terms that touch the vocabulary (gdrf_set_rows_form): "auto" = the LDS row forms (Phi and its gradient in LDS; K x V
-        # bounded, larger shapes fail with "too large"); "streamed" = Phi through LDS in tiles of words, any V and K <= 128 (csrc/rows_vstream.h)
+        # bounded, larger shapes fail with "too large"); "streamed" = Phi through LDS in tiles of words, any V and K <= 128 (csrc/rows_vstream.h).
+        # "auto" governs the ordinary step and predict; a custom link_function and the two-point step (xs_guide) are streamed in either setting
         if rows_form not in ("auto", "streamed"):
             raise ValueError("rows_form must be 'auto' or 'streamed'")
         if rows_form == "streamed":

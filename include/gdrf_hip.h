@@ -72,16 +72,18 @@ int gdrf_get_mfma_mode(const gdrf_ctx* ctx);
 int gdrf_set_hyper_backward(gdrf_ctx* ctx, int mode);
 int gdrf_get_hyper_backward(const gdrf_ctx* ctx);
 /* How the per-row terms that touch the vocabulary (p = theta Phi, the Multinomial log-likelihood, thetabar = Phi pbar, Phi-bar) are formed
- * by gdrf_step_local, gdrf_step_local2, all three phases of gdrf_step_local_link and gdrf_predict modes 0-3:
+ * by gdrf_step_local and gdrf_predict modes 0-3:
  *   0  (default) the LDS forms: the matrix-core row kernel for K <= 32, V <= 64, else one thread per row; each keeps the whole (K, V) Phi
  *      (and most its gradient and a (V + 1) row per thread) in LDS, so K x V is bounded by the LDS budget and larger shapes fail with
  *      "too large".  Their Phi-bar partials take [1024][K][V] elements, allocated on the first call that needs them.
  *   1  vocabulary-streamed (csrc/rows_vstream.h), any V >= 1 and K <= 128: a workgroup keeps only the theta of its 64 rows (K x 64) in
  *      LDS and streams Phi through LDS in tiles of 64 words (float) or 32 (double), each count read once; the V-free terms run in kernels
- *      without any K x V array.  Workspace: a (K, n_cap) array, Phi-bar slots [G][K][V] and [G][K] with
+ *      without any K x V array (csrc/rows_lds.h).  Workspace: a (K, n_cap) array, Phi-bar slots [G][K][V] and [G][K] with
  *      G = min(1024, max(16, 256 MiB / (K V element size)), ceil(n_cap / 64)), all allocated on the first form-1 call.  gdrf_predict
  *      modes 0-1 read no Phi; modes 2-3 stream it over n_cap rows at a time.  Same element type and precision as form 0; sums are
  *      formed in another order, so results agree with form 0 to rounding, and are bit-identical from run to run.
+ * gdrf_step_local2 and all three phases of gdrf_step_local_link have the one route of form 1 and take it whatever the form is set to
+ * (same kernels, grid and workspace, so the same bits in either form); they have no K x V bound beyond K <= 128.
  * Any other value is an error. */
 int gdrf_set_rows_form(gdrf_ctx* ctx, int form);
 int gdrf_get_rows_form(const gdrf_ctx* ctx);

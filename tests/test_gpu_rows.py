@@ -1,4 +1,4 @@
-"""GPU tests of the per-row ELBO kernels (rows_mfma.h: elbo_rows_mfma_kernel; kernels_n.h: elbo_rows_kernel) at the edges of
+"""GPU tests of the per-row ELBO kernels (rows_mfma.h: elbo_rows_mfma_kernel; rows_lds.h: elbo_rows_kernel) at the edges of
 their dispatch and of their tiles, against the fp64 reference at the same parameters and the same jitter level.
 
 The host picks the form from (K, V): the matrix-core form <NKT, NVT> for K <= 16 / <= 32 and V <= 32 / <= 64, the one-thread-per-row
