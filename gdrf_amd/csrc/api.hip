@@ -10,6 +10,7 @@
 #include "kernels_n.h"
 #include "predict.h"
 #include "predict_mc.h"
+#include "predict_cov.h"
 #include "rows_lds.h"
 #include "rows_mfma.h"
 #include "rows_vstream.h"
@@ -114,6 +115,10 @@ struct gdrf_ctx {
   void *csr_phiT, *csr_thN, *csr_cn, *csr_cpart, *csr_slot;
   // ... and the arrays that grow with nnz: pbar and the row of every entry, the column segments' table and partial sums
   void *csr_pb, *csr_parts; int32_t *csr_erow, *csr_segcol; int64_t *csr_segoff; int64_t csr_cap;
+  // the joint posterior (predict_cov.h), allocated on first use and grown with the call: W (jrows, Mp), R (jnp, jnp), the Cholesky work
+  // matrix (jgnp, jgnp), T_k (K, jtrows, Mp), the sampler's V (jsk, Mp) and zeta (jzel elements), all in the solve precision; its failure flag
+  void *jW, *jR, *jG, *jT, *jV, *jZ; int64_t jrows, jnp, jgnp, jtrows, jsk, jzel; int* jflag;
+  int64_t jlast_n, jlast_sk;  // rows and (sample, topic) pairs of the gdrf_sample_joint whose W, R, V and zeta are still in place (0: none)
   std::vector<void*> allocs;
   // optional per-kernel HIP-event timing (gdrf_set_timing): events recorded on the launch stream
   int timing;
@@ -1857,6 +1862,103 @@ template <typename T, typename TS> struct Impl {
     LAUNCHCHK("predict_mc");
     return 0;
   }
+
+  // ---- the joint posterior at new inputs (predict_cov.h)
+  // a joint buffer of at least `bytes`: a larger request replaces it.  Only the joint calls read these blocks, so the replaced one is
+  // freed here, once the device has finished whatever was queued on it (a growth is rare: the wait costs one call, not every call)
+  static int joint_buf(gdrf_ctx* c, void** p, int64_t* have, int64_t want, size_t bytes) {
+    if (want <= *have && *p) return 0;
+    if (*p) {
+      HIPCHK(hipDeviceSynchronize());
+      c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), *p), c->allocs.end());
+      HIPCHK(hipFree(*p));
+      *p = nullptr; *have = 0;
+    }
+    if (int rc = ctx_alloc(c, p, bytes, "hipMalloc(joint posterior)")) return rc;
+    *have = want;
+    return 0;
+  }
+  template <int EPI, typename TB, typename TO>
+  static void joint_nt(gdrf_ctx* c, const JointNT<TS, TB, T, TO>& p, int batch, hipStream_t s) {
+    const dim3 grid((unsigned)((p.nj + GDRF_JT - 1) / GDRF_JT), (unsigned)((p.ni + GDRF_JT - 1) / GDRF_JT), (unsigned)batch);
+    if (EPI == JT_RESID && ard_fwd(c)) hipLaunchKernelGGL((joint_nt_kernel<TS, TB, T, TO, EPI, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((joint_nt_kernel<TS, TB, T, TO, EPI, false>), grid, dim3(256), 0, s, p);
+  }
+  // the step's forward as mode 4 of predict runs it, then W in the solve precision (c->jW) and R = K_** - W W^T (c->jR, leading dimension
+  // *np_out = round_up(n, 32))
+  static int joint_forward(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, int64_t* np_out, hipStream_t s) {
+    const int Mp = c->Mp;
+    const int64_t np = round_up(n, 32);
+    if (int rc = joint_buf(c, &c->jW, &c->jrows, n, (size_t)n * Mp * sizeof(TS))) return rc;
+    if (int rc = joint_buf(c, &c->jR, &c->jnp, np, (size_t)np * np * sizeof(TS))) return rc;
+    if (!c->jflag)
+      if (int rc = ctx_alloc(c, &c->jflag, 64, "hipMalloc(joint posterior)", true)) return rc;
+    if (int rc = step_local(c, X, nullptr, nullptr, n, Z, params, nullptr, nullptr, s, SL_TRANSFORMS | SL_FORWARD | SL_NO_DK)) return rc;
+    const T* Xc = c->per ? (const T*)c->Xe : X;               // periodic and product contexts: the embedded rows the forward just wrote
+    JointNT<TS, TS, T, TS> w{(const TS*)Q(c->Knm), Mp, 0, n, (const TS*)Q(c->Linv), Mp, 0, Mp, Mp, Q(c->jW), Mp, 0, nullptr, 0, nullptr, 0, 0, nullptr};
+    joint_nt<JT_PLAIN>(c, w, 1, s);
+    JointNT<TS, TS, T, TS> r{(const TS*)Q(c->jW), Mp, 0, n, (const TS*)Q(c->jW), Mp, 0, n, Mp, Q(c->jR), np, 0, nullptr, 0, Xc, c->D, c->kind, c->hyp};
+    joint_nt<JT_RESID>(c, r, 1, s);
+    LAUNCHCHK("joint posterior (W, R)");
+    *np_out = np;
+    return 0;
+  }
+
+  static int predict_cov(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, int which, T* out, hipStream_t s) {
+    const int Mp = c->Mp, K = c->K;
+    int64_t np = 0;
+    c->jlast_n = c->jlast_sk = 0;              // W and R are about to be rewritten: no gdrf_sample_joint_retry on the old ones
+    if (which == COV_FULL)
+      if (int rc = joint_buf(c, &c->jT, &c->jtrows, n, (size_t)K * n * Mp * sizeof(TS))) return rc;
+    if (int rc = joint_forward(c, X, n, Z, params, &np, s)) return rc;
+    if (which == COV_RESID) {
+      hipLaunchKernelGGL((joint_copy_out_kernel<TS, T>), dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, s, (const TS*)Q(c->jR), n, np, out);
+    } else {
+      // T_k = W S_k (S_k^T in the array precision, as the step's tt reads it), then C_k = R + T_k T_k^T
+      JointNT<TS, T, T, TS> t{(const TS*)Q(c->jW), Mp, 0, n, (const T*)P(c->ST), Mp, (int64_t)Mp * Mp, Mp, Mp, Q(c->jT), Mp, n * Mp, nullptr, 0, nullptr, 0, 0,
+                              nullptr};
+      joint_nt<JT_PLAIN>(c, t, K, s);
+      JointNT<TS, TS, T, T> f{(const TS*)Q(c->jT), Mp, n * Mp, n, (const TS*)Q(c->jT), Mp, n * Mp, n, Mp, out, n, n * n, (const TS*)Q(c->jR), np, nullptr, 0, 0,
+                              nullptr};
+      joint_nt<JT_FULL>(c, f, K, s);
+    }
+    LAUNCHCHK("predict_cov");
+    return 0;
+  }
+
+  static int sample_joint(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, int S, uint64_t seed, const T* xi, const T* zeta,
+                          double jitter, T* out, hipStream_t s) {
+    const int Mp = c->Mp, M = c->M, K = c->K;
+    const int64_t nsk = (int64_t)S * K;
+    int64_t np = 0;
+    if ((size_t)M * sizeof(T) > 64 * 1024) return fail(-1, "gdrf_sample_joint", "M array-precision elements exceed the LDS budget (64 KB)");
+    if (int rc = joint_buf(c, &c->jV, &c->jsk, nsk, (size_t)nsk * Mp * sizeof(TS))) return rc;
+    if (int rc = joint_buf(c, &c->jZ, &c->jzel, nsk * round_up(n, 32), (size_t)nsk * round_up(n, 32) * sizeof(TS))) return rc;
+    if (int rc = joint_buf(c, &c->jG, &c->jgnp, round_up(n, 32), (size_t)round_up(n, 32) * round_up(n, 32) * sizeof(TS))) return rc;   // the sampler's alone
+    c->jlast_n = c->jlast_sk = 0;
+    if (int rc = joint_forward(c, X, n, Z, params, &np, s)) return rc;
+    const T* U = c->unwhitened ? (const T*)c->Uw : params + param_lay(c).uloc;      // the forward's transforms left L^-1 u in c->Uw
+    if (int rc = launch_lds((joint_v_kernel<TS, T>), dim3((unsigned)((Mp + 255) / 256), (unsigned)nsk), dim3(256), (size_t)M * sizeof(T), s, U, (const T*)P(c->ST), M,
+                            Mp, K, xi, seed, Q(c->jV))) return rc;
+    hipLaunchKernelGGL((joint_zeta_kernel<TS, T>), dim3((unsigned)((np + 255) / 256), (unsigned)nsk), dim3(256), 0, s, n, np, K, zeta, seed, Q(c->jZ));
+    LAUNCHCHK("sample_joint");
+    c->jlast_n = n; c->jlast_sk = nsk;
+    return joint_draw(c, n, S, jitter, out, s);
+  }
+  // the part of sample_joint that depends on the jitter: G G^T = R + jitter I by the one-workgroup Cholesky on a buffer of its own, its
+  // failure flag in c->jflag (gdrf_joint_failed), then the two sample products from the W, R, V and zeta the last sample_joint left
+  static int joint_draw(gdrf_ctx* c, int64_t n, int S, double jitter, T* out, hipStream_t s) {
+    const int Mp = c->Mp, K = c->K;
+    const int64_t nsk = (int64_t)S * K, np = round_up(n, 32);
+    HIPCHK(hipMemsetAsync(c->jflag, 0, sizeof(int), s));
+    hipLaunchKernelGGL(joint_chol_in_kernel<TS>, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, (const TS*)Q(c->jR), n, np, jitter, Q(c->jG));
+    if (int rc = launch_lds(chol_kernel<TS>, dim3(1), dim3(1024), chol_lds_bytes<TS>((int)n), s, Q(c->jG), (int)n, (int)np, c->jflag, (int64_t)0)) return rc;
+    const dim3 grid((unsigned)((n + GDRF_JT - 1) / GDRF_JT), (unsigned)((nsk + GDRF_JT - 1) / GDRF_JT));
+    hipLaunchKernelGGL((joint_sample_kernel<TS, T>), grid, dim3(256), 0, s, (const TS*)Q(c->jV), nsk, K, (const TS*)Q(c->jW), Mp, (const TS*)Q(c->jZ),
+                       (const TS*)Q(c->jG), n, np, (const T*)c->mean, c->mean_sk, c->mean_sn, out);
+    LAUNCHCHK("sample_joint (draw)");
+    return 0;
+  }
 };
 
 
@@ -2122,6 +2224,52 @@ int gdrf_predict_mc(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const 
   if (mode != MC_SCORE && !out) return fail(-1, "gdrf_predict_mc", "out is required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict_mc, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, mode, num_samples, seed, row_offset, (const T*)eps, (T*)out, out_d, s);
+}
+
+// the shape limits of the joint calls: the launches index rows and sample-topic pairs with a 16-bit grid dimension
+static int joint_check(const gdrf_ctx* c, const char* fn, int64_t n, int64_t nsk) {
+  if (n < 1) return fail(-1, fn, "n must be >= 1");
+  if (n > c->ncap) return fail(-1, fn, "needs n <= n_cap");
+  if (n > 65535 - 32 || nsk > 65535) return fail(-1, fn, "a joint call takes at most 65503 rows and 65535 (sample, topic) pairs");
+  return 0;
+}
+
+int gdrf_predict_cov(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, int which, void* out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (which != COV_FULL && which != COV_RESID) return fail(-1, "gdrf_predict_cov", "which");
+  if (int rc = joint_check(c, "gdrf_predict_cov", n, 1)) return rc;
+  if (!out) return fail(-1, "gdrf_predict_cov", "out is required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, predict_cov, c, (const T*)X, n, (const T*)Z, (const T*)params, which, (T*)out, s);
+}
+
+int gdrf_sample_joint(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, int num_samples, uint64_t seed, const void* xi,
+                      const void* zeta, double jitter_total, void* out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (num_samples < 1) return fail(-1, "gdrf_sample_joint", "num_samples must be >= 1");
+  if (int rc = joint_check(c, "gdrf_sample_joint", n, (int64_t)num_samples * c->K)) return rc;
+  if (!out) return fail(-1, "gdrf_sample_joint", "out is required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, sample_joint, c, (const T*)X, n, (const T*)Z, (const T*)params, num_samples, seed, (const T*)xi, (const T*)zeta, jitter_total, (T*)out, s);
+}
+
+int gdrf_sample_joint_retry(gdrf_ctx* c, int64_t n, int num_samples, double jitter_total, void* out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (n < 1 || num_samples < 1 || n != c->jlast_n || (int64_t)num_samples * c->K != c->jlast_sk)
+    return fail(-1, "gdrf_sample_joint_retry", "needs the gdrf_sample_joint call with this n and num_samples directly in front of it");
+  if (!out) return fail(-1, "gdrf_sample_joint_retry", "out is required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, joint_draw, c, n, num_samples, jitter_total, (T*)out, s);
+}
+
+int gdrf_joint_failed(gdrf_ctx* c, int* failed, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  hipStream_t s = (hipStream_t)stream;
+  *failed = 0;
+  if (!c->jflag) return 0;
+  HIPCHK(hipMemcpyAsync(failed, c->jflag, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
 }
 
 int gdrf_chol_failed(gdrf_ctx* c, int* failed, void* stream) {

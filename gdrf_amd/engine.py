@@ -48,8 +48,39 @@ def check_mc_args(num_samples, K: int, n: int, eps=None, ws=None) -> int:
     return S
 
 
+# The most rows a joint call (Engine.predict_cov, Engine.sample_joint and the model methods above them) takes: a joint draw cannot be cut
+# into row pieces, its n x n factorisation runs in one workgroup and its covariances take K n^2 elements (DESIGN.md section 19 has the
+# times and the memory measured at this size).
+JOINT_MAX_ROWS = 4096
+# the two Philox streams of gdrf_sample_joint (include/gdrf_hip.h): fill_eps(seed, s, n_offset=JOINT_XI_OFFSET, n=M) is xi[s]
+JOINT_XI_OFFSET, JOINT_ZETA_OFFSET = 1 << 61, 1 << 62
+
+
+def check_joint_args(num_samples, K: int, M: int, n: int, xi=None, zeta=None) -> int:
+    """The argument errors of the joint calls (Engine.predict_cov, Engine.sample_joint and the model methods above them), raised before
+    the device is touched: at most JOINT_MAX_ROWS rows, an integral ``num_samples`` >= 1, an injected ``xi`` of shape (num_samples, K, M)
+    and ``zeta`` of shape (num_samples, K, n).  Returns num_samples as an int."""
+    if n < 1:
+        raise ValueError(f"a joint call needs at least one row, got {n}")
+    if n > JOINT_MAX_ROWS:
+        raise ValueError(f"a joint call takes all its rows at once and at most JOINT_MAX_ROWS = {JOINT_MAX_ROWS} of them, got {n}")
+    if isinstance(num_samples, bool) or int(num_samples) != num_samples:
+        raise ValueError(f"num_samples must be an integer, got {num_samples!r}")
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+    if xi is not None and tuple(xi.shape) != (S, K, M):
+        raise ValueError(f"xi must have shape (num_samples, K, M) = ({S}, {K}, {M}), got {tuple(xi.shape)}")
+    if zeta is not None and tuple(zeta.shape) != (S, K, n):
+        raise ValueError(f"zeta must have shape (num_samples, K, n) = ({S}, {K}, {n}), got {tuple(zeta.shape)}")
+    return S
+
+
 class Engine:
     """One device context for fixed (n_cap, M, K, V, D, dtype, kernel)."""
+
+    last_joint_jitter: Optional[float] = None    # cumulative jitter on R of the most recent sample_joint, and its level of the schedule
+    last_joint_level: Optional[int] = None
 
     opt_extra: Optional[torch.Tensor] = None     # third optimizer state vector (RMSprop with momentum and centered), on demand
     period_count = 0                             # log-periods of a Periodic kernel's context (1 or D), 0 for the other kernels
@@ -867,5 +898,77 @@ class Engine:
 
         try:
             return self._speculated(run)
+        finally:
+            self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)
+
+    # ---- the joint posterior at new inputs (csrc/predict_cov.h) -----------------------------------------
+    def _chk_joint_rows(self, xs: torch.Tensor, what: str) -> int:
+        self._chk_rows(xs)
+        n = xs.shape[0]
+        if n > self.n_cap:
+            raise ValueError(f"{what} needs n <= n_cap ({n} > {self.n_cap})")
+        return n
+
+    def predict_cov(self, xs: torch.Tensor, which: int = 0) -> torch.Tensor:
+        """The joint posterior covariance at the rows ``xs`` (gdrf_predict_cov): which = 0 the K matrices C_k = R + (W S_k)(W S_k)^T as
+        (K, n, n), 1 the topic-independent R = K_** - W W^T as (n, n); each equal to its transpose to the bit.  All rows at once:
+        n <= min(n_cap, JOINT_MAX_ROWS).  Same jitter-level protocol for K_uu as predict()."""
+        if which not in (0, 1):
+            raise ValueError("predict_cov: which must be 0 (the K full covariances) or 1 (the residual R)")
+        check_joint_args(1, self.K, self.M, int(xs.shape[0]))
+        n = self._chk_joint_rows(xs, "predict_cov")
+        self.refresh_inducing()
+
+        def run():
+            out = torch.empty((self.K, n, n) if which == 0 else (n, n), dtype=self.dtype, device=self.device)
+            _lib.check(self.lib.gdrf_predict_cov(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), which, out.data_ptr(),
+                                                 _stream_ptr(self.device)), "gdrf_predict_cov")
+            return out
+
+        return self._speculated(run)
+
+    def sample_joint(self, xs: torch.Tensor, num_samples: int, seed: Optional[int] = None, xi: Optional[torch.Tensor] = None,
+                     zeta: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(S, K, n) joint samples of the latent field at the rows ``xs`` (gdrf_sample_joint):
+        f[s, k] = W (u_k + S_k xi[s, k]) + G zeta[s, k] + mean[k], G G^T = R + j I.  ``xi`` (S, K, M) / ``zeta`` (S, K, n): injected standard
+        normals; None = Philox draws keyed by ``seed`` (fill_eps(seed, s, JOINT_XI_OFFSET, M) is xi[s], fill_eps(seed, s, JOINT_ZETA_OFFSET, n)
+        is zeta[s]).  ``mean``: the mean_function's values on these rows, broadcastable to (K, n).  j is the cumulative jitter of the first
+        level of the engine's schedule (jitter, maxjitter; cumulative as for K_uu) at which R + j I factorises without a failed pivot - a flag
+        the kernel sets, read back after every attempt; ``last_joint_jitter`` / ``last_joint_level`` hold what was used.  RuntimeError when
+        every level fails.  K_uu's own level follows the protocol of predict().  All rows at once: n <= min(n_cap, JOINT_MAX_ROWS)."""
+        S = check_joint_args(num_samples, self.K, self.M, int(xs.shape[0]), xi, zeta)
+        n = self._chk_joint_rows(xs, "sample_joint")
+        for name, t in (("xi", xi), ("zeta", zeta)):
+            if t is not None and (t.dtype != self.dtype or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {self.dtype} tensor on {self.device}")
+        if (xi is None or zeta is None) and seed is None:
+            raise ValueError("sample_joint needs a seed unless both xi and zeta are injected")
+        seed = 0 if seed is None else int(seed) & (2 ** 64 - 1)
+        self.refresh_inducing()
+        self._set_mean(mean, n)
+        failed = C.c_int()
+
+        def run(jit):
+            out = torch.empty(S, self.K, n, dtype=self.dtype, device=self.device)
+            _lib.check(self.lib.gdrf_sample_joint(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), S, seed,
+                                                  xi.data_ptr() if xi is not None else None, zeta.data_ptr() if zeta is not None else None,
+                                                  jit, out.data_ptr(), _stream_ptr(self.device)), "gdrf_sample_joint")
+            return out
+
+        try:
+            for level in range(self.maxjitter):
+                jit = self.jitter_total(level)
+                if level == 0:
+                    out = self._speculated(lambda: run(jit))         # settles K_uu's level as well
+                else:
+                    # only R + j I, its factorisation and the two sample products depend on the level: W, R, u + S xi and zeta stay in place
+                    _lib.check(self.lib.gdrf_sample_joint_retry(self.ctx, n, S, jit, out.data_ptr(), _stream_ptr(self.device)),
+                               "gdrf_sample_joint_retry")
+                _lib.check(self.lib.gdrf_joint_failed(self.ctx, C.byref(failed), _stream_ptr(self.device)), "gdrf_joint_failed")
+                if not failed.value:
+                    self.last_joint_jitter, self.last_joint_level = jit, level
+                    return out
+            raise RuntimeError(f"sample_joint: R + j I has a non-positive pivot at every one of the {self.maxjitter} jitter levels, "
+                               "the residual covariance is unstable")
         finally:
             self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)

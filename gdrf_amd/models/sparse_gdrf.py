@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..data import check_counts, csr_to, is_sparse_counts
-from ..engine import Engine, check_mc_args
+from ..engine import Engine, check_joint_args, check_mc_args
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -236,6 +236,15 @@ class ModelSnapshot:
 
     def predictive_perplexity(self, x, w, num_samples=64, seed=None):
         return self.restore().predictive_perplexity(x, w, num_samples, seed=seed)
+
+    def posterior(self, Xnew):
+        return self.restore().posterior(Xnew)
+
+    def sample_fields(self, xs, num_samples, seed=None, xi=None, zeta=None):
+        return self.restore().sample_fields(xs, num_samples, seed=seed, xi=xi, zeta=zeta)
+
+    def sample_topic_maps(self, xs, num_samples, seed=None):
+        return self.restore().sample_topic_maps(xs, num_samples, seed=seed)
 
 
 class SparseMultinomialGDRF:
@@ -577,9 +586,10 @@ class SparseMultinomialGDRF:
         ``gp.util.conditional(Xnew, Z, kernel, u_loc, u_scale_tril, Luu, full_cov=False, whiten=...)`` with the mean_function
         added to loc.  (The reference's own body reads ``self.jitter`` / ``self.maxjitter``, attributes that do not exist - quirk
         Q10 -; this is what it evaluates once those are spelled ``_jitter`` / ``_maxjitter``.)  ``full_cov=True`` would be K dense
-        N x N matrices: outside this build's hot path."""
+        N x N matrices: ``posterior(Xnew)`` returns them."""
         if full_cov:
-            raise NotImplementedError("forward(full_cov=True): the K dense N x N posterior covariances are outside the sparse hot path")
+            raise NotImplementedError("forward(full_cov=True): the K dense N x N posterior covariances are not returned here; "
+                                      "posterior(Xnew) returns (loc, cov) with cov of shape (K, N, N)")
         xs_s, _ = self._prepare_inputs(Xnew)
         lv = self._engine_for(xs_s.shape[0]).predict(xs_s, 4)
         loc, var = lv[0], lv[1]
@@ -676,6 +686,46 @@ class SparseMultinomialGDRF:
         xs_s, ws_d = self._prepare_inputs(x, w)
         s = self._predict_mc(xs_s, 2, S, ws_d=ws_d, seed=seed)
         return torch.exp(-s[0] / s[1])
+
+    # ------------------------------------------------------------------ joint posterior at new inputs (csrc/predict_cov.h)
+    def posterior(self, Xnew) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(loc (K, N), cov (K, N, N)) of the GP posterior q(f(Xnew)): what ``gp.util.conditional(..., full_cov=True)`` gives inside
+        ``SparseGDRF.forward(Xnew, full_cov=True)`` (gdrf/models/sparse_gdrf.py:277-319), with the mean_function added to loc.  loc is
+        ``forward(Xnew)[0]``; the diagonal of cov[k] is ``forward(Xnew)[1][k]`` except that K_** - W W^T is not clamped at 0 here.  Every
+        cov[k] equals its transpose to the bit.  All rows at once, at most JOINT_MAX_ROWS of them."""
+        check_joint_args(1, self._K, self.M, int(torch.as_tensor(Xnew).shape[0]))
+        xs_s, _ = self._prepare_inputs(Xnew)
+        eng = self._engine_for(xs_s.shape[0])
+        loc = eng.predict(xs_s, 4)[0]
+        mean = self._mean_values(xs_s)
+        if mean is not None:
+            loc = loc + mean.to(loc)
+        return loc, eng.predict_cov(xs_s, 0)
+
+    def sample_fields(self, xs, num_samples, seed=None, xi=None, zeta=None) -> torch.Tensor:
+        """(S, K, N) joint samples of the latent field f under the GP posterior at the rows ``xs``, mean_function included: every
+        sample is one spatially coherent draw over all the rows, f[s, k] ~ N(loc_k, cov_k + j I) with (loc, cov) = posterior(xs) and j the
+        jitter the engine had to add to factorise the residual covariance (``_engine.last_joint_jitter``).  ``xi`` (S, K, M) and ``zeta``
+        (S, K, N): injected standard normals; otherwise counter-based Philox draws keyed by ``seed`` (default: the model's rng_seed).
+        The rows of sample_topic_probs' samples are independent of each other; these are not.  At most JOINT_MAX_ROWS rows."""
+        n = int(torch.as_tensor(xs).shape[0])
+        S = check_joint_args(num_samples, self._K, self.M, n, xi, zeta)
+        xs_s, _ = self._prepare_inputs(xs)
+        eng = self._engine_for(n)
+        seed = self.rng_seed if seed is None else int(seed)
+        inj = [None if t is None else torch.as_tensor(t).to(device=self.device, dtype=self.dtype).contiguous() for t in (xi, zeta)]
+        return eng.sample_joint(xs_s, S, seed=seed, xi=inj[0], zeta=inj[1], mean=self._mean_values(xs_s))
+
+    def sample_topic_maps(self, xs, num_samples, seed=None) -> torch.Tensor:
+        """(S, N, K) spatially coherent samples of the topic proportions: the link - softmax over the topics, or the custom
+        ``link_function`` applied with torch as sample_topic_probs applies it - of the joint field samples ``sample_fields(xs, ...)``.
+        The guide's extra noise layer mu ~ Normal(f_loc, f_var), which sample_topic_probs draws per row, is NOT added: a map is the
+        link of the latent field itself."""
+        check_joint_args(num_samples, self._K, self.M, int(torch.as_tensor(xs).shape[0]))
+        f = self.sample_fields(xs, num_samples, seed=seed)
+        if self._link_function is not None:
+            return torch.stack([self._link_function(f[s]).T for s in range(f.shape[0])])
+        return torch.softmax(f, dim=1).transpose(1, 2).contiguous()
 
     @property
     def word_topic_matrix(self) -> torch.Tensor:

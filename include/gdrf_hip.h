@@ -342,6 +342,47 @@ enum { GDRF_MC_THETA = 0, GDRF_MC_MOMENTS = 1, GDRF_MC_SCORE = 2, GDRF_MC_MU = 3
 int gdrf_predict_mc(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const int32_t* ws_dev, int mode,
                     int num_samples, uint64_t seed, int64_t row_offset, const void* eps_dev, void* out_dev, double* out_d_dev, void* stream);
 
+/* The joint posterior q(f_k(X*)) = N(loc_k, C_k) at n new inputs (csrc/predict_cov.h; gp.util.conditional(..., full_cov=True) as
+ * SparseGDRF.forward(Xnew, full_cov=True) calls it, gdrf/models/sparse_gdrf.py:277-319).  With W = K_*m L^-T (n x M, the step's forward):
+ *   R   = K_** - W W^T                       (n x n, the same for every topic; nothing added to its diagonal, no clamp)
+ *   C_k = R + (W S_k)(W S_k)^T               (whiten = 0: S_k, u_k stand for L^-1 S_k, L^-1 u_k, as in mode 4 of gdrf_predict)
+ * K_** is the context's kernel between the rows (Periodic and Product contexts: on the embedded coordinates).  Apart from mode 4's
+ * clamp(variance - |w|^2, 0), the diagonal of C_k is mode 4's f_var; loc_k is mode 4's f_loc (this call does not return it).
+ *   GDRF_COV_FULL   out (K, n, n)
+ *   GDRF_COV_RESID  out (n, n) = R
+ * in the context's element type, equal to their transposes to the bit (the tiles on and below the diagonal are computed and mirrored).
+ * Everything n x n is formed in the solve precision (W is recomputed in it from the step's solve-precision K_nm and L^-1: K_** - W W^T
+ * cancels almost completely near the inducing points) on the solve-precision matrix instruction, and rounded on output.  X: the inputs
+ * scaled ONCE; n <= n_cap; needs gdrf_factorize().  Runs the step's forward (as mode 4), so it overwrites the same workspaces, which every
+ * step recomputes; its own buffers (n x M, n x n and, for GDRF_COV_FULL, K x n x M solve-precision elements) are allocated on first use
+ * and grow with n.  No atomics: bit-identical from call to call. */
+enum { GDRF_COV_FULL = 0, GDRF_COV_RESID = 1 };
+int gdrf_predict_cov(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, int which, void* out_dev, void* stream);
+/* Joint (spatially coherent) samples of the latent field at n new inputs, in the pathwise form, which needs one n x n factorisation
+ * instead of K:
+ *   f[s][k][:] = W (u_k + S_k xi[s][k][:]) + G zeta[s][k][:] + mean[k][:],    G G^T = R + jitter_total I,
+ * out (S, K, n), S = num_samples; xi (S, K, M) and zeta (S, K, n) standard normal; mean = the values set with gdrf_set_mean (NULL: zero).
+ * The covariance of f[.][k][:] is C_k + jitter_total I (gdrf_predict_cov).  R + jitter_total I is factorised in the solve precision by the
+ * one-workgroup Cholesky of the jitter probe, on a buffer of this call's own; a non-positive pivot sets a flag (and is replaced by 1, so
+ * the output stays finite but is not a sample): read it with gdrf_joint_failed and call again with the next cumulative jitter of the
+ * schedule, as for gdrf_factorize / gdrf_chol_failed.
+ * xi_dev, zeta_dev: arrays of the context's element type, or NULL for Philox4x32-10 draws keyed by `seed`, rounded to the element type,
+ * with the counter words (index, topic, sample) of gdrf_fill_eps on two streams of their own:
+ *   xi[s][k][m]   = the number gdrf_fill_eps(seed, step = s, n_offset = 2^61) writes at [k][m],
+ *   zeta[s][k][i] = the number gdrf_fill_eps(seed, step = s, n_offset = 2^62) writes at [k][i],  i = the row's position within THIS call.
+ * No xi draw is a zeta draw, and neither is a draw of gdrf_predict_mc or of a training step's eps for rows below 2^61.  A joint draw
+ * cannot be cut into row pieces: there is no row_offset, and n <= n_cap (at most 65503 rows and 65535 (sample, topic) pairs).
+ * Needs gdrf_factorize(); workspaces as for gdrf_predict_cov.  No atomics: bit-identical from call to call. */
+int gdrf_sample_joint(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, int num_samples, uint64_t seed,
+                      const void* xi_dev, const void* zeta_dev, double jitter_total, void* out_dev, void* stream);
+/* The same samples on another jitter: only R + jitter_total I, its factorisation and the two sample products are redone, from the W, R,
+ * u_k + S_k xi and zeta that the gdrf_sample_joint call directly in front of it left in the context (same n and num_samples, same stream;
+ * the same mean still set).  Anything else is an error: gdrf_predict_cov or another gdrf_sample_joint in between rewrites those buffers.
+ * The output is bit for bit what gdrf_sample_joint with this jitter_total would have written. */
+int gdrf_sample_joint_retry(gdrf_ctx* ctx, int64_t n, int num_samples, double jitter_total, void* out_dev, void* stream);
+/* Did the factorisation of the last gdrf_sample_joint() / gdrf_sample_joint_retry() hit a non-positive pivot?  Synchronises the stream. */
+int gdrf_joint_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
+
 /* Did the last gdrf_factorize() hit a non-positive pivot?  Synchronises the stream. */
 int gdrf_chol_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
 
