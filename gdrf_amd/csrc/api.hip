@@ -10,6 +10,7 @@
 #include "kernels_n.h"
 #include "predict.h"
 #include "predict_mc.h"
+#include "foldin.h"
 #include "predict_cov.h"
 #include "rows_lds.h"
 #include "rows_mfma.h"
@@ -1863,6 +1864,35 @@ template <typename T, typename TS> struct Impl {
     return 0;
   }
 
+  // Fold-in (foldin.h): the step's forward as in mode 4 of predict, then one kernel that runs the per-row MAP from the rows' own counts -
+  // dense (Phi, the counts and c in LDS) or CSR (the stored entries only, Phi from global memory); mode 3 ends in the partials' sum
+  static int fold_in(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, const int64_t* crow, const int32_t* col,
+                     const int32_t* val, const int32_t* ws2, const int64_t* crow2, const int32_t* col2, const int32_t* val2, int mode,
+                     int num_iters, double tol, T* out, double* diag, double* out_d, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    const int LG = K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64, KJ = K <= 64 ? 1 : 2;
+    const bool csr = crow != nullptr;
+    const size_t lds = csr ? fi_csr_lds<T>(LG, KJ) : fi_dense_lds<T>(K, V, LG, KJ);
+    if (!csr && 128 + lds > 150 * 1024) return rows_lds_fail("gdrf_fold_in");      // the LDS budget of the default row forms
+    if (int rc = step_local(c, X, nullptr, nullptr, n, Z, params, nullptr, nullptr, s, SL_TRANSFORMS | SL_FORWARD | SL_NO_DK)) return rc;
+    const int64_t nblk = (n + 256 / LG - 1) / (256 / LG);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
+    auto go = [&](auto kern) {
+      return launch_lds(kern, dim3(grid), dim3(256), lds, s, mode, n, K, V, num_iters, tol, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c),
+                        (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk, c->mean_sn, (const T*)P(c->phi), ws, crow, col,
+                        val, ws2, crow2, col2, val2, out, diag, c->dpart);
+    };
+    int rc;
+    if (csr) rc = LG == 8 ? go(foldin_kernel<T, 8, 1, true>) : LG == 16 ? go(foldin_kernel<T, 16, 1, true>) : LG == 32 ? go(foldin_kernel<T, 32, 1, true>)
+                : KJ == 1 ? go(foldin_kernel<T, 64, 1, true>) : go(foldin_kernel<T, 64, 2, true>);
+    else rc = LG == 8 ? go(foldin_kernel<T, 8, 1, false>) : LG == 16 ? go(foldin_kernel<T, 16, 1, false>) : LG == 32 ? go(foldin_kernel<T, 32, 1, false>)
+            : KJ == 1 ? go(foldin_kernel<T, 64, 1, false>) : go(foldin_kernel<T, 64, 2, false>);
+    if (rc) return rc;
+    if (mode == FI_SCORE) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)grid, 2, out_d);
+    LAUNCHCHK("fold_in");
+    return 0;
+  }
+
   // ---- the joint posterior at new inputs (predict_cov.h)
   // a joint buffer of at least `bytes`: a larger request replaces it.  Only the joint calls read these blocks, so the replaced one is
   // freed here, once the device has finished whatever was queued on it (a growth is rare: the wait costs one call, not every call)
@@ -2224,6 +2254,29 @@ int gdrf_predict_mc(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const 
   if (mode != MC_SCORE && !out) return fail(-1, "gdrf_predict_mc", "out is required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict_mc, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, mode, num_samples, seed, row_offset, (const T*)eps, (T*)out, out_d, s);
+}
+
+int gdrf_fold_in(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, const int32_t* ws, const int64_t* crow, const int32_t* col,
+                 const int32_t* val, const int32_t* ws2, const int64_t* crow2, const int32_t* col2, const int32_t* val2, int mode, int num_iters,
+                 double tol, void* out, double* diag, double* out_d, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (mode < 0 || mode > 3) return fail(-1, "gdrf_fold_in", "mode");
+  if (n < 1) return fail(-1, "gdrf_fold_in", "n must be >= 1");
+  if (n > c->ncap) return fail(-1, "gdrf_fold_in", "needs n <= n_cap");
+  if (num_iters < 0) return fail(-1, "gdrf_fold_in", "num_iters must be >= 0");
+  if (!(tol >= 0) || !std::isfinite(tol)) return fail(-1, "gdrf_fold_in", "tol must be finite and >= 0");
+  if ((ws != nullptr) == (crow != nullptr)) return fail(-1, "gdrf_fold_in", "needs the counts either dense (ws_dev) or CSR (crow_dev)");
+  if (crow && (!col || !val)) return fail(-1, "gdrf_fold_in", "CSR counts need col_dev and val_dev");
+  if (mode == FI_SCORE) {
+    if (!out_d) return fail(-1, "gdrf_fold_in", "the score needs out_d");
+    if (!ws2 && !crow2) { ws2 = ws; crow2 = crow; col2 = col; val2 = val; }
+    if ((ws2 != nullptr) != (ws != nullptr) || (crow2 != nullptr) != (crow != nullptr) || (crow2 && (!col2 || !val2)))
+      return fail(-1, "gdrf_fold_in", "the scored counts must have the layout of the fitted ones");
+  } else if (!out) return fail(-1, "gdrf_fold_in", "out is required");
+  if (!diag) return fail(-1, "gdrf_fold_in", "diag is required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, fold_in, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, crow, col, val, ws2, crow2, col2, val2, mode, num_iters, tol, (T*)out, diag,
+         out_d, s);
 }
 
 // the shape limits of the joint calls: the launches index rows and sample-topic pairs with a 16-bit grid dimension

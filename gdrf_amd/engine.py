@@ -48,6 +48,29 @@ def check_mc_args(num_samples, K: int, n: int, eps=None, ws=None) -> int:
     return S
 
 
+def check_fold_args(num_iters, tol, n: int, V: int, ws, ws_score=None):
+    """The argument errors of the fold-in calls (Engine.fold_in and the model methods above it), raised before the device is touched: an
+    integral ``num_iters`` >= 0, a finite ``tol`` >= 0, counts ``ws`` of shape (n, V) with n >= 1, dense or CSR, and a ``ws_score`` of the
+    same shape and sparsity.  Returns (num_iters, tol) as an int and a float."""
+    if isinstance(num_iters, bool) or int(num_iters) != num_iters:
+        raise ValueError(f"num_iters must be an integer, got {num_iters!r}")
+    if int(num_iters) < 0:
+        raise ValueError(f"num_iters must be >= 0, got {num_iters}")
+    tol = float(tol)
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError(f"tol must be finite and >= 0, got {tol}")
+    if n < 1:
+        raise ValueError(f"fold-in needs at least one row, got {n}")
+    for name, w in (("ws", ws), ("ws_score", ws_score)):
+        if w is None and name == "ws_score":
+            continue
+        if w is None or not hasattr(w, "shape") or tuple(w.shape) != (n, V):
+            raise ValueError(f"{name} must be counts of shape (n, V) = ({n}, {V}), got {None if w is None else tuple(getattr(w, 'shape', ()))}")
+    if ws_score is not None and is_sparse_counts(ws_score) != is_sparse_counts(ws):
+        raise ValueError("ws_score must be sparse (CSR) exactly when ws is: the scored counts take the layout of the fitted ones")
+    return int(num_iters), tol
+
+
 # The most rows a joint call (Engine.predict_cov, Engine.sample_joint and the model methods above them) takes: a joint draw cannot be cut
 # into row pieces, its n x n factorisation runs in one workgroup and its covariances take K n^2 elements (DESIGN.md section 19 has the
 # times and the memory measured at this size).
@@ -895,6 +918,56 @@ class Engine:
                                                 eps.data_ptr() if eps is not None else None, out.data_ptr() if out is not None else None,
                                                 self.out_d.data_ptr(), _stream_ptr(self.device)), "gdrf_predict_mc")
             return self.out_d[:2].clone() if mode == 2 else out
+
+        try:
+            return self._speculated(run)
+        finally:
+            self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)
+
+    # ---- fold-in: topic proportions of observed rows from their own counts (csrc/foldin.h) ---------------
+    def _csr_arrays(self, ws: torch.Tensor):
+        """(crow int64, col int32, val int32) of a CSR count matrix, contiguous, as gdrf_fold_in reads them"""
+        return (ws.crow_indices().to(torch.int64).contiguous(), ws.col_indices().to(torch.int32).contiguous(), ws.values().contiguous())
+
+    def fold_in(self, xs: torch.Tensor, ws: torch.Tensor, mode: int, num_iters: int = 64, tol: float = 1e-6,
+                ws_score: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None):
+        """The per-row MAP of mu given the rows' own counts ``ws`` with the GP as the prior (gdrf_fold_in, csrc/foldin.h has the
+        definition): mode 0 theta_hat (n, K), 1 mu_hat (K, n), 2 the expected topic counts at theta_hat (n, K), 3 {sum w2 log p_hat, sum w2}
+        for the counts ``ws_score`` (default: ``ws``).  ``ws`` / ``ws_score``: dense (n, V) int32 or ``torch.sparse_csr``, both in the same
+        layout.  At most ``num_iters`` iterations per row; a row stops once |g|_inf / max(1, R) <= ``tol``.  ``mean``: the mean_function's
+        values on these rows, broadcastable to (K, n).  Returns (result, diag) with diag (3, n) float64: J at the result, |g|_inf /
+        max(1, R), the iterations used.  n <= n_cap.  Same jitter-level protocol as predict()."""
+        if mode not in (0, 1, 2, 3):
+            raise ValueError("fold_in: mode must be 0 (theta), 1 (mu), 2 (expected topic counts) or 3 (completion score)")
+        num_iters, tol = check_fold_args(num_iters, tol, int(xs.shape[0]), self.V, ws, ws_score)
+        if ws_score is not None and mode != 3:
+            raise ValueError("fold_in: ws_score is read by mode 3 only")
+        self._chk_rows(xs, ws)
+        if ws_score is not None:
+            self._chk_rows(xs, ws_score)
+        n = xs.shape[0]
+        if n > self.n_cap:
+            raise ValueError(f"fold_in needs n <= n_cap ({n} > {self.n_cap})")
+        sparse = is_sparse_counts(ws)
+        fit = self._csr_arrays(ws) if sparse else None
+        score = None if ws_score is None else (self._csr_arrays(ws_score) if sparse else ws_score)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self.refresh_inducing()
+        self._set_mean(mean, n)
+
+        def run():
+            out = None
+            if mode != 3:
+                out = torch.empty((self.K, n) if mode == 1 else (n, self.K), dtype=self.dtype, device=self.device)
+            diag = torch.empty(3, n, dtype=torch.float64, device=self.device)
+            a = (None,) + tuple(ptr(t) for t in fit) if sparse else (ws.data_ptr(), None, None, None)
+            if score is None:
+                b = (None, None, None, None)
+            else:
+                b = (None,) + tuple(ptr(t) for t in score) if sparse else (score.data_ptr(), None, None, None)
+            _lib.check(self.lib.gdrf_fold_in(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), *a, *b, mode, num_iters,
+                                             tol, ptr(out), diag.data_ptr(), self.out_d.data_ptr(), _stream_ptr(self.device)), "gdrf_fold_in")
+            return (self.out_d[:2].clone() if mode == 3 else out), diag
 
         try:
             return self._speculated(run)

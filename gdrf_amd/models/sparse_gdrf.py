@@ -14,8 +14,8 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from ..data import check_counts, csr_to, is_sparse_counts
-from ..engine import Engine, check_joint_args, check_mc_args
+from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
+from ..engine import Engine, check_fold_args, check_joint_args, check_mc_args
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -236,6 +236,18 @@ class ModelSnapshot:
 
     def predictive_perplexity(self, x, w, num_samples=64, seed=None):
         return self.restore().predictive_perplexity(x, w, num_samples, seed=seed)
+
+    def infer_topic_probs(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
+        return self.restore().infer_topic_probs(xs, ws, num_iters, tol, return_diagnostics)
+
+    def infer_log_topic_probs(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
+        return self.restore().infer_log_topic_probs(xs, ws, num_iters, tol, return_diagnostics)
+
+    def topic_counts(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
+        return self.restore().topic_counts(xs, ws, num_iters, tol, return_diagnostics)
+
+    def completion_perplexity(self, x, w_fit, w_score, num_iters=64, tol=1e-6, return_diagnostics=False):
+        return self.restore().completion_perplexity(x, w_fit, w_score, num_iters, tol, return_diagnostics)
 
     def posterior(self, Xnew):
         return self.restore().posterior(Xnew)
@@ -686,6 +698,67 @@ class SparseMultinomialGDRF:
         xs_s, ws_d = self._prepare_inputs(x, w)
         s = self._predict_mc(xs_s, 2, S, ws_d=ws_d, seed=seed)
         return torch.exp(-s[0] / s[1])
+
+    # ------------------------------------------------------------------ fold-in: observed samples from their own counts (csrc/foldin.h)
+    def _fold_in(self, xs, ws, mode: int, num_iters, tol, ws_score=None, return_diagnostics: bool = False):
+        """Engine.fold_in on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows (a row's result depends on
+        no other row, so the pieces change nothing but mode 3's order of summation).  The pieces are joined along the row axis, mode 3's two
+        sums are added; with ``return_diagnostics`` the (3, N) float64 diagnostics - J, |g|_inf / max(1, R), iterations used - follow."""
+        if self._link_function is not None:
+            raise NotImplementedError("fold-in with a custom link_function: the kernel fuses the softmax link")
+        n = int(torch.as_tensor(xs).shape[0])
+        num_iters, tol = check_fold_args(num_iters, tol, n, self._V, ws, ws_score)
+        xs_s, ws_d = self._prepare_inputs(xs, ws)
+        sc_d = None if ws_score is None else self._prepare_inputs(xs, ws_score)[1]
+        eng = self._engine_for(min(n, MC_PIECE_ROWS))
+        mean = self._mean_values(xs_s)
+        if mean is not None:
+            mean = mean.to(device=self.device, dtype=self.dtype)
+            try:
+                mean = mean.expand(self._K, n)
+            except RuntimeError:
+                raise ValueError(f"mean_function returned shape {tuple(mean.shape)}, not broadcastable to ({self._K}, {n})") from None
+        rows = lambda w, a, b: None if w is None else (csr_rows(w, slice(a, b)) if is_sparse_counts(w) else w[a:b])
+        parts, diags = [], []
+        for a in range(0, n, eng.n_cap):
+            b = min(n, a + eng.n_cap)
+            one = (a, b) == (0, n)
+            out, diag = eng.fold_in(xs_s[a:b], ws_d if one else rows(ws_d, a, b), mode, num_iters, tol,
+                                    ws_score=sc_d if one else rows(sc_d, a, b), mean=None if mean is None else mean[:, a:b])
+            parts.append(out)
+            diags.append(diag)
+        if mode == 3:
+            res = torch.stack(parts).sum(0)
+        else:
+            res = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1 if mode == 1 else 0)
+        if return_diagnostics:
+            return res, (diags[0] if len(diags) == 1 else torch.cat(diags, dim=1))
+        return res
+
+    def infer_topic_probs(self, xs, ws, num_iters: int = 64, tol: float = 1e-6, return_diagnostics: bool = False):
+        """(N, K) topic proportions of the OBSERVED samples (xs, ws): theta_hat = softmax(mu_hat), mu_hat the per-row maximiser of
+        sum_v w_v log (softmax(mu) Phi)_v - 1/2 sum_k ((mu_k - m_k) / s_k)^2 reached from mu = m, where m = forward(xs)[0] and
+        s = forward(xs)[1] + noise are the location and scale of the model's mu site (LDA's transform with the GP as the prior).
+        ``ws``: dense int32 counts or a ``torch.sparse_csr`` matrix.  topic_probs(xs) is softmax(m): it cannot use the counts."""
+        return self._fold_in(xs, ws, 0, num_iters, tol, return_diagnostics=return_diagnostics)
+
+    def infer_log_topic_probs(self, xs, ws, num_iters: int = 64, tol: float = 1e-6, return_diagnostics: bool = False):
+        """(K, N): mu_hat of infer_topic_probs, laid out as log_topic_probs lays out f_loc."""
+        return self._fold_in(xs, ws, 1, num_iters, tol, return_diagnostics=return_diagnostics)
+
+    def topic_counts(self, xs, ws, num_iters: int = 64, tol: float = 1e-6, return_diagnostics: bool = False):
+        """(N, K) expected topic counts r_k = theta_k sum_v w_v Phi_kv / p_v at infer_topic_probs' theta_hat: a row sums to its total."""
+        return self._fold_in(xs, ws, 2, num_iters, tol, return_diagnostics=return_diagnostics)
+
+    def completion_perplexity(self, x, w_fit, w_score, num_iters: int = 64, tol: float = 1e-6, return_diagnostics: bool = False):
+        """The document-completion score exp(-sum w_score log p_hat / sum w_score) as a 0-d tensor: p_hat = theta_hat Phi with theta_hat
+        folded in from ``w_fit`` alone; ``w_score`` has the shape and layout (dense or CSR) of ``w_fit``."""
+        if w_score is None:
+            raise ValueError("completion_perplexity needs w_score, counts of the shape and layout of w_fit")
+        res = self._fold_in(x, w_fit, 3, num_iters, tol, ws_score=w_score, return_diagnostics=return_diagnostics)
+        s, diag = res if return_diagnostics else (res, None)
+        ppl = torch.exp(-s[0] / s[1])
+        return (ppl, diag) if return_diagnostics else ppl
 
     # ------------------------------------------------------------------ joint posterior at new inputs (csrc/predict_cov.h)
     def posterior(self, Xnew) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -342,6 +342,31 @@ enum { GDRF_MC_THETA = 0, GDRF_MC_MOMENTS = 1, GDRF_MC_SCORE = 2, GDRF_MC_MU = 3
 int gdrf_predict_mc(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const int32_t* ws_dev, int mode,
                     int num_samples, uint64_t seed, int64_t row_offset, const void* eps_dev, void* out_dev, double* out_d_dev, void* stream);
 
+/* Fold-in (csrc/foldin.h): the topic proportions of OBSERVED rows from their own counts, with the GP as the prior.  For row n, with
+ *   m_k = f_loc[k][n] + mean[k][n],  s_k = f_var[k][n] + noise   ((f_loc, f_var) as mode 4 of gdrf_predict gives them; s_k is the scale of the
+ *   model's mu site, Normal(f_loc, f_var + noise), gdrf/models/sparse_gdrf.py:354-357),  R = sum_v w_v,  theta = softmax(mu),  p = theta Phi:
+ *   J(mu) = sum_{v: w_v > 0} w_v log p_v - 1/2 sum_k ((mu_k - m_k) / s_k)^2
+ * the result mu_hat is a local maximiser of J reached from mu = m by at most num_iters monotone EM / Newton iterations (J never decreases;
+ * csrc/foldin.h has the iteration); a row stops early once |g|_inf / max(1, R) <= tol, g the gradient of J.  theta_hat = softmax(mu_hat).
+ * The counts are either dense - ws_dev (n, V) int32, crow_dev NULL; Phi, the counts and theta of a workgroup's rows live in LDS, so K x V is
+ * bounded as for the LDS row forms ("too large" otherwise) - or CSR - ws_dev NULL, crow_dev (n + 1) int64 row pointers from 0, col_dev /
+ * val_dev int32; only the stored entries are visited, a stored zero is an absent entry, no limit on V.  A CSR matrix bound with
+ * gdrf_bind_counts_csr plays no part.
+ *   GDRF_FI_THETA   out (n, K): theta_hat
+ *   GDRF_FI_MU      out (K, n): mu_hat
+ *   GDRF_FI_COUNTS  out (n, K): the expected topic counts r_k = theta_k sum_v w_v Phi_kv / p_v at theta_hat (a row sums to R)
+ *   GDRF_FI_SCORE   out_d_dev[0..1] = {sum_n sum_v w2 log p_hat, sum w2} for a second count matrix (ws2_dev or crow2_dev / col2_dev /
+ *                   val2_dev) in the layout of the first; all four NULL: the fitted counts themselves.  Deterministic sums, no atomics.
+ * Every mode also writes diag_dev (3, n) doubles: J at the result, |g|_inf / max(1, R) there, the iterations used.
+ * n <= n_cap, num_iters >= 0, tol finite and >= 0.  Runs the step's forward (as mode 4 of gdrf_predict), so it overwrites the same
+ * workspaces; every step recomputes them.  Everything but the two sums of GDRF_FI_SCORE is bit-identical however the rows are batched.
+ * Needs gdrf_factorize(). */
+enum { GDRF_FI_THETA = 0, GDRF_FI_MU = 1, GDRF_FI_COUNTS = 2, GDRF_FI_SCORE = 3 };
+int gdrf_fold_in(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const int32_t* ws_dev,
+                 const int64_t* crow_dev, const int32_t* col_dev, const int32_t* val_dev, const int32_t* ws2_dev, const int64_t* crow2_dev,
+                 const int32_t* col2_dev, const int32_t* val2_dev, int mode, int num_iters, double tol, void* out_dev, double* diag_dev,
+                 double* out_d_dev, void* stream);
+
 /* The joint posterior q(f_k(X*)) = N(loc_k, C_k) at n new inputs (csrc/predict_cov.h; gp.util.conditional(..., full_cov=True) as
  * SparseGDRF.forward(Xnew, full_cov=True) calls it, gdrf/models/sparse_gdrf.py:277-319).  With W = K_*m L^-T (n x M, the step's forward):
  *   R   = K_** - W W^T                       (n x n, the same for every topic; nothing added to its diagonal, no clamp)
