@@ -11,6 +11,7 @@
 #include "predict.h"
 #include "predict_mc.h"
 #include "foldin.h"
+#include "sample_counts.h"
 #include "predict_cov.h"
 #include "rows_lds.h"
 #include "rows_mfma.h"
@@ -1893,6 +1894,36 @@ template <typename T, typename TS> struct Impl {
     return 0;
   }
 
+  // Posterior-predictive count samples (sample_counts.h): Phi from the parameters, then one kernel in which a wave or a workgroup owns a
+  // (row, sample) pair; SC_STATS ends in the per-sample sums of the per-workgroup partials.  No GP quantity is read: no factorisation is needed.
+  static int sample_counts(gdrf_ctx* c, const T* theta, int64_t n, const T* params, const int32_t* totals, int tmax, const int32_t* ws, int mode,
+                           int S, uint64_t seed, int64_t row_offset, const double* u, int32_t* out, double* dev, int64_t* zeros, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    // up to GDRF_SC_WAVE_V words four waves share a workgroup, each with a pair of its own, and Phi joins them in LDS while four such
+    // workgroups still fit a CU (40 KB each); above it the workgroup owns one pair and Phi is read from global memory (L2)
+    const bool blk = V > GDRF_SC_WAVE_V;
+    const int units = blk ? 1 : 4;
+    const bool phi_lds = !blk && sc_lds<T>(K, V, mode, units, true) <= 40 * 1024;
+    const size_t lds = sc_lds<T>(K, V, mode, units, phi_lds);
+    if (128 + lds > 150 * 1024) return rows_lds_fail("gdrf_sample_counts");      // the LDS budget of the default row forms
+    int64_t grid = std::min<int64_t>((n + units - 1) / units, 1024);
+    if (mode == SC_STATS) {
+      if (2 * (int64_t)S > c->dpart_len) return fail(-1, "gdrf_sample_counts", "num_samples exceeds the context's partial-sum scratch");
+      grid = std::min<int64_t>(grid, c->dpart_len / (2 * (int64_t)S));
+      HIPCHK(hipMemsetAsync(zeros, 0, (size_t)S * V * sizeof(int64_t), s));
+    }
+    hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + param_lay(c).phi, K, V, P(c->phi));
+    auto go = [&](auto kern) {
+      return launch_lds(kern, dim3((unsigned)grid, (unsigned)S), dim3(256), lds, s, mode, n, K, V, theta, (const T*)P(c->phi), totals, tmax, ws, seed,
+                        row_offset, u, out, c->dpart, (unsigned long long*)zeros);
+    };
+    if (int rc = blk ? go(sample_counts_kernel<T, SC_BLOCK>) : phi_lds ? go(sample_counts_kernel<T, SC_WAVE_PHI>) : go(sample_counts_kernel<T, SC_WAVE>))
+      return rc;
+    if (mode == SC_STATS) hipLaunchKernelGGL(sc_reduce_kernel, dim3(S), dim3(256), 0, s, c->dpart, (int)grid, S, dev);
+    LAUNCHCHK("sample_counts");
+    return 0;
+  }
+
   // ---- the joint posterior at new inputs (predict_cov.h)
   // a joint buffer of at least `bytes`: a larger request replaces it.  Only the joint calls read these blocks, so the replaced one is
   // freed here, once the device has finished whatever was queued on it (a growth is rare: the wait costs one call, not every call)
@@ -2277,6 +2308,35 @@ int gdrf_fold_in(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const voi
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, fold_in, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, crow, col, val, ws2, crow2, col2, val2, mode, num_iters, tol, (T*)out, diag,
          out_d, s);
+}
+
+int gdrf_sample_counts(gdrf_ctx* c, const void* theta, int64_t n, const void* params, const int32_t* totals, int tmax, const int32_t* ws, int mode,
+                       int num_samples, uint64_t seed, int64_t row_offset, double* u, int32_t* out, double* dev, int64_t* zeros, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (mode < 0 || mode > 2) return fail(-1, "gdrf_sample_counts", "mode");
+  if (n < 1) return fail(-1, "gdrf_sample_counts", "n must be >= 1");
+  if (num_samples < 1) return fail(-1, "gdrf_sample_counts", "num_samples must be >= 1");
+  if (num_samples > 65535) return fail(-1, "gdrf_sample_counts", "a call takes at most 65535 samples");
+  if (row_offset < 0) return fail(-1, "gdrf_sample_counts", "row_offset must be >= 0");
+  if (tmax < 0) return fail(-1, "gdrf_sample_counts", "totals must be non-negative (tmax < 0)");
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == SC_UNIFORMS) {
+    if (!u) return fail(-1, "gdrf_sample_counts", "the uniforms need u_dev to be written to");
+    const int64_t nthr = n * ((tmax + 3) / 4);
+    if (nthr > (int64_t)256 * 0x7fffffff) return fail(-1, "gdrf_sample_counts", "n x tmax too large for one call");
+    if (nthr > 0)
+      hipLaunchKernelGGL(sc_fill_uniforms_kernel, dim3((unsigned)((nthr + 255) / 256), (unsigned)num_samples), dim3(256), 0, s, seed, row_offset, n, tmax, u);
+    LAUNCHCHK("sample_counts");
+    return 0;
+  }
+  if (c->V > GDRF_SC_MAX_V)
+    return fail(-1, "gdrf_sample_counts", "num_observation_categories exceeds the limit of 4096 words (one wave's CDF, counts and p live in LDS)");
+  if (c->K > GDRF_SC_KP) return fail(-1, "gdrf_sample_counts", "num_topic_categories exceeds the 128 topics a wave holds in LDS");
+  if (!theta || !params || !totals) return fail(-1, "gdrf_sample_counts", "theta, params and totals are required");
+  if (mode == SC_STATS && (!ws || !dev || !zeros)) return fail(-1, "gdrf_sample_counts", "the check statistics need ws, dev and zeros");
+  if (mode == SC_COUNTS && !out) return fail(-1, "gdrf_sample_counts", "out is required");
+  TYPED3(c, sample_counts, c, (const T*)theta, n, (const T*)params, totals, tmax, ws, mode, num_samples, seed, row_offset, (const double*)u, out, dev,
+         zeros, s);
 }
 
 // the shape limits of the joint calls: the launches index rows and sample-topic pairs with a 16-bit grid dimension

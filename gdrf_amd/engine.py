@@ -71,6 +71,53 @@ def check_fold_args(num_iters, tol, n: int, V: int, ws, ws_score=None):
     return int(num_iters), tol
 
 
+# The most words (V) the count sampler serves (GDRF_SC_MAX_V of include/gdrf_hip.h): a wave keeps a row's CDF, counts and p in LDS.
+SAMPLE_COUNTS_MAX_V = 4096
+
+
+def check_count_args(theta, totals, K: int, V: int, mode: int = 0, ws=None, u=None, row_offset=0):
+    """The argument errors of the count sampler (Engine.sample_counts and the model methods above it), raised before the device is
+    touched: V <= SAMPLE_COUNTS_MAX_V, ``theta`` of shape (S, n, K) with S, n >= 1, ``totals`` (n,) integers >= 0, ``row_offset`` >= 0,
+    for mode 1 dense counts ``ws`` of shape (n, V), an injected ``u`` of shape (S, n, >= max totals) float64 with every entry in [0, 1).
+    Returns (S, n, tmax)."""
+    if V > SAMPLE_COUNTS_MAX_V:
+        raise ValueError(f"sample_counts serves at most SAMPLE_COUNTS_MAX_V = {SAMPLE_COUNTS_MAX_V} observation categories, the model has {V}")
+    if mode not in (0, 1):
+        raise ValueError("sample_counts: mode must be 0 (replicated counts) or 1 (predictive-check statistics)")
+    if theta is None or not hasattr(theta, "shape") or len(theta.shape) != 3 or theta.shape[2] != K or theta.shape[0] < 1 or theta.shape[1] < 1:
+        raise ValueError(f"theta must have shape (num_samples, n, K = {K}) with num_samples, n >= 1, "
+                         f"got {None if theta is None else tuple(getattr(theta, 'shape', ()))}")
+    S, n = int(theta.shape[0]), int(theta.shape[1])
+    if S > 65535:
+        raise ValueError(f"sample_counts takes at most 65535 samples in one call, got {S}")
+    if not torch.is_tensor(totals) or tuple(totals.shape) != (n,):
+        raise ValueError(f"totals must be a tensor of shape (n,) = ({n},), got {tuple(getattr(totals, 'shape', ()))}")
+    if totals.dtype.is_floating_point or totals.dtype.is_complex or totals.dtype == torch.bool:
+        raise ValueError(f"totals must be integers, got {totals.dtype}")
+    tmin, tmax = int(totals.min()), int(totals.max())
+    if tmin < 0:
+        raise ValueError(f"totals must be >= 0, got {tmin}")
+    if tmax > 2 ** 31 - 4:
+        raise ValueError(f"totals must fit an int32, got {tmax}")
+    if int(row_offset) < 0:
+        raise ValueError(f"row_offset must be >= 0, got {row_offset}")
+    if ws is not None and is_sparse_counts(ws):
+        raise ValueError("the predictive check reads dense counts: a sparse (CSR) ws is not supported")
+    if mode == 1 and (ws is None or not hasattr(ws, "shape") or tuple(ws.shape) != (n, V)):
+        raise ValueError(f"mode 1 needs the observed counts ws of shape (n, V) = ({n}, {V}), got {None if ws is None else tuple(getattr(ws, 'shape', ()))}")
+    if mode == 0 and ws is not None:
+        raise ValueError("sample_counts: ws is read by mode 1 only")
+    if u is not None:
+        if not torch.is_tensor(u) or u.dim() != 3 or tuple(u.shape[:2]) != (S, n) or u.dtype != torch.float64:
+            raise ValueError(f"u must be a float64 tensor of shape (num_samples, n, tmax) = ({S}, {n}, >= {tmax}), "
+                             f"got {getattr(u, 'dtype', None)} {tuple(getattr(u, 'shape', ()))}")
+        if u.shape[2] < tmax:
+            raise ValueError(f"u holds {u.shape[2]} tokens per row, the largest total is {tmax}: too few tokens")
+        if u.numel() and not bool(((u >= 0.0) & (u < 1.0)).all()):
+            raise ValueError("u must lie in [0, 1)")
+    return S, n, tmax
+
+
 # The most rows a joint call (Engine.predict_cov, Engine.sample_joint and the model methods above them) takes: a joint draw cannot be cut
 # into row pieces, its n x n factorisation runs in one workgroup and its covariances take K n^2 elements (DESIGN.md section 19 has the
 # times and the memory measured at this size).
@@ -973,6 +1020,50 @@ class Engine:
             return self._speculated(run)
         finally:
             self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)
+
+    # ---- posterior-predictive count samples (csrc/sample_counts.h) ------------------------------------
+    def fill_token_uniforms(self, seed: int, num_samples: int, row_offset: int, n: int, tmax: int) -> torch.Tensor:
+        """(S, n, tmax) float64: exactly the uniforms sample_counts draws inline from ``seed`` for the rows row_offset .. row_offset + n - 1
+        (Philox keyed by the seed, counter (global row, 2^31 | token // 4, sample), word token % 4): the counterpart of fill_eps."""
+        S, n, tmax = int(num_samples), int(n), int(tmax)
+        if S < 1 or n < 1 or tmax < 0 or int(row_offset) < 0:
+            raise ValueError(f"fill_token_uniforms needs num_samples >= 1, n >= 1, tmax >= 0 and row_offset >= 0, got {(num_samples, n, tmax, row_offset)}")
+        out = torch.empty(S, n, tmax, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.gdrf_sample_counts(self.ctx, None, n, None, None, tmax, None, 2, S, int(seed) & (2 ** 64 - 1), int(row_offset),
+                                               out.data_ptr(), None, None, None, _stream_ptr(self.device)), "gdrf_sample_counts")
+        return out
+
+    def sample_counts(self, theta: torch.Tensor, totals: torch.Tensor, mode: int = 0, ws: Optional[torch.Tensor] = None,
+                      seed: Optional[int] = None, row_offset: int = 0, u: Optional[torch.Tensor] = None):
+        """Counts drawn from Multinomial(totals[n], theta[s, n] Phi) (gdrf_sample_counts, csrc/sample_counts.h has the definition), Phi
+        from the engine's parameters.  ``theta``: (S, n, K) samples of the topic proportions in the engine's dtype; ``totals``: (n,) int32.
+        mode 0: w_rep (S, n, V) int32.  mode 1: the predictive-check statistics of the same draws against the dense counts ``ws`` (n, V),
+        no replicate stored: (dev (2, S) float64 = the deviances of the replicates and of ``ws`` under each draw, zeros (S, V) int64 = the
+        rows in which a word was not drawn).  ``u``: injected uniforms (S, n, >= max totals) float64 in [0, 1); None = Philox draws keyed
+        by ``seed`` with counter (row_offset + row, token block, sample), so rows cut into several calls, each with its ``row_offset``,
+        draw what one call draws.  Any n: nothing here is held per row in the engine."""
+        S, n, tmax = check_count_args(theta, totals, self.K, self.V, mode, ws, u, row_offset)
+        for name, t, dt in (("theta", theta, self.dtype), ("totals", totals, torch.int32), ("ws", ws, torch.int32), ("u", u, torch.float64)):
+            if t is not None and (t.dtype != dt or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor on {self.device}")
+        if u is None and seed is None:
+            raise ValueError("sample_counts needs a seed or injected uniforms u")
+        seed = 0 if seed is None else int(seed) & (2 ** 64 - 1)
+        if u is not None and u.shape[2] != tmax:
+            u = u[:, :, :tmax].contiguous()      # the kernel strides a row's uniforms by tmax
+        if u is not None and tmax == 0:
+            u = None
+        out = dev = zeros = None
+        if mode == 0:
+            out = torch.empty(S, n, self.V, dtype=torch.int32, device=self.device)
+        else:
+            dev = torch.empty(2, S, dtype=torch.float64, device=self.device)
+            zeros = torch.empty(S, self.V, dtype=torch.int64, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.lib.gdrf_sample_counts(self.ctx, theta.data_ptr(), n, self.params.data_ptr(), totals.data_ptr(), tmax, ptr(ws), mode, S,
+                                               seed, int(row_offset), ptr(u), ptr(out), ptr(dev), ptr(zeros), _stream_ptr(self.device)),
+                   "gdrf_sample_counts")
+        return out if mode == 0 else (dev, zeros)
 
     # ---- the joint posterior at new inputs (csrc/predict_cov.h) -----------------------------------------
     def _chk_joint_rows(self, xs: torch.Tensor, what: str) -> int:

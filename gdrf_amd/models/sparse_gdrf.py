@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
-from ..engine import Engine, check_fold_args, check_joint_args, check_mc_args
+from ..engine import Engine, check_count_args, check_fold_args, check_joint_args, check_mc_args
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -257,6 +257,12 @@ class ModelSnapshot:
 
     def sample_topic_maps(self, xs, num_samples, seed=None):
         return self.restore().sample_topic_maps(xs, num_samples, seed=seed)
+
+    def sample_counts(self, xs, totals, num_samples, seed=None, coherent=False, theta=None, u=None):
+        return self.restore().sample_counts(xs, totals, num_samples, seed=seed, coherent=coherent, theta=theta, u=u)
+
+    def predictive_check(self, xs, ws, num_samples=200, seed=None, coherent=False):
+        return self.restore().predictive_check(xs, ws, num_samples, seed=seed, coherent=coherent)
 
 
 class SparseMultinomialGDRF:
@@ -799,6 +805,82 @@ class SparseMultinomialGDRF:
         if self._link_function is not None:
             return torch.stack([self._link_function(f[s]).T for s in range(f.shape[0])])
         return torch.softmax(f, dim=1).transpose(1, 2).contiguous()
+
+    # ------------------------------------------------------------------ posterior-predictive counts (csrc/sample_counts.h)
+    def _count_args(self, xs, totals, num_samples, coherent=False, theta=None, u=None, ws=None):
+        """The argument errors of sample_counts / predictive_check, raised before the device is touched; returns (S, N, totals as a
+        (N,) tensor of integers)."""
+        if isinstance(num_samples, bool) or int(num_samples) != num_samples:
+            raise ValueError(f"num_samples must be an integer, got {num_samples!r}")
+        S, N = int(num_samples), int(torch.as_tensor(xs).shape[0])
+        if S < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        if N < 1:
+            raise ValueError(f"sample_counts needs at least one row, got {N}")
+        if theta is not None and tuple(torch.as_tensor(theta).shape) != (S, N, self._K):
+            raise ValueError(f"theta must have shape (num_samples, N, K) = ({S}, {N}, {self._K}), got {tuple(torch.as_tensor(theta).shape)}")
+        tot = torch.as_tensor(totals)
+        if tot.dim() == 0:
+            tot = tot.expand(N)
+        check_count_args(torch.empty(S, N, self._K, device="meta"), tot, self._K, self._V, 0 if ws is None else 1, ws,
+                         None if u is None else torch.as_tensor(u))
+        if coherent and theta is None:
+            check_joint_args(S, self._K, self.M, N)
+        return S, N, tot
+
+    def _count_theta(self, xs, S: int, seed, coherent: bool, theta) -> torch.Tensor:
+        """(S, N, K) topic proportions for the count sampler: injected, one coherent map per sample, or independent rows"""
+        if theta is not None:
+            return torch.as_tensor(theta).to(device=self.device, dtype=self.dtype).contiguous()
+        return self.sample_topic_maps(xs, S, seed=seed) if coherent else self.sample_topic_probs(xs, S, seed=seed)
+
+    def _sample_counts(self, theta: torch.Tensor, totals: torch.Tensor, mode: int, seed, ws_d=None, u=None):
+        """Engine.sample_counts over pieces of at most MC_PIECE_ROWS rows, each with its row_offset: the draws are keyed by the global row,
+        so the counts do not depend on the piece size.  Mode 0: joined along the row axis; mode 1: the pieces' sums and zero counts added."""
+        eng, n = self._engine_for(1), theta.shape[1]
+        totals = totals.to(device=self.device, dtype=torch.int32).contiguous()
+        if u is not None:
+            u = torch.as_tensor(u).to(device=self.device, dtype=torch.float64)
+        parts = []
+        for a in range(0, n, MC_PIECE_ROWS):
+            b = min(n, a + MC_PIECE_ROWS)
+            one = (a, b) == (0, n)
+            parts.append(eng.sample_counts(theta if one else theta[:, a:b].contiguous(), totals[a:b], mode,
+                                           ws=None if ws_d is None else ws_d[a:b], seed=seed, row_offset=a,
+                                           u=None if u is None else u[:, a:b].contiguous()))
+        if mode == 0:
+            return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        return torch.stack([p[0] for p in parts]).sum(0), torch.stack([p[1] for p in parts]).sum(0)
+
+    def sample_counts(self, xs, totals, num_samples, seed=None, coherent=False, theta=None, u=None) -> torch.Tensor:
+        """(S, N, V) int32 counts drawn from the fitted model, what ``pyro.infer.Predictive(model, guide=guide, num_samples=S)`` samples at
+        the ``w`` site: w_rep[s, n] ~ Multinomial(totals[n], theta[s, n] Phi).  ``totals``: an int or (N,) ints >= 0.  theta comes from
+        ``sample_topic_probs(xs, S, seed)`` (independent rows, any N, a custom link_function honoured), with ``coherent=True`` from
+        ``sample_topic_maps(xs, S, seed)`` (one spatially coherent field per replicate, at most JOINT_MAX_ROWS rows), or is the injected
+        ``theta`` (S, N, K).  ``u``: injected uniforms (S, N, >= max totals) float64 in [0, 1), one per token; otherwise counter-based Philox
+        draws keyed by ``seed`` (default: the model's rng_seed) and (row, token, sample), on a stream apart from the one that draws theta."""
+        S, _, tot = self._count_args(xs, totals, num_samples, coherent, theta, u)
+        seed = self.rng_seed if seed is None else int(seed)
+        return self._sample_counts(self._count_theta(xs, S, seed, coherent, theta), tot, 0, seed, u=u)
+
+    def predictive_check(self, xs, ws, num_samples: int = 200, seed=None, coherent=False) -> Dict[str, torch.Tensor]:
+        """A posterior predictive check of the dense counts ``ws`` (N, V): ``num_samples`` replicates at the observed row totals, reduced
+        on the device without storing them.  With q_s = theta_s Phi of draw s and the deviance D(w; q) = 2 sum_n sum_{v: w > 0} w log(w /
+        (T_n q_v)) it returns ``deviance_obs`` (S,) = D(ws; q_s), ``deviance_rep`` (S,) = D(w_rep_s; q_s), ``p_deviance`` = the share of s
+        with deviance_rep >= deviance_obs, ``zeros_obs`` (V,) = the rows in which a word is absent, ``zeros_rep`` (S, V) the same for each
+        replicate, ``p_zeros`` (V,) = the share of s with zeros_rep >= zeros_obs.  theta and the seed as in sample_counts."""
+        check_mc_args(num_samples, self._K, 0, ws=ws)
+        wt = torch.as_tensor(ws)
+        N = int(torch.as_tensor(xs).shape[0])
+        if tuple(wt.shape) != (N, self._V) or wt.dtype.is_floating_point:
+            raise ValueError(f"ws must be dense integer counts of shape (N, V) = ({N}, {self._V}), got {wt.dtype} {tuple(wt.shape)}")
+        S, _, tot = self._count_args(xs, wt.sum(1), num_samples, coherent, ws=wt)
+        seed = self.rng_seed if seed is None else int(seed)
+        _, ws_d = self._prepare_inputs(xs, ws)
+        dev, zeros_rep = self._sample_counts(self._count_theta(xs, S, seed, coherent, None), tot, 1, seed, ws_d=ws_d)
+        zeros_obs = (ws_d == 0).sum(0)
+        return dict(deviance_obs=dev[1], deviance_rep=dev[0], p_deviance=(dev[0] >= dev[1]).double().mean(),
+                    zeros_obs=zeros_obs, zeros_rep=zeros_rep, p_zeros=(zeros_rep >= zeros_obs[None]).double().mean(0))
 
     @property
     def word_topic_matrix(self) -> torch.Tensor:

@@ -367,6 +367,33 @@ int gdrf_fold_in(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev,
                  const int32_t* col2_dev, const int32_t* val2_dev, int mode, int num_iters, double tol, void* out_dev, double* diag_dev,
                  double* out_d_dev, void* stream);
 
+/* Posterior-predictive count samples (csrc/sample_counts.h): replicated counts w_rep drawn from Multinomial(T_n, theta_s Phi), what
+ * pyro.infer.Predictive(model, guide=guide, num_samples=S) samples at the model's `w` site.  theta_dev: (S, n, K) samples of the topic
+ * proportions in the context's element type (as GDRF_MC_THETA returns them); Phi = softmax of the phi block of params_dev, as the
+ * predictive calls form it; totals_dev: (n) int32 row totals T_n, tmax their maximum (a row's total is read as min(max(T_n, 0), tmax)).
+ *   p[s][n][v] = sum_k theta[s][n][k] Phi[k][v]                        (array precision)
+ *   c[s][n][v] = p[s][n][0] + ... + p[s][n][v]                         (inclusive prefix sum, in double)
+ *   word(s,n,t) = the smallest v with u[s][n][t] c[s][n][V-1] < c[s][n][v]  (in double),  t = 0 .. T_n - 1
+ *   w_rep[s][n][v] = #{ t : word(s,n,t) = v }
+ * u_dev: injected uniforms (S, n, tmax) double in [0, 1), or NULL for Philox4x32-10 draws keyed by `seed` with counter
+ * (row_offset + n, 2^31 | t / 4, s): word t % 4 of the block gives u = (word + 0.5) / 2^32.  The 2^31 keeps the token draws of a seed apart
+ * from the normals gdrf_fill_eps / gdrf_predict_mc draw under it (their third counter word is a topic index), and cutting the rows into
+ * several calls, each with its row_offset, changes no draw.
+ *   GDRF_SC_COUNTS    out_dev (S, n, V) int32: w_rep
+ *   GDRF_SC_STATS     the statistics of a posterior predictive check against the observed dense counts ws_dev (n, V) int32, from the draws
+ *                     GDRF_SC_COUNTS makes (bit for bit) without storing them: with q = p / c[V-1], dev_dev (2, S) doubles =
+ *                     {dev_rep[s] = 2 sum_n sum_{v: w_rep > 0} w_rep log(w_rep / (T_n q_v)); dev_obs[s] = the same for ws[n] with its own row
+ *                     sum as T_n}, and zeros_dev (S, V) int64 = #{ n : w_rep[s][n][v] = 0 }.  The sums: per-workgroup partials added in a
+ *                     fixed order, no float atomics; the integers are exact however the rows are batched.
+ *   GDRF_SC_UNIFORMS  u_dev (S, n, tmax) is WRITTEN: the uniforms the other modes draw from `seed` and `row_offset`; nothing else is read
+ * 1 <= num_samples <= 65535; any n >= 1 (no workspace is per row); V <= GDRF_SC_MAX_V (error otherwise); every K the context supports.
+ * Overwrites the context's Phi workspace and partial-sum scratch, as every predictive call does.  Needs no factorisation. */
+enum { GDRF_SC_COUNTS = 0, GDRF_SC_STATS = 1, GDRF_SC_UNIFORMS = 2 };
+#define GDRF_SC_MAX_V 4096
+int gdrf_sample_counts(gdrf_ctx* ctx, const void* theta_dev, int64_t n, const void* params_dev, const int32_t* totals_dev, int tmax,
+                       const int32_t* ws_dev, int mode, int num_samples, uint64_t seed, int64_t row_offset, double* u_dev, int32_t* out_dev,
+                       double* dev_dev, int64_t* zeros_dev, void* stream);
+
 /* The joint posterior q(f_k(X*)) = N(loc_k, C_k) at n new inputs (csrc/predict_cov.h; gp.util.conditional(..., full_cov=True) as
  * SparseGDRF.forward(Xnew, full_cov=True) calls it, gdrf/models/sparse_gdrf.py:277-319).  With W = K_*m L^-T (n x M, the step's forward):
  *   R   = K_** - W W^T                       (n x n, the same for every topic; nothing added to its diagonal, no clamp)
