@@ -1764,6 +1764,7 @@ template <typename T, typename TS> struct Impl {
       const size_t lds = 128 + (size_t)M * c->D * sizeof(TS);
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D solve-precision elements exceed the LDS budget (150 KB)");
       auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
+      c->forms[GDRF_FORM_PREDICT] = 5; c->forms[GDRF_FORM_PREDICT_NB] = 0;
       if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       auto rows = [&](const T* Xc, int64_t m, int md, T* o, int64_t ldo) {
         int64_t blocks = (m + 127) / 128; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
@@ -1796,6 +1797,7 @@ template <typename T, typename TS> struct Impl {
       const size_t lds = 128 + ((size_t)M4 * DDt + (size_t)K * V + (size_t)4 * 16 * (16 * NB + 1)) * sizeof(TS);
       if (K <= 32 && lds <= 64 * 1024) {
         const int ldc = 16 * NB;
+        c->forms[GDRF_FORM_PREDICT] = 1; c->forms[GDRF_FORM_PREDICT_NB] = NB;
         hipLaunchKernelGGL((predict_coeff_t_kernel<TS, T>), dim3(M4), dim3(64), 0, s, (const TS*)Q(c->LinvT), U, M, Mp, M4, K, ldc, Q(c->CfT));
         const int64_t groups = (n + 15) / 16;
         int64_t blocks = (groups + 3) / 4; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
@@ -1822,6 +1824,7 @@ template <typename T, typename TS> struct Impl {
       const size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)128 * (V + 1)) * sizeof(TS);
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V + 128*(V+1) solve-precision elements exceed the LDS budget (150 KB)");
       auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
+      c->forms[GDRF_FORM_PREDICT] = 4; c->forms[GDRF_FORM_PREDICT_NB] = 0;
       if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
                               (const T*)P(c->phi), ws, mode, out, ldo, c->dpart)) return rc;
     } else {
@@ -1830,6 +1833,7 @@ template <typename T, typename TS> struct Impl {
       if (lds > 64 * 1024) { in_lds = 0; lds -= (size_t)K * M * sizeof(TS); }
       if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V solve-precision elements exceed the LDS budget (150 KB)");
       auto kfn = ard_fwd(c) ? predict_rows_kernel<TS, T, true> : predict_rows_kernel<TS, T>;
+      c->forms[GDRF_FORM_PREDICT] = in_lds ? 2 : 3; c->forms[GDRF_FORM_PREDICT_NB] = 0;
       if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
                               (const T*)P(c->phi), ws, mode, out, ldo, c->dpart, in_lds)) return rc;
     }

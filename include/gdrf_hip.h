@@ -468,9 +468,14 @@ int gdrf_get_timing(gdrf_ctx* ctx, double* ms_out, int64_t* count_out, int nslot
  *   GDRF_FORM_ROWS         row terms: 1 elbo_rows_mfma, 2 elbo_rows (one thread per row), 3 vocabulary-streamed
  *   GDRF_FORM_ROWS_KT, _VT 16-topic and 16-word tiles of elbo_rows_mfma (0 for the others)
  *   GDRF_FORM_GT           G^T = W^T Wbar: 1 gemm_tn, 2 gemm_tn_split
- *   GDRF_FORM_HYPER        K_nm parts of the hyper-parameter gradients: 1 the backward GEMM (form 0 of gdrf_set_hyper_backward), 2 Hd (form 1) */
+ *   GDRF_FORM_HYPER        K_nm parts of the hyper-parameter gradients: 1 the backward GEMM (form 0 of gdrf_set_hyper_backward), 2 Hd (form 1)
+ *   GDRF_FORM_PREDICT      gdrf_predict modes 0-3: 1 predict_mfma, 2 predict_rows with the coefficients in LDS, 3 predict_rows reading them
+ *                          from memory, 4 predict_rows_bigk (K > 32), 5 the streamed route (row form 1, or mode 3 on a bound CSR matrix);
+ *                          mode 4 runs the step's forward and leaves both slots as they are
+ *   GDRF_FORM_PREDICT_NB   16-topic column blocks of predict_mfma (0 for the others) */
 enum { GDRF_FORM_WBAR = 0, GDRF_FORM_WBAR_NSLICE, GDRF_FORM_AK, GDRF_FORM_AK_KGROUPS, GDRF_FORM_FWD_T, GDRF_FORM_FWD_T_KG, GDRF_FORM_LOC,
-       GDRF_FORM_UBAR_Q4, GDRF_FORM_ROWS, GDRF_FORM_ROWS_KT, GDRF_FORM_ROWS_VT, GDRF_FORM_GT, GDRF_FORM_HYPER, GDRF_NFORMS };
+       GDRF_FORM_UBAR_Q4, GDRF_FORM_ROWS, GDRF_FORM_ROWS_KT, GDRF_FORM_ROWS_VT, GDRF_FORM_GT, GDRF_FORM_HYPER, GDRF_FORM_PREDICT,
+       GDRF_FORM_PREDICT_NB, GDRF_NFORMS };
 int gdrf_last_forms(const gdrf_ctx* ctx, int* out, int n);
 
 #ifdef __cplusplus
