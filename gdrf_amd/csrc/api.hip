@@ -807,9 +807,13 @@ template <typename T, typename TS> struct Impl {
     }
     return zout;
   }
-  // periodic and product contexts: the embedded rows (n, D) of this call into c->Xe.  More rows than it holds (gdrf_knm, gdrf_predict) grow it; the
-  // old buffer stays allocated until gdrf_ctx_destroy, since work queued before may still read it.
-  static int per_rows(gdrf_ctx* c, const T* X, int64_t n, const T* params, hipStream_t s) {
+  // The rows of one call: X is what K_nm is evaluated at, Xr the caller's raw rows (the period sums of the backward).  They differ in periodic
+  // and product contexts only, where step_inputs writes the embedded rows (n, D) into c->Xe.  More rows than it holds (gdrf_knm, gdrf_predict)
+  // grow it; the old buffer stays allocated until gdrf_ctx_destroy, since work queued before may still read it.
+  struct StepRows { const T* X; const T* Xr; };
+  static int step_inputs(gdrf_ctx* c, const T* X, int64_t n, const T* params, hipStream_t s, StepRows* r) {
+    *r = {X, X};
+    if (!c->per) return 0;
     if (n > c->xe_cap) {
       if (int rc = ctx_alloc(c, &c->Xe, (size_t)n * c->D * c->esz, "hipMalloc(embedded rows)")) return rc;
       c->xe_cap = n;
@@ -819,6 +823,7 @@ template <typename T, typename TS> struct Impl {
     if (nx > 0)
       hipLaunchKernelGGL((embed_per_kernel<T, T>), dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, n, tb, X, params, (T*)c->Xe, (T*)nullptr);
     LAUNCHCHK("embed rows (periodic)");
+    r->X = (const T*)c->Xe;
     return 0;
   }
   // nlev (<= 8) Cholesky attempts in ONE launch, in the N-side precision (what the reference's fp32
@@ -896,10 +901,9 @@ template <typename T, typename TS> struct Impl {
 
   static int knm(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, T* out, int64_t ldo, hipStream_t s) {
     Z = cov_inputs<T>(c, Z, params, c->hyp, P(c->Zp), nullptr, false, s);
-    if (c->per) {
-      if (int rc = per_rows(c, X, n, params, s)) return rc;
-      X = (const T*)c->Xe;
-    }
+    StepRows r;
+    if (int rc = step_inputs(c, X, n, params, s, &r)) return rc;
+    X = r.X;
     ScopedTimer tm(c, 1, s);
     const int VE = Vec16<T>::N;
     const int vpr = (c->M + VE - 1) / VE, rpp = vpr <= 256 ? 256 / vpr : 1;
@@ -1220,54 +1224,49 @@ template <typename T, typename TS> struct Impl {
     hipLaunchKernelGGL((gemm_nt_kernel<TS, Prob>), dim3((unsigned)nb), dim3(256), CS::LDS_BYTES, s, p);
   }
 
-  // parts of one evaluation: the parameter transforms, the forward over the rows (K_nm, W, loc, tt), the per-row terms, the backward
-  // over the rows.  gdrf_step_local runs them all; the two-point evaluation (step_local2: guide and model on different inputs) runs
-  // them selectively.
-  enum { SL_TRANSFORMS = 1, SL_FORWARD = 2, SL_ROWS = 4, SL_BACKWARD = 8, SL_ALL = 15, SL_NO_DK = 16 /* forward for the predictive path: no backward follows */ };
-  static int step_local(gdrf_ctx* c, const T* X, const int32_t* ws, const T* eps, int64_t n, const T* Z, const T* params,
-                        T* redT, double* redd, hipStream_t s, int mask = SL_ALL) {
+  // ---- the stages of one evaluation: step_inputs, the parameter transforms, the forward over the rows (K_nm, W, loc, tt),
+  // the per-row terms, the backward over the rows.  step_local runs them in that order; step_local2, step_local_link and the predictive
+  // entry points compose the ones they need.
+  // u_loc as the stages behind step_transforms read it: whitened contexts keep it in the parameters, unwhitened ones in c->Uw (u' = L^-1 u)
+  static const T* step_u(const gdrf_ctx* c, const T* params) { return c->unwhitened ? (const T*)c->Uw : params + param_lay(c).uloc; }
+  static int64_t row_tiles(int64_t n) { return (n + GDRF_TILE - 1) / GDRF_TILE; }
+
+  // S_k, S_k^T, Phi, the padded u_loc, B_k = S_k S_k^T and the block scales of the split modes.  Caller's stream.
+  static int step_transforms(gdrf_ctx* c, const T* params, hipStream_t s) {
     const int Mp = c->Mp, M = c->M, K = c->K, V = c->V;
-    const int64_t mm = (int64_t)Mp * Mp, ldk = c->ldk;
-    int rc;
+    const int64_t mm = (int64_t)Mp * Mp;
     const ParamLay pl = param_lay(c);
-    const RedLay rl = red_lay(c);
-    const T* U = params + pl.uloc;
-    const T* phi_unc = params + pl.phi;
-    const T* Sunc = params + pl.S;
-    const T* Xr = X;             // periodic contexts: the raw rows (the period sums of the backward); X becomes their embedding
-    if (c->per && X && (mask & (SL_FORWARD | SL_BACKWARD))) {
-      if ((rc = per_rows(c, X, n, params, s))) return rc;
-      X = (const T*)c->Xe;
-    }
-    if (c->unwhitened && !(mask & SL_TRANSFORMS)) U = (const T*)c->Uw;
-    if (mask & SL_TRANSFORMS) {
-      ScopedTimer tm(c, 2, s);
-      dim3 g3((Mp + 255) / 256, Mp, K);
-      hipLaunchKernelGGL(build_s_kernel<T>, g3, dim3(256), 0, s, Sunc, M, Mp, P(c->S), P(c->ST));
-      hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, phi_unc, K, V, P(c->phi));
-      if (c->unwhitened) {
-        if ((rc = unwhiten_forward(c, U, s))) return rc;     // S, ST now hold S' = L^-1 S; c->Uw holds u' = L^-1 u
-        U = (const T*)c->Uw;
-      }
-      hipLaunchKernelGGL(build_upad_kernel<T>, dim3((Mp + 255) / 256, GDRF_TILE), dim3(256), 0, s, U, K, M, Mp, P(c->Upad));
-      if (!c->Tst && (rc = mm_nt<T>(c, P(c->S), mm, P(c->S), mm, P(c->Bm), mm, T(1), K, s))) return rc;      // B_k = S_k S_k^T
-      if constexpr (std::is_same<T, float>::value) {
-        if (c->split) {            // block scales of W (from the variance), B_k and S_k^T (from their maxima)
-          const SplitLay SL{K};
-          HIPCHK(hipMemsetAsync(c->smx, 0, (size_t)SL.nmax() * sizeof(unsigned), s));
-          if (c->split == 2) {
-            hipLaunchKernelGGL(absmax_batched_kernel, dim3(64, K), dim3(256), 0, s, (const float*)c->Bm, mm, mm, c->smx + SL.mx_b(0));
-            hipLaunchKernelGGL(absmax_batched_kernel, dim3(64, K), dim3(256), 0, s, (const float*)c->ST, mm, mm, c->smx + SL.mx_st(0));
-          }
-          split_scales(c, SPLIT_SC_W | SPLIT_SC_BST, s);
+    int rc;
+    ScopedTimer tm(c, 2, s);
+    dim3 g3((Mp + 255) / 256, Mp, K);
+    hipLaunchKernelGGL(build_s_kernel<T>, g3, dim3(256), 0, s, params + pl.S, M, Mp, P(c->S), P(c->ST));
+    hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + pl.phi, K, V, P(c->phi));
+    if (c->unwhitened && (rc = unwhiten_forward(c, params + pl.uloc, s))) return rc;     // S, ST now hold S' = L^-1 S; c->Uw holds u' = L^-1 u
+    hipLaunchKernelGGL(build_upad_kernel<T>, dim3((Mp + 255) / 256, GDRF_TILE), dim3(256), 0, s, step_u(c, params), K, M, Mp, P(c->Upad));
+    if (!c->Tst && (rc = mm_nt<T>(c, P(c->S), mm, P(c->S), mm, P(c->Bm), mm, T(1), K, s))) return rc;      // B_k = S_k S_k^T
+    if constexpr (std::is_same<T, float>::value) {
+      if (c->split) {            // block scales of W (from the variance), B_k and S_k^T (from their maxima)
+        const SplitLay SL{K};
+        HIPCHK(hipMemsetAsync(c->smx, 0, (size_t)SL.nmax() * sizeof(unsigned), s));
+        if (c->split == 2) {
+          hipLaunchKernelGGL(absmax_batched_kernel, dim3(64, K), dim3(256), 0, s, (const float*)c->Bm, mm, mm, c->smx + SL.mx_b(0));
+          hipLaunchKernelGGL(absmax_batched_kernel, dim3(64, K), dim3(256), 0, s, (const float*)c->ST, mm, mm, c->smx + SL.mx_st(0));
         }
+        split_scales(c, SPLIT_SC_W | SPLIT_SC_BST, s);
       }
     }
-    const int64_t rtiles = (n + GDRF_TILE - 1) / GDRF_TILE;
-    if (mask & SL_FORWARD) {
+    return 0;
+  }
+
+  // K_nm, W, loc and tt at the rows r.X.  W and tt on the caller's stream; loc (and, with want_dk, the dK_nm pieces of the hyper-TN
+  // backward) on the side stream behind ev_fork; the caller's stream waits for loc (ev_loc) before it returns, not for the pieces.
+  static int step_forward(gdrf_ctx* c, const StepRows& r, int64_t n, hipStream_t s, bool want_dk) {
+    const int Mp = c->Mp, M = c->M, K = c->K;
+    const int64_t ldk = c->ldk, rtiles = row_tiles(n);
+    int rc;
     // (1) W = Knm Linv^T in the solve precision, stored in the N-side precision
     {
-      if ((rc = knm_solve(c, X, n, s))) return rc;
+      if ((rc = knm_solve(c, r.X, n, s))) return rc;
       if ((rc = join_fact(c, s))) return rc;          // W needs L^-1
       ScopedTimer tm(c, 3, s);
       FwdWProb<TS, T> p{{}, {}, (const TS*)Q(c->Knm), n, Mp, (const TS*)Q(c->Linv), P(c->W), P(c->qpart), ldk};
@@ -1305,14 +1304,14 @@ template <typename T, typename TS> struct Impl {
     }
     HIPCHK(hipEventRecord(c->ev_loc, c->side));
     if constexpr (std::is_same<T, float>::value && sizeof(TS) == 8) {
-      if (hyper_tn_on(c) && !(mask & SL_NO_DK)) {
+      if (hyper_tn_on(c) && want_dk) {
         // pieces of dK_nm / d log(lengthscale) for the backward's Hd = dK^T Wbar; on the side stream behind loc: the main stream does not wait for it
         const int vpr = Mp / 8, rpp = 256 / vpr;
         const int64_t blocks = std::min<int64_t>((n + rpp - 1) / rpp, 256 * 16);
         if (!c->dKh && (rc = ctx_alloc(c, &c->dKh, (size_t)2 * c->ncap * Mp * 2, "hipMalloc(dKh)"))) return rc;
         _Float16* dkh = (_Float16*)c->dKh;
         const float* dsc = (const float*)c->ssc + SplitLay{K}.dk();
-        hipLaunchKernelGGL((c->D <= 2 ? dk_pieces_kernel<T, 2> : dk_pieces_kernel<T, GDRF_DMAX>), dim3((unsigned)blocks), dim3(256), 0, c->side, X, n,
+        hipLaunchKernelGGL((c->D <= 2 ? dk_pieces_kernel<T, 2> : dk_pieces_kernel<T, GDRF_DMAX>), dim3((unsigned)blocks), dim3(256), 0, c->side, r.X, n,
                            (const double*)c->Zs, M, c->D, c->kind, c->hyp, dkh, (int64_t)c->ncap * Mp, Mp, dsc);
         LAUNCHCHK("dk_pieces");
       }
@@ -1328,16 +1327,20 @@ template <typename T, typename TS> struct Impl {
     }
     LAUNCHCHK("forward");
     HIPCHK(hipStreamWaitEvent(s, c->ev_loc, 0));
-    }
-    // per-row ELBO terms and row-local backward
-    int egrid;
-    if ((mask & SL_ROWS) && (c->rows_form == 1 || c->csr_crow)) {
-      ScopedTimer tm(c, 6, s);
-      if (int rc = rows_streamed(c, ws, eps, n, redT, redd, s)) return rc;
+    return 0;
+  }
+
+  // per-row ELBO terms and row-local backward: the streamed or sparse route, or one of the two forms with Phi in LDS.  Caller's stream.
+  static int step_rows(gdrf_ctx* c, const int32_t* ws, const T* eps, int64_t n, T* redT, double* redd, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    const int64_t ldk = c->ldk;
+    int rc, egrid;
+    ScopedTimer tm(c, 6, s);
+    if (c->rows_form == 1 || c->csr_crow) {
+      if ((rc = rows_streamed(c, ws, eps, n, redT, redd, s))) return rc;
       c->forms[GDRF_FORM_ROWS] = 3; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
-    } else if (mask & SL_ROWS) {
-      ScopedTimer tm(c, 6, s);
-      if (int rc = phibar_part_ensure(c)) return rc;
+    } else {
+      if ((rc = phibar_part_ensure(c))) return rc;
       auto rows = [&](auto kern, int threads, size_t lds) {         // the LDS row forms take the same arguments
         return launch_lds(kern, dim3(egrid), dim3(threads), lds, s, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt), eps, ldk, n, ws, P(c->phi),
                           (const T*)c->mean, c->mean_sk, c->mean_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart, P(c->phibar_part));
@@ -1370,184 +1373,232 @@ template <typename T, typename TS> struct Impl {
       }
       rows_reduce(c, P(c->phibar_part), egrid, redT, redd, s);
     }
-    if (!(mask & SL_BACKWARD)) return 0;
+    return 0;
+  }
+
+  // ---- the pieces of step_backward, in its order.  None of them records or awaits an event: step_backward does.
+  // block scale of diag(vbar_k) W, the scaled operand of the A_k contraction.  Stream s (main), no event.
+  static int bwd_vscale(gdrf_ctx* c, int64_t n, hipStream_t s) {
     if constexpr (std::is_same<T, float>::value) {
-      if (c->split) {            // block scale of diag(vbar_k) W, the scaled operand of the A_k contraction
-        const SplitLay SL{K};
+      if (c->split) {
+        const SplitLay SL{c->K};
         if (c->split == 2) {
-          HIPCHK(hipMemsetAsync(c->smx + SL.mx_v(0), 0, (size_t)K * sizeof(unsigned), s));
+          HIPCHK(hipMemsetAsync(c->smx + SL.mx_v(0), 0, (size_t)c->K * sizeof(unsigned), s));
           HIPCHK(hipMemsetAsync(c->smx + SL.mx_wbar(), 0, sizeof(unsigned), s));
-          hipLaunchKernelGGL(absmax_batched_kernel, dim3(64, K), dim3(256), 0, s, (const float*)c->vbar, n, ldk, c->smx + SL.mx_v(0));
+          hipLaunchKernelGGL(absmax_batched_kernel, dim3(64, c->K), dim3(256), 0, s, (const float*)c->vbar, n, c->ldk, c->smx + SL.mx_v(0));
         }
         split_scales(c, SPLIT_SC_V, s);
       }
     }
-    // ubar = locbar W needs only the row kernel's locbar: on the side stream BESIDE the Wbar contraction (a vector / HBM pass next to a
-    // matrix-pipe kernel that leaves half of each SIMD's registers free) instead of inside bwd_knm with G^T
-    HIPCHK(hipEventRecord(c->ev_fork, s));
-    HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    {
-      hipStream_t ss = c->side;
-      ScopedTimer tm(c, 12, ss);
-      const int64_t rpb = ubar_rows_per_block(n), nb = (n + rpb - 1) / rpb;
-      if (nb > c->ubar_blocks_cap) return fail(-1, "gdrf_step_local", "ubar partial buffer too small");
-      const int kq = K <= 16 ? (K + 3) / 4 : 4;
-      c->forms[GDRF_FORM_UBAR_Q4] = kq;
-      hipLaunchKernelGGL((kq == 1 ? ubar_part_kernel<T, 1> : kq == 2 ? ubar_part_kernel<T, 2> : kq == 3 ? ubar_part_kernel<T, 3> : ubar_part_kernel<T, 4>),
-                         dim3((unsigned)nb, (Mp + 255) / 256), dim3(256), 0, ss, P(c->W), n, Mp, K, P(c->locbar), ldk, rpb, P(c->ubar_part));
-      hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * Mp + 255) / 256), dim3(256), 0, ss, P(c->ubar_part), nb, (int64_t)K * Mp, redT + rl.ubar);
+    return 0;
+  }
+  // ubar = locbar W needs only the row kernel's locbar: BESIDE the Wbar contraction (a vector / HBM pass next to a matrix-pipe kernel that
+  // leaves half of each SIMD's registers free) instead of inside bwd_knm with G^T.  Stream ss (side), behind ev_fork.
+  static int bwd_ubar(gdrf_ctx* c, int64_t n, T* redT, hipStream_t ss) {
+    const int Mp = c->Mp, K = c->K;
+    ScopedTimer tm(c, 12, ss);
+    const int64_t rpb = ubar_rows_per_block(n), nb = (n + rpb - 1) / rpb;
+    if (nb > c->ubar_blocks_cap) return fail(-1, "gdrf_step_local", "ubar partial buffer too small");
+    const int kq = K <= 16 ? (K + 3) / 4 : 4;
+    c->forms[GDRF_FORM_UBAR_Q4] = kq;
+    hipLaunchKernelGGL((kq == 1 ? ubar_part_kernel<T, 1> : kq == 2 ? ubar_part_kernel<T, 2> : kq == 3 ? ubar_part_kernel<T, 3> : ubar_part_kernel<T, 4>),
+                       dim3((unsigned)nb, (Mp + 255) / 256), dim3(256), 0, ss, P(c->W), n, Mp, K, P(c->locbar), c->ldk, rpb, P(c->ubar_part));
+    hipLaunchKernelGGL(reduce_parts_kernel<T>, dim3((K * Mp + 255) / 256), dim3(256), 0, ss, P(c->ubar_part), nb, (int64_t)K * Mp, redT + red_lay(c).ubar);
+    return 0;
+  }
+  // (3) Wbar.  Stream s (main), no event: the side stream's G^T and hyper-TN wait for it through ev_fork2.
+  static int bwd_wbar(gdrf_ctx* c, int64_t n, const T* U, hipStream_t s) {
+    const int Mp = c->Mp, M = c->M, K = c->K;
+    const int64_t ldk = c->ldk, rtiles = row_tiles(n);
+    int rc;
+    ScopedTimer tm(c, 7, s);
+    const size_t lds = C::LDS_BYTES + (size_t)K * GDRF_TILE * sizeof(T);
+    const dim3 grid(c->Tst ? nt_xcd_pair_grid(rtiles, nct<T>(c)) : (unsigned)round_up(rtiles * nct<T>(c), 8));
+    if (c->Tst) {
+      BwdWbarTProb<T> p{{}, {}, P(c->Tst), c->t_bs, c->t_ts, P(c->W), n, M, Mp, K, P(c->S), P(c->vbar), P(c->locbar), ldk,
+                        P(c->asum), U, P(c->Wbar)};
+      if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarTProb<T>>, grid, dim3(256), lds, s, p))) return rc;
+      c->forms[GDRF_FORM_WBAR] = 2; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
+    } else if (c->split) {
+      if ((rc = BY_SPLIT(c, wbar_split, c, n, U, rtiles, s))) return rc;
+      split_scales(c, SPLIT_SC_WBAR, s);           // max |Wbar| came out of the epilogue: scale of the G^T contraction's operand
+    } else {
+      BwdWbarProb<T> p{{}, {}, P(c->W), n, M, Mp, K, P(c->Bm), P(c->vbar), P(c->locbar), ldk, P(c->asum), U, P(c->Wbar)};
+      if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarProb<T>>, grid, dim3(256), lds, s, p))) return rc;
+      c->forms[GDRF_FORM_WBAR] = 1; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
     }
-    // (3) Wbar
-    {
-      ScopedTimer tm(c, 7, s);
-      const size_t lds = C::LDS_BYTES + (size_t)K * GDRF_TILE * sizeof(T);
-      const dim3 grid(c->Tst ? nt_xcd_pair_grid(rtiles, nct<T>(c)) : (unsigned)round_up(rtiles * nct<T>(c), 8));
-      if (c->Tst) {
-        BwdWbarTProb<T> p{{}, {}, P(c->Tst), c->t_bs, c->t_ts, P(c->W), n, M, Mp, K, P(c->S), P(c->vbar), P(c->locbar), ldk,
-                          P(c->asum), U, P(c->Wbar)};
-        if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarTProb<T>>, grid, dim3(256), lds, s, p))) return rc;
-        c->forms[GDRF_FORM_WBAR] = 2; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
-      } else if (c->split) {
-        if ((rc = BY_SPLIT(c, wbar_split, c, n, U, rtiles, s))) return rc;
-        split_scales(c, SPLIT_SC_WBAR, s);           // max |Wbar| came out of the epilogue: scale of the G^T contraction's operand
+    return 0;
+  }
+  // G^T = W^T Wbar, where it fills the last-round tails of bwd_knm and the A_k contraction on the main stream.  Stream ss (side), behind ev_fork2.
+  static int bwd_gt(gdrf_ctx* c, int64_t n, T* redT, hipStream_t ss) {
+    const int Mp = c->Mp, K = c->K, BR = TNCfg<T>::BR;
+    const int ns = std::min(c->split ? tn_nsplit_gt(c, n, BR) : tn_nsplit(c, n, BR, 3), c->nsplit_cap);
+    const int64_t rps = round_up((n + ns - 1) / ns, BR);
+    T* slab_gt = P(c->slab) + (int64_t)c->nsplit_cap * K * Mp * Mp;           // the (K+1)-th batch region of the slab buffer
+    TNArgs<T> b{P(c->W), Mp, P(c->Wbar), Mp, nullptr, 0, n, rps, Mp, 0, slab_gt, 1, ns};
+    { ScopedTimer tm(c, 10, ss);
+      c->forms[GDRF_FORM_GT] = c->split ? 2 : 1;
+      if (c->split) {
+        const int ib = SplitLay{K}.wbar();
+        if (int rc = BY_SPLIT(c, tn_split, c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, (float*)slab_gt, 1, ns, c->nt * c->nt, ib, 0, ss)) return rc;
       } else {
-        BwdWbarProb<T> p{{}, {}, P(c->W), n, M, Mp, K, P(c->Bm), P(c->vbar), P(c->locbar), ldk, P(c->asum), U, P(c->Wbar)};
-        if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarProb<T>>, grid, dim3(256), lds, s, p))) return rc;
-        c->forms[GDRF_FORM_WBAR] = 1; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
-      }
-    }
-    // Wbar is ready: G^T = W^T Wbar and ubar = locbar W go to the side stream, where they fill the last-round tails of
-    // bwd_knm and the A_k contraction on the main stream
-    HIPCHK(hipEventRecord(c->ev_fork2, s));
-    HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork2, 0));
-    {
-      hipStream_t ss = c->side;
-      const int BR = TNCfg<T>::BR;
-      const int ns = std::min(c->split ? tn_nsplit_gt(c, n, BR) : tn_nsplit(c, n, BR, 3), c->nsplit_cap);
-      const int64_t rps = round_up((n + ns - 1) / ns, BR);
-      T* slab_gt = P(c->slab) + (int64_t)c->nsplit_cap * K * mm;           // the (K+1)-th batch region of the slab buffer
-      TNArgs<T> b{P(c->W), Mp, P(c->Wbar), Mp, nullptr, 0, n, rps, Mp, 0, slab_gt, 1, ns};
-      { ScopedTimer tm(c, 10, ss);
-        c->forms[GDRF_FORM_GT] = c->split ? 2 : 1;
-        if (c->split) {
-          const int ib = SplitLay{K}.wbar();
-          if ((rc = BY_SPLIT(c, tn_split, c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, (float*)slab_gt, 1, ns, c->nt * c->nt, ib, 0, ss))) return rc;
-        } else {
-          hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * c->nt * ns)), dim3(256), TNCfg<T>::LDS_BYTES, ss, b);
-        } }
-      { ScopedTimer tm(c, 11, ss);
-        dim3 gr1((Mp + 255) / 256, Mp, 1);
-        hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr1, dim3(256), 0, ss, (const T*)slab_gt, ns, 1, Mp, 0, redT + rl.GT); }
-    }
-    HIPCHK(hipEventRecord(c->ev_join, c->side));
-    // (4) kernel hyper-parameter partials through K_nm
-    bool hyper_done = false;
+        hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * c->nt * ns)), dim3(256), TNCfg<T>::LDS_BYTES, ss, b);
+      } }
+    { ScopedTimer tm(c, 11, ss);
+      dim3 gr1((Mp + 255) / 256, Mp, 1);
+      hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr1, dim3(256), 0, ss, (const T*)slab_gt, ns, 1, Mp, 0, redT + red_lay(c).GT); }
+    return 0;
+  }
+  // (4) kernel hyper-parameter partials through K_nm, in one of two forms.
+  // Hyper-TN (hyper_tn.h): stream ss (side), behind G^T: Hd = dK^T Wbar on the same TN kernel (slab batch K + 1), its contraction with L^-1
+  // in double -> red_d[5]; sum Wbar o W -> red_d[4]; red_d[6] = 0.  No backward solve GEMM.
+  // Otherwise the bwd_knm fan and its reductions: stream s (main), no event.
+  static int bwd_hyper(gdrf_ctx* c, const StepRows& r, int64_t n, double* redd, hipStream_t s, hipStream_t ss) {
+    const int Mp = c->Mp, M = c->M;
     if constexpr (std::is_same<T, float>::value && sizeof(TS) == 8) {
       if (hyper_tn_on(c)) {
-        // on the side stream, behind G^T: Hd = dK^T Wbar on the same TN kernel (slab batch K + 1), its contraction with L^-1 in double ->
-        // red_d[5]; sum Wbar o W -> red_d[4]; red_d[6] = 0.  No backward solve GEMM (hyper_tn.h).
-        hipStream_t ss = c->side;
         ScopedTimer tm(c, 8, ss);
         const int BR = TNCfg<T>::BR;
         const int ns = std::min(tn_nsplit_gt(c, n, BR), c->nsplit_cap);
         const int64_t rps = round_up((n + ns - 1) / ns, BR);
-        float* slab_hd = (float*)c->slab + (int64_t)c->nsplit_cap * (K + 1) * mm;
-        const SplitLay SL{K};
-        if ((rc = tn_split<SplitF16>(c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, slab_hd, 1, ns, c->nt * c->nt, SL.wbar(), 0, ss, c->dKh, SL.dk()))) return rc;
+        float* slab_hd = (float*)c->slab + (int64_t)c->nsplit_cap * (c->K + 1) * Mp * Mp;
+        const SplitLay SL{c->K};
+        if (int rc = tn_split<SplitF16>(c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, slab_hd, 1, ns, c->nt * c->nt, SL.wbar(), 0, ss, c->dKh, SL.dk())) return rc;
         hipLaunchKernelGGL(slab_linvt_dot_kernel<TS>, dim3((unsigned)M), dim3(256), 0, ss, (const float*)slab_hd, ns, Mp, M, (const TS*)Q(c->LinvT), c->hpart);
         hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, ss, c->hpart, (int64_t)M, 1, redd + 5);
         hipLaunchKernelGGL(wbar_w_dot_kernel<T>, dim3(2048), dim3(256), 0, ss, (const T*)P(c->Wbar), (const T*)P(c->W), n, Mp, c->hpart + Mp);
         hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, ss, c->hpart + Mp, (int64_t)2048, 1, redd + 4);
         HIPCHK(hipMemsetAsync(redd + 6, 0, sizeof(double), ss));
         LAUNCHCHK("hyper_tn");
-        HIPCHK(hipEventRecord(c->ev_join, c->side));           // the join event now also covers these
-        hyper_done = true;
         c->forms[GDRF_FORM_HYPER] = 2;
+        return 0;
       }
     }
-    if (!hyper_done) {
-      ScopedTimer tm(c, 8, s);
-      c->forms[GDRF_FORM_HYPER] = 1;
-      const int64_t nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
-      if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
-      if (c->per) { if (c->learn_z) bwd_knm<true, true, true>(c, X, Xr, n, nb, s); else bwd_knm<false, true, true>(c, X, Xr, n, nb, s); }
-      else if (c->ard) { if (c->learn_z) bwd_knm<true, true, false>(c, X, Xr, n, nb, s); else bwd_knm<false, true, false>(c, X, Xr, n, nb, s); }
-      else if (c->learn_z) bwd_knm<true, false, false>(c, X, Xr, n, nb, s);
-      else bwd_knm<false, false, false>(c, X, Xr, n, nb, s);
-      if (c->learn_z)
-        hipLaunchKernelGGL(reduce_parts_kernel<double>, dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, s, (const double*)c->zpart, rtiles,
-                           (int64_t)M * c->D, redd + 8);
-      // red_d[8 + M D ..): the ARD tail; periodic and product contexts: the coordinate sums, then the period sums
-      if (c->per || c->ard)
-        hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D + (c->per ? c->npair : 0), redd + 8 + (int64_t)M * c->D);
-      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, nb, 3, redd + 4);      // red_d[4..6]
-    }
-    LAUNCHCHK("backward");
-    // (5) A_k = W^T diag(vbar_k) W.  It needs W and vbar only - not Wbar - but stays on the caller's stream: beside the f64 backward GEMM
-    // the two kernels time-slice the CUs instead of filling each other's stalls
-    {
-      const int BR = TNCfg<T>::BR;
-      const int ns = std::min(tn_nsplit(c, n, BR, c->split ? 2 : 3), c->nsplit_cap);
-      const int64_t rps = round_up((n + ns - 1) / ns, BR);
-      TNArgs<T> a{P(c->W), Mp, P(c->W), Mp, P(c->vbar), ldk, n, rps, Mp, 1, P(c->slab), K, ns};
-      int red_ns = ns, red_qd = GDRF_TILE / 2;
-      { ScopedTimer tm(c, 9, s);
-        if (c->split == 2) {
-          if constexpr (std::is_same<T, float>::value) {
-            const SplitLay SL{K};
-            const int nst = std::min(tn_topics_nsplit(c, n), c->nsplit_cap);
-            const int64_t rpst = round_up((n + nst - 1) / nst, 32);
-            const int ntl = tnt_ntiles(Mp), kgroups = (K + TNT_KT - 1) / TNT_KT;
-            TNTopicsArgs ta{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbar, ldk, n, rpst, Mp,
-                            (float*)c->slab, K, nst, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
-            // The one-wave forms run every stage of their 10-topic groups whatever K: with more than 40 % of the topic slots empty (K <= 5, K = 11)
-            // the two-wave form, which walks the topic pairs that exist, is the faster one.
-            c->forms[GDRF_FORM_AK_KGROUPS] = kgroups;
-            if (10 * K >= 6 * kgroups * TNT_KT) {      // one-wave-per-SIMD form (gemm_tn_topics1.h): 128 rows per wave
-              c->forms[GDRF_FORM_AK] = 4;
-              int ns1 = c->nsplit_cap < 64 ? c->nsplit_cap : 64;                            // 8 k splits: every XCD owns whole splits
-              while (ns1 > 8 && (n + ns1 - 1) / ns1 < 8 * TN1_CH) ns1 -= 8;                 // at least 8 chunks per split
-              if (ns1 >= 8) ns1 &= ~7;
-              const int64_t rps1 = round_up((n + ns1 - 1) / ns1, TN1_CH);
-              const int64_t lds64 = round_up(c->ncap, 64);
-              hipLaunchKernelGGL(tn1_scale_rows_kernel, dim3(256, K), dim3(256), 0, s, (const float*)c->vbar, ldk, n, (float*)c->vbs, lds64,
-                                 (const float*)c->ssc, SL.v(0));
-              TNTopicsArgs t1{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbs, lds64, n, rps1, Mp,
-                              (float*)c->slab, K, ns1, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
-              // two launches: the tiles whose upper 64 rows lie above the diagonal (J = 2 I + 1) multiply half the A tiles (gemm_tn_topics1.h)
-              const int nth = tn2_ntiles_half(Mp);
-              TNTopicsArgs t0 = t1, t4 = t1;
-              t0.ntiles = ntl - nth; t4.ntiles = nth;
-              HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
-              HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
-              if (t0.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<0>, dim3((unsigned)(t0.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t0);
-              if (t4.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<4>, dim3((unsigned)(t4.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t4);
-              LAUNCHCHK("tn_topics_w2");
-              red_ns = ns1; red_qd = 32;
-            } else {
-              c->forms[GDRF_FORM_AK] = 3;
-              HIPCHK(hipFuncSetAttribute((const void*)tn_topics_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tnt_lds_bytes()));
-              hipLaunchKernelGGL(tn_topics_f16_kernel, dim3((unsigned)(ntl * kgroups * nst)), dim3(512), tnt_lds_bytes(), s, ta);
-              LAUNCHCHK("tn_topics");
-              red_ns = nst; red_qd = 32;
-            }
+    ScopedTimer tm(c, 8, s);
+    c->forms[GDRF_FORM_HYPER] = 1;
+    const int64_t rtiles = row_tiles(n), nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
+    if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
+    const T *X = r.X, *Xr = r.Xr;
+    if (c->per) { if (c->learn_z) bwd_knm<true, true, true>(c, X, Xr, n, nb, s); else bwd_knm<false, true, true>(c, X, Xr, n, nb, s); }
+    else if (c->ard) { if (c->learn_z) bwd_knm<true, true, false>(c, X, Xr, n, nb, s); else bwd_knm<false, true, false>(c, X, Xr, n, nb, s); }
+    else if (c->learn_z) bwd_knm<true, false, false>(c, X, Xr, n, nb, s);
+    else bwd_knm<false, false, false>(c, X, Xr, n, nb, s);
+    if (c->learn_z)
+      hipLaunchKernelGGL(reduce_parts_kernel<double>, dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, s, (const double*)c->zpart, rtiles,
+                         (int64_t)M * c->D, redd + 8);
+    // red_d[8 + M D ..): the ARD tail; periodic and product contexts: the coordinate sums, then the period sums
+    if (c->per || c->ard)
+      hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->apart, nb, c->D + (c->per ? c->npair : 0), redd + 8 + (int64_t)M * c->D);
+    hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, nb, 3, redd + 4);      // red_d[4..6]
+    return 0;
+  }
+  // (5) A_k = W^T diag(vbar_k) W.  It needs W and vbar only - not Wbar - but stays on stream s (main), no event: beside the f64 backward GEMM
+  // the two kernels time-slice the CUs instead of filling each other's stalls
+  static int bwd_ak(gdrf_ctx* c, int64_t n, T* redT, hipStream_t s) {
+    const int Mp = c->Mp, K = c->K;
+    const int64_t ldk = c->ldk;
+    int rc;
+    const int BR = TNCfg<T>::BR;
+    const int ns = std::min(tn_nsplit(c, n, BR, c->split ? 2 : 3), c->nsplit_cap);
+    const int64_t rps = round_up((n + ns - 1) / ns, BR);
+    TNArgs<T> a{P(c->W), Mp, P(c->W), Mp, P(c->vbar), ldk, n, rps, Mp, 1, P(c->slab), K, ns};
+    int red_ns = ns, red_qd = GDRF_TILE / 2;
+    { ScopedTimer tm(c, 9, s);
+      if (c->split == 2) {
+        if constexpr (std::is_same<T, float>::value) {
+          const SplitLay SL{K};
+          const int nst = std::min(tn_topics_nsplit(c, n), c->nsplit_cap);
+          const int64_t rpst = round_up((n + nst - 1) / nst, 32);
+          const int ntl = tnt_ntiles(Mp), kgroups = (K + TNT_KT - 1) / TNT_KT;
+          TNTopicsArgs ta{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbar, ldk, n, rpst, Mp,
+                          (float*)c->slab, K, nst, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
+          // The one-wave forms run every stage of their 10-topic groups whatever K: with more than 40 % of the topic slots empty (K <= 5, K = 11)
+          // the two-wave form, which walks the topic pairs that exist, is the faster one.
+          c->forms[GDRF_FORM_AK_KGROUPS] = kgroups;
+          if (10 * K >= 6 * kgroups * TNT_KT) {      // one-wave-per-SIMD form (gemm_tn_topics1.h): 128 rows per wave
+            c->forms[GDRF_FORM_AK] = 4;
+            int ns1 = c->nsplit_cap < 64 ? c->nsplit_cap : 64;                            // 8 k splits: every XCD owns whole splits
+            while (ns1 > 8 && (n + ns1 - 1) / ns1 < 8 * TN1_CH) ns1 -= 8;                 // at least 8 chunks per split
+            if (ns1 >= 8) ns1 &= ~7;
+            const int64_t rps1 = round_up((n + ns1 - 1) / ns1, TN1_CH);
+            const int64_t lds64 = round_up(c->ncap, 64);
+            hipLaunchKernelGGL(tn1_scale_rows_kernel, dim3(256, K), dim3(256), 0, s, (const float*)c->vbar, ldk, n, (float*)c->vbs, lds64,
+                               (const float*)c->ssc, SL.v(0));
+            TNTopicsArgs t1{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbs, lds64, n, rps1, Mp,
+                            (float*)c->slab, K, ns1, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
+            // two launches: the tiles whose upper 64 rows lie above the diagonal (J = 2 I + 1) multiply half the A tiles (gemm_tn_topics1.h)
+            const int nth = tn2_ntiles_half(Mp);
+            TNTopicsArgs t0 = t1, t4 = t1;
+            t0.ntiles = ntl - nth; t4.ntiles = nth;
+            HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
+            HIPCHK(hipFuncSetAttribute((const void*)tn_topics_w2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, tn2_lds_bytes()));
+            if (t0.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<0>, dim3((unsigned)(t0.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t0);
+            if (t4.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<4>, dim3((unsigned)(t4.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t4);
+            LAUNCHCHK("tn_topics_w2");
+            red_ns = ns1; red_qd = 32;
+          } else {
+            c->forms[GDRF_FORM_AK] = 3;
+            HIPCHK(hipFuncSetAttribute((const void*)tn_topics_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tnt_lds_bytes()));
+            hipLaunchKernelGGL(tn_topics_f16_kernel, dim3((unsigned)(ntl * kgroups * nst)), dim3(512), tnt_lds_bytes(), s, ta);
+            LAUNCHCHK("tn_topics");
+            red_ns = nst; red_qd = 32;
           }
-        } else if (c->split) {
-          c->forms[GDRF_FORM_AK] = 2; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
-          const int ib = SplitLay{K}.v(0), ntl = c->nt * (c->nt + 1) / 2;
-          // bf16x6 (f16x3 took the branch above)
-          if ((rc = tn_split<SplitBf16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s))) return rc;
-        } else {
-          c->forms[GDRF_FORM_AK] = 1; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
-          hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * (c->nt + 1) / 2 * K * ns)), dim3(256), TNCfg<T>::LDS_BYTES, s, a);
-        } }
-      { ScopedTimer tm(c, 11, s);
-        dim3 gr((Mp + 255) / 256, Mp, K);
-        hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr, dim3(256), 0, s, P(c->slab), red_ns, K, Mp, 1, redT + rl.A, red_qd); }
-    }
+        }
+      } else if (c->split) {
+        c->forms[GDRF_FORM_AK] = 2; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
+        const int ib = SplitLay{K}.v(0), ntl = c->nt * (c->nt + 1) / 2;
+        // bf16x6 (f16x3 took the branch above)
+        if ((rc = tn_split<SplitBf16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s))) return rc;
+      } else {
+        c->forms[GDRF_FORM_AK] = 1; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
+        hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * (c->nt + 1) / 2 * K * ns)), dim3(256), TNCfg<T>::LDS_BYTES, s, a);
+      } }
+    { ScopedTimer tm(c, 11, s);
+      dim3 gr((Mp + 255) / 256, Mp, K);
+      hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr, dim3(256), 0, s, P(c->slab), red_ns, K, Mp, 1, redT + red_lay(c).A, red_qd); }
+    return 0;
+  }
+
+  // The backward over the rows: ubar, A_k, G^T into redT and the K_nm hyper-parameter partials into redd, from the row stage's vbar, locbar
+  // and asum and the forward's W.  Every event of the backward is recorded and awaited here:
+  //   main s : vscale | fork ------- wbar | fork2 ---------- (hyper: bwd_knm fan) - ak ----- wait(join)
+  //   side   :         wait(fork) ubar     wait(fork2) gt - (hyper: TN form) ----- join
+  static int step_backward(gdrf_ctx* c, const StepRows& r, int64_t n, const T* params, T* redT, double* redd, hipStream_t s) {
+    int rc;
+    if ((rc = bwd_vscale(c, n, s))) return rc;
+    HIPCHK(hipEventRecord(c->ev_fork, s));
+    HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    if ((rc = bwd_ubar(c, n, redT, c->side))) return rc;
+    if ((rc = bwd_wbar(c, n, step_u(c, params), s))) return rc;
+    HIPCHK(hipEventRecord(c->ev_fork2, s));
+    HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork2, 0));
+    if ((rc = bwd_gt(c, n, redT, c->side))) return rc;
+    if ((rc = bwd_hyper(c, r, n, redd, s, c->side))) return rc;
+    HIPCHK(hipEventRecord(c->ev_join, c->side));         // behind everything the side stream took: ubar, G^T and the hyper-TN form
+    LAUNCHCHK("backward");
+    if ((rc = bwd_ak(c, n, redT, s))) return rc;
     HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
     LAUNCHCHK("reductions");
     return 0;
+  }
+
+  // the forward of the predictive entry points (mode 4 of predict, predict_mc, fold_in, the joint posterior): no backward follows, so no dK_nm pieces
+  static int predictive_forward(gdrf_ctx* c, const T* X, int64_t n, const T* params, hipStream_t s) {
+    StepRows r;
+    if (int rc = step_inputs(c, X, n, params, s, &r)) return rc;
+    if (int rc = step_transforms(c, params, s)) return rc;
+    return step_forward(c, r, n, s, false);
+  }
+
+  static int step_local(gdrf_ctx* c, const T* X, const int32_t* ws, const T* eps, int64_t n, const T* Z, const T* params,
+                        T* redT, double* redd, hipStream_t s) {
+    StepRows r;
+    int rc;
+    if ((rc = step_inputs(c, X, n, params, s, &r))) return rc;
+    if ((rc = step_transforms(c, params, s))) return rc;
+    if ((rc = step_forward(c, r, n, s, true))) return rc;
+    if ((rc = step_rows(c, ws, eps, n, redT, redd, s))) return rc;
+    return step_backward(c, r, n, params, redT, redd, s);
   }
 
   // Guide and model evaluated at DIFFERENT inputs (the reference's quirk Q3, sparse_gdrf.py:376-380): forward at the guide's inputs,
@@ -1560,6 +1611,7 @@ template <typename T, typename TS> struct Impl {
     const int64_t ldk = c->ldk, kn = (int64_t)K * ldk, nq = (int64_t)((c->Mp + 63) / 64) * ldk;
     const RedLay rl = red_lay(c);
     const int64_t nT = rl.total, nd = red_nd(c);
+    StepRows rg, rm;
     int rc;
     if (!c->g_loc) {
       void** ps[] = {&c->g_loc, &c->g_tt, &c->g_qpart, &c->g_vbar, &c->g_locbar, &c->g_asum, &c->g_redT, (void**)&c->g_redd};
@@ -1568,11 +1620,11 @@ template <typename T, typename TS> struct Impl {
       for (int i = 0; i < 8; ++i)
         if ((rc = ctx_alloc(c, ps[i], sz[i], "hipMalloc(two-point scratch)"))) return rc;
     }
-    if ((rc = step_local(c, Xg, ws, eps, n, Z, params, redT, redd, s, SL_TRANSFORMS | SL_FORWARD))) return rc;
+    if ((rc = step_inputs(c, Xg, n, params, s, &rg)) || (rc = step_transforms(c, params, s)) || (rc = step_forward(c, rg, n, s, true))) return rc;
     HIPCHK(hipMemcpyAsync(c->g_loc, c->loc, (size_t)kn * c->esz, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->g_tt, c->tt, (size_t)kn * c->esz, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->g_qpart, c->qpart, (size_t)nq * c->esz, hipMemcpyDeviceToDevice, s));
-    if ((rc = step_local(c, Xm, ws, eps, n, Z, params, redT, redd, s, SL_FORWARD))) return rc;
+    if ((rc = step_inputs(c, Xm, n, params, s, &rm)) || (rc = step_forward(c, rm, n, s, true))) return rc;
     {
       // the guide-side mu (its q is rewritten below), the streamed or sparse likelihood -> mubar, the two-point sites (V-free)
       ScopedTimer tm(c, 6, s);
@@ -1589,13 +1641,13 @@ template <typename T, typename TS> struct Impl {
       rows_reduce(c, vs_parts(c), G, redT, redd, s, vs_nparts(c, G));
     }
     // backward through the model-side predictive (the buffers hold its W), payload aside
-    if ((rc = step_local(c, Xm, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD))) return rc;
+    if ((rc = step_inputs(c, Xm, n, params, s, &rm)) || (rc = step_backward(c, rm, n, params, redT, redd, s))) return rc;
     HIPCHK(hipMemcpyAsync(c->g_redT, redT, (size_t)nT * c->esz, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->g_redd, redd, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, s));
     // the guide side: its forward again, its row-local gradients in place of the model's
-    if ((rc = step_local(c, Xg, ws, eps, n, Z, params, redT, redd, s, SL_FORWARD))) return rc;
+    if ((rc = step_inputs(c, Xg, n, params, s, &rg)) || (rc = step_forward(c, rg, n, s, true))) return rc;
     std::swap(c->vbar, c->g_vbar); std::swap(c->locbar, c->g_locbar); std::swap(c->asum, c->g_asum);
-    rc = step_local(c, Xg, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD);
+    if (!(rc = step_inputs(c, Xg, n, params, s, &rg))) rc = step_backward(c, rg, n, params, redT, redd, s);
     std::swap(c->vbar, c->g_vbar); std::swap(c->locbar, c->g_locbar); std::swap(c->asum, c->g_asum);
     if (rc) return rc;
     // payload = model side + guide side: ubar, A_k, G^T (not the phibar block, which the row kernel wrote once) and red_d[4..]
@@ -1617,8 +1669,9 @@ template <typename T, typename TS> struct Impl {
   static int step_local_link(gdrf_ctx* c, const T* X, const int32_t* ws, const T* eps, int64_t n, const T* Z, const T* params,
                              T* redT, double* redd, hipStream_t s, int phase, const T* ext, int64_t ext_ld) {
     const int K = c->K, V = c->V;
+    StepRows r;
     int rc;
-    if (phase == 0 && (rc = step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_TRANSFORMS | SL_FORWARD))) return rc;
+    if (phase == 0 && ((rc = step_inputs(c, X, n, params, s, &r)) || (rc = step_transforms(c, params, s)) || (rc = step_forward(c, r, n, s, true)))) return rc;
     if ((rc = vs_ensure(c))) return rc;
     const int G = vs_grid(c, n);
     if (phase == 0) {
@@ -1636,7 +1689,9 @@ template <typename T, typename TS> struct Impl {
       hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 4, redd);
     }
     LAUNCHCHK("elbo_rows_link");
-    return phase == 2 ? step_local(c, X, ws, eps, n, Z, params, redT, redd, s, SL_BACKWARD) : 0;
+    if (phase != 2) return 0;
+    if ((rc = step_inputs(c, X, n, params, s, &r))) return rc;
+    return step_backward(c, r, n, params, redT, redd, s);
   }
 
   static int step_finish(gdrf_ctx* c, const T* Z, const T* params, const T* redT, const double* redd, double n_global,
@@ -1746,16 +1801,15 @@ template <typename T, typename TS> struct Impl {
       // (f_loc, f_var) of gp.util.conditional(full_cov=False) (gdrf/models/sparse_gdrf.py:277-319): the step's own forward - transforms,
       // K_nm, W = K_nm L^-T with its row norms, loc = W U^T, tt = |S_k^T w|^2 - and one pass that assembles the variance
       if (n > c->ncap) return fail(-1, "gdrf_predict", "mode 4 (loc, var) needs n <= n_cap");
-      if (int rc = step_local(c, X, nullptr, nullptr, n, Z, params, nullptr, nullptr, s, SL_TRANSFORMS | SL_FORWARD | SL_NO_DK)) return rc;
+      if (int rc = predictive_forward(c, X, n, params, s)) return rc;
       hipLaunchKernelGGL(predict_var_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, K, c->hyp, (const T*)P(c->qpart), nct<TS>(c),
                          (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, out);
       LAUNCHCHK("predict (loc, var)");
       return 0;
     }
-    if (c->per) {
-      if (int rc = per_rows(c, X, n, params, s)) return rc;
-      X = (const T*)c->Xe;
-    }
+    StepRows r;
+    if (int rc = step_inputs(c, X, n, params, s, &r)) return rc;
+    X = r.X;
     if (mode >= 2) hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + param_lay(c).phi, K, V, P(c->phi));
     if (c->rows_form == 1 || (mode == 3 && c->csr_crow)) {
       // form 1: the any-K row kernel without Phi in LDS gives f_loc / topic_probs; for word_probs and perplexity it writes topic_probs of
@@ -1853,7 +1907,7 @@ template <typename T, typename TS> struct Impl {
       lds = mc_score_lds<T>(K, V, LG, KJ);
       if (128 + lds > 150 * 1024) return rows_lds_fail("gdrf_predict_mc");
     }
-    if (int rc = step_local(c, X, nullptr, nullptr, n, Z, params, nullptr, nullptr, s, SL_TRANSFORMS | SL_FORWARD | SL_NO_DK)) return rc;
+    if (int rc = predictive_forward(c, X, n, params, s)) return rc;
     const int64_t nblk = (n + 256 / LG - 1) / (256 / LG);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
     auto go = [&](auto kern) {
@@ -1879,7 +1933,7 @@ template <typename T, typename TS> struct Impl {
     const bool csr = crow != nullptr;
     const size_t lds = csr ? fi_csr_lds<T>(LG, KJ) : fi_dense_lds<T>(K, V, LG, KJ);
     if (!csr && 128 + lds > 150 * 1024) return rows_lds_fail("gdrf_fold_in");      // the LDS budget of the default row forms
-    if (int rc = step_local(c, X, nullptr, nullptr, n, Z, params, nullptr, nullptr, s, SL_TRANSFORMS | SL_FORWARD | SL_NO_DK)) return rc;
+    if (int rc = predictive_forward(c, X, n, params, s)) return rc;
     const int64_t nblk = (n + 256 / LG - 1) / (256 / LG);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
     auto go = [&](auto kern) {
@@ -1958,7 +2012,7 @@ template <typename T, typename TS> struct Impl {
     if (int rc = joint_buf(c, &c->jR, &c->jnp, np, (size_t)np * np * sizeof(TS))) return rc;
     if (!c->jflag)
       if (int rc = ctx_alloc(c, &c->jflag, 64, "hipMalloc(joint posterior)", true)) return rc;
-    if (int rc = step_local(c, X, nullptr, nullptr, n, Z, params, nullptr, nullptr, s, SL_TRANSFORMS | SL_FORWARD | SL_NO_DK)) return rc;
+    if (int rc = predictive_forward(c, X, n, params, s)) return rc;
     const T* Xc = c->per ? (const T*)c->Xe : X;               // periodic and product contexts: the embedded rows the forward just wrote
     JointNT<TS, TS, T, TS> w{(const TS*)Q(c->Knm), Mp, 0, n, (const TS*)Q(c->Linv), Mp, 0, Mp, Mp, Q(c->jW), Mp, 0, nullptr, 0, nullptr, 0, 0, nullptr};
     joint_nt<JT_PLAIN>(c, w, 1, s);

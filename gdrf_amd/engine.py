@@ -9,6 +9,7 @@ Reference behaviour mirrored here (paths under /root/reference):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Dict, Optional
@@ -570,18 +571,8 @@ class Engine:
         are attempted concurrently per launch), then the factor and its inverse in the solve precision."""
         s = _stream_ptr(self.device)
         failed = C.c_int()
-        level = 0 if force_level is None else force_level
+        level = self._probe_level(s) if force_level is None else force_level
         while level < self.maxjitter:
-            if force_level is None:
-                nlev = min(4 if level == 0 else 8, self.maxjitter - level)
-                jit = (C.c_double * nlev)(*[self.jitter_total(level + l) for l in range(nlev)])
-                flags = (C.c_int * nlev)()
-                _lib.check(self.lib.gdrf_probe(self.ctx, self.Z.data_ptr(), self.params.data_ptr(), jit, nlev, flags, s), "gdrf_probe")
-                ok = [l for l in range(nlev) if not flags[l]]
-                if not ok:
-                    level += nlev
-                    continue
-                level += ok[0]
             _lib.check(self.lib.gdrf_factorize(self.ctx, self.Z.data_ptr(), self.params.data_ptr(), self.jitter_total(level), s),
                        "gdrf_factorize")
             _lib.check(self.lib.gdrf_chol_failed(self.ctx, C.byref(failed), s), "gdrf_chol_failed")
@@ -590,7 +581,7 @@ class Engine:
                 return level
             if force_level is not None:
                 break
-            level += 1
+            level = self._probe_level(s, level + 1)      # the f64 factorisation failed where the f32 probe passed: the next level
         raise RuntimeError("reached max jitter, covariance is unstable")
 
     def loss_and_grads(self, xs, ws, eps, n_global: Optional[int] = None, ll_const: Optional[float] = None,
@@ -627,44 +618,7 @@ class Engine:
         else:
             llc = torch.full((1,), float(ll_const), dtype=torch.float64, device=self.device)
         ng = float(n if n_global is None else n_global)
-        guess = self._guess_level if (force_level is None and self.speculate) else None
-        if guess is None:
-            self.factorize(force_level)
-            self._local_and_finish(xs, ws, eps, P, n, ng, llc, s, renyi_alpha)
-        else:
-            # Speculate on the previous step's jitter level: the solve-precision factorisation and the whole step go onto
-            # the main stream at once, the array-precision probe (which decides the level, as the reference's fp32
-            # jittercholesky would) runs beside them on a second stream, and the host only waits for the probe and for the
-            # factorisation flag while the GPU is busy with the N-side kernels.  A wrong guess (the level moved, or the
-            # f64 factorisation failed where the f32 one passed) redoes the step on the right level; every rank holds the
-            # same parameters, so every rank takes the same branch.
-            main = torch.cuda.current_stream(self.device)
-            self._probe_stream.wait_stream(main)
-            ps = self._probe_stream.cuda_stream
-            # the probe of the first levels goes out FIRST, without waiting: it runs while the host enqueues the step
-            nlev0 = min(4, self.maxjitter)
-            jit0 = (C.c_double * nlev0)(*[self.jitter_total(l) for l in range(nlev0)])
-            _lib.check(self.lib.gdrf_probe_launch(self.ctx, self.Z.data_ptr(), self.params.data_ptr(), jit0, nlev0, ps), "gdrf_probe_launch")
-            # mode 2: a factorisation made ahead of this step (behind the previous optimizer update, see adam()) is reused after a
-            # device-side check that its inputs are still the current ones; gdrf_chol_failed reports a mismatch like a failure
-            _lib.check(self.lib.gdrf_factorize_mode(self.ctx, self.Z.data_ptr(), self.params.data_ptr(), self.jitter_total(guess), s, 2),
-                       "gdrf_factorize_mode")
-            fact_done = torch.cuda.Event()
-            fact_done.record(main)
-            self._local_and_finish(xs, ws, eps, P, n, ng, llc, s, renyi_alpha)
-            flags0 = (C.c_int * nlev0)()
-            _lib.check(self.lib.gdrf_probe_read(self.ctx, nlev0, flags0, ps), "gdrf_probe_read")
-            ok0 = [l for l in range(nlev0) if not flags0[l]]
-            level = ok0[0] if ok0 else self._probe_level(ps, start=nlev0)
-            failed = C.c_int()
-            self._probe_stream.wait_event(fact_done)
-            _lib.check(self.lib.gdrf_chol_failed(self.ctx, C.byref(failed), ps), "gdrf_chol_failed")
-            if level == guess and not failed.value:
-                self.last_jitter_level = level
-            else:
-                torch.cuda.synchronize(self.device)
-                self.factorize(None)
-                self._local_and_finish(xs, ws, eps, P, n, ng, llc, s, renyi_alpha)
+        self._speculated(lambda: self._local_and_finish(xs, ws, eps, P, n, ng, llc, s, renyi_alpha), force_level)
         self._guess_level = self.last_jitter_level if force_level is None else None
         self._mean_vjp = None
 
@@ -681,6 +635,15 @@ class Engine:
             raise ValueError(f"mean_function returned shape {tuple(mean.shape)}, not broadcastable to ({self.K}, {n})") from None
         setattr(self, "_mean_g" if guide else "_mean", mean)    # keeps the storage alive while the context borrows it
         _lib.check(fn(self.ctx, mean.data_ptr(), mean.stride(0), mean.stride(1)), "gdrf_set_mean")
+
+    @contextlib.contextmanager
+    def _borrowed_mean(self, mean, n: int):
+        """The context borrows ``mean`` inside the block and keeps none behind (a step sets its own)."""
+        self._set_mean(mean, n)
+        try:
+            yield
+        finally:
+            self._set_mean(None, n)
 
     def _probe_level(self, stream_ptr: int, start: int = 0) -> int:
         """First cumulative-jitter level >= start whose array-precision Cholesky succeeds (probe only; raises past maxjitter)."""
@@ -898,20 +861,26 @@ class Engine:
 
         return self._speculated(run)
 
-    def _speculated(self, run):
-        """``run()`` under the jitter-level protocol of the predictive calls: start on the previous level (and on the factorisation adam()
-        queued ahead, if its inputs still match) while the array-precision probe that decides the level runs on the second stream; a wrong
-        guess redoes ``run()`` on the right level."""
-        guess = self._guess_level if self.speculate else None
+    def _speculated(self, run, force_level: Optional[int] = None):
+        """``run()`` under the jitter-level protocol of the step and the predictive calls.  Speculate on the previous step's level: the
+        solve-precision factorisation and ``run()`` go onto the main stream at once, the array-precision probe (which decides the level, as
+        the reference's fp32 jittercholesky would) runs beside them on a second stream, and the host only waits for the probe and for the
+        factorisation flag while the GPU is busy with ``run()``'s kernels.  A wrong guess (the level moved, or the f64 factorisation failed
+        where the f32 one passed) redoes ``run()`` on the right level; every rank holds the same parameters, so every rank takes the same
+        branch.  ``force_level`` (or no previous level, or ``speculate`` off): factorise on that level first, then ``run()``."""
+        guess = self._guess_level if (force_level is None and self.speculate) else None
         if guess is None:
-            self.factorize()
+            self.factorize(force_level)
             return run()
         main = torch.cuda.current_stream(self.device)
         self._probe_stream.wait_stream(main)
         ps = self._probe_stream.cuda_stream
+        # the probe of the first levels goes out FIRST, without waiting: it runs while the host enqueues run()
         nlev0 = min(4, self.maxjitter)
         jit0 = (C.c_double * nlev0)(*[self.jitter_total(l) for l in range(nlev0)])
         _lib.check(self.lib.gdrf_probe_launch(self.ctx, self.Z.data_ptr(), self.params.data_ptr(), jit0, nlev0, ps), "gdrf_probe_launch")
+        # mode 2: a factorisation made ahead of this call (behind the previous optimizer update, see adam()) is reused after a
+        # device-side check that its inputs are still the current ones; gdrf_chol_failed reports a mismatch like a failure
         _lib.check(self.lib.gdrf_factorize_mode(self.ctx, self.Z.data_ptr(), self.params.data_ptr(), self.jitter_total(guess),
                                                 main.cuda_stream, 2), "gdrf_factorize_mode")
         fact_done = torch.cuda.Event()
@@ -954,7 +923,6 @@ class Engine:
             raise ValueError("predict_mc needs a seed or an injected eps")
         seed = 0 if seed is None else int(seed) & (2 ** 64 - 1)
         self.refresh_inducing()
-        self._set_mean(mean, n)
 
         def run():
             out = None
@@ -966,10 +934,8 @@ class Engine:
                                                 self.out_d.data_ptr(), _stream_ptr(self.device)), "gdrf_predict_mc")
             return self.out_d[:2].clone() if mode == 2 else out
 
-        try:
+        with self._borrowed_mean(mean, n):
             return self._speculated(run)
-        finally:
-            self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)
 
     # ---- fold-in: topic proportions of observed rows from their own counts (csrc/foldin.h) ---------------
     def _csr_arrays(self, ws: torch.Tensor):
@@ -1000,7 +966,6 @@ class Engine:
         score = None if ws_score is None else (self._csr_arrays(ws_score) if sparse else ws_score)
         ptr = lambda t: None if t is None else t.data_ptr()
         self.refresh_inducing()
-        self._set_mean(mean, n)
 
         def run():
             out = None
@@ -1016,10 +981,8 @@ class Engine:
                                              tol, ptr(out), diag.data_ptr(), self.out_d.data_ptr(), _stream_ptr(self.device)), "gdrf_fold_in")
             return (self.out_d[:2].clone() if mode == 3 else out), diag
 
-        try:
+        with self._borrowed_mean(mean, n):
             return self._speculated(run)
-        finally:
-            self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)
 
     # ---- posterior-predictive count samples (csrc/sample_counts.h) ------------------------------------
     def fill_token_uniforms(self, seed: int, num_samples: int, row_offset: int, n: int, tmax: int) -> torch.Tensor:
@@ -1109,7 +1072,6 @@ class Engine:
             raise ValueError("sample_joint needs a seed unless both xi and zeta are injected")
         seed = 0 if seed is None else int(seed) & (2 ** 64 - 1)
         self.refresh_inducing()
-        self._set_mean(mean, n)
         failed = C.c_int()
 
         def run(jit):
@@ -1119,7 +1081,7 @@ class Engine:
                                                   jit, out.data_ptr(), _stream_ptr(self.device)), "gdrf_sample_joint")
             return out
 
-        try:
+        with self._borrowed_mean(mean, n):
             for level in range(self.maxjitter):
                 jit = self.jitter_total(level)
                 if level == 0:
@@ -1134,5 +1096,3 @@ class Engine:
                     return out
             raise RuntimeError(f"sample_joint: R + j I has a non-positive pivot at every one of the {self.maxjitter} jitter levels, "
                                "the residual covariance is unstable")
-        finally:
-            self._set_mean(None, n)              # the context keeps no mean behind (a step sets its own)

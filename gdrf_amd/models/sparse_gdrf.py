@@ -538,12 +538,16 @@ class SparseMultinomialGDRF:
                 p.copy_(self._engine.view(name))
         self._mean_versions = [p._version for _, p in self._mean_params]
 
-    def _mean_graph(self, xs_scaled: torch.Tensor, n: int) -> torch.Tensor:
-        out = torch.as_tensor(self._mean_function(xs_scaled)).to(device=self.device, dtype=self.dtype)
+    def _mean_kn(self, values, n: int) -> torch.Tensor:
+        """mean_function values on the model's device and in its dtype, expanded to (K, n); ValueError when they do not broadcast."""
+        out = torch.as_tensor(values).to(device=self.device, dtype=self.dtype)
         try:
             return out.expand(self._K, n)
         except RuntimeError:
             raise ValueError(f"mean_function returned shape {tuple(out.shape)}, not broadcastable to ({self._K}, {n})") from None
+
+    def _mean_graph(self, xs_scaled: torch.Tensor, n: int) -> torch.Tensor:
+        return self._mean_kn(self._mean_function(xs_scaled), n)
 
     def _step_means(self, xs_scaled: torch.Tensor, xs_guide: Optional[torch.Tensor]):
         """(mean, mean_guide, mean_vjp) of one training step.  Without trainable mean parameters: the values as data, mean_vjp None.
@@ -652,11 +656,7 @@ class SparseMultinomialGDRF:
             eps = torch.as_tensor(eps).to(device=self.device, dtype=self.dtype)
         mean = self._mean_values(xs_s)
         if mean is not None:
-            mean = mean.to(device=self.device, dtype=self.dtype)
-            try:
-                mean = mean.expand(self._K, n)
-            except RuntimeError:
-                raise ValueError(f"mean_function returned shape {tuple(mean.shape)}, not broadcastable to ({self._K}, {n})") from None
+            mean = self._mean_kn(mean, n)
         parts = []
         for a in range(0, n, eng.n_cap):
             b = min(n, a + eng.n_cap)
@@ -719,11 +719,7 @@ class SparseMultinomialGDRF:
         eng = self._engine_for(min(n, MC_PIECE_ROWS))
         mean = self._mean_values(xs_s)
         if mean is not None:
-            mean = mean.to(device=self.device, dtype=self.dtype)
-            try:
-                mean = mean.expand(self._K, n)
-            except RuntimeError:
-                raise ValueError(f"mean_function returned shape {tuple(mean.shape)}, not broadcastable to ({self._K}, {n})") from None
+            mean = self._mean_kn(mean, n)
         rows = lambda w, a, b: None if w is None else (csr_rows(w, slice(a, b)) if is_sparse_counts(w) else w[a:b])
         parts, diags = [], []
         for a in range(0, n, eng.n_cap):

@@ -23,11 +23,11 @@ def _perturb(m, g):
         m.params["phi_unc"].add_(0.5 * torch.randn(m.params["phi_unc"].shape, generator=g, dtype=torch.float64))
 
 
-def _link_oracle(link, V, K=4, W=17, H=9, n_points=(4, 3), jitter=1e-6):
+def _link_oracle(link, V, K=4, W=17, H=9, n_points=(4, 3), jitter=1e-6, whiten=True):
     from gdrf_amd.data import synth_circles
     xs, ws, _ = synth_circles(W, H, V, K, seed=4)
     m = RefShapedGDRF(xs, ws, kind="rbf", K=K, n_points=n_points, lengthscale=0.2, dtype=torch.float64, jitter=jitter,
-                      link_function=_LINKS[link], optimizer="adam", lr=1e-2)
+                      link_function=_LINKS[link], optimizer="adam", lr=1e-2, whiten=whiten)
     g = torch.Generator().manual_seed(21)
     _perturb(m, g)
     return m, torch.randn(K, m.N, generator=g, dtype=torch.float64)
@@ -104,6 +104,38 @@ def test_two_point_step_past_the_lds_ceiling_in_row_form_0():
     g = torch.Generator().manual_seed(5)
     _perturb(m, g)
     eps = torch.randn(5, m.N, generator=g, dtype=torch.float64)
+    ref = m.loss_and_grads(eps)
+    eng, res = _world_step(m, eps, xs_w, "auto", torch.float64)
+    _assert_oracle(eng, res, *ref)
+
+
+# ---- 3. unwhitened contexts: the backward of both side paths runs in a call of its own, behind a forward that is not the one the
+# transforms ran in front of, and has to read u' = L^-1 u (not the parameter u) for Wbar.  K = 4, V = 13, N = 17 x 9, M = 12 (Mp padded)
+def _perturb_scale(m, g):
+    with torch.no_grad():
+        m.params["u_scale_tril_unc"].add_(0.1 * torch.randn(m.params["u_scale_tril_unc"].shape, generator=g, dtype=torch.float64).tril())
+
+
+def test_link_step_unwhitened():
+    m, eps = _link_oracle("sigmoid", V=13, whiten=False)
+    _perturb_scale(m, torch.Generator().manual_seed(22))
+    eng, res = _link_step(m, eps, "sigmoid", "auto", torch.float64)
+    m.force_jitter_level = eng.last_jitter_level
+    _assert_oracle(eng, res, *m.loss_and_grads(eps))
+
+
+def test_two_point_step_unwhitened():
+    from gdrf_amd.data import synth_circles
+    xs, ws, _ = synth_circles(17, 9, 13, 4, seed=4)
+    lower = torch.tensor([w[0] for w in WORLD], dtype=torch.float64)
+    delta = torch.tensor([w[1] - w[0] for w in WORLD], dtype=torch.float64)
+    xs_w = torch.from_numpy(xs).double() * delta + lower
+    m = RefShapedGDRF(xs_w, ws, kind="rbf", K=4, n_points=(4, 3), lengthscale=0.3, dtype=torch.float64, jitter=1e-6, world=WORLD,
+                      guide_rescale=True, optimizer="adam", lr=1e-2, whiten=False)
+    g = torch.Generator().manual_seed(5)
+    _perturb(m, g)
+    _perturb_scale(m, g)
+    eps = torch.randn(4, m.N, generator=g, dtype=torch.float64)
     ref = m.loss_and_grads(eps)
     eng, res = _world_step(m, eps, xs_w, "auto", torch.float64)
     _assert_oracle(eng, res, *ref)
