@@ -743,6 +743,27 @@ static int rows_lds_fail(const char* fn) {
   return fail(-1, fn, "num_topic_categories x num_observation_categories too large for the row kernel's LDS; " GDRF_STREAMED_HINT);
 }
 
+// The (LG, KJ) forms of the lane-group row kernels (lane_group.h: LG lanes own a row, KJ topics per lane, LG x KJ >= K), by K:
+//   K <=          8        16        32        64       128
+//   predictive  (8, 1)   (16, 1)   (32, 1)   (64, 1)   (64, 2)     predict_mc_kernel, foldin_kernel
+//   sparse      (8, 1)   (16, 2)   (16, 2)   (16, 8)   (16, 8)     rows_csr_kernel, csr_phibar_seg_kernel
+// They differ and are kept: the sparse kernels pay a butterfly over the group (and LG entries fetched) per stored entry, so their groups
+// stop at 16 lanes and more topics go into a lane's registers; the predictive kernels reduce over the group per row and sample only and
+// spread the words over the same lanes, so they widen the group with K first.  Each dispatcher hands the pair to f as the compile-time
+// constants F::LG, F::KJ of its argument's type F.
+template <int LG_, int KJ_> struct LaneForm { static constexpr int LG = LG_, KJ = KJ_; };
+template <typename F> static int predictive_form(int K, F&& f) {
+  return K <= 8 ? f(LaneForm<8, 1>()) : K <= 16 ? f(LaneForm<16, 1>()) : K <= 32 ? f(LaneForm<32, 1>()) : K <= 64 ? f(LaneForm<64, 1>()) : f(LaneForm<64, 2>());
+}
+template <typename F> static int sparse_form(int K, F&& f) {
+  return K <= 8 ? f(LaneForm<8, 1>()) : K <= 32 ? f(LaneForm<16, 2>()) : f(LaneForm<16, 8>());
+}
+// the grid of the predictive lane-group kernels: 256 / LG rows per workgroup pass, at most 1024 workgroups striding over the rows
+static int lane_group_grid(int64_t n, int LG) {
+  const int64_t nblk = (n + 256 / LG - 1) / (256 / LG);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
+}
+
 // ------------------------------------------------------------------------------------------------
 // T = N-side element type, TS = solve element type
 template <typename T, typename TS> struct Impl {
@@ -1117,7 +1138,7 @@ template <typename T, typename TS> struct Impl {
   static int csr_launch(gdrf_ctx* c, int64_t n, int grid, const T* src, int64_t sk, int64_t sn, int64_t row_off, T* dst, int64_t dld,
                         double* dpart, int dacc, hipStream_t s, bool new_phi) {
     constexpr bool ELBO = MODE == VS_SOFTMAX || MODE == VS_LINK;
-    const int K = c->K, V = c->V, LG = K <= 8 ? 8 : 16, Kp = (int)round_up(K, LG);
+    const int K = c->K, V = c->V, Kp = (int)round_up(K, K <= 8 ? 8 : 16);      // Phi^T rows padded to sparse_form's LG
     const int64_t nnz = c->csr_nnz;
     if (row_off < 0 || row_off + n > c->csr_n) return fail(-1, "rows_csr", "rows outside the bound CSR count matrix");
     if (ELBO && nnz > 0 && !c->csr_ccol) return fail(-1, "rows_csr", "a step needs the column grouping (ccol_dev, cperm_dev) of the bound CSR count matrix");
@@ -1135,26 +1156,25 @@ template <typename T, typename TS> struct Impl {
     if (new_phi) {                   // Phi^T of this call's Phi; the later pieces of a gdrf_predict call reuse it
       hipLaunchKernelGGL(csr_transpose_phi_kernel<T>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, (const T*)P(c->phi), K, Kp, V, (T*)c->csr_phiT);
     }
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, n, K, Kp, V, nnz, src, sk, sn, c->csr_crow + row_off, c->csr_col, c->csr_val,
-                         (const T*)c->csr_phiT, (const T*)c->vs_rs, dst, dld, dpart, dacc, (T*)c->csr_thN, (T*)c->csr_pb, (T*)c->csr_cn);
-    };
-    if (K <= 8) go(rows_csr_kernel<T, MODE, 8, 1>);
-    else if (K <= 32) go(rows_csr_kernel<T, MODE, 16, 2>);
-    else go(rows_csr_kernel<T, MODE, 16, 8>);
+    sparse_form(K, [&](auto fm) {
+      using F = decltype(fm);
+      hipLaunchKernelGGL((rows_csr_kernel<T, MODE, F::LG, F::KJ>), dim3(grid), dim3(256), 0, s, n, K, Kp, V, nnz, src, sk, sn, c->csr_crow + row_off,
+                         c->csr_col, c->csr_val, (const T*)c->csr_phiT, (const T*)c->vs_rs, dst, dld, dpart, dacc, (T*)c->csr_thN, (T*)c->csr_pb,
+                         (T*)c->csr_cn);
+      return 0;
+    });
     if constexpr (MODE == VS_LINK)
       hipLaunchKernelGGL(csr_link_const_kernel<T>, dim3(grid), dim3(128), 0, s, n, K, (const T*)c->csr_thN, (const T*)c->csr_cn, (T*)c->csr_cpart);
     if constexpr (ELBO) {
       if (nnz > 0) {
         const int64_t nseg = V + nnz / CSR_SEG + 1;         // an upper bound of the table's length; the kernel reads the length itself
-        auto seg = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3((unsigned)((nseg * LG + 255) / 256)), dim3(256), 0, s, K, V, nnz, n, c->csr_ccol, c->csr_cperm,
-                             (const int64_t*)c->csr_segoff, (const int32_t*)c->csr_segcol, (const int32_t*)c->csr_erow, (const T*)c->csr_pb,
-                             (const T*)c->csr_thN, (T*)c->csr_parts);
-        };
-        if (K <= 8) seg(csr_phibar_seg_kernel<T, 8, 1>);
-        else if (K <= 32) seg(csr_phibar_seg_kernel<T, 16, 2>);
-        else seg(csr_phibar_seg_kernel<T, 16, 8>);
+        sparse_form(K, [&](auto fm) {
+          using F = decltype(fm);
+          hipLaunchKernelGGL((csr_phibar_seg_kernel<T, F::LG, F::KJ>), dim3((unsigned)((nseg * F::LG + 255) / 256)), dim3(256), 0, s, K, V, nnz, n,
+                             c->csr_ccol, c->csr_cperm, (const int64_t*)c->csr_segoff, (const int32_t*)c->csr_segcol, (const int32_t*)c->csr_erow,
+                             (const T*)c->csr_pb, (const T*)c->csr_thN, (T*)c->csr_parts);
+          return 0;
+        });
         hipLaunchKernelGGL(csr_phibar_combine_kernel<T>, dim3((unsigned)(((int64_t)K * V + 255) / 256)), dim3(256), 0, s, K, V,
                            (const int64_t*)c->csr_segoff, (const T*)c->csr_parts, (T*)c->csr_slot);
       } else {
@@ -1901,26 +1921,19 @@ template <typename T, typename TS> struct Impl {
   static int predict_mc(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, int mode, int S, uint64_t seed,
                         int64_t row_offset, const T* eps, T* out, double* out_d, hipStream_t s) {
     const int K = c->K, V = c->V;
-    const int LG = K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64, KJ = K <= 64 ? 1 : 2;
-    size_t lds = 0;
-    if (mode == MC_SCORE) {          // the LDS budget of the default row forms
-      lds = mc_score_lds<T>(K, V, LG, KJ);
-      if (128 + lds > 150 * 1024) return rows_lds_fail("gdrf_predict_mc");
-    }
-    if (int rc = predictive_forward(c, X, n, params, s)) return rc;
-    const int64_t nblk = (n + 256 / LG - 1) / (256 / LG);
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
-    auto go = [&](auto kern) {
-      return launch_lds(kern, dim3(grid), dim3(256), lds, s, mode, n, K, V, S, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c),
-                        (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk, c->mean_sn, eps, seed, row_offset,
-                        (const T*)P(c->phi), ws, out, c->dpart);
-    };
-    const int rc = LG == 8 ? go(predict_mc_kernel<T, 8, 1>) : LG == 16 ? go(predict_mc_kernel<T, 16, 1>) : LG == 32 ? go(predict_mc_kernel<T, 32, 1>)
-                 : KJ == 1 ? go(predict_mc_kernel<T, 64, 1>) : go(predict_mc_kernel<T, 64, 2>);
-    if (rc) return rc;
-    if (mode == MC_SCORE) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)grid, 2, out_d);
-    LAUNCHCHK("predict_mc");
-    return 0;
+    return predictive_form(K, [&](auto fm) -> int {
+      using F = decltype(fm);
+      const size_t lds = mode == MC_SCORE ? mc_score_lds<T>(K, V, F::LG, F::KJ) : 0;
+      if (128 + lds > 150 * 1024) return rows_lds_fail("gdrf_predict_mc");      // the LDS budget of the default row forms
+      if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+      const int grid = lane_group_grid(n, F::LG);
+      if (int rc = launch_lds(predict_mc_kernel<T, F::LG, F::KJ>, dim3(grid), dim3(256), lds, s, mode, n, K, V, S, (const Hyper*)c->hyp,
+                              (const T*)P(c->qpart), nct<TS>(c), (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk,
+                              c->mean_sn, eps, seed, row_offset, (const T*)P(c->phi), ws, out, c->dpart)) return rc;
+      if (mode == MC_SCORE) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)grid, 2, out_d);
+      LAUNCHCHK("predict_mc");
+      return 0;
+    });
   }
 
   // Fold-in (foldin.h): the step's forward as in mode 4 of predict, then one kernel that runs the per-row MAP from the rows' own counts -
@@ -1929,27 +1942,23 @@ template <typename T, typename TS> struct Impl {
                      const int32_t* val, const int32_t* ws2, const int64_t* crow2, const int32_t* col2, const int32_t* val2, int mode,
                      int num_iters, double tol, T* out, double* diag, double* out_d, hipStream_t s) {
     const int K = c->K, V = c->V;
-    const int LG = K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64, KJ = K <= 64 ? 1 : 2;
     const bool csr = crow != nullptr;
-    const size_t lds = csr ? fi_csr_lds<T>(LG, KJ) : fi_dense_lds<T>(K, V, LG, KJ);
-    if (!csr && 128 + lds > 150 * 1024) return rows_lds_fail("gdrf_fold_in");      // the LDS budget of the default row forms
-    if (int rc = predictive_forward(c, X, n, params, s)) return rc;
-    const int64_t nblk = (n + 256 / LG - 1) / (256 / LG);
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
-    auto go = [&](auto kern) {
-      return launch_lds(kern, dim3(grid), dim3(256), lds, s, mode, n, K, V, num_iters, tol, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c),
-                        (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk, c->mean_sn, (const T*)P(c->phi), ws, crow, col,
-                        val, ws2, crow2, col2, val2, out, diag, c->dpart);
-    };
-    int rc;
-    if (csr) rc = LG == 8 ? go(foldin_kernel<T, 8, 1, true>) : LG == 16 ? go(foldin_kernel<T, 16, 1, true>) : LG == 32 ? go(foldin_kernel<T, 32, 1, true>)
-                : KJ == 1 ? go(foldin_kernel<T, 64, 1, true>) : go(foldin_kernel<T, 64, 2, true>);
-    else rc = LG == 8 ? go(foldin_kernel<T, 8, 1, false>) : LG == 16 ? go(foldin_kernel<T, 16, 1, false>) : LG == 32 ? go(foldin_kernel<T, 32, 1, false>)
-            : KJ == 1 ? go(foldin_kernel<T, 64, 1, false>) : go(foldin_kernel<T, 64, 2, false>);
-    if (rc) return rc;
-    if (mode == FI_SCORE) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)grid, 2, out_d);
-    LAUNCHCHK("fold_in");
-    return 0;
+    return predictive_form(K, [&](auto fm) -> int {
+      using F = decltype(fm);
+      const size_t lds = csr ? fi_csr_lds<T>(F::LG, F::KJ) : fi_dense_lds<T>(K, V, F::LG, F::KJ);
+      if (!csr && 128 + lds > 150 * 1024) return rows_lds_fail("gdrf_fold_in");      // the LDS budget of the default row forms
+      if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+      const int grid = lane_group_grid(n, F::LG);
+      auto go = [&](auto kern) {
+        return launch_lds(kern, dim3(grid), dim3(256), lds, s, mode, n, K, V, num_iters, tol, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c),
+                          (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk, c->mean_sn, (const T*)P(c->phi), ws, crow,
+                          col, val, ws2, crow2, col2, val2, out, diag, c->dpart);
+      };
+      if (int rc = csr ? go(foldin_kernel<T, F::LG, F::KJ, true>) : go(foldin_kernel<T, F::LG, F::KJ, false>)) return rc;
+      if (mode == FI_SCORE) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)grid, 2, out_d);
+      LAUNCHCHK("fold_in");
+      return 0;
+    });
   }
 
   // Posterior-predictive count samples (sample_counts.h): Phi from the parameters, then one kernel in which a wave or a workgroup owns a

@@ -85,6 +85,16 @@ __device__ __forceinline__ void dpart_store(double* __restrict__ dpart, double* 
   }
 }
 
+// The two-slot score tail, dpart[grid][2] = block sums of (a, b), written by thread 0 - added to what is there when dacc
+__device__ __forceinline__ void dpart_store2(double* __restrict__ dpart, double* scratch, double a, double b, int dacc = 0) {
+  a = block_sum(a, scratch);
+  b = block_sum(b, scratch);
+  if (threadIdx.x == 0) {
+    double* d = dpart + 2 * (int64_t)blockIdx.x;
+    if (dacc) { d[0] += a; d[1] += b; } else { d[0] = a; d[1] = b; }
+  }
+}
+
 template <typename T> __device__ __forceinline__ T t_exp(T x);
 template <> __device__ __forceinline__ float  t_exp<float>(float x)   { return expf(x); }
 template <> __device__ __forceinline__ double t_exp<double>(double x) { return exp(x); }

@@ -25,10 +25,10 @@
 // theta_k (1 + expm1(td_k)) / (1 + sum_j theta_j expm1(td_j)); every E-step recomputes it from mu.  The O(K V) part (p_v, c_v = w_v / p_v,
 // r_k) runs in the array precision, its logs summed in double.
 //
-// Layout, as predict_mc_kernel: a group of LG lanes owns a row, lane l holds the topics l, l + LG, ... (KJ of them).  The row's theta goes
-// through LDS; lanes run over the words for p_v and c_v, over the topics for r_k.  A group lies inside one wave, whose LDS accesses
-// complete in order: no barrier.  No atomics; nothing about a row depends on another row or on the grid, so every output but the score's
-// sum over rows is bit-identical however the rows are batched.
+// Layout, as predict_mc_kernel: a group of LG lanes owns a row, lane l holds the topics l, l + LG, ... (KJ of them; lane_group.h).  The
+// row's theta goes through LDS; lanes run over the words for p_v and c_v, over the topics for r_k; what a group exchanges through LDS is
+// its own, so wave_lds_fence stands between the phases and no barrier.  No atomics; nothing about a row depends on another row or on the
+// grid, so every output but the score's sum over rows is bit-identical however the rows are batched.
 //   dense  Phi (K, V) in LDS for the workgroup with the row stride padded to an odd number of elements (lanes that walk k for r_k hit
 //          different banks), the row's counts and c_v in LDS
 //   CSR    a row's stored entries only, LG at a time: one entry per lane for p and c, then every entry's (column, c) is handed round the
@@ -40,7 +40,7 @@
 #pragma once
 #include "common.h"
 #include "kernels_n.h"
-#include "predict_mc.h"
+#include "lane_group.h"
 
 namespace gdrf {
 
@@ -88,10 +88,7 @@ __global__ __launch_bounds__(256) void foldin_kernel(
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int64_t n = blk * RPB + g;
     if (n >= nrows) continue;                                 // the lanes of a group leave together
-    // f_var = clamp(variance - |w_n|^2, 0) + tt, as predict_var_kernel forms it
-    T qn = 0;
-    for (int c = 0; c < nqpart; ++c) qn += qpart[(int64_t)c * ldk + n];
-    const T v0 = (var0 - qn > T(0)) ? var0 - qn : T(0);
+    const T v0 = row_prior_v0(qpart, nqpart, ldk, n, var0);
     double m[KJ], is2[KJ], mu[KJ], th[KJ], r[KJ];
     bool on[KJ];
 #pragma unroll
@@ -100,9 +97,9 @@ __global__ __launch_bounds__(256) void foldin_kernel(
       on[j] = k < K;
       m[j] = is2[j] = r[j] = th[j] = 0;
       if (on[j]) {
-        T mk = loc[(int64_t)k * ldk + n];
-        if (mean) mk += mean[(int64_t)k * mean_sk + n * mean_sn];
-        const double s = (double)(v0 + tt[(int64_t)k * ldk + n]) + noise;
+        T mk, fv;
+        row_prior_topic(v0, loc, tt, ldk, mean, mean_sk, mean_sn, k, n, mk, fv);
+        const double s = (double)fv + noise;
         m[j] = (double)mk;
         is2[j] = 1.0 / (s * s);
       }
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(256) void foldin_kernel(
     } else {
       for (int v = l; v < V; v += LG) { const int32_t w = ws[n * V + v]; w_row[v] = w; R += (double)w; }
     }
-    R = mc_group_sum<LG>(R);
+    R = group_sum<LG>(R);
     const double Rn = R > 1.0 ? R : 1.0;
     double J = 0, gn = 0;
     int used = 0;
@@ -126,15 +123,15 @@ __global__ __launch_bounds__(256) void foldin_kernel(
       double mx = -1.0e300;
 #pragma unroll
       for (int j = 0; j < KJ; ++j) if (on[j]) mx = fmax(mx, mu[j]);
-      mx = mc_group_max<LG>(mx);
+      mx = group_max<LG>(mx);
       double se = 0;
 #pragma unroll
       for (int j = 0; j < KJ; ++j) { th[j] = on[j] ? exp(mu[j] - mx) : 0.0; se += th[j]; }
-      se = mc_group_sum<LG>(se);
+      se = group_sum<LG>(se);
       const double ise = 1.0 / se;
 #pragma unroll
       for (int j = 0; j < KJ; ++j) { th[j] *= ise; th_row[l + LG * j] = (T)th[j]; }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wave_lds_fence();
       double ll = 0;
       T acc[KJ];
 #pragma unroll
@@ -148,8 +145,7 @@ __global__ __launch_bounds__(256) void foldin_kernel(
             const int32_t w = val[e];
             cv = col[e];
             if (w != 0) {
-              T p = 0;
-              for (int k = 0; k < K; ++k) p += th_row[k] * phi[(int64_t)k * V + cv];
+              const T p = theta_phi(th_row, phi + cv, (int64_t)V, K);
               ll += (double)w * (double)t_log<T>(p);
               c = (T)w / p;
             }
@@ -167,19 +163,18 @@ __global__ __launch_bounds__(256) void foldin_kernel(
           const int32_t w = w_row[v];
           T c = 0;
           if (w != 0) {
-            T p = 0;
-            for (int k = 0; k < K; ++k) p += th_row[k] * phiS[k * Vs + v];
+            const T p = theta_phi(th_row, phiS + v, Vs, K);
             ll += (double)w * (double)t_log<T>(p);
             c = (T)w / p;
           }
           c_row[v] = c;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_fence();
 #pragma unroll
         for (int j = 0; j < KJ; ++j)
           if (on[j]) { const T* pr = phiS + (l + LG * j) * Vs; for (int v = 0; v < V; ++v) acc[j] += c_row[v] * pr[v]; }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // theta and c are rewritten by the next E-step
+      wave_lds_fence();                                      // theta and c are rewritten by the next E-step
       double pr2 = 0, gmax = 0;
 #pragma unroll
       for (int j = 0; j < KJ; ++j) {
@@ -188,8 +183,8 @@ __global__ __launch_bounds__(256) void foldin_kernel(
         pr2 += d * d * is2[j];
         gmax = fmax(gmax, fabs(r[j] - R * th[j] - d * is2[j]));
       }
-      J = mc_group_sum<LG>(ll) - 0.5 * mc_group_sum<LG>(pr2);
-      gn = mc_group_max<LG>(gmax) / Rn;
+      J = group_sum<LG>(ll) - 0.5 * group_sum<LG>(pr2);
+      gn = group_max<LG>(gmax) / Rn;
       if (used >= num_iters || gn <= tol) break;
       // ---- M-step: FI_INNER capped, line-searched Newton steps on Q; theta follows mu multiplicatively
       for (int in = 0; in < FI_INNER; ++in) {
@@ -202,13 +197,13 @@ __global__ __launch_bounds__(256) void foldin_kernel(
           sa += th[j] * q[j] / D[j];
           den += th[j] * is2[j] / D[j];
         }
-        sa = mc_group_sum<LG>(sa);
-        den = mc_group_sum<LG>(den);
+        sa = group_sum<LG>(sa);
+        den = group_sum<LG>(den);
         const double f = R * sa / den;
         double dmax = 0;
 #pragma unroll
         for (int j = 0; j < KJ; ++j) { dl[j] = on[j] ? (q[j] + th[j] * f) / D[j] : 0.0; dmax = fmax(dmax, fabs(dl[j])); }
-        dmax = mc_group_max<LG>(dmax);
+        dmax = group_max<LG>(dmax);
         if (!(dmax > 0.0)) break;
         double t = dmax > GDRF_FI_CAP ? GDRF_FI_CAP / dmax : 1.0;
         bool ok = false;
@@ -226,9 +221,9 @@ __global__ __launch_bounds__(256) void foldin_kernel(
             a1 += th[j] * td;
             lin += td * (q[j] - 0.5 * is2[j] * td);
           }
-          u = mc_group_sum<LG>(u);
-          a1 = mc_group_sum<LG>(a1);
-          lin = mc_group_sum<LG>(lin);
+          u = group_sum<LG>(u);
+          a1 = group_sum<LG>(a1);
+          lin = group_sum<LG>(lin);
           if (lin - R * (log1p(u) - a1) >= 0.0) { ok = true; break; }
         }
         if (!ok) break;                                      // no step accepted: a second try from the same point gives the same
@@ -254,30 +249,22 @@ __global__ __launch_bounds__(256) void foldin_kernel(
         for (int64_t e = crow2[n] + l; e < crow2[n + 1]; e += LG) {
           const int32_t w = val2[e];
           if (w == 0) continue;
-          const int cv = col2[e];
-          T p = 0;
-          for (int k = 0; k < K; ++k) p += th_row[k] * phi[(int64_t)k * V + cv];
-          a += (double)w * (double)t_log<T>(p);
+          a += (double)w * (double)t_log<T>(theta_phi(th_row, phi + col2[e], (int64_t)V, K));
           sw += (double)w;
         }
       } else {
         for (int v = l; v < V; v += LG) {
           const int32_t w = ws2[n * V + v];
           if (w == 0) continue;
-          T p = 0;
-          for (int k = 0; k < K; ++k) p += th_row[k] * phiS[k * Vs + v];
-          a += (double)w * (double)t_log<T>(p);
+          a += (double)w * (double)t_log<T>(theta_phi(th_row, phiS + v, Vs, K));
           sw += (double)w;
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // theta is rewritten by the group's next row
+      wave_lds_fence();                                      // theta is rewritten by the group's next row
       s_l += a; s_w += sw;                                   // per lane: the block sum below adds the lanes
     }
   }
-  if (mode == FI_SCORE) {
-    const double a = block_sum(s_l, scratch), b = block_sum(s_w, scratch);
-    if (tid == 0) { dpart[2 * (int64_t)blockIdx.x] = a; dpart[2 * (int64_t)blockIdx.x + 1] = b; }
-  }
+  if (mode == FI_SCORE) dpart_store2(dpart, scratch, s_l, s_w);
 }
 
 }  // namespace gdrf

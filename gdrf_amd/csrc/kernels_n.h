@@ -1383,10 +1383,7 @@ __global__ __launch_bounds__(128) void predict_rows_kernel(const TN* __restrict_
       else { const double w = (double)ws[n * V + v]; s_wlp += w * (double)t_log<T>(p); s_w += w; }
     }
   }
-  if (mode == 3) {
-    const double a = block_sum(s_wlp, scratch), b = block_sum(s_w, scratch);
-    if (threadIdx.x == 0) { dpart[2 * (int64_t)blockIdx.x] = a; dpart[2 * (int64_t)blockIdx.x + 1] = b; }
-  }
+  if (mode == 3) dpart_store2(dpart, scratch, s_wlp, s_w);
 }
 
 // the same for K > GDRF_KMAX: topics in chunks of GDRF_KMAX (the covariance row is re-evaluated per chunk), softmax over all K
@@ -1455,10 +1452,7 @@ __global__ __launch_bounds__(128) void predict_rows_bigk_kernel(const TN* __rest
     if (mode == 2) for (int v = 0; v < V; ++v) out[n * ldo + v] = (TN)pb[v];
     if (mode == 3) for (int v = 0; v < V; ++v) { const double w = (double)ws[n * V + v]; s_wlp += w * (double)t_log<T>(pb[v]); s_w += w; }
   }
-  if (mode == 3) {
-    const double a = block_sum(s_wlp, scratch), b = block_sum(s_w, scratch);
-    if (threadIdx.x == 0) { dpart[2 * (int64_t)blockIdx.x] = a; dpart[2 * (int64_t)blockIdx.x + 1] = b; }
-  }
+  if (mode == 3) dpart_store2(dpart, scratch, s_wlp, s_w);
 }
 
 // =====================================================================================

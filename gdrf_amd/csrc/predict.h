@@ -12,6 +12,7 @@
 #include "common.h"
 #include "kernels_mm.h"
 #include "kernels_n.h"
+#include "lane_group.h"
 
 namespace gdrf {
 
@@ -113,12 +114,12 @@ __global__ __launch_bounds__(256) void predict_mfma_kernel(const TN* __restrict_
         for (int b = 0; b < NB; ++b) acc[b] = MF::mma(kv, cf[(size_t)s * 4 * LDC + b * 16], acc[b]);
       }
     }
-    // accumulators -> this wave's tile [row][topic]  (LDS is in order per wave: no barrier, waits only)
+    // accumulators -> this wave's tile [row][topic]; the tile is wave-private: fences, no barrier
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r) tile[MF::crow(lane, r) * TLD + b * 16 + lr] = acc[b][r];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
     if (mode == 0) {
       for (int k = lg; k < K; k += 4)
         if (n < nrows) out[(int64_t)k * ldo + n] = (TN)tile[lr * TLD + k];
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void predict_mfma_kernel(const TN* __restrict_
       se += __shfl_xor(se, 32, 64);
       const T ise = T(1) / se;
       for (int k = lg; k < K; k += 4) tile[lr * TLD + k] *= ise;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wave_lds_fence();
       const int rows = (int)((nrows - n0 < 16) ? nrows - n0 : 16);
       if (mode == 1) {               // (n, K) row-major with ldo == K: the 16 rows are one contiguous run
         for (int e = lane; e < rows * K; e += 64) { const int r = e / K, k = e - r * K; out[(n0 + r) * ldo + k] = (TN)tile[r * TLD + k]; }
@@ -148,28 +149,24 @@ __global__ __launch_bounds__(256) void predict_mfma_kernel(const TN* __restrict_
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the tile is rewritten by the next group
+    wave_lds_fence();                                        // the tile is rewritten by the next group
   }
-  if (mode == 3) {
-    const double sa = block_sum(s_wlp, scratch), sb = block_sum(s_w, scratch);
-    if (threadIdx.x == 0) { dpart[2 * (int64_t)blockIdx.x] = sa; dpart[2 * (int64_t)blockIdx.x + 1] = sb; }
-  }
+  if (mode == 3) dpart_store2(dpart, scratch, s_wlp, s_w);
 }
 
 // f_var of gp.util.conditional(full_cov=False) from the step's forward by-products: var_kn = clamp(variance - q_n, 0) + tt_kn,
-// q_n = sum of the partial row norms of W, tt = |S_k^T w_n|^2; out = [f_loc (K, n) | f_var (K, n)]
+// q_n = sum of the partial row norms of W, tt = |S_k^T w_n|^2 (lane_group.h: row_prior_*); out = [f_loc (K, n) | f_var (K, n)]
 template <typename T>
 __global__ void predict_var_kernel(int64_t nrows, int K, const Hyper* __restrict__ h, const T* __restrict__ qpart, int nqpart, const T* __restrict__ loc,
                                    const T* __restrict__ tt, int64_t ldk, T* __restrict__ out) {
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= nrows) return;
-  T qn = 0;
-  for (int c = 0; c < nqpart; ++c) qn += qpart[(int64_t)c * ldk + n];
-  const T var = (T)h->var;
-  const T v0 = (var - qn > T(0)) ? var - qn : T(0);
+  const T v0 = row_prior_v0(qpart, nqpart, ldk, n, (T)h->var);
   for (int k = 0; k < K; ++k) {
-    out[(int64_t)k * nrows + n] = loc[(int64_t)k * ldk + n];
-    out[((int64_t)K + k) * nrows + n] = v0 + tt[(int64_t)k * ldk + n];
+    T m, fv;
+    row_prior_topic<T>(v0, loc, tt, ldk, nullptr, 0, 0, k, n, m, fv);
+    out[(int64_t)k * nrows + n] = m;
+    out[((int64_t)K + k) * nrows + n] = fv;
   }
 }
 

@@ -10,8 +10,8 @@
 // do not depend on how the rows are cut into calls.
 //
 // A group of LG lanes owns a row, lane l holds the topics l, l + LG, ... (KJ of them: LG x KJ >= K, two per lane above 64 topics); the
-// softmax maximum and sum are butterfly shuffles over the group, the same bits in every lane.  Nothing about a row depends on another
-// row or on the grid, so every output but the score's sum over rows is bit-identical however the rows are batched.
+// group's reductions, its softmax and the row prior are those of lane_group.h.  Nothing about a row depends on another row or on the
+// grid, so every output but the score's sum over rows is bit-identical however the rows are batched.
 //   mode 0  theta samples (S, n, K)
 //   mode 1  mean and variance (divisor S) of theta over the samples, (2, n, K): sums of theta_s - theta_0 and of its square in double
 //           registers (the shift removes the cancellation of E[x^2] - E[x]^2); no sample is stored
@@ -23,21 +23,11 @@
 #pragma once
 #include "common.h"
 #include "kernels_n.h"
+#include "lane_group.h"
 
 namespace gdrf {
 
 enum { MC_THETA = 0, MC_MOMENTS = 1, MC_SCORE = 2, MC_MU = 3 };
-
-template <int LG, typename T> __device__ __forceinline__ T mc_group_sum(T v) {
-#pragma unroll
-  for (int o = LG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-template <int LG, typename T> __device__ __forceinline__ T mc_group_max(T v) {
-#pragma unroll
-  for (int o = LG / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // dynamic LDS of mode 2: Phi [K][V] | theta [rows][LG KJ] | counts [rows][V], rows = 256 / LG
 template <typename T> inline size_t mc_score_lds(int K, int V, int LG, int KJ) {
@@ -71,25 +61,18 @@ __global__ __launch_bounds__(256) void predict_mc_kernel(
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int64_t n = blk * RPB + g;
     if (n >= nrows) continue;                                // the lanes of a group leave together
-    // f_var = clamp(variance - |w_n|^2, 0) + tt, as predict_var_kernel forms it
-    T qn = 0;
-    for (int c = 0; c < nqpart; ++c) qn += qpart[(int64_t)c * ldk + n];
-    const T v0 = (var0 - qn > T(0)) ? var0 - qn : T(0);
+    const T v0 = row_prior_v0(qpart, nqpart, ldk, n, var0);
     T m[KJ], sd[KJ];
 #pragma unroll
     for (int j = 0; j < KJ; ++j) {
       const int k = l + LG * j;
       m[j] = sd[j] = 0;
-      if (k < K) {
-        m[j] = loc[(int64_t)k * ldk + n];
-        if (mean) m[j] += mean[(int64_t)k * mean_sk + n * mean_sn];
-        sd[j] = v0 + tt[(int64_t)k * ldk + n];
-      }
+      if (k < K) row_prior_topic(v0, loc, tt, ldk, mean, mean_sk, mean_sn, k, n, m[j], sd[j]);
     }
     double wsum = 0;
     if (mode == MC_SCORE) {
       for (int v = l; v < V; v += LG) { const int32_t w = ws[n * V + v]; w_row[v] = w; wsum += (double)w; }
-      wsum = mc_group_sum<LG>(wsum);
+      wsum = group_sum<LG>(wsum);
     }
     T t0[KJ];
     double d1[KJ], d2[KJ];
@@ -101,7 +84,7 @@ __global__ __launch_bounds__(256) void predict_mc_kernel(
 #pragma unroll
       for (int j = 0; j < KJ; ++j) {
         const int k = l + LG * j;
-        th[j] = T(-3.0e38f);
+        th[j] = T(GROUP_PAD);
         if (k < K) {
           const T e = eps ? eps[((int64_t)s * K + k) * nrows + n] : philox_normal<T>(seed, (uint64_t)(n + row_offset), k, (uint32_t)s);
           th[j] = m[j] + sd[j] * e;
@@ -112,17 +95,7 @@ __global__ __launch_bounds__(256) void predict_mc_kernel(
         for (int j = 0; j < KJ; ++j) { const int k = l + LG * j; if (k < K) out[((int64_t)s * K + k) * nrows + n] = th[j]; }
         continue;
       }
-      T mx = th[0];
-#pragma unroll
-      for (int j = 1; j < KJ; ++j) mx = fmax(mx, th[j]);
-      mx = mc_group_max<LG>(mx);
-      T se = 0;
-#pragma unroll
-      for (int j = 0; j < KJ; ++j) { th[j] = l + LG * j < K ? t_exp<T>(th[j] - mx) : T(0); se += th[j]; }
-      se = mc_group_sum<LG>(se);
-      const T ise = T(1) / se;
-#pragma unroll
-      for (int j = 0; j < KJ; ++j) th[j] *= ise;
+      group_softmax<LG>(th, l, K);
       if (mode == MC_THETA) {
 #pragma unroll
         for (int j = 0; j < KJ; ++j) { const int k = l + LG * j; if (k < K) out[((int64_t)s * nrows + n) * K + k] = th[j]; }
@@ -134,20 +107,18 @@ __global__ __launch_bounds__(256) void predict_mc_kernel(
           d1[j] += d; d2[j] += d * d;
         }
       } else {
-        // this row's theta through LDS (a group lies inside one wave, whose LDS accesses complete in order: no barrier), lanes over words
+        // this row's theta through the group's LDS slots, lanes over words
 #pragma unroll
         for (int j = 0; j < KJ; ++j) { const int k = l + LG * j; if (k < K) th_row[k] = th[j]; }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wave_lds_fence();
         double a = 0;
         for (int v = l; v < V; v += LG) {
           const int32_t w = w_row[v];
           if (w == 0) continue;
-          T p = 0;
-          for (int k = 0; k < K; ++k) p += th_row[k] * phiS[k * V + v];
-          a += (double)w * (double)t_log<T>(p);
+          a += (double)w * (double)t_log<T>(theta_phi(th_row, phiS + v, V, K));
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // theta is rewritten by the next sample
-        a = mc_group_sum<LG>(a);
+        wave_lds_fence();                                    // theta is rewritten by the next sample
+        a = group_sum<LG>(a);
         if (s == 0) { lse_m = a; lse_a = 1.0; }
         else if (a > lse_m) { lse_a = lse_a * exp(lse_m - a) + 1.0; lse_m = a; }
         else lse_a += exp(a - lse_m);
@@ -169,10 +140,7 @@ __global__ __launch_bounds__(256) void predict_mc_kernel(
       s_w += wsum;
     }
   }
-  if (mode == MC_SCORE) {
-    const double a = block_sum(s_l, scratch), b = block_sum(s_w, scratch);
-    if (tid == 0) { dpart[2 * (int64_t)blockIdx.x] = a; dpart[2 * (int64_t)blockIdx.x + 1] = b; }
-  }
+  if (mode == MC_SCORE) dpart_store2(dpart, scratch, s_l, s_w);
 }
 
 }  // namespace gdrf

@@ -27,17 +27,11 @@
 #pragma once
 #include "common.h"
 #include "rows_vstream.h"
+#include "lane_group.h"
 
 namespace gdrf {
 
 enum { CSR_SEG = 256 };          // entries of a column segment
-
-// sum over the LG lanes of a group (LG a power of two <= 64, groups aligned): the same bits in every lane
-template <int LG, typename T> __device__ __forceinline__ T csr_group_sum(T v) {
-#pragma unroll
-  for (int o = LG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // phiT[v][k] = phi[k][v] for k < K, 0 for K <= k < Kp
 template <typename T>
@@ -104,36 +98,18 @@ __global__ __launch_bounds__(256) void rows_csr_kernel(
     T ips = 0;
     int kd = 0;
     if constexpr (MODE == VS_SOFTMAX) {
-      T mx = -3.0e38f;
 #pragma unroll
-      for (int j = 0; j < KJ; ++j) {
-        const int k = l + LG * j;
-        th[j] = k < K ? src[(int64_t)k * src_sk + n * src_sn] : T(-3.0e38f);
-        mx = fmax(mx, th[j]);
-      }
-#pragma unroll
-      for (int o = LG / 2; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-      T se = 0;
-#pragma unroll
-      for (int j = 0; j < KJ; ++j) { th[j] = l + LG * j < K ? t_exp<T>(th[j] - mx) : T(0); se += th[j]; }
-      se = csr_group_sum<LG>(se);
-      const T ise = T(1) / se;
+      for (int j = 0; j < KJ; ++j) { const int k = l + LG * j; th[j] = k < K ? src[(int64_t)k * src_sk + n * src_sn] : T(GROUP_PAD); }
+      group_softmax<LG>(th, l, K);
       T ps = 0, tmax = -1;
 #pragma unroll
       for (int j = 0; j < KJ; ++j) {
         const int k = l + LG * j;
-        th[j] *= ise;
         if (k < K) { ps += th[j] * rowsum[k]; if (th[j] > tmax) { tmax = th[j]; kd = k; } }
       }
-      ps = csr_group_sum<LG>(ps);
+      ps = group_sum<LG>(ps);
       ips = T(1) / ps;
-      // the dominant topic: the largest theta, the lowest index among equals
-#pragma unroll
-      for (int o = LG / 2; o > 0; o >>= 1) {
-        const T om = __shfl_xor(tmax, o, 64);
-        const int ok = __shfl_xor(kd, o, 64);
-        if (om > tmax || (om == tmax && ok < kd)) { tmax = om; kd = ok; }
-      }
+      group_argmax<LG>(tmax, kd);                          // the dominant topic: the largest theta, the lowest index among equals
     } else {
       T ps = 0;
 #pragma unroll
@@ -142,7 +118,7 @@ __global__ __launch_bounds__(256) void rows_csr_kernel(
         th[j] = k < K ? src[(int64_t)k * src_sk + n * src_sn] : T(0);
         if constexpr (ELBO) { if (k < K) ps += th[j] * rowsum[k]; }
       }
-      if constexpr (ELBO) { ps = csr_group_sum<LG>(ps); ips = T(1) / ps; }
+      if constexpr (ELBO) { ps = group_sum<LG>(ps); ips = T(1) / ps; }
     }
     if constexpr (ELBO) {
 #pragma unroll
@@ -169,7 +145,7 @@ __global__ __launch_bounds__(256) void rows_csr_kernel(
           f[j] = LG * j < Kp ? pc[LG * j] : T(0);
           p += th[j] * f[j];
         }
-        p = csr_group_sum<LG>(p);
+        p = group_sum<LG>(p);
         if constexpr (MODE == VS_PERP) {
           if (l == 0 && w != 0) { s_a += (double)w * (double)t_log<T>(p); s_b += (double)w; }
         } else {
@@ -192,11 +168,11 @@ __global__ __launch_bounds__(256) void rows_csr_kernel(
       T cref = 0;
 #pragma unroll
       for (int j = 0; j < KJ; ++j) if (l + LG * j == kd) cref = tb[j];
-      cref = csr_group_sum<LG>(cref);                      // one lane holds it, the others add zeros
+      cref = group_sum<LG>(cref);                      // one lane holds it, the others add zeros
       T d = 0;
 #pragma unroll
       for (int j = 0; j < KJ; ++j) if (l + LG * j < K) d += th[j] * (cref - tb[j]);
-      d = csr_group_sum<LG>(d);
+      d = group_sum<LG>(d);
 #pragma unroll
       for (int j = 0; j < KJ; ++j) { const int k = l + LG * j; if (k < K) dst[(int64_t)k * dst_ld + n] = th[j] * ((tb[j] - cref) + d); }
     } else if constexpr (MODE == VS_LINK) {
@@ -209,11 +185,7 @@ __global__ __launch_bounds__(256) void rows_csr_kernel(
   if constexpr (ELBO) {
     dpart_store<DP_LOGLIK>(dpart, scratch, 0, s_a, 0, 0);
   } else {
-    const double a = block_sum(s_a, scratch), b = block_sum(s_b, scratch);
-    if (tid == 0) {
-      double* d = dpart + 2 * (int64_t)blockIdx.x;
-      if (dacc) { d[0] += a; d[1] += b; } else { d[0] = a; d[1] = b; }
-    }
+    dpart_store2(dpart, scratch, s_a, s_b, dacc);
   }
 }
 
@@ -292,7 +264,7 @@ __global__ __launch_bounds__(256) void ll_const_csr_kernel(const int64_t* __rest
     const int64_t a = max((int64_t)0, crow[n]), b = min(nnz, crow[n + 1]);
     double tot = 0, sl = 0;
     for (int64_t e = a + l; e < b; e += 16) { const double w = (double)val[e]; tot += w; sl += lgamma(w + 1.0); }
-    tot = csr_group_sum<16>(tot);
+    tot = group_sum<16>(tot);
     if (l == 0) s += lgamma(tot + 1.0);
     s -= sl;
   }

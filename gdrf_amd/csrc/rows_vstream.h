@@ -232,11 +232,7 @@ __global__ __launch_bounds__(256) void rows_vstream_kernel(
     dpart_store<DP_LOGLIK>(dpart, scratch, 0, s_a, 0, 0);
     if constexpr (MODE == VS_LINK) { if (tid < K) cpart[(int64_t)blockIdx.x * K + tid] = cacc; }
   } else if constexpr (MODE == VS_PERP) {
-    const double a = block_sum(s_a, scratch), b = block_sum(s_b, scratch);
-    if (tid == 0) {
-      double* d = dpart + 2 * (int64_t)blockIdx.x;
-      if (dacc) { d[0] += a; d[1] += b; } else { d[0] = a; d[1] = b; }
-    }
+    dpart_store2(dpart, scratch, s_a, s_b, dacc);
   }
 }
 

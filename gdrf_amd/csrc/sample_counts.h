@@ -19,8 +19,8 @@
 // the chunk offsets by a serial sum over the 64 lanes (every lane the same bits), c[v] = offset + the chunk's running sum.  That order
 // makes c non-decreasing to the bit (x -> fl(a + x) is monotone and a chunk's last value IS the next offset), which the binary search
 // needs to be well defined.  Lanes over blocks of four tokens then draw, search the CDF and add into the counts with integer LDS
-// atomics (order-independent, so deterministic); lanes over the words store.  The LDS accesses of a wave complete in order: between
-// the phases of a wave-owned pair stands a wait, not a barrier.
+// atomics (order-independent, so deterministic); lanes over the words store.  Between the phases of a wave-owned pair stands
+// wave_lds_fence (lane_group.h), not a barrier.
 //   SC_COUNTS    out (S, n, V) int32: w_rep
 //   SC_STATS     the check statistics of the same draws, no replicate stored: with q = p / c[V-1] in double,
 //                dev_rep[s] = 2 sum_n sum_{v: w_rep > 0} w_rep log(w_rep / (T_n q_v)), dev_obs[s] the same for the observed counts ws[n]
@@ -31,6 +31,7 @@
 #pragma once
 #include "common.h"
 #include "kernels_n.h"
+#include "lane_group.h"
 
 namespace gdrf {
 
@@ -63,10 +64,6 @@ __global__ void sc_fill_uniforms_kernel(uint64_t seed, int64_t row_offset, int64
 #pragma unroll
   for (int j = 0; j < 4; ++j) if (4 * b + j < tmax) dst[4 * b + j] = r[j];
 }
-
-// the LDS accesses of one wave complete in the order they were issued: a wait (which the compiler may not move accesses across)
-// is all that separates a phase's writes from the next phase's reads by other lanes of the same wave
-__device__ __forceinline__ void sc_wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // dynamic LDS: Phi [K][V] (PHI_LDS) | zeros [Vp] int32 (SC_STATS) | per wave: cdf [Vp] double | counts [Vp] int32 | p [Vp] T (SC_STATS) |
 // theta [GDRF_SC_KP] T;  Vp = V rounded up to 4, so that every array starts on 16 bytes
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(256) void sample_counts_kernel(
   T* pS = reinterpret_cast<T*>(cnt + Vp);
   T* thS = pS + (stats ? Vp : 0);
   if (PHI_LDS || stats) __syncthreads();
-  auto phase = [&]() { if (BLK) __syncthreads(); else sc_wave_lds_fence(); };
+  auto phase = [&]() { if (BLK) __syncthreads(); else wave_lds_fence(); };      // a wave-owned pair: the fence; a workgroup-owned one: a barrier
 
   const int chunk = (V + 63) >> 6, v0 = min(V, lane * chunk), v1 = min(V, v0 + chunk);
   double a_rep = 0, a_obs = 0;

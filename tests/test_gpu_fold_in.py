@@ -36,7 +36,8 @@ DTYPES = [torch.float64, torch.float32]
 IDS = ["fp64", "fp32"]
 NS = (1, 63, 257)
 NT = 63                    # rows of the checks against the float64 iteration (its two thousand iterations run on the host)
-CASES = [(1, 9), (2, 1), (5, 9), (17, 64), (65, 65), (128, 64)]          # (K, V): every K of the issue, every V
+# (K, V): every lane-group form of the kernel (8, 16, 32, 64 lanes, two topics per lane above 64), the 16- and 64-lane ones at both ends; every V
+CASES = [(1, 9), (2, 1), (5, 9), (9, 9), (16, 64), (17, 64), (33, 9), (64, 65), (65, 65), (128, 64)]
 CASE_IDS = [f"K{k}-V{v}" for k, v in CASES]
 TOTALS = (3000, 0, 1, 20)
 CAP, INNER, HALVINGS = 4.0, 2, 12
@@ -299,7 +300,7 @@ def test_counts_and_scores_follow_from_the_returned_theta(K, V, dtype):
 
 # ---- 7
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
-@pytest.mark.parametrize("K,V", [(5, 9), (17, 64), (128, 64)], ids=["K5-V9", "K17-V64", "K128-V64"])
+@pytest.mark.parametrize("K,V", [(5, 9), (16, 9), (17, 64), (64, 64), (128, 64)], ids=["K5-V9", "K16-V9", "K17-V64", "K64-V64", "K128-V64"])
 def test_results_do_not_depend_on_how_the_rows_are_batched(K, V, dtype):
     from gdrf_amd.data import csr_rows, to_csr
     c = case(K, V, dtype)

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 TOL = {torch.float64: 1e-9, torch.float32: 5e-4}
 DTYPES = [torch.float64, torch.float32]
 IDS = ["fp64", "fp32"]
-NS, KS, SS = (1, 63, 257), (1, 2, 5, 65, 128), (1, 2, 7, 64)
+NS, KS, SS = (1, 63, 257), (1, 2, 5, 8, 9, 16, 17, 32, 33, 64, 65, 128), (1, 2, 7, 64)      # KS: the last K of every lane-group form and the first of the next
 V, NPTS = 9, (5, 4)
 
 
@@ -143,7 +143,8 @@ def test_one_sample_with_zero_eps_is_the_plug_in(dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
-@pytest.mark.parametrize("K,n,S,off", [(5, 63, 7, 1000), (128, 257, 2, 2 ** 33 + 5), (2, 1, 64, 0)])
+@pytest.mark.parametrize("K,n,S,off", [(5, 63, 7, 1000), (128, 257, 2, 2 ** 33 + 5), (2, 1, 64, 0),
+                                        (33, 4101, 2, 7)])          # 4 rows per workgroup, 1024 workgroups: the first ones take a second trip
 def test_philox_draws_equal_their_own_injection_bitwise(K, n, S, off, dtype):
     m = build(K, n, dtype)
     eng = engine(m, dtype)

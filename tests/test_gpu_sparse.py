@@ -82,7 +82,7 @@ def _both(m, eps, dtype, ws_sparse=None, setup=None, **kw):
 # ---- 1. sparse equals dense streamed, by shape and density
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
 @pytest.mark.parametrize("density", [0.02, 0.3, 1.0])
-@pytest.mark.parametrize("K,V", [(10, 50), (32, 64), (5, 300), (40, 100), (128, 65)])
+@pytest.mark.parametrize("K,V", [(10, 50), (32, 64), (5, 300), (40, 100), (128, 65), (8, 50), (9, 50), (33, 64)])
 def test_sparse_equals_dense_streamed(K, V, density, dtype):
     m, eps = _loud_oracle(K, V, 37, 9, dtype)
     _thin(m, density)
