@@ -10,6 +10,7 @@
 #include "kernels_n.h"
 #include "predict.h"
 #include "predict_mc.h"
+#include "predict_info.h"
 #include "foldin.h"
 #include "sample_counts.h"
 #include "predict_cov.h"
@@ -745,7 +746,7 @@ static int rows_lds_fail(const char* fn) {
 
 // The (LG, KJ) forms of the lane-group row kernels (lane_group.h: LG lanes own a row, KJ topics per lane, LG x KJ >= K), by K:
 //   K <=          8        16        32        64       128
-//   predictive  (8, 1)   (16, 1)   (32, 1)   (64, 1)   (64, 2)     predict_mc_kernel, foldin_kernel
+//   predictive  (8, 1)   (16, 1)   (32, 1)   (64, 1)   (64, 2)     predict_mc_kernel, predict_info_kernel, foldin_kernel
 //   sparse      (8, 1)   (16, 2)   (16, 2)   (16, 8)   (16, 8)     rows_csr_kernel, csr_phibar_seg_kernel
 // They differ and are kept: the sparse kernels pay a butterfly over the group (and LG entries fetched) per stored entry, so their groups
 // stop at 16 lanes and more topics go into a lane's registers; the predictive kernels reduce over the group per row and sample only and
@@ -1936,6 +1937,22 @@ template <typename T, typename TS> struct Impl {
     });
   }
 
+  // Entropy and information-gain maps (predict_info.h): the step's forward as in mode 4 of predict, then one kernel over the rows that
+  // integrates the entropies over the draws; Phi goes through LDS in chunks of GDRF_INFO_V_CHUNK words, so no V is too large
+  static int predict_info(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, int S, uint64_t seed, int64_t row_offset,
+                          const T* eps, double* out, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    return predictive_form(K, [&](auto fm) -> int {
+      using F = decltype(fm);
+      if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+      if (int rc = launch_lds(predict_info_kernel<T, F::LG, F::KJ>, dim3(lane_group_grid(n, F::LG)), dim3(256), info_lds<T>(K, V, F::LG, F::KJ), s,
+                              n, K, V, S, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c), (const T*)P(c->loc), (const T*)P(c->tt), c->ldk,
+                              (const T*)c->mean, c->mean_sk, c->mean_sn, eps, seed, row_offset, (const T*)P(c->phi), out)) return rc;
+      LAUNCHCHK("predict_info");
+      return 0;
+    });
+  }
+
   // Fold-in (foldin.h): the step's forward as in mode 4 of predict, then one kernel that runs the per-row MAP from the rows' own counts -
   // dense (Phi, the counts and c in LDS) or CSR (the stored entries only, Phi from global memory); mode 3 ends in the partials' sum
   static int fold_in(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, const int64_t* crow, const int32_t* col,
@@ -2352,6 +2369,18 @@ int gdrf_predict_mc(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const 
   if (mode != MC_SCORE && !out) return fail(-1, "gdrf_predict_mc", "out is required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict_mc, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, mode, num_samples, seed, row_offset, (const T*)eps, (T*)out, out_d, s);
+}
+
+int gdrf_predict_info(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, int num_samples, uint64_t seed,
+                      int64_t row_offset, const void* eps, double* out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (n < 1) return fail(-1, "gdrf_predict_info", "n must be >= 1");
+  if (n > c->ncap) return fail(-1, "gdrf_predict_info", "needs n <= n_cap");
+  if (num_samples < 1) return fail(-1, "gdrf_predict_info", "num_samples must be >= 1");
+  if (row_offset < 0) return fail(-1, "gdrf_predict_info", "row_offset must be >= 0");
+  if (!out) return fail(-1, "gdrf_predict_info", "out is required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, predict_info, c, (const T*)X, n, (const T*)Z, (const T*)params, num_samples, seed, row_offset, (const T*)eps, out, s);
 }
 
 int gdrf_fold_in(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, const int32_t* ws, const int64_t* crow, const int32_t* col,

@@ -72,6 +72,11 @@ def check_fold_args(num_iters, tol, n: int, V: int, ws, ws_score=None):
     return int(num_iters), tol
 
 
+# The rows of Engine.predict_info's (6, n) result, in order, and the words of Phi its kernel stages in LDS at a time (GDRF_INFO_V_CHUNK of
+# include/gdrf_hip.h): a larger V is served chunk by chunk.
+INFO_NAMES = ("topic_entropy", "topic_expected_entropy", "topic_information", "word_entropy", "word_expected_entropy", "word_information")
+INFO_V_CHUNK = 128
+
 # The most words (V) the count sampler serves (GDRF_SC_MAX_V of include/gdrf_hip.h): a wave keeps a row's CDF, counts and p in LDS.
 SAMPLE_COUNTS_MAX_V = 4096
 
@@ -901,6 +906,17 @@ class Engine:
         self._guess_level = self.last_jitter_level
         return run()
 
+    def _mc_seed(self, what: str, n: int, eps, seed) -> int:
+        """What the Monte-Carlo predictive calls check once the rows are known: n <= n_cap, an injected ``eps`` that the kernel can read
+        in place, a seed where there is none.  Returns the seed as the library takes it."""
+        if n > self.n_cap:
+            raise ValueError(f"{what} needs n <= n_cap ({n} > {self.n_cap})")
+        if eps is not None and (eps.dtype != self.dtype or eps.device != self.device or not eps.is_contiguous()):
+            raise ValueError(f"eps must be a contiguous {self.dtype} tensor on {self.device}")
+        if eps is None and seed is None:
+            raise ValueError(f"{what} needs a seed or an injected eps")
+        return 0 if seed is None else int(seed) & (2 ** 64 - 1)
+
     def predict_mc(self, xs: torch.Tensor, mode: int, num_samples: int, ws: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                    row_offset: int = 0, eps: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None):
         """Monte-Carlo integration over the guide's q(mu) at the rows ``xs`` (gdrf_predict_mc, csrc/predict_mc.h): mode 0 theta samples
@@ -915,13 +931,7 @@ class Engine:
             raise ValueError("predict_mc(mode=2) needs ws")
         self._chk_rows(xs, ws if mode == 2 else None)
         n = xs.shape[0]
-        if n > self.n_cap:
-            raise ValueError(f"predict_mc needs n <= n_cap ({n} > {self.n_cap})")
-        if eps is not None and (eps.dtype != self.dtype or eps.device != self.device or not eps.is_contiguous()):
-            raise ValueError(f"eps must be a contiguous {self.dtype} tensor on {self.device}")
-        if eps is None and seed is None:
-            raise ValueError("predict_mc needs a seed or an injected eps")
-        seed = 0 if seed is None else int(seed) & (2 ** 64 - 1)
+        seed = self._mc_seed("predict_mc", n, eps, seed)
         self.refresh_inducing()
 
         def run():
@@ -933,6 +943,27 @@ class Engine:
                                                 eps.data_ptr() if eps is not None else None, out.data_ptr() if out is not None else None,
                                                 self.out_d.data_ptr(), _stream_ptr(self.device)), "gdrf_predict_mc")
             return self.out_d[:2].clone() if mode == 2 else out
+
+        with self._borrowed_mean(mean, n):
+            return self._speculated(run)
+
+    def predict_info(self, xs: torch.Tensor, num_samples: int, seed: Optional[int] = None, row_offset: int = 0,
+                     eps: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The entropy and information-gain maps at the rows ``xs`` (gdrf_predict_info, csrc/predict_info.h), (6, n) float64 in the order
+        of INFO_NAMES, integrated over the ``num_samples`` draws predict_mc makes under the same ``seed`` / ``row_offset`` / ``eps`` /
+        ``mean`` without storing a sample.  n <= n_cap.  Same jitter-level protocol as predict()."""
+        S = check_mc_args(num_samples, self.K, int(xs.shape[0]), eps)
+        self._chk_rows(xs, None)
+        n = xs.shape[0]
+        seed = self._mc_seed("predict_info", n, eps, seed)
+        self.refresh_inducing()
+
+        def run():
+            out = torch.empty(len(INFO_NAMES), n, dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.gdrf_predict_info(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), S, seed,
+                                                  int(row_offset), eps.data_ptr() if eps is not None else None, out.data_ptr(),
+                                                  _stream_ptr(self.device)), "gdrf_predict_info")
+            return out
 
         with self._borrowed_mean(mean, n):
             return self._speculated(run)

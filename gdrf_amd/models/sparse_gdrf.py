@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
-from ..engine import Engine, check_count_args, check_fold_args, check_joint_args, check_mc_args
+from ..engine import INFO_NAMES, Engine, check_count_args, check_fold_args, check_joint_args, check_mc_args
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -236,6 +236,12 @@ class ModelSnapshot:
 
     def predictive_perplexity(self, x, w, num_samples=64, seed=None):
         return self.restore().predictive_perplexity(x, w, num_samples, seed=seed)
+
+    def information(self, xs, num_samples=256, seed=None, eps=None):
+        return self.restore().information(xs, num_samples, seed=seed, eps=eps)
+
+    def most_informative(self, xs, count, criterion="word_information", num_samples=256, seed=None):
+        return self.restore().most_informative(xs, count, criterion, num_samples, seed=seed)
 
     def infer_topic_probs(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
         return self.restore().infer_topic_probs(xs, ws, num_iters, tol, return_diagnostics)
@@ -647,7 +653,7 @@ class SparseMultinomialGDRF:
 
     # ------------------------------------------------------------------ Monte-Carlo predictive path (csrc/predict_mc.h)
     def _predict_mc(self, xs_s: torch.Tensor, mode: int, S: int, ws_d=None, seed=None, eps=None) -> torch.Tensor:
-        """Engine.predict_mc on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows, each with its row_offset: the draws are keyed by the global row, so
+        """Engine.predict_mc (``mode`` "info": Engine.predict_info) on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows, each with its row_offset: the draws are keyed by the global row, so
         the result does not depend on the piece size.  The pieces are joined along the row axis; mode 2's two sums are added."""
         n = xs_s.shape[0]
         eng = self._engine_for(min(n, MC_PIECE_ROWS))
@@ -660,9 +666,9 @@ class SparseMultinomialGDRF:
         parts = []
         for a in range(0, n, eng.n_cap):
             b = min(n, a + eng.n_cap)
-            parts.append(eng.predict_mc(xs_s[a:b], mode, S, ws=None if ws_d is None else ws_d[a:b], seed=seed, row_offset=a,
-                                        eps=None if eps is None else eps[:, :, a:b].contiguous(),
-                                        mean=None if mean is None else mean[:, a:b]))
+            kw = dict(seed=seed, row_offset=a, eps=None if eps is None else eps[:, :, a:b].contiguous(), mean=None if mean is None else mean[:, a:b])
+            parts.append(eng.predict_info(xs_s[a:b], S, **kw) if mode == "info" else
+                         eng.predict_mc(xs_s[a:b], mode, S, ws=None if ws_d is None else ws_d[a:b], **kw))
         if mode == 2:
             return torch.stack(parts).sum(0)
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=2 if mode == 3 else 1)
@@ -704,6 +710,36 @@ class SparseMultinomialGDRF:
         xs_s, ws_d = self._prepare_inputs(x, w)
         s = self._predict_mc(xs_s, 2, S, ws_d=ws_d, seed=seed)
         return torch.exp(-s[0] / s[1])
+
+    # ------------------------------------------------------------------ entropy and information-gain maps (csrc/predict_info.h)
+    def information(self, xs, num_samples: int = 256, seed=None, eps=None) -> Dict[str, torch.Tensor]:
+        """Where the field is still uncertain, and how much of that a sample at x would remove: a dict of six (N,) float64 tensors over
+        ``num_samples`` draws theta_s of sample_topic_probs (the same ``seed`` / ``eps``), p_s = theta_s Phi, h(q) = -sum q log q:
+        ``topic_entropy`` h(mean_s theta_s), ``topic_expected_entropy`` mean_s h(theta_s), ``topic_information`` their difference, and
+        ``word_entropy`` / ``word_expected_entropy`` / ``word_information`` the same for p.  The information values are the Monte-Carlo
+        estimates of the mutual information between one token's topic (word) observed at x and the latent field there (BALD); they are
+        not clamped, 0 <= word_information <= topic_information <= log min(K, S) up to rounding.  Reduced on the device without storing
+        a sample, over pieces of at most the engine's n_cap rows as the other Monte-Carlo calls (_predict_mc)."""
+        if self._link_function is not None:
+            raise NotImplementedError("information with a custom link_function: the kernel fuses the softmax link")
+        n = int(torch.as_tensor(xs).shape[0])
+        S = check_mc_args(num_samples, self._K, n, eps)
+        xs_s, _ = self._prepare_inputs(xs)
+        out = self._predict_mc(xs_s, "info", S, seed=seed, eps=eps)
+        return dict(zip(INFO_NAMES, out))
+
+    def most_informative(self, xs, count: int, criterion: str = "word_information", num_samples: int = 256,
+                         seed=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(indices, scores) of the ``count`` rows of ``xs`` with the largest ``criterion`` (one of the six names of information()), in
+        descending order, equal scores by the lower index.  Each row is ranked on its own: the rows are not chosen to be non-redundant."""
+        if criterion not in INFO_NAMES:
+            raise ValueError(f"criterion must be one of {INFO_NAMES}, got {criterion!r}")
+        n = int(torch.as_tensor(xs).shape[0])
+        if isinstance(count, bool) or int(count) != count or not 1 <= int(count) <= n:
+            raise ValueError(f"count must be an integer in [1, N = {n}], got {count!r}")
+        scores = self.information(xs, num_samples, seed=seed)[criterion]
+        order = torch.sort(scores, descending=True, stable=True).indices[:int(count)]
+        return order, scores[order]
 
     # ------------------------------------------------------------------ fold-in: observed samples from their own counts (csrc/foldin.h)
     def _fold_in(self, xs, ws, mode: int, num_iters, tol, ws_score=None, return_diagnostics: bool = False):

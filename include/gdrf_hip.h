@@ -342,6 +342,24 @@ enum { GDRF_MC_THETA = 0, GDRF_MC_MOMENTS = 1, GDRF_MC_SCORE = 2, GDRF_MC_MU = 3
 int gdrf_predict_mc(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const int32_t* ws_dev, int mode,
                     int num_samples, uint64_t seed, int64_t row_offset, const void* eps_dev, void* out_dev, double* out_d_dev, void* stream);
 
+/* Per-location entropy and information-gain maps (csrc/predict_info.h): how uncertain the field is at the n new inputs and how much of
+ * that comes from the latent field not being known there - the part that shrinks when the location is sampled.  Over the S = num_samples
+ * draws gdrf_predict_mc makes (the same mu, theta_s, p_s = theta_s Phi, the same eps_dev / seed / row_offset, bit for bit), with
+ * h(q) = -sum_i q_i log q_i (0 log 0 = 0) and theta_bar = (1/S) sum_s theta_s, out_dev (6, n) doubles holds the rows
+ *   0  topic_entropy           h(theta_bar)                     3  word_entropy           h(theta_bar Phi)
+ *   1  topic_expected_entropy  (1/S) sum_s h(theta_s)           4  word_expected_entropy  (1/S) sum_s h(p_s)
+ *   2  topic_information       row 0 - row 1                    5  word_information       row 3 - row 4
+ * Rows 2 and 5 are the Monte-Carlo estimates of the mutual information between the topic (the word) of one token observed at x and the
+ * latent field there (BALD): Jensen-Shannon divergences of the sampled distributions, 0 <= row 5 <= row 2 <= log min(K, S) up to
+ * rounding, returned as computed (not clamped).  theta_bar is bit for bit the mean GDRF_MC_MOMENTS returns.  p and p log p are formed in
+ * the array precision, every sum over topics, words and samples in double.  No sample is stored; Phi passes through LDS in chunks of
+ * GDRF_INFO_V_CHUNK words, so any V is served, and every K the context supports; 1 <= num_samples <= 65535.
+ * n <= n_cap.  Runs the step's forward (as mode 4 of gdrf_predict), so it overwrites the same workspaces; every step recomputes them.
+ * Every output is bit-identical however the rows are batched (no atomics, no sum over rows).  Needs gdrf_factorize(). */
+#define GDRF_INFO_V_CHUNK 128
+int gdrf_predict_info(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, int num_samples, uint64_t seed,
+                      int64_t row_offset, const void* eps_dev, double* out_dev, void* stream);
+
 /* Fold-in (csrc/foldin.h): the topic proportions of OBSERVED rows from their own counts, with the GP as the prior.  For row n, with
  *   m_k = f_loc[k][n] + mean[k][n],  s_k = f_var[k][n] + noise   ((f_loc, f_var) as mode 4 of gdrf_predict gives them; s_k is the scale of the
  *   model's mu site, Normal(f_loc, f_var + noise), gdrf/models/sparse_gdrf.py:354-357),  R = sum_v w_v,  theta = softmax(mu),  p = theta Phi:
