@@ -14,6 +14,7 @@
 #include "foldin.h"
 #include "sample_counts.h"
 #include "predict_cov.h"
+#include "select_batch.h"
 #include "rows_lds.h"
 #include "rows_mfma.h"
 #include "rows_vstream.h"
@@ -122,6 +123,10 @@ struct gdrf_ctx {
   // matrix (jgnp, jgnp), T_k (K, jtrows, Mp), the sampler's V (jsk, Mp) and zeta (jzel elements), all in the solve precision; its failure flag
   void *jW, *jR, *jG, *jT, *jV, *jZ; int64_t jrows, jnp, jgnp, jtrows, jsk, jzel; int* jflag;
   int64_t jlast_n, jlast_sk;  // rows and (sample, topic) pairs of the gdrf_sample_joint whose W, R, V and zeta are still in place (0: none)
+  // the batch choice (select_batch.h), allocated on first use and grown with the call: the candidates and the given rows in one array
+  // (sX, sxrows rows), the factor columns c[k][t][row] (sC) and the conditional variances d[k][row] (sD) in the solve precision, the picked
+  // flags (sTk); of fixed size: B = (w_p, b_k) with the pivot's history and variances behind it (sB), the pass's partials and the picks (sPg, sPi)
+  void *sX, *sC, *sD, *sB; int* sTk; double* sPg; long long* sPi; int64_t sxrows, sc_el, sd_el, stk_el;
   std::vector<void*> allocs;
   // optional per-kernel HIP-event timing (gdrf_set_timing): events recorded on the launch stream
   int timing;
@@ -2029,19 +2034,24 @@ template <typename T, typename TS> struct Impl {
     if (EPI == JT_RESID && ard_fwd(c)) hipLaunchKernelGGL((joint_nt_kernel<TS, TB, T, TO, EPI, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((joint_nt_kernel<TS, TB, T, TO, EPI, false>), grid, dim3(256), 0, s, p);
   }
-  // the step's forward as mode 4 of predict runs it, then W in the solve precision (c->jW) and R = K_** - W W^T (c->jR, leading dimension
-  // *np_out = round_up(n, 32))
+  // the step's forward as mode 4 of predict runs it, then W = K_nm L^-T in the solve precision (c->jW): none of the n x n buffers
+  static int joint_w(gdrf_ctx* c, const T* X, int64_t n, const T* params, hipStream_t s) {
+    const int Mp = c->Mp;
+    if (int rc = joint_buf(c, &c->jW, &c->jrows, n, (size_t)n * Mp * sizeof(TS))) return rc;
+    if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+    JointNT<TS, TS, T, TS> w{(const TS*)Q(c->Knm), Mp, 0, n, (const TS*)Q(c->Linv), Mp, 0, Mp, Mp, Q(c->jW), Mp, 0, nullptr, 0, nullptr, 0, 0, nullptr};
+    joint_nt<JT_PLAIN>(c, w, 1, s);
+    return 0;
+  }
+  // joint_w, then R = K_** - W W^T (c->jR, leading dimension *np_out = round_up(n, 32))
   static int joint_forward(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, int64_t* np_out, hipStream_t s) {
     const int Mp = c->Mp;
     const int64_t np = round_up(n, 32);
-    if (int rc = joint_buf(c, &c->jW, &c->jrows, n, (size_t)n * Mp * sizeof(TS))) return rc;
     if (int rc = joint_buf(c, &c->jR, &c->jnp, np, (size_t)np * np * sizeof(TS))) return rc;
     if (!c->jflag)
       if (int rc = ctx_alloc(c, &c->jflag, 64, "hipMalloc(joint posterior)", true)) return rc;
-    if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+    if (int rc = joint_w(c, X, n, params, s)) return rc;
     const T* Xc = c->per ? (const T*)c->Xe : X;               // periodic and product contexts: the embedded rows the forward just wrote
-    JointNT<TS, TS, T, TS> w{(const TS*)Q(c->Knm), Mp, 0, n, (const TS*)Q(c->Linv), Mp, 0, Mp, Mp, Q(c->jW), Mp, 0, nullptr, 0, nullptr, 0, 0, nullptr};
-    joint_nt<JT_PLAIN>(c, w, 1, s);
     JointNT<TS, TS, T, TS> r{(const TS*)Q(c->jW), Mp, 0, n, (const TS*)Q(c->jW), Mp, 0, n, Mp, Q(c->jR), np, 0, nullptr, 0, Xc, c->D, c->kind, c->hyp};
     joint_nt<JT_RESID>(c, r, 1, s);
     LAUNCHCHK("joint posterior (W, R)");
@@ -2102,6 +2112,58 @@ template <typename T, typename TS> struct Impl {
     hipLaunchKernelGGL((joint_sample_kernel<TS, T>), grid, dim3(256), 0, s, (const TS*)Q(c->jV), nsk, K, (const TS*)Q(c->jW), Mp, (const TS*)Q(c->jZ),
                        (const TS*)Q(c->jG), n, np, (const T*)c->mean, c->mean_sk, c->mean_sn, out);
     LAUNCHCHK("sample_joint (draw)");
+    return 0;
+  }
+
+  // ---- the greedy choice of a non-redundant batch of rows (select_batch.h): the forward over the n candidates and the G given rows in one
+  // array, W in the solve precision, then per pick the preparation and the pass over the rows; nothing is read back in between
+  static int select_batch(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const T* given, int G, int count, double noise,
+                          int64_t* idx_out, double* gains_out, double* var_out, hipStream_t s) {
+    const int Mp = c->Mp, M = c->M, K = c->K, Tm = G + count;
+    const int64_t nt = n + G;
+    const size_t pass_lds = sel_pass_lds<TS>(Mp);
+    if (pass_lds > 150 * 1024) return fail(-1, "gdrf_select_batch", "16 right-hand sides of M solve-precision elements exceed the LDS budget (150 KB)");
+    if (int rc = joint_buf(c, &c->sC, &c->sc_el, (int64_t)K * Tm * nt, (size_t)K * Tm * nt * sizeof(TS))) return rc;
+    if (int rc = joint_buf(c, &c->sD, &c->sd_el, (int64_t)K * nt, (size_t)K * nt * sizeof(TS))) return rc;
+    if (int rc = joint_buf(c, (void**)&c->sTk, &c->stk_el, nt, (size_t)nt * sizeof(int))) return rc;
+    if (!c->sB) {
+      // B (K + 1, Mp), the pivot's history (K, GDRF_SELECT_MAX_PICKS) and its variances (K); the partials; their indices and the picks
+      const size_t nb = (size_t)(K + 1) * Mp + (size_t)K * GDRF_SELECT_MAX_PICKS + K;
+      if (int rc = ctx_alloc(c, &c->sB, nb * sizeof(TS), "hipMalloc(batch choice)")) return rc;
+      if (int rc = ctx_alloc(c, &c->sPg, (size_t)GDRF_SEL_PARTS * sizeof(double), "hipMalloc(batch choice)")) return rc;
+      if (int rc = ctx_alloc(c, &c->sPi, (size_t)(GDRF_SEL_PARTS + GDRF_SELECT_MAX_PICKS) * sizeof(long long), "hipMalloc(batch choice)")) return rc;
+    }
+    const T* Xa = X;
+    if (G > 0) {
+      const size_t row = (size_t)c->Dr * c->esz;
+      if (int rc = joint_buf(c, &c->sX, &c->sxrows, nt, (size_t)nt * row)) return rc;
+      HIPCHK(hipMemcpyAsync(c->sX, X, (size_t)n * row, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync((char*)c->sX + (size_t)n * row, given, (size_t)G * row, hipMemcpyDeviceToDevice, s));
+      Xa = (const T*)c->sX;
+    }
+    c->jlast_n = c->jlast_sk = 0;              // W is about to be rewritten: no gdrf_sample_joint_retry on the old one
+    if (int rc = joint_w(c, Xa, nt, params, s)) return rc;
+    const T* Xc = c->per ? (const T*)c->Xe : Xa;
+    TS* B = Q(c->sB);
+    TS* hp = B + (size_t)(K + 1) * Mp;
+    TS* dp = hp + (size_t)K * GDRF_SELECT_MAX_PICKS;
+    long long* picks = c->sPi + GDRF_SEL_PARTS;
+    const int nparts = (int)std::min<int64_t>((nt + GDRF_SEL_ROWS - 1) / GDRF_SEL_ROWS, GDRF_SEL_PARTS);
+    hipLaunchKernelGGL((select_init_kernel<TS, T>), dim3((unsigned)nparts), dim3(256), 0, s, n, nt, K, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c),
+                       (const T*)P(c->tt), c->ldk, noise, Q(c->sD), c->sTk, c->sPg, c->sPi);
+    SelPrep<TS, T> pr{0, G, K, M, Mp, Tm, nparts, n, nt, c->sPg, c->sPi, (const TS*)Q(c->jW), (const T*)P(c->S), (const T*)P(c->ST), (const TS*)Q(c->sC),
+                      (const TS*)Q(c->sD), B, hp, dp, picks, c->sTk, (long long*)idx_out, gains_out};
+    SelPass<TS, T> ps{0, K, Mp, Tm, c->D, c->kind, n, nt, noise, (const Hyper*)c->hyp, Xc, (const TS*)Q(c->jW), (const TS*)B, (const TS*)hp,
+                      (const TS*)dp, Q(c->sC), Q(c->sD), picks, c->sTk, c->sPg, c->sPi};
+    for (int t = 0; t < Tm; ++t) {
+      pr.t = ps.t = t;
+      if (int rc = launch_lds((select_prep_kernel<TS, T>), dim3((unsigned)K), dim3(256), (size_t)2 * Mp * sizeof(TS), s, pr)) return rc;
+      if (int rc = ard_fwd(c) ? launch_lds((select_pass_kernel<TS, T, true>), dim3((unsigned)nparts), dim3(256), pass_lds, s, ps)
+                              : launch_lds((select_pass_kernel<TS, T, false>), dim3((unsigned)nparts), dim3(256), pass_lds, s, ps)) return rc;
+    }
+    if (var_out)
+      hipLaunchKernelGGL(select_var_out_kernel<TS>, dim3((unsigned)((n + 255) / 256), (unsigned)K), dim3(256), 0, s, (const TS*)Q(c->sD), n, nt, var_out);
+    LAUNCHCHK("select_batch");
     return 0;
   }
 };
@@ -2469,6 +2531,21 @@ int gdrf_sample_joint_retry(gdrf_ctx* c, int64_t n, int num_samples, double jitt
   if (!out) return fail(-1, "gdrf_sample_joint_retry", "out is required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, joint_draw, c, n, num_samples, jitter_total, (T*)out, s);
+}
+
+int gdrf_select_batch(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, const void* given, int G, int count, double noise,
+                      int64_t* idx_out, double* gains_out, double* var_out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (n < 1) return fail(-1, "gdrf_select_batch", "n must be >= 1");
+  if (G < 0) return fail(-1, "gdrf_select_batch", "G must be >= 0");
+  if (n + G > c->ncap) return fail(-1, "gdrf_select_batch", "needs n + G <= n_cap");
+  if (count < 1 || count > n) return fail(-1, "gdrf_select_batch", "count must be in [1, n]");
+  if (G + count > GDRF_SELECT_MAX_PICKS) return fail(-1, "gdrf_select_batch", "G + count exceeds GDRF_SELECT_MAX_PICKS (256)");
+  if (!(noise > 0) || !std::isfinite(noise)) return fail(-1, "gdrf_select_batch", "noise must be positive and finite");
+  if (G > 0 && !given) return fail(-1, "gdrf_select_batch", "G > 0 needs given_dev");
+  if (!idx_out || !gains_out) return fail(-1, "gdrf_select_batch", "idx_out and gains_out are required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, select_batch, c, (const T*)X, n, (const T*)Z, (const T*)params, (const T*)given, G, count, noise, idx_out, gains_out, var_out, s);
 }
 
 int gdrf_joint_failed(gdrf_ctx* c, int* failed, void* stream) {

@@ -152,6 +152,39 @@ def check_joint_args(num_samples, K: int, M: int, n: int, xi=None, zeta=None) ->
     return S
 
 
+# The most pivots a batch choice takes (Engine.select_batch): the given rows and the free picks together (GDRF_SELECT_MAX_PICKS of
+# include/gdrf_hip.h).  Its factor storage is K x (G + count) x (n + G) solve-precision elements.
+SELECT_MAX_PICKS = 256
+
+
+def check_select_args(count, noise, n: int, given=None, dims: Optional[int] = None):
+    """The argument errors of the batch choice (Engine.select_batch and the model method above it), raised before the device is touched:
+    an integral ``count`` in [1, n], a ``given`` of shape (G, dims) with G + count <= SELECT_MAX_PICKS, a positive finite ``noise`` (None:
+    the caller fills in the model's own and the check is skipped).  Returns (count as an int, noise as a float or None, G)."""
+    if n < 1:
+        raise ValueError(f"select_batch needs at least one row, got {n}")
+    if isinstance(count, bool) or isinstance(count, str) or int(count) != count:
+        raise ValueError(f"count must be an integer, got {count!r}")
+    cnt = int(count)
+    if not 1 <= cnt <= n:
+        raise ValueError(f"count must be in [1, N = {n}], got {count}")
+    G = 0
+    if given is not None:
+        shape = tuple(given.shape)
+        if len(shape) == 1 and dims == 1:
+            shape = (shape[0], 1)
+        if len(shape) != 2 or (dims is not None and shape[1] != dims):
+            raise ValueError(f"given must have shape (G, {dims}), the columns of xs, got {tuple(given.shape)}")
+        G = int(shape[0])
+    if G + cnt > SELECT_MAX_PICKS:
+        raise ValueError(f"the given rows and the picks together are at most SELECT_MAX_PICKS = {SELECT_MAX_PICKS}, got {G} + {cnt}")
+    if noise is not None:
+        if isinstance(noise, bool) or not math.isfinite(float(noise)) or not float(noise) > 0.0:
+            raise ValueError(f"noise must be a positive finite number, got {noise!r}")
+        noise = float(noise)
+    return cnt, noise, G
+
+
 class Engine:
     """One device context for fixed (n_cap, M, K, V, D, dtype, kernel)."""
 
@@ -1127,3 +1160,32 @@ class Engine:
                     return out
             raise RuntimeError(f"sample_joint: R + j I has a non-positive pivot at every one of the {self.maxjitter} jitter levels, "
                                "the residual covariance is unstable")
+
+    # ---- the greedy choice of a non-redundant batch of rows (csrc/select_batch.h) -----------------------
+    def select_batch(self, xs: torch.Tensor, count: int, noise: float, given: Optional[torch.Tensor] = None, return_variance: bool = False):
+        """The ``count`` rows of ``xs`` a greedy maximisation of I(A) = 1/2 sum_k log det(I + C_k[A, A] / noise) picks (gdrf_select_batch,
+        csrc/select_batch.h has the definition), C_k the covariances of predict_cov: (indices (count,) int64 in the order picked, gains
+        (count,) float64[, variance (K, n) float64: the conditional variances after the last pick]).  ``given`` (G, D): rows already
+        sampled, conditioned on first.  All rows at once: n + G <= n_cap and G + count <= SELECT_MAX_PICKS.  No n x n matrix is formed.
+        Same jitter-level protocol for K_uu as predict()."""
+        count, noise, G = check_select_args(count, noise, int(xs.shape[0]), given, int(xs.shape[1]) if xs.dim() == 2 else None)
+        if noise is None:
+            raise ValueError("noise must be a positive finite number, got None")
+        self._chk_rows(xs)
+        n = xs.shape[0]
+        if G:
+            self._chk_rows(given)
+        if n + G > self.n_cap:
+            raise ValueError(f"select_batch needs n + G <= n_cap ({n} + {G} > {self.n_cap})")
+        self.refresh_inducing()
+
+        def run():
+            idx = torch.empty(count, dtype=torch.int64, device=self.device)
+            gains = torch.empty(count, dtype=torch.float64, device=self.device)
+            var = torch.empty(self.K, n, dtype=torch.float64, device=self.device) if return_variance else None
+            _lib.check(self.lib.gdrf_select_batch(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(),
+                                                  given.data_ptr() if G else None, G, count, noise, idx.data_ptr(), gains.data_ptr(),
+                                                  var.data_ptr() if var is not None else None, _stream_ptr(self.device)), "gdrf_select_batch")
+            return (idx, gains, var) if return_variance else (idx, gains)
+
+        return self._speculated(run)

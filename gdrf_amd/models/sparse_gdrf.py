@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
-from ..engine import INFO_NAMES, Engine, check_count_args, check_fold_args, check_joint_args, check_mc_args
+from ..engine import INFO_NAMES, Engine, check_count_args, check_fold_args, check_joint_args, check_mc_args, check_select_args
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -242,6 +242,9 @@ class ModelSnapshot:
 
     def most_informative(self, xs, count, criterion="word_information", num_samples=256, seed=None):
         return self.restore().most_informative(xs, count, criterion, num_samples, seed=seed)
+
+    def select_batch(self, xs, count, noise=None, given=None, return_variance=False):
+        return self.restore().select_batch(xs, count, noise=noise, given=given, return_variance=return_variance)
 
     def infer_topic_probs(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
         return self.restore().infer_topic_probs(xs, ws, num_iters, tol, return_diagnostics)
@@ -731,7 +734,8 @@ class SparseMultinomialGDRF:
     def most_informative(self, xs, count: int, criterion: str = "word_information", num_samples: int = 256,
                          seed=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(indices, scores) of the ``count`` rows of ``xs`` with the largest ``criterion`` (one of the six names of information()), in
-        descending order, equal scores by the lower index.  Each row is ranked on its own: the rows are not chosen to be non-redundant."""
+        descending order, equal scores by the lower index.  Each row is ranked on its own: the rows are not chosen to be non-redundant.
+        select_batch(xs, count) chooses a non-redundant batch."""
         if criterion not in INFO_NAMES:
             raise ValueError(f"criterion must be one of {INFO_NAMES}, got {criterion!r}")
         n = int(torch.as_tensor(xs).shape[0])
@@ -740,6 +744,30 @@ class SparseMultinomialGDRF:
         scores = self.information(xs, num_samples, seed=seed)[criterion]
         order = torch.sort(scores, descending=True, stable=True).indices[:int(count)]
         return order, scores[order]
+
+    # ------------------------------------------------------------------ non-redundant batches of locations (csrc/select_batch.h)
+    def select_batch(self, xs, count: int, noise=None, given=None, return_variance: bool = False):
+        """Where to take the next ``count`` samples: (indices (count,) int64, gains (count,) float64[, variance (K, N) float64]) of the
+        rows of ``xs`` that a greedy maximisation of I(A) = 1/2 sum_k log det(I + C_k[A, A] / s2) picks, in the order picked.  C_k is
+        ``posterior(xs)[1][k]`` (never formed here: N is not limited by JOINT_MAX_ROWS), s2 = ``noise`` the variance of the observation
+        noise (None: the model's ``noise`` parameter, which governs the independent term between the field and the mu site that a sample's
+        tokens inform about).  I(A) is the mutual information between the K latent fields and noisy observations of them at the rows A;
+        it is monotone and submodular, so the greedy batch is within (1 - 1/e) of the best one.  gains[t] is what pick t added:
+        sum(gains) = I(picked), and the gains never increase.  Equal gains go to the lower index.  ``given`` (G, D): places already
+        sampled but not trained on yet; they are conditioned on first, are no candidates and return no gain.  ``return_variance``: the
+        variance of every f_k(x_j) given noisy observations at ``given`` and the picks (it starts as ``forward(xs)[1]``).  The link, Phi
+        and the mean_function do not enter.  All rows in one call - a greedy choice cannot be cut into row pieces -, G + count <=
+        SELECT_MAX_PICKS.  most_informative ranks each row on its own instead."""
+        xs_t = torch.as_tensor(xs)
+        g_t = None if given is None else torch.as_tensor(given)
+        n = int(xs_t.shape[0])
+        count, noise, G = check_select_args(count, noise, n, g_t, 1 if xs_t.dim() == 1 else int(xs_t.shape[1]))
+        xs_s, _ = self._prepare_inputs(xs_t)
+        given_s = self._prepare_inputs(g_t)[0] if G else None
+        eng = self._engine_for(n + G)
+        if noise is None:
+            noise = check_select_args(count, float(self.noise), n)[1]
+        return eng.select_batch(xs_s, count, noise, given=given_s, return_variance=return_variance)
 
     # ------------------------------------------------------------------ fold-in: observed samples from their own counts (csrc/foldin.h)
     def _fold_in(self, xs, ws, mode: int, num_iters, tol, ws_score=None, return_diagnostics: bool = False):

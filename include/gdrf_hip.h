@@ -453,6 +453,27 @@ int gdrf_sample_joint_retry(gdrf_ctx* ctx, int64_t n, int num_samples, double ji
 /* Did the factorisation of the last gdrf_sample_joint() / gdrf_sample_joint_retry() hit a non-positive pivot?  Synchronises the stream. */
 int gdrf_joint_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
 
+/* The greedy choice of a non-redundant batch of `count` of the n rows X (csrc/select_batch.h).  With C_k the joint posterior covariances of
+ * gdrf_predict_cov and s2 = noise > 0 an observation-noise variance, the information in noisy observations f_k(x_a) + N(0, s2) at the rows A is
+ *   I(A) = 1/2 sum_k log det(I + C_k[A, A] / s2)
+ * (monotone and submodular).  `count` times the row not picked yet with the largest gain g_j = 1/2 sum_k log1p(max(d_k[j], 0) / s2) is
+ * picked, ties to the lower index; d_k[j] is the variance of f_k(x_j) given noisy observations at every pick so far, and starts as mode 4's
+ * f_var (its clamp included) widened to the solve precision.  Pick t at row p updates, per topic,
+ *   c_k,t[j] = (C_k[j][p] - sum_{s<t} c_k,s[j] c_k,s[p]) / sqrt(d_k[p] + s2),    d_k[j] -= c_k,t[j]^2
+ * so sum_t gain_t = I(picked).  s2 > 0 keeps every pivot positive: there is no failure flag and no jitter.  Link, Phi and mean do not enter.
+ *   given_dev  G rows (scaled once, as X), or NULL with G = 0: places already sampled.  They are forced pivots, in their order, ahead of the
+ *              free picks; they are no candidates and their gains are not returned
+ *   idx_out    count int64 row indices in the order picked;  gains_out  count doubles, the gain of each pick when it was made
+ *   var_out    NULL, or (K, n) doubles: d after the last pick
+ * No n x n matrix is formed: one covariance column per pick comes from the solve-precision W of gdrf_predict_cov.  n >= 1, G >= 0,
+ * n + G <= n_cap, 1 <= count <= n, G + count <= GDRF_SELECT_MAX_PICKS, noise positive and finite; 16 M solve-precision elements must fit
+ * the pass's LDS (M <= 1120 with the f64 solve).  Needs gdrf_factorize().  Runs the step's forward (as mode 4) over the n + G rows, so it
+ * overwrites the same workspaces; its own buffers ((n + G) M, K (G + count) (n + G) and K (n + G) solve-precision elements) are allocated on
+ * first use and grow with the call.  Nothing is read back between the picks.  No atomics: bit-identical from call to call. */
+#define GDRF_SELECT_MAX_PICKS 256
+int gdrf_select_batch(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const void* given_dev, int G, int count,
+                      double noise, int64_t* idx_out_dev, double* gains_out_dev, double* var_out_dev, void* stream);
+
 /* Did the last gdrf_factorize() hit a non-positive pivot?  Synchronises the stream. */
 int gdrf_chol_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
 
