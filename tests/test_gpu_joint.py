@@ -39,15 +39,27 @@ def rnd(t, dtype):
     return t.to(dtype).double()
 
 
+def grid_points(grid, M, span=1.0):
+    """the first M points, last axis fastest, of the grid of `grid` points per axis on [0, span]^D"""
+    axes = [torch.linspace(0.0, span, g, dtype=torch.float64) for g in grid]
+    return torch.stack([a.flatten() for a in torch.meshgrid(*axes, indexing="ij")], -1).reshape(-1, len(grid))[:M]
+
+
 class Case:
     """One engine and the float64 numbers it was loaded with.  kernel: "rbf", "matern52", "ard", "periodic" (D = 1) or "product"
-    (RBF on axis 0 times Periodic on axis 1)."""
+    (RBF on axis 0 times Periodic on axis 1).  D: 2 unless given ("rbf", "matern52" and "ard" take up to GDRF_DMAX = 4).  grid: the
+    inducing points are the first M points of that grid on [0, span]^D, and the rows are drawn from the same cube.  pure: the all-fp32
+    context (dtype float32, the solves in float32 too).  engine=False: the numbers alone, no device."""
 
-    def __init__(self, kernel, M, K, dtype, whiten=True, n_cap=129, seed=0, jitter=None, maxjitter=15, Z=None, ls=0.3):
-        from gdrf_amd.engine import Engine
+    def __init__(self, kernel, M, K, dtype, whiten=True, n_cap=129, seed=0, jitter=None, maxjitter=15, Z=None, ls=0.3, D=None, grid=None,
+                 span=1.0, pure=False, engine=True):
         g = torch.Generator().manual_seed(10 * M + K + seed)
-        self.kernel, self.M, self.K, self.dtype, self.whiten = kernel, M, K, dtype, whiten
-        self.D = D = 1 if kernel == "periodic" else 2
+        self.kernel, self.M, self.K, self.dtype, self.whiten, self.pure, self.span = kernel, M, K, dtype, whiten, pure, span
+        self.D = D = (1 if kernel == "periodic" else 2) if D is None else D
+        self.grid = grid
+        if grid is not None:
+            assert Z is None and len(grid) == D and int(np.prod(grid)) >= M
+            Z = grid_points(grid, M, span)
         self.Z = rnd(torch.rand(M, D, generator=g, dtype=torch.float64) if Z is None else torch.as_tensor(Z, dtype=torch.float64), dtype)
         self.u = rnd(0.5 * torch.randn(K, M, generator=g, dtype=torch.float64), dtype)
         s_unc = 0.1 * torch.randn(K, M, M, generator=g, dtype=torch.float64).tril(-1)
@@ -59,7 +71,7 @@ class Case:
             self.hyp = dict(log_lengthscale=lg(ls), log_variance=lg(25.0))
         elif kernel == "ard":
             kw = dict(ard=True)
-            self.hyp = dict(log_lengthscale=lg([0.25, 0.4]), log_variance=lg(25.0))
+            self.hyp = dict(log_lengthscale=lg([0.25, 0.4] if D == 2 else [ls * (1 + 0.15 * d) for d in range(D)]), log_variance=lg(25.0))
         elif kernel == "periodic":
             kw = dict(period_count=1)
             self.hyp = dict(log_lengthscale=lg(0.8), log_variance=lg(4.0), log_period=lg(0.45))
@@ -68,18 +80,28 @@ class Case:
                                dict(name="kern1", kind="periodic", active_dims=[1], lengthscales=1, periods=1)])
             self.hyp = {"kern0.log_variance": lg(2.0), "kern0.log_lengthscale": lg(0.4), "kern1.log_variance": lg(3.0),
                         "kern1.log_lengthscale": lg(0.8), "kern1.log_period": lg(0.45)}
+        self.s_unc = s_unc
+        self.jitter = JIT[dtype] if jitter is None else jitter
+        if not engine:
+            return
+        from gdrf_amd.engine import Engine
         name = {"ard": "rbf"}.get(kernel, kernel)
-        self.eng = eng = Engine(n_cap, M, K, V, D, dtype=dtype, kernel=name, jitter=JIT[dtype] if jitter is None else jitter,
-                                maxjitter=maxjitter, process_group=None, whiten=whiten, **kw)
+        self.eng = eng = Engine(n_cap, M, K, V, D, dtype=dtype, kernel=name, jitter=self.jitter, maxjitter=maxjitter, process_group=None,
+                                whiten=whiten, pure_fp32=pure, **kw)
         eng.set_inducing_points(self.Z)
         eng.view("u_loc").copy_(self.u)
         eng.view("u_scale_tril_unc").copy_(s_unc)
         for k, v in self.hyp.items():
             eng.view(k).copy_(v)
 
-    def rows(self, n, seed=1):
+    def rows(self, n, seed=1, near=True):
+        """n rows of the cube.  Grid cases with near: row 0 sits next to the LAST inducing point, where the last column of W - alone in
+        its 32-column block when M = 32 b + 1 - carries most of the prior variance"""
         g = torch.Generator().manual_seed(n + seed)
-        return rnd(torch.rand(n, self.D, generator=g, dtype=torch.float64), self.dtype)
+        X = self.span * torch.rand(n, self.D, generator=g, dtype=torch.float64)
+        if self.grid is not None and near:
+            X[0] = self.Z[-1] * (1 - 1 / 64)
+        return rnd(X, self.dtype)
 
     def dev(self, t):
         return torch.as_tensor(t).to(device=self.eng.device, dtype=self.dtype).contiguous()
@@ -169,26 +191,41 @@ def mean_fn(K):
     return f
 
 
-def model_case(K, n, dtype, mean=False, link_function=None, jitter=None, maxjitter=15, seed=0, ls=0.3):
-    """(model, case): a SparseMultinomialGDRF holding n rows and a Case-shaped restatement of its numbers"""
-    from gdrf_amd.kernels import RBF
-    from gdrf_amd.models import SparseMultinomialGDRF
+def model_numbers(K, n, dtype, seed=0, twin=None):
+    """the rows, counts, u and unconstrained S of model_case, drawn in its order; no device.  twin: the last row is the one before it
+    moved by that much along axis 0 (the last row's entry of the factor of R then leans on the 32 columns before it)"""
+    M = int(np.prod(NPTS))
     g = torch.Generator().manual_seed(100 * K + n + seed)
-    xs = rnd(torch.rand(n, 2, generator=g, dtype=torch.float64), dtype)
+    xs = torch.rand(n, 2, generator=g, dtype=torch.float64)
+    if twin and n > 1:
+        xs[-1] = xs[-2] + torch.tensor([twin if float(xs[-2, 0]) < 0.5 else -twin, 0.0], dtype=torch.float64)
+    xs = rnd(xs, dtype)
     ws = torch.randint(0, 5, (n, V), generator=g, dtype=torch.int32)
+    u = rnd(0.5 * torch.randn(K, M, generator=g, dtype=torch.float64), dtype)
+    s_unc = 0.1 * torch.randn(K, M, M, generator=g, dtype=torch.float64).tril(-1)
+    s_unc = rnd(s_unc + torch.diag_embed(torch.full((K, M), math.log(0.3), dtype=torch.float64)), dtype)
+    return xs, ws, u, s_unc
+
+
+def model_case(K, n, dtype, mean=False, link_function=None, jitter=None, maxjitter=15, seed=0, ls=0.3, kernel="rbf", pure=False, twin=None):
+    """(model, case): a SparseMultinomialGDRF holding n rows and a Case-shaped restatement of its numbers"""
+    from gdrf_amd import kernels
+    from gdrf_amd.models import SparseMultinomialGDRF
+    xs, ws, u, s_unc = model_numbers(K, n, dtype, seed, twin)
     jit = JIT[dtype] if jitter is None else jitter
+    kern = {"rbf": kernels.RBF, "matern52": kernels.Matern52}[kernel]
     model = SparseMultinomialGDRF(xs=xs.to(dtype), ws=ws, world=[(0.0, 1.0)] * 2, num_observation_categories=V,
-                                  kernel=RBF(input_dim=2, lengthscale=torch.tensor(ls), variance=torch.tensor(25.0)),
+                                  kernel=kern(input_dim=2, lengthscale=torch.tensor(ls), variance=torch.tensor(25.0)),
                                   num_topic_categories=K, dirichlet_param=0.01, n_points=list(NPTS), fixed_inducing_points=True,
                                   inducing_init="grid", jitter=jit, maxjitter=maxjitter, dtype=dtype, seed=5, device="cuda:0",
-                                  link_function=link_function, mean_function=mean_fn(K) if mean else None)
+                                  link_function=link_function, mean_function=mean_fn(K) if mean else None, pure_fp32=pure)
     eng = model._engine
+    assert eng.M == u.shape[1]
     case = Case.__new__(Case)
-    case.kernel, case.M, case.K, case.dtype, case.whiten, case.D, case.eng = "rbf", eng.M, K, dtype, True, 2, eng
+    case.kernel, case.M, case.K, case.dtype, case.whiten, case.D, case.eng = kernel, eng.M, K, dtype, True, 2, eng
+    case.pure, case.span, case.jitter, case.s_unc, case.grid = pure, 1.0, jit, s_unc, None
     case.Z = eng.Z.detach().cpu().double()
-    case.u = rnd(0.5 * torch.randn(K, eng.M, generator=g, dtype=torch.float64), dtype)
-    s_unc = 0.1 * torch.randn(K, eng.M, eng.M, generator=g, dtype=torch.float64).tril(-1)
-    s_unc = rnd(s_unc + torch.diag_embed(torch.full((K, eng.M), math.log(0.3), dtype=torch.float64)), dtype)
+    case.u = u
     case.S = s_unc.tril(-1) + torch.diag_embed(s_unc.diagonal(dim1=1, dim2=2).exp())
     eng.view("u_loc").copy_(case.u)
     eng.view("u_scale_tril_unc").copy_(s_unc)
@@ -223,7 +260,8 @@ def test_structure_of_the_covariance():
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("K", [1, 3])
 def test_samples_with_injected_normals(K, dtype):
-    """n at the Cholesky's 32-column panel edges and its 256-column chunk edge"""
+    """n at the Cholesky's 32-column panel edges, and one n past 256 rows: nine panels, every one still within the first 256-column chunk of
+    the panel update (the second chunk needs n > 288; tests/test_gpu_joint_edges.py has those shapes)"""
     g = torch.Generator().manual_seed(3)
     for n in (1, 31, 32, 33, 257):
         model, case, xs, _ = model_case(K, n, dtype, mean=True)

@@ -35,10 +35,11 @@ def note(key, val):
     print(f"{key}: {val:.3e} (largest so far {FIGS[key]:.3e})")
 
 
-def check(case, X, count, s2=S2, given=None, exact=None, label=""):
-    """run the engine on the rows X and hold the result against the restatement; returns (idx, gains, var) on the CPU"""
+def check(case, X, count, s2=S2, given=None, exact=None, label="", tol=None):
+    """run the engine on the rows X and hold the result against the restatement; returns (idx, gains, var) on the CPU.  tol: the bound,
+    where it is not the context's fixed one (the all-fp32 context: the case's computed bound for C_k)"""
     eng, dtype, n = case.eng, case.dtype, X.shape[0]
-    tol = TOL[dtype]
+    tol = TOL[dtype] if tol is None else tol
     out = eng.select_batch(case.dev(X), count, s2, given=None if given is None else case.dev(given), return_variance=True)
     idx, gains, var = (t.cpu() for t in out)
     assert idx.dtype == torch.int64 and gains.dtype == torch.float64 and var.dtype == torch.float64
