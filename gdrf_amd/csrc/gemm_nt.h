@@ -248,6 +248,13 @@ struct NTXcdMap {
     rtile = (int64_t)idx * per + xcd / (unsigned)nct;
   }
 };
+// NTXcdMap with TWO row tiles per workgroup (the 512-thread split-operand W-bar kernels, gemm_split.h: one tile per wave group gp = 0, 1):
+// the map deals row-tile PAIRS, so the XCD <-> column tile affinity is the same, and the two groups take the adjacent row tiles of one
+// column tile.  Grid: col tiles x ceil(row tiles / 2).
+__device__ __forceinline__ void nt_xcd_map_paired(unsigned bid, int nct, int gp, int64_t& rtile, int& ct) {
+  NTXcdMap{}.map_block(bid, nct, false, rtile, ct);
+  rtile = 2 * rtile + gp;
+}
 
 // XCD-aware map that keeps ALL column tiles of a row tile on one XCD, dispatched back to back: their A operand (the
 // row tile's slab, cold in HBM) is then fetched once into that XCD's L2 and shared, instead of once per column tile.

@@ -112,6 +112,15 @@ __global__ void split_scales_kernel(int f16, const Hyper* __restrict__ h, const 
     if (what & SPLIT_SC_V) put(L.v(k), f16 ? split_pow2_scale(__uint_as_float(mx[L.mx_v(k)]) * sqrtf((float)h->var), 13) : 1.0f);
   }
 }
+// A wave's maximum of m >= 0 (one value per lane) into *mx.  Order-independent, hence deterministic: non-negative floats order like their
+// bit patterns, so the butterfly and the integer atomicMax give the same bits whichever wave or workgroup arrives first.  A zero is not
+// published (mx starts at zero: zeroed by the caller).  Call it with the whole wave.
+__device__ __forceinline__ void wave_max_publish(unsigned* mx, float m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(mx, __float_as_uint(m));
+}
+
 // mx[b] = max |x[b][i]|, i < n (grid: (blocks, batches)); mx zeroed by the caller
 __global__ __launch_bounds__(256) void absmax_batched_kernel(const float* __restrict__ x, int64_t n, int64_t ld, unsigned* __restrict__ mx) {
   const int b = blockIdx.y;
@@ -122,9 +131,7 @@ __global__ __launch_bounds__(256) void absmax_batched_kernel(const float* __rest
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = fmaxf(m, fabsf(x[(int64_t)b * ld + (n & ~(int64_t)3) + threadIdx.x]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(mx + b, __float_as_uint(m));
+  wave_max_publish(mx + b, m);
 }
 
 template <class SP> struct SplitCfg {
@@ -160,6 +167,76 @@ __device__ __forceinline__ void glds16_asm_s(const void* sbase, unsigned voff, u
 }
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
+}
+
+// ---- device helpers shared by the W-bar and tt kernels ------------------------------------------------------------------------
+// A kernel below is its staging and its phase schedule on top of these.  All of them inline; what a kernel does not use costs nothing.
+
+// Where a thread sits in its wave group: 256 threads = 4 waves as 2 x 2 on a 128 x 128 tile, each wave 4 x 4 MFMA tiles of 16 x 16.
+// The derived values are functions: a kernel takes the ones it needs where its schedule wants them computed (computed up front, in the
+// constructor, they cost bwd_wbar_split_cc_kernel two registers and bwd_wbar_f16_k64_kernel 60 bytes of scratch).
+struct SplitLane {
+  int tid, lane, wave;   // inside the wave group
+  int wr, wc;            // the wave's 64-row / 64-column quadrant of the tile
+  int lr, lg;            // MFMA operand lane: row (A) or column (B) lr of a 16-row group, k quad lg; accumulator: column lr, rows 4 lg + r
+  __device__ __forceinline__ SplitLane() {
+    tid = threadIdx.x & 255; lane = tid & 63; wave = tid >> 6;
+    wr = wave >> 1; wc = wave & 1; lr = lane & 15; lg = lane >> 4;
+  }
+  // = wave, provably wave-uniform: a DMA's LDS base goes to M0 without a waterfall loop
+  __device__ __forceinline__ int wave_u() const { return __builtin_amdgcn_readfirstlane(wave); }
+  // this lane's fragment offset (halfwords) inside a 16-row group of a swizzled image
+  __device__ __forceinline__ int frag() const { return lr * 32 + ((lg ^ split_swz(lr)) << 3); }
+  // LDS-DMA (global_load_lds_dwordx4): one wave-instruction moves a 16-row block of one piece image, 1 KB: lane l lands at block + 16 l =
+  // row l>>2, physical quad l&3, so its SOURCE is logical quad (l&3) ^ swz(row) - the image swizzle goes on the global address
+  // (cdna_hip_programming.md 5.4 rule 21): row drow of the block, halfword dq of the 32-deep chunk
+  __device__ __forceinline__ int drow() const { return lane >> 2; }
+  __device__ __forceinline__ int dq() const { return ((lane & 3) ^ split_swz(drow())) * 8; }
+};
+
+__device__ __forceinline__ void split_zero(f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0, 0, 0, 0};
+}
+// this lane's MFMA fragment (8 halfwords) of piece p of a swizzled operand image, for the 16 rows from row0
+template <class SP> __device__ __forceinline__ typename SP::V8 split_frag(const typename SP::E* img, int p, int row0, int frag) {
+  return *reinterpret_cast<const typename SP::V8*>(img + p * SplitCfg<SP>::PIECE + row0 * 32 + frag);
+}
+// the same for all pieces
+template <class SP> __device__ __forceinline__ void split_frags(typename SP::V8 (&f)[SP::NP], const typename SP::E* img, int row0, int frag) {
+#pragma unroll
+  for (int p = 0; p < SP::NP; ++p) f[p] = split_frag<SP>(img, p, row0, frag);
+}
+// P (+)= A B^T, a wave's four 16-row groups against one 16-column group, through the cross products in the order SP::pa/pb(t), small terms
+// first; FIRST: P starts from zero
+template <class SP, bool FIRST>
+__device__ __forceinline__ void split_products(f32x4 (&P)[4], const typename SP::V8 (&fa)[4][SP::NP], const typename SP::V8 (&fb)[SP::NP]) {
+#pragma unroll
+  for (int t = 0; t < SP::NPROD; ++t)
+#pragma unroll
+    for (int a = 0; a < 4; ++a) P[a] = SP::mma(fa[a][SP::pa(t)], fb[SP::pb(t)], (FIRST && t == 0) ? f32x4{0, 0, 0, 0} : P[a]);
+}
+// the per-row factors of a wave's accumulator rows (4 lg + r of each 16-row group) from one topic's row of a [K][128] table in LDS
+__device__ __forceinline__ void split_row_scales(f32x4 (&s4)[4], const float* sc_row, const SplitLane& L) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a) s4[a] = *reinterpret_cast<const f32x4*>(sc_row + L.wr * 64 + a * 16 + L.lg * 4);
+}
+// acc[.][b] += diag(s4) P, column group b
+__device__ __forceinline__ void split_scaled_acc(f32x4 (&acc)[4][4], int b, const f32x4 (&s4)[4], const f32x4 (&P)[4]) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P[a][r];
+}
+// End of a phase of the concurrent forms.  vmcnt(0): this wave's DMAs of the next chunk have landed (they were requested inside the phase and
+// had it to land); lgkmcnt(0): its fragment reads of this chunk are done; the barrier publishes both, so that after it every wave may
+// read the buffers just filled and request into the buffers just read.  A raw s_barrier: the waits it needs stand in front of it.
+__device__ __forceinline__ void split_phase_end() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  gdrf_raw_barrier();
 }
 
 
@@ -221,6 +298,94 @@ template <class SP> struct BwdWbarSplitArgs {
   float* slab = nullptr; int64_t slab_stride = 0; int nslice = 1;
 };
 
+// the [K][128] table of the per-(topic, row) factors of the row tile at m0: 2 vbar_kn, with the block scales of W and B_k taken off;
+// rows past the end get 0.  Filled by the 256 threads of a wave group; a barrier publishes it.
+template <class SP> __device__ __forceinline__ void wbar_fill_scales(const BwdWbarSplitArgs<SP>& g, float* scaleS, int64_t m0, int tid) {
+  const SplitLay SL{g.K};
+  const float unw = g.sc[SL.w() + 1];
+  for (int e = tid; e < g.K * GDRF_TILE; e += 256) {
+    const int k = e / GDRF_TILE, r = e - k * GDRF_TILE;
+    scaleS[e] = (m0 + r < g.nrows) ? 2.0f * g.vbar[(int64_t)k * g.ldk + m0 + r] * (unw * g.sc[SL.b(k) + 1]) : 0.0f;
+  }
+}
+// rank-K epilogue term locbar^T U on the native f32 matrix instruction (exact f32, no split, no range question): lane (lr, lg) supplies
+// A[row lr][k = lg] and B[k = lg][col lr] of v_mfma_f32_16x16x4_f32, whose C/D layout is the accumulators'.  Four topics per round of loads
+// (bwd_wbar_f16_k64_kernel batches sixteen and keeps its own form).
+template <class SP>
+__device__ __forceinline__ void wbar_rank_k(f32x4 (&acc)[4][4], const BwdWbarSplitArgs<SP>& g, int64_t m0, int n0, const SplitLane& L) {
+  for (int k0 = 0; k0 < g.K; k0 += 4) {
+    const int k = k0 + L.lg;
+    float av[4], bv[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int64_t row = m0 + L.wr * 64 + a * 16 + L.lr;
+      av[a] = (k < g.K && row < g.nrows) ? g.locbar[(int64_t)k * g.ldk + row] : 0.0f;
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int col = n0 + L.wc * 64 + b * 16 + L.lr;
+      bv[b] = (k < g.K && col < g.M) ? g.U[(int64_t)k * g.M + col] : 0.0f;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
+  }
+}
+// The epilogue Wbar = acc - 2 asum W of a wave's 64 x 64 quadrant; returns the lane's max |Wbar|.  The MFMA accumulator layout (a lane owns
+// one column of four rows) would make this 64 scalar loads of W and 64 scalar stores per lane in a dependent sequence - measured ~300k
+// cycles per workgroup, a third of its lifetime.  Instead each wave transposes its quadrant through a private LDS tile (over the operand
+// images, which every wave is done with after the barrier), 32 rows at a time, and moves whole 256-byte row segments: 16 float4 loads and
+// 16 float4 stores per lane.  In round i (of 8) of half h a lane moves row wbar_seg_row, columns wbar_seg_col .. + 3 of the tile; Mp is a
+// multiple of 32, so a float4 never straddles the edge.  The pieces: the wave's tile, half h of the accumulators into it, a lane's
+// segment out of it, and o = t - as2 w stored with the running maximum; wbar_store_transposed puts them together with W and asum loaded
+// behind the bounds test (bwd_wbar_f16_k64_kernel puts them together itself, with the values it loaded up front).
+constexpr int WBAR_TS = 68;   // tile row stride in floats (272 B: 16-byte aligned, bank-shifted)
+__device__ __forceinline__ float* wbar_tile(char* smem, int gp, const SplitLane& L) {
+  return reinterpret_cast<float*>(smem) + (size_t)(gp * 4 + L.wave) * (32 * WBAR_TS);
+}
+__device__ __forceinline__ void wbar_tile_put(float* tile, const f32x4 (&acc)[4][4], int h, const SplitLane& L) {
+#pragma unroll
+  for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tile[(a2 * 16 + L.lg * 4 + r) * WBAR_TS + b * 16 + L.lr] = acc[2 * h + a2][b][r];
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // same wave writes and reads: LDS is in order per wave
+}
+__device__ __forceinline__ f32x4 wbar_tile_get(const float* tile, int i, const SplitLane& L) {
+  return *reinterpret_cast<const f32x4*>(tile + ((L.lane >> 4) + 4 * i) * WBAR_TS + (L.lane & 15) * 4);
+}
+__device__ __forceinline__ int wbar_seg_row(const SplitLane& L, int h, int i) { return L.wr * 64 + h * 32 + (L.lane >> 4) + 4 * i; }
+__device__ __forceinline__ int wbar_seg_col(const SplitLane& L) { return L.wc * 64 + (L.lane & 15) * 4; }
+__device__ __forceinline__ void wbar_seg_store(float* dst, const f32x4& t, float as2, const f32x4& w, float& wmax) {
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { o[e] = t[e] - as2 * w[e]; wmax = fmaxf(wmax, fabsf(o[e])); }
+  *reinterpret_cast<f32x4*>(dst) = o;
+}
+template <class SP>
+__device__ __forceinline__ float wbar_store_transposed(const f32x4 (&acc)[4][4], char* smem, int gp, const SplitLane& L, const BwdWbarSplitArgs<SP>& g,
+                                                       int64_t m0, int n0) {
+  __syncthreads();                                           // every wave is done with the operand images
+  float wmax = 0.0f;
+  float* tile = wbar_tile(smem, gp, L);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    wbar_tile_put(tile, acc, h, L);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int64_t m = m0 + wbar_seg_row(L, h, i);
+      const int n = n0 + wbar_seg_col(L);
+      const f32x4 t = wbar_tile_get(tile, i, L);
+      if (m < g.nrows && n < g.Mp)
+        wbar_seg_store(g.Wbar + m * g.Mp + n, t, 2.0f * g.asum[m], *reinterpret_cast<const f32x4*>(g.W + m * g.Mp + n), wmax);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // reads done before the tile is overwritten with the other half
+  }
+  return wmax;
+}
+
 // NG = 1: one 256-thread workgroup per tile, two workgroups per CU (they share the CU's SIMDs at random).
 // NG = 2: one 512-thread workgroup per CU holding TWO such tiles, one per wave group (waves 0-3 / 4-7: a workgroup's waves
 // go to the SIMDs cyclically, so every SIMD hosts one wave of each group), run phase-shifted on purpose: in every phase one
@@ -246,43 +411,21 @@ __global__ __launch_bounds__(256 * NG, 2) void bwd_wbar_split_kernel(BwdWbarSpli
   E* Bs = reinterpret_cast<E*>(smem) + (NG == 2 ? 2 * IMG : IMG);             // [NG][NP][128][LDH]
   float* scaleS = reinterpret_cast<float*>(smem + (size_t)(NG == 2 ? 4 : 2) * IMG * 2 + (size_t)gp * tab);  // [K][128]  2 vbar_kn / (sW sB_k)
 
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lg = lane >> 4;
+  const SplitLane L;
+  const int tid = L.tid;
   const int nct = (g.Mp + GDRF_TILE - 1) / GDRF_TILE;
   int64_t rtile; int ct;
-  if constexpr (NG == 1) {
-    NTXcdMap{}.map_block(blockIdx.x, nct, false, rtile, ct);
-  } else {        // the same XCD <-> column tile affinity; the two groups take adjacent row tiles of one column tile
-    const unsigned w = blockIdx.x;
-    if (nct <= 8 && (8 % nct) == 0 && (gridDim.x % 8u) == 0) {
-      const unsigned xcd = w & 7u, idx = w >> 3, per = 8u / (unsigned)nct;
-      ct = (int)(xcd % (unsigned)nct);
-      rtile = 2 * ((int64_t)idx * per + xcd / (unsigned)nct) + gp;
-    } else {
-      ct = (int)(w % (unsigned)nct);
-      rtile = 2 * (int64_t)(w / (unsigned)nct) + gp;
-    }
-  }
+  if constexpr (NG == 1) NTXcdMap{}.map_block(blockIdx.x, nct, false, rtile, ct);
+  else nt_xcd_map_paired(blockIdx.x, nct, gp, rtile, ct);
   const int64_t m0 = rtile * GDRF_TILE;
   const int n0 = ct * GDRF_TILE;
   const int K = g.K, Mp = g.Mp;
-  const SplitLay SL{K};
+  wbar_fill_scales(g, scaleS, m0, tid);
+  f32x4 acc[4][4];
+  split_zero(acc);
 
-  {
-    const float unw = g.sc[SL.w() + 1];
-    for (int e = tid; e < K * GDRF_TILE; e += 256) {
-      const int k = e / GDRF_TILE, r = e - k * GDRF_TILE;
-      scaleS[e] = (m0 + r < g.nrows) ? 2.0f * g.vbar[(int64_t)k * g.ldk + m0 + r] * (unw * g.sc[SL.b(k) + 1]) : 0.0f;
-    }
-  }
   // staging map, both operands: per piece 2 x 16-byte vectors of 8 halfwords per thread (vector v = tid + 256 j: row v>>2,
   // k offset 8*(v&3))
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0, 0, 0, 0};
-
   V8 ra[NP][2], rb[NP][2];
   auto load_a = [&](int kA) {
 #pragma unroll
@@ -324,36 +467,23 @@ __global__ __launch_bounds__(256 * NG, 2) void bwd_wbar_split_kernel(BwdWbarSpli
   // The A fragments of a chunk serve all K topic reps, so they are read from LDS once (rep 0) and stay in registers; the
   // B fragments are read one 16-column group at a time.
   V8 fa[4][NP];
-  const int frag = lr * 32 + ((lg ^ split_swz(lr)) << 3);      // this lane's fragment offset inside a 16-row group
+  const int frag = L.frag();
   auto read_a = [&]() {
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int p = 0; p < NP; ++p) fa[a][p] = *reinterpret_cast<const V8*>(As + p * CF::PIECE + (wr * 64 + a * 16) * 32 + frag);
-  };
-  auto read_b = [&](V8 (&fb)[NP], int b, int buf) {
-#pragma unroll
-    for (int p = 0; p < NP; ++p) fb[p] = *reinterpret_cast<const V8*>(Bs + (buf * NP + p) * CF::PIECE + (wc * 64 + b * 16) * 32 + frag);
+    for (int a = 0; a < 4; ++a) split_frags<SP>(fa[a], As, L.wr * 64 + a * 16, frag);
   };
   auto compute = [&](const float* sc_row /* scaleS + rep*128 */, int buf) {
+    const E* Bb = Bs + buf * IMG;
     f32x4 s4[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) s4[a] = *reinterpret_cast<const f32x4*>(sc_row + wr * 64 + a * 16 + lg * 4);   // rows 4*lg + r
+    split_row_scales(s4, sc_row, L);
     V8 fbq[2][NP];                         // the next column group's fragments are read while this one multiplies
-    read_b(fbq[0], 0, buf);
+    split_frags<SP>(fbq[0], Bb, L.wc * 64, frag);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      V8 (&fb)[NP] = fbq[b & 1];
-      if (b + 1 < 4) read_b(fbq[(b + 1) & 1], b + 1, buf);
+      if (b + 1 < 4) split_frags<SP>(fbq[(b + 1) & 1], Bb, L.wc * 64 + (b + 1) * 16, frag);
       f32x4 P[4];
-#pragma unroll
-      for (int t = 0; t < SP::NPROD; ++t)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) P[a] = SP::mma(fa[a][SP::pa(t)], fb[SP::pb(t)], t == 0 ? f32x4{0, 0, 0, 0} : P[a]);
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P[a][r];
+      split_products<SP, true>(P, fa, fbq[b & 1]);
+      split_scaled_acc(acc, b, s4, P);
     }
   };
 
@@ -377,11 +507,8 @@ __global__ __launch_bounds__(256 * NG, 2) void bwd_wbar_split_kernel(BwdWbarSpli
     }
   } else {
     // Staging by LDS-DMA (global_load_lds_dwordx4: no destination registers, no ds_write - a staging wave's ds_write_b128
-    // were measured starving, ~1600 cycles for six, while its SIMD's other wave streams MFMAs).  One wave-instruction moves a
-    // 16-row block of one piece image, 1 KB: lane l lands at block + 16 l = row l>>2, physical quad l&3, so its SOURCE is
-    // logical quad (l&3) ^ swz(row) - the image swizzle goes on the global address (cdna_hip_programming.md 5.4 rule 21).
-    const int drow = lane >> 2, dq = ((lane & 3) ^ split_swz(drow)) * 8;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // provably wave-uniform: the DMA's LDS base goes to M0 without a waterfall loop
+    // were measured starving, ~1600 cycles for six, while its SIMD's other wave streams MFMAs); lane map: SplitLane.
+    const int drow = L.drow(), dq = L.dq(), wave_u = L.wave_u();
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
     auto dma_b = [&](int c) {             // B chunk c -> buffer c & 1; this wave moves row blocks wave and wave + 4 of each piece
@@ -447,67 +574,9 @@ __global__ __launch_bounds__(256 * NG, 2) void bwd_wbar_split_kernel(BwdWbarSpli
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  // rank-K epilogue term locbar^T U on the native f32 matrix instruction (exact f32, no split, no range question): lane
-  // (lr, lg) supplies A[row lr][k = lg] and B[k = lg][col lr] of v_mfma_f32_16x16x4_f32, whose C/D layout is the accumulators'
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const int k = k0 + lg;
-    float av[4], bv[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int64_t row = m0 + wr * 64 + a * 16 + lr;
-      av[a] = (k < K && row < g.nrows) ? g.locbar[(int64_t)k * g.ldk + row] : 0.0f;
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int col = n0 + wc * 64 + b * 16 + lr;
-      bv[b] = (k < K && col < g.M) ? g.U[(int64_t)k * g.M + col] : 0.0f;
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-  }
-  // Wbar = acc - 2 asum W.  The MFMA accumulator layout (a lane owns one column of four rows) would make this 64 scalar
-  // loads of W and 64 scalar stores per lane in a dependent sequence - measured ~300k cycles per workgroup, a third of its
-  // lifetime.  Instead each wave transposes its 64 x 64 quadrant through a private LDS tile, 32 rows at a time, and moves whole
-  // 256-byte row segments: 16 float4 loads and 16 float4 stores per lane.
-  __syncthreads();                                           // every wave is done with the operand images
-  float wmax = 0.0f;
-  {
-    constexpr int TS = 68;                                   // tile row stride in floats (272 B: 16-byte aligned, bank-shifted)
-    float* tile = reinterpret_cast<float*>(smem) + (size_t)((NG == 2 ? gp * 4 : 0) + wave) * (32 * TS);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) tile[(a2 * 16 + lg * 4 + r) * TS + b * 16 + lr] = acc[2 * h + a2][b][r];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // same wave writes and reads: LDS is in order per wave
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int rr = (lane >> 4) + 4 * i, cv = (lane & 15) * 4;
-        const int64_t m = m0 + wr * 64 + h * 32 + rr;
-        const int n = n0 + wc * 64 + cv;
-        const f32x4 t = *reinterpret_cast<const f32x4*>(tile + rr * TS + cv);
-        if (m < g.nrows && n < Mp) {                         // Mp is a multiple of 32: a float4 never straddles the edge
-          const float as2 = 2.0f * g.asum[m];
-          const f32x4 w = *reinterpret_cast<const f32x4*>(g.W + m * Mp + n);
-          f32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { o[e] = t[e] - as2 * w[e]; wmax = fmaxf(wmax, fabsf(o[e])); }
-          *reinterpret_cast<f32x4*>(g.Wbar + m * Mp + n) = o;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // reads done before the tile is overwritten with the other half
-    }
-  }
-  if (g.wbar_max) {                                          // order-independent: the maximum of non-negative floats as integers
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));
-    if (lane == 0 && wmax > 0.0f) atomicMax(g.wbar_max, __float_as_uint(wmax));
-  }
+  wbar_rank_k(acc, g, m0, n0, L);
+  const float wmax = wbar_store_transposed(acc, smem, gp, L, g, m0, n0);   // Wbar = acc - 2 asum W
+  if (g.wbar_max) wave_max_publish(g.wbar_max, wmax);
 }
 
 // bwd_wbar with BOTH wave groups multiplying in every phase (see fwd_t_split_cc_kernel): one phase = one (reduction block q,
@@ -528,41 +597,18 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_split_cc_kernel(BwdWbarSplitA
   E* Bs = reinterpret_cast<E*>(smem) + 4 * IMG;                          // [2 buffers][NP][128][LDH] shared
   float* scaleS = reinterpret_cast<float*>(smem + (size_t)6 * IMG * 2 + (size_t)gp * tab);  // [K][128]  2 vbar_kn / (sW sB_k)
 
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lg = lane >> 4;
+  const SplitLane L;
   const int nct = (g.Mp + GDRF_TILE - 1) / GDRF_TILE;
   int64_t rtile; int ct;
-  {
-    const unsigned w = blockIdx.x;
-    if (nct <= 8 && (8 % nct) == 0 && (gridDim.x % 8u) == 0) {
-      const unsigned xcd = w & 7u, idx = w >> 3, per = 8u / (unsigned)nct;
-      ct = (int)(xcd % (unsigned)nct);
-      rtile = 2 * ((int64_t)idx * per + xcd / (unsigned)nct) + gp;
-    } else {
-      ct = (int)(w % (unsigned)nct);
-      rtile = 2 * (int64_t)(w / (unsigned)nct) + gp;
-    }
-  }
+  nt_xcd_map_paired(blockIdx.x, nct, gp, rtile, ct);
   const int64_t m0 = rtile * GDRF_TILE;
   const int n0 = ct * GDRF_TILE;
   const int K = g.K, Mp = g.Mp;
-  const SplitLay SL{K};
-  {
-    const float unw = g.sc[SL.w() + 1];
-    for (int e = tid; e < K * GDRF_TILE; e += 256) {
-      const int k = e / GDRF_TILE, r = e - k * GDRF_TILE;
-      scaleS[e] = (m0 + r < g.nrows) ? 2.0f * g.vbar[(int64_t)k * g.ldk + m0 + r] * (unw * g.sc[SL.b(k) + 1]) : 0.0f;
-    }
-  }
+  wbar_fill_scales(g, scaleS, m0, L.tid);
   f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0, 0, 0, 0};
+  split_zero(acc);
   V8 fa[4][NP];
-  const int frag = lr * 32 + ((lg ^ split_swz(lr)) << 3);
-  const int drow = lane >> 2, dq = ((lane & 3) ^ split_swz(drow)) * 8;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int frag = L.frag(), drow = L.drow(), dq = L.dq(), wave_u = L.wave_u();
   const unsigned a_lds = lds_addr(As), b_lds = lds_addr(Bs);
   const int nk = Mp / CF::BK, nchunks = nk * K;
   // One LDS-DMA instruction costs its wave ~190 cycles of issue here (s_memtime: 380 cycles for two, in front of the MFMAs, with the
@@ -590,31 +636,19 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_split_cc_kernel(BwdWbarSplitA
     const bool more = c + 1 < nchunks, more_a = more && rep == K - 1;
     const E* Ab = As + (q & 1) * IMG;
     const E* Bb = Bs + (c & 1) * IMG;
-    if (rep == 0) {
+    if (rep == 0) {                       // the A fragments serve all K topic reps of the block
 #pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) fa[a][p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64 + a * 16) * 32 + frag);
+      for (int a = 0; a < 4; ++a) split_frags<SP>(fa[a], Ab, L.wr * 64 + a * 16, frag);
     }
-    const float* sc_row = scaleS + rep * GDRF_TILE;
     f32x4 s4[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) s4[a] = *reinterpret_cast<const f32x4*>(sc_row + wr * 64 + a * 16 + lg * 4);
-    V8 fbq[2][NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) fbq[0][p] = *reinterpret_cast<const V8*>(Bb + p * CF::PIECE + (wc * 64) * 32 + frag);
+    split_row_scales(s4, scaleS + rep * GDRF_TILE, L);
+    V8 fbq[2][NP];                        // the next column group's fragments are read while this one multiplies
+    split_frags<SP>(fbq[0], Bb, L.wc * 64, frag);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      V8 (&fb)[NP] = fbq[b & 1];
-      if (b + 1 < 4) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) fbq[(b + 1) & 1][p] = *reinterpret_cast<const V8*>(Bb + p * CF::PIECE + (wc * 64 + (b + 1) * 16) * 32 + frag);
-      }
+      if (b + 1 < 4) split_frags<SP>(fbq[(b + 1) & 1], Bb, L.wc * 64 + (b + 1) * 16, frag);
       f32x4 P[4];
-#pragma unroll
-      for (int t = 0; t < SP::NPROD; ++t)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) P[a] = SP::mma(fa[a][SP::pa(t)], fb[SP::pb(t)], t == 0 ? f32x4{0, 0, 0, 0} : P[a]);
+      split_products<SP, true>(P, fa, fbq[b & 1]);
       // the next chunk's requests, behind this column group's MFMAs: B (buffer (c + 1) & 1, last read one phase ago) after groups
       // 0 .. NP - 1; when the next chunk opens a reduction block, the group's next A image (last read K phases ago) after them
       if (more && b < NP) dma_b1(c + 1, b);
@@ -622,76 +656,13 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_split_cc_kernel(BwdWbarSplitA
         if (NP == 2) { dma_a1(q + 1, b >> 1, b & 1); }
         else if (b < 3) { dma_a1(q + 1, 0, b); dma_a1(q + 1, 1, b); }
       }
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P[a][r];
+      split_scaled_acc(acc, b, s4, P);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    gdrf_raw_barrier();
+    split_phase_end();
   }
-  // rank-K epilogue term locbar^T U on the native f32 matrix instruction (exact f32, no split, no range question): lane
-  // (lr, lg) supplies A[row lr][k = lg] and B[k = lg][col lr] of v_mfma_f32_16x16x4_f32, whose C/D layout is the accumulators'
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const int k = k0 + lg;
-    float av[4], bv[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int64_t row = m0 + wr * 64 + a * 16 + lr;
-      av[a] = (k < K && row < g.nrows) ? g.locbar[(int64_t)k * g.ldk + row] : 0.0f;
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int col = n0 + wc * 64 + b * 16 + lr;
-      bv[b] = (k < K && col < g.M) ? g.U[(int64_t)k * g.M + col] : 0.0f;
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-  }
-  // Wbar = acc - 2 asum W.  The MFMA accumulator layout (a lane owns one column of four rows) would make this 64 scalar
-  // loads of W and 64 scalar stores per lane in a dependent sequence - measured ~300k cycles per workgroup, a third of its
-  // lifetime.  Instead each wave transposes its 64 x 64 quadrant through a private LDS tile, 32 rows at a time, and moves whole
-  // 256-byte row segments: 16 float4 loads and 16 float4 stores per lane.
-  __syncthreads();                                           // every wave is done with the operand images
-  float wmax = 0.0f;
-  {
-    constexpr int TS = 68;                                   // tile row stride in floats (272 B: 16-byte aligned, bank-shifted)
-    float* tile = reinterpret_cast<float*>(smem) + (size_t)(gp * 4 + wave) * (32 * TS);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) tile[(a2 * 16 + lg * 4 + r) * TS + b * 16 + lr] = acc[2 * h + a2][b][r];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // same wave writes and reads: LDS is in order per wave
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int rr = (lane >> 4) + 4 * i, cv = (lane & 15) * 4;
-        const int64_t m = m0 + wr * 64 + h * 32 + rr;
-        const int n = n0 + wc * 64 + cv;
-        const f32x4 t = *reinterpret_cast<const f32x4*>(tile + rr * TS + cv);
-        if (m < g.nrows && n < Mp) {                         // Mp is a multiple of 32: a float4 never straddles the edge
-          const float as2 = 2.0f * g.asum[m];
-          const f32x4 w = *reinterpret_cast<const f32x4*>(g.W + m * Mp + n);
-          f32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { o[e] = t[e] - as2 * w[e]; wmax = fmaxf(wmax, fabsf(o[e])); }
-          *reinterpret_cast<f32x4*>(g.Wbar + m * Mp + n) = o;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // reads done before the tile is overwritten with the other half
-    }
-  }
-  if (g.wbar_max) {                                          // order-independent: the maximum of non-negative floats as integers
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));
-    if (lane == 0 && wmax > 0.0f) atomicMax(g.wbar_max, __float_as_uint(wmax));
-  }
+  wbar_rank_k(acc, g, m0, n0, L);
+  const float wmax = wbar_store_transposed(acc, smem, gp, L, g, m0, n0);   // Wbar = acc - 2 asum W
+  if (g.wbar_max) wave_max_publish(g.wbar_max, wmax);
 }
 
 
@@ -715,41 +686,18 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
   E* Bs = reinterpret_cast<E*>(smem) + 4 * IMG;                          // [2 buffers][2 k-steps][NP][128][32] shared
   float* scaleS = reinterpret_cast<float*>(smem + (size_t)8 * IMG * 2 + (size_t)gp * tab);
 
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lg = lane >> 4;
+  const SplitLane L;
   const int nct = (g.Mp + GDRF_TILE - 1) / GDRF_TILE;
   int64_t rtile; int ct;
-  {
-    const unsigned w = blockIdx.x;
-    if (nct <= 8 && (8 % nct) == 0 && (gridDim.x % 8u) == 0) {
-      const unsigned xcd = w & 7u, idx = w >> 3, per = 8u / (unsigned)nct;
-      ct = (int)(xcd % (unsigned)nct);
-      rtile = 2 * ((int64_t)idx * per + xcd / (unsigned)nct) + gp;
-    } else {
-      ct = (int)(w % (unsigned)nct);
-      rtile = 2 * (int64_t)(w / (unsigned)nct) + gp;
-    }
-  }
+  nt_xcd_map_paired(blockIdx.x, nct, gp, rtile, ct);
   const int64_t m0 = rtile * GDRF_TILE;
   const int n0 = ct * GDRF_TILE;
   const int K = g.K, Mp = g.Mp;
-  const SplitLay SL{K};
-  {
-    const float unw = g.sc[SL.w() + 1];
-    for (int e = tid; e < K * GDRF_TILE; e += 256) {
-      const int k = e / GDRF_TILE, r = e - k * GDRF_TILE;
-      scaleS[e] = (m0 + r < g.nrows) ? 2.0f * g.vbar[(int64_t)k * g.ldk + m0 + r] * (unw * g.sc[SL.b(k) + 1]) : 0.0f;
-    }
-  }
+  wbar_fill_scales(g, scaleS, m0, L.tid);
   f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0, 0, 0, 0};
+  split_zero(acc);
   V8 fa[2][4][NP];
-  const int frag = lr * 32 + ((lg ^ split_swz(lr)) << 3);
-  const int drow = lane >> 2, dq = ((lane & 3) ^ split_swz(drow)) * 8;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int frag = L.frag(), drow = L.drow(), dq = L.dq(), wave_u = L.wave_u();
   const unsigned a_lds = lds_addr(As), b_lds = lds_addr(Bs);
   const int nk = Mp / 64;                                               // Mp % 64 == 0 (checked by the host)
   // this workgroup's reduction blocks [q_lo, q_hi): all of them, or slice blockIdx.y of nslice
@@ -782,40 +730,26 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
     const int q = c / K, rep = c - q * K;
     const bool more = c + 1 < nchunks, more_a = rep == 1 && q + 1 < q_hi;   // A(q + 1) into the image whose fragments were read one phase ago
     const E* Bb = Bs + (c & 1) * 2 * IMG;
-    if (rep == 0) {
+    if (rep == 0) {                       // the A fragments serve all K topic reps of the block
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int p = 0; p < NP; ++p) fa[ks][a][p] = *reinterpret_cast<const V8*>(As + (ks * NP + p) * CF::PIECE + (wr * 64 + a * 16) * 32 + frag);
+        for (int a = 0; a < 4; ++a) split_frags<SP>(fa[ks][a], As + ks * IMG, L.wr * 64 + a * 16, frag);
     }
-    const float* sc_row = scaleS + rep * GDRF_TILE;
     f32x4 s4[4];
+    split_row_scales(s4, scaleS + rep * GDRF_TILE, L);
+    V8 fbq[2][2][NP];                     // the next column group's fragments are read while this one multiplies
 #pragma unroll
-    for (int a = 0; a < 4; ++a) s4[a] = *reinterpret_cast<const f32x4*>(sc_row + wr * 64 + a * 16 + lg * 4);
-    V8 fbq[2][2][NP];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int p = 0; p < NP; ++p) fbq[0][ks][p] = *reinterpret_cast<const V8*>(Bb + (ks * NP + p) * CF::PIECE + (wc * 64) * 32 + frag);
+    for (int ks = 0; ks < 2; ++ks) split_frags<SP>(fbq[0][ks], Bb + ks * IMG, L.wc * 64, frag);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      V8 (&fb)[2][NP] = fbq[b & 1];
       if (b + 1 < 4) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int p = 0; p < NP; ++p)
-            fbq[(b + 1) & 1][ks][p] = *reinterpret_cast<const V8*>(Bb + (ks * NP + p) * CF::PIECE + (wc * 64 + (b + 1) * 16) * 32 + frag);
+        for (int ks = 0; ks < 2; ++ks) split_frags<SP>(fbq[(b + 1) & 1][ks], Bb + ks * IMG, L.wc * 64 + (b + 1) * 16, frag);
       }
       f32x4 P[4];
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int t = 0; t < SP::NPROD; ++t)
-#pragma unroll
-          for (int a = 0; a < 4; ++a) P[a] = SP::mma(fa[ks][a][SP::pa(t)], fb[ks][SP::pb(t)], (ks == 0 && t == 0) ? f32x4{0, 0, 0, 0} : P[a]);
+      split_products<SP, true>(P, fa[0], fbq[b & 1][0]);      // the two 32-deep k-steps, the second on top of the first
+      split_products<SP, false>(P, fa[1], fbq[b & 1][1]);
       // the next chunk's requests behind the first two column groups' MFMAs, so that they have the second half of the phase to land: an
       // LDS-DMA instruction stalls its wave at issue, but spread over all four groups (one or two each) the last request was issued just
       // in front of the phase's closing vmcnt(0) and its whole latency showed - 13.3 -> 12.1 ms.  (Also measured: the two wave groups
@@ -824,14 +758,9 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
         if (more) { dma_b1(c + 1, b, 0); dma_b1(c + 1, b, 1); }
         if (more_a) { dma_a1(q + 1, b, 0, 0); dma_a1(q + 1, b, 1, 0); dma_a1(q + 1, b, 0, 1); dma_a1(q + 1, b, 1, 1); }
       }
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[a][b][r] += s4[a][r] * P[a][r];
+      split_scaled_acc(acc, b, s4, P);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    gdrf_raw_barrier();
+    split_phase_end();
   }
   // ---- epilogue.  One workgroup per CU: nothing else runs on the CU while it reads and writes, so every global load it needs is issued up
   // front, from clamped addresses and unconditionally (the fragment registers of the loop are free now) - the W tile of both 32-row halves,
@@ -843,16 +772,15 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const int rr = (lane >> 4) + 4 * i, cv = (lane & 15) * 4;
-      const int64_t m = m0 + wr * 64 + h * 32 + rr;
-      const int n = n0 + wc * 64 + cv;
+      const int64_t m = m0 + wbar_seg_row(L, h, i);           // the row segment this lane moves in round i of half h of the store
+      const int n = n0 + wbar_seg_col(L);
       const int64_t mc = m < g.nrows ? m : 0;
       const int nc = n < Mp ? n : 0;
       wv[h][i] = *reinterpret_cast<const f32x4*>(g.W + mc * Mp + nc);
       as2v[h][i] = first_slice ? 2.0f * g.asum[mc] : 0.0f;
     }
-  // rank-K term locbar^T U on the native f32 matrix instruction (exact f32, no split, no range question): lane (lr, lg) supplies
-  // A[row lr][k = lg] and B[k = lg][col lr] of v_mfma_f32_16x16x4_f32, whose C/D layout is the accumulators'; 16 topics per batch of loads
+  // rank-K term as wbar_rank_k, but 16 topics per batch of loads, from clamped addresses
+  const int wr = L.wr, wc = L.wc, lr = L.lr, lg = L.lg;
   for (int kb = 0; kb < (first_slice ? K : 0); kb += 16) {
     float av[4][4], bv[4][4];
 #pragma unroll
@@ -881,49 +809,25 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
       }
     }
   }
-  // Wbar = acc - 2 asum W.  The MFMA accumulator layout (a lane owns one column of four rows) would make this 64 scalar
-  // loads of W and 64 scalar stores per lane in a dependent sequence - measured ~300k cycles per workgroup, a third of its
-  // lifetime.  Instead each wave transposes its 64 x 64 quadrant through a private LDS tile, 32 rows at a time, and moves whole
-  // 256-byte row segments: 16 float4 loads and 16 float4 stores per lane.
+  // out = acc - 2 asum W as wbar_store_transposed, from the registers loaded above
   __syncthreads();                                           // every wave is done with the operand images
   float wmax = 0.0f;
-  {
-    constexpr int TS = 68;                                   // tile row stride in floats (272 B: 16-byte aligned, bank-shifted)
-    float* tile = reinterpret_cast<float*>(smem) + (size_t)(gp * 4 + wave) * (32 * TS);
+  float* tile = wbar_tile(smem, gp, L);
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+  for (int h = 0; h < 2; ++h) {
+    wbar_tile_put(tile, acc, h, L);
 #pragma unroll
-      for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            tile[(a2 * 16 + lg * 4 + r) * TS + b * 16 + lr] = acc[2 * h + a2][b][r];
-          }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // same wave writes and reads: LDS is in order per wave
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int rr = (lane >> 4) + 4 * i, cv = (lane & 15) * 4;
-        const int64_t m = m0 + wr * 64 + h * 32 + rr;
-        const int n = n0 + wc * 64 + cv;
-        const f32x4 t = *reinterpret_cast<const f32x4*>(tile + rr * TS + cv);
-        if (m < g.nrows && n < Mp) {                         // Mp is a multiple of 32: a float4 never straddles the edge
-          f32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { o[e] = t[e] - as2v[h][i] * wv[h][i][e]; wmax = fmaxf(wmax, fabsf(o[e])); }
-          *reinterpret_cast<f32x4*>(out_base + m * Mp + n) = o;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // reads done before the tile is overwritten with the other half
+    for (int i = 0; i < 8; ++i) {
+      // = m0 + wbar_seg_row, n0 + wbar_seg_col in this kernel's tuned order (scratch)
+      const int64_t m = m0 + L.wr * 64 + h * 32 + ((L.lane >> 4) + 4 * i);
+      const int n = n0 + L.wc * 64 + (L.lane & 15) * 4;
+      const f32x4 t = wbar_tile_get(tile, i, L);
+      if (m < g.nrows && n < Mp) wbar_seg_store(out_base + m * Mp + n, t, as2v[h][i], wv[h][i], wmax);
     }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // reads done before the tile is overwritten with the other half
   }
-  if (g.wbar_max && g.nslice == 1) {                         // order-independent: the maximum of non-negative floats as integers
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));
-    if (lane == 0 && wmax > 0.0f) atomicMax(g.wbar_max, __float_as_uint(wmax));
-  }
+  if (g.wbar_max && g.nslice == 1) wave_max_publish(g.wbar_max, wmax);   // sliced: wbar_slab_sum_kernel publishes the maximum of the sum
 }
-
 
 
 // Wbar = the sum of the slices' partial sums (fixed order), and its maximum for the block scale of the G^T operand
@@ -942,11 +846,7 @@ __global__ __launch_bounds__(256) void wbar_slab_sum_kernel(const float* __restr
 #pragma unroll
     for (int e = 0; e < 4; ++e) wmax = fmaxf(wmax, fabsf(acc[e]));
   }
-  if (wbar_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));
-    if ((threadIdx.x & 63) == 0 && wmax > 0.0f) atomicMax(wbar_max, __float_as_uint(wmax));
-  }
+  if (wbar_max) wave_max_publish(wbar_max, wmax);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -960,13 +860,35 @@ template <class SP> struct FwdTSplitArgs {
   const float* sc;
 };
 
+// Block map of both tt kernels.  Grid: 8 * K * rt8 with rt8 = ceil(row-tile pairs / 8).  XCD = blockIdx & 7 owns the pairs r * 8 + xcd; topics
+// go in groups of KG, group-major (every XCD first runs all its pairs for topics [0, KG), then [KG, 2 KG), ...) so that only KG topics'
+// S^T pieces are live in its 4 MB L2 at a time; the KG workgroups of one pair are adjacent.  rt0: the pair's first row tile; bz: the topic.
+template <class SP> __device__ __forceinline__ void fwd_t_map_block(const FwdTSplitArgs<SP>& g, int64_t& rt0, int& bz) {
+  const unsigned xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
+  const unsigned per_group = (unsigned)g.KG * (unsigned)g.rt8;
+  const int grp = (int)(idx / per_group);
+  const unsigned rem = idx - (unsigned)grp * per_group;
+  const int kg = min(g.KG, g.K - grp * g.KG);
+  rt0 = 2 * ((int64_t)(rem / (unsigned)kg) * 8 + xcd);
+  bz = grp * g.KG + (int)(rem % (unsigned)kg);
+}
+// Folding a finished column tile ct into the row sums of squares: a lane's column of 16-column group b counts if it lies inside Mp, and
+// an accumulator entry then adds its square.  The two kernels sum these in different fixed orders (registers / per-wave LDS slots), so each keeps
+// its loop.
+__device__ __forceinline__ bool fwd_t_col_ok(int ct, int b, int Mp, const SplitLane& L) { return ct * GDRF_TILE + L.wc * 64 + b * 16 + L.lr < Mp; }
+__device__ __forceinline__ float fwd_t_sq(float x, bool cok) { return cok ? x * x : 0.0f; }
+// tt of row m0 + tid (tid < 128) and topic bz from its sum of squares v; the block scales of W and S_k^T come off here
+template <class SP> __device__ __forceinline__ void fwd_t_store_tt(const FwdTSplitArgs<SP>& g, int bz, int64_t m0, int tid, float v) {
+  const int64_t m = m0 + tid;
+  const SplitLay SL{g.K};
+  const float un = g.sc[SL.w() + 1] * g.sc[SL.st(bz) + 1];
+  if (m < g.nrows) g.tt[(int64_t)bz * g.ldt + m] = v * (un * un);
+}
+
 
 // tt[k][n] = |S_k^T w_n|^2: a 512-thread workgroup holds two adjacent row tiles of one topic, one per wave group, with BOTH wave
 // groups multiplying in every phase ("concurrent" form).  Both walk the same (column tile, reduction chunk) sequence, so the S_k^T
-// chunk is staged once into a double-buffered image both read, and every group double-buffers its own W chunk.
-// Grid: 8 * K * rt8 with rt8 = ceil(row-tile pairs / 8).  Block map: XCD = blockIdx & 7 owns the pairs r * 8 + xcd; topics go
-// in groups of KG, group-major (every XCD first runs all its pairs for topics [0, KG), then [KG, 2 KG), ...) so that only KG
-// topics' S^T pieces are live in its 4 MB L2 at a time; the KG workgroups of one pair are adjacent.
+// chunk is staged once into a double-buffered image both read, and every group double-buffers its own W chunk.  Grid: fwd_t_map_block.
 // A removed form alternated the groups so that a SIMD's matrix pipe served one wave at a time; measured per phase (s_memtime, f16x3, mid-launch
 // workgroup): multiply 1184 cycles for 768 cycles of MFMA, + ~110 (vmcnt) + ~180 (barrier) + ~400 (loop / address code) = ~1900
 // cycles during which the OTHER group's wave on that SIMD idles - the pipe is busy 40 %.  That structure paid off when a chunk was
@@ -983,23 +905,17 @@ __global__ __launch_bounds__(512, 2) void fwd_t_split_cc_kernel(FwdTSplitArgs<SP
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int IMG = CF::IMG;
   const int gp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lg = lane >> 4;
   E* As = reinterpret_cast<E*>(smem) + gp * 2 * IMG;      // [2 buffers][NP][128][32] of this group
   E* Bs = reinterpret_cast<E*>(smem) + 4 * IMG;           // [2 buffers][NP][128][32] shared
   const int Mp = g.Mp;
   const int nct = (Mp + GDRF_TILE - 1) / GDRF_TILE;
-  const unsigned xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-  const unsigned per_group = (unsigned)g.KG * (unsigned)g.rt8;
-  const int grp = (int)(idx / per_group);
-  const unsigned rem = idx - (unsigned)grp * per_group;
-  const int kg = min(g.KG, g.K - grp * g.KG);
-  const int64_t rtile = 2 * ((int64_t)(rem / (unsigned)kg) * 8 + xcd) + gp;
-  const int bz = grp * g.KG + (int)(rem % (unsigned)kg);
-  const int64_t m0 = rtile * GDRF_TILE;                        // a tile past the end runs on clamped rows; its tt is never stored
+  int64_t rt0; int bz;
+  fwd_t_map_block(g, rt0, bz);
+  const int64_t m0 = (rt0 + gp) * GDRF_TILE;                   // a tile past the end runs on clamped rows; its tt is never stored
+  const SplitLane L;
+  const int tid = L.tid, wr = L.wr, wc = L.wc, lr = L.lr, lg = L.lg;
 
-  const int drow = lane >> 2, dq = ((lane & 3) ^ split_swz(drow)) * 8;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int drow = L.drow(), dq = L.dq(), wave_u = L.wave_u();
   const unsigned a_lds = lds_addr(As), b_lds = lds_addr(Bs);
   // chunk (ct, kA) -> buffer buf: A rows of this group (2 row blocks per wave), B columns (1 row block per wave of the 8)
   // the requests of a chunk, one at a time (see bwd_wbar_split_cc_kernel: an LDS-DMA instruction stalls its wave ~190 cycles at issue,
@@ -1029,16 +945,11 @@ __global__ __launch_bounds__(512, 2) void fwd_t_split_cc_kernel(FwdTSplitArgs<SP
 #pragma unroll
     for (int r = 0; r < 4; ++r) rs[a][r] = 0;
   f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0, 0, 0, 0};
-  const int frag = lr * 32 + ((lg ^ split_swz(lr)) << 3);
+  split_zero(acc);
+  const int frag = L.frag();
   int ct = 0, kA = 0, buf = 0;
   dma(0, 0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  gdrf_raw_barrier();
+  split_phase_end();
   while (ct < nct) {
     // the chunk after this one: next k block of the column tile, or the first one (k = 128 ct') of the next column tile
     int ct1 = ct, kA1 = kA + CF::BK;
@@ -1051,21 +962,16 @@ __global__ __launch_bounds__(512, 2) void fwd_t_split_cc_kernel(FwdTSplitArgs<SP
 #pragma unroll
     for (int p = 0; p < NP; ++p)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) fb[p][b] = *reinterpret_cast<const V8*>(Bb + p * CF::PIECE + (wc * 64 + b * 16) * 32 + frag);
-    V8 faq[2][NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) faq[0][p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64) * 32 + frag);
+      for (int b = 0; b < 4; ++b) fb[p][b] = split_frag<SP>(Bb, p, wc * 64 + b * 16, frag);
+    V8 faq[2][NP];                                              // the next row group's fragments are read while this one multiplies
+    split_frags<SP>(faq[0], Ab, wr * 64, frag);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      V8 (&fa)[NP] = faq[a & 1];
-      if (a + 1 < 4) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) faq[(a + 1) & 1][p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64 + (a + 1) * 16) * 32 + frag);
-      }
+      if (a + 1 < 4) split_frags<SP>(faq[(a + 1) & 1], Ab, wr * 64 + (a + 1) * 16, frag);
 #pragma unroll
       for (int t = 0; t < SP::NPROD; ++t)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = SP::mma(fa[SP::pa(t)], fb[SP::pb(t)][b], acc[a][b]);
+        for (int b = 0; b < 4; ++b) acc[a][b] = SP::mma(faq[a & 1][SP::pa(t)], fb[SP::pb(t)][b], acc[a][b]);
       if (more) {                                               // the next chunk's requests, spread behind the MFMA groups
         constexpr int NS = 3 * NP, PER = (NS + 2) / 3;          // over a = 0, 1, 2
 #pragma unroll
@@ -1075,18 +981,16 @@ __global__ __launch_bounds__(512, 2) void fwd_t_split_cc_kernel(FwdTSplitArgs<SP
     if (last) {                                                 // fold the finished column tile into the row sums, restart the accumulators
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        const bool cok = ct * GDRF_TILE + wc * 64 + b * 16 + lr < Mp;
+        const bool cok = fwd_t_col_ok(ct, b, Mp, L);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) rs[a][r] += cok ? acc[a][b][r] * acc[a][b][r] : 0.0f;
+          for (int r = 0; r < 4; ++r) rs[a][r] += fwd_t_sq(acc[a][b][r], cok);
           acc[a][b] = f32x4{0, 0, 0, 0};
         }
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's DMAs of the next chunk have landed (they had the whole phase)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    gdrf_raw_barrier();
+    split_phase_end();
     ct = ct1; kA = kA1; buf ^= 1;
   }
   // row sums: 16-lane groups, then the two waves of a group that share the rows, through LDS; the block scales come off here
@@ -1110,12 +1014,7 @@ __global__ __launch_bounds__(512, 2) void fwd_t_split_cc_kernel(FwdTSplitArgs<SP
       for (int r = 0; r < 4; ++r) rsum[wr * 64 + a * 16 + lg * 4 + r] += rs[a][r];
   }
   __syncthreads();
-  if (tid < GDRF_TILE) {
-    const int64_t m = m0 + tid;
-    const SplitLay SL{g.K};
-    const float un = g.sc[SL.w() + 1] * g.sc[SL.st(bz) + 1];
-    if (m < g.nrows) g.tt[(int64_t)bz * g.ldt + m] = rsum[tid] * (un * un);
-  }
+  if (tid < GDRF_TILE) fwd_t_store_tt(g, bz, m0, tid, rsum[tid]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1139,23 +1038,18 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
   constexpr int IMG = CF::IMG;
   const int gp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
   const int gr = gp >> 1, gc = gp & 1;
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  const int w16 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lg = lane >> 4;
+  const SplitLane L;
+  const int tid = L.tid, lane = L.lane, wr = L.wr, wc = L.wc, lr = L.lr, lg = L.lg;
+  const int w16 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // the wave among the workgroup's 16
   E* Asm = reinterpret_cast<E*>(smem);                    // [2 row groups][2 buffers][NP][128][32]
   E* Bsm = reinterpret_cast<E*>(smem) + 4 * IMG;          // [2 column groups][2 buffers][NP][128][32]
   const int Mp = g.Mp;
   const int nct = (Mp + GDRF_TILE - 1) / GDRF_TILE, ncp = (nct + 1) / 2;
-  const unsigned xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-  const unsigned per_group = (unsigned)g.KG * (unsigned)g.rt8;
-  const int grp = (int)(idx / per_group);
-  const unsigned rem = idx - (unsigned)grp * per_group;
-  const int kg = min(g.KG, g.K - grp * g.KG);
-  const int64_t rt0 = 2 * ((int64_t)(rem / (unsigned)kg) * 8 + xcd);   // the pair's first row tile
-  const int bz = grp * g.KG + (int)(rem % (unsigned)kg);
+  int64_t rt0; int bz;
+  fwd_t_map_block(g, rt0, bz);
   const int64_t m0 = (rt0 + gr) * GDRF_TILE;                   // a tile past the end runs on clamped rows; its tt is never stored
 
-  const int drow = lane >> 2, dq = ((lane & 3) ^ split_swz(drow)) * 8;
+  const int drow = L.drow(), dq = L.dq();
   const unsigned a_lds = lds_addr(Asm), b_lds = lds_addr(Bsm);
   // the 2 x NP x 8 requests (16 rows each) of either operand of a chunk are dealt over the 16 waves: slot s < NP of a wave is
   // request w16 NP + s of the W images, slot NP + s the same request of the S_k^T images (skipped while that column group is idle).
@@ -1190,17 +1084,12 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
   float* rsum = reinterpret_cast<float*>(smem + (size_t)8 * IMG * 2) + (gp * 2 + wc) * GDRF_TILE;
   rsum[wr * 64 + lane] = 0.0f;                            // this wave's 64 rows (ordered before its own later updates: same wave, LDS in order)
   f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0, 0, 0, 0};
-  const int frag = lr * 32 + ((lg ^ split_swz(lr)) << 3);
+  split_zero(acc);
+  const int frag = L.frag();
   int buf = 0;
 #pragma unroll
   for (int sl = 0; sl < 2 * NP; ++sl) dma1(0, 0, 0, sl);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  gdrf_raw_barrier();
+  split_phase_end();
   // Every chunk issues the requests of the chunk after it (the last one re-requests itself into the idle buffers: nobody reads them),
   // so the multiply loop has no branch around its DMAs; a group's idle chunks run in a loop of their own that never touches the
   // accumulators (with both in one loop body hipcc kept copies of them across the branch and spilled at 128 registers).
@@ -1239,31 +1128,28 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
 #pragma unroll
       for (int p = 0; p < NP; ++p)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) fb[p][b] = *reinterpret_cast<const V8*>(Bb + p * CF::PIECE + (wc * 64 + b * 16) * 32 + frag);
+        for (int b = 0; b < 4; ++b) fb[p][b] = split_frag<SP>(Bb, p, wc * 64 + b * 16, frag);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         __builtin_amdgcn_sched_barrier(0);                       // keeps hipcc from hoisting the later row blocks' reads
         V8 fa[NP];                                               // one row block at a time: the SIMD's other three waves cover the read
-#pragma unroll
-        for (int p = 0; p < NP; ++p) fa[p] = *reinterpret_cast<const V8*>(Ab + p * CF::PIECE + (wr * 64 + a * 16) * 32 + frag);
+        split_frags<SP>(fa, Ab, wr * 64 + a * 16, frag);
 #pragma unroll
         for (int t = 0; t < SP::NPROD; ++t)
 #pragma unroll
           for (int b = 0; b < 4; ++b) acc[a][b] = SP::mma(fa[SP::pa(t)], fb[SP::pb(t)][b], acc[a][b]);
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's DMAs of the next chunk have landed (they had the whole phase)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      gdrf_raw_barrier();
+      split_phase_end();
       buf ^= 1;
     }
     if (ct < nct) {                                             // fold the finished column tile into the row sums, restart the accumulators
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        const bool cok = ct * GDRF_TILE + wc * 64 + b * 16 + lr < Mp;
+        const bool cok = fwd_t_col_ok(ct, b, Mp, L);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc[a][b][r] = cok ? acc[a][b][r] * acc[a][b][r] : 0.0f;
+          for (int r = 0; r < 4; ++r) acc[a][b][r] = fwd_t_sq(acc[a][b][r], cok);
         }
       }
 #pragma unroll
@@ -1282,11 +1168,7 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
   __syncthreads();
   if (gc == 0 && tid < GDRF_TILE) {
     const float* q = reinterpret_cast<const float*>(smem + (size_t)8 * IMG * 2) + (gr * 2) * 2 * GDRF_TILE + tid;
-    const float v = (q[0] + q[GDRF_TILE]) + (q[2 * GDRF_TILE] + q[3 * GDRF_TILE]);
-    const int64_t m = m0 + tid;
-    const SplitLay SL{g.K};
-    const float un = g.sc[SL.w() + 1] * g.sc[SL.st(bz) + 1];
-    if (m < g.nrows) g.tt[(int64_t)bz * g.ldt + m] = v * (un * un);
+    fwd_t_store_tt(g, bz, m0, tid, (q[0] + q[GDRF_TILE]) + (q[2 * GDRF_TILE] + q[3 * GDRF_TILE]));
   }
 }
 

@@ -526,6 +526,48 @@ template <typename T> struct FwdTProb : NTXcdRowBatchMap, NTPlainA<T>, NTNoExtra
   }
 };
 
+// What the two forms of the Wbar contraction, (3) and (3'), share, over the fields both problems name alike (P = BwdWbarProb<T> or
+// BwdWbarTProb<T>): the per-(topic, row) factor, the rank-K term and the epilogue.
+// sc[k][r] = 2 vbar_k of row m0 + r, 0 past the end: the [K][128] LDS table that scales the A fragments (SCALE_A); a barrier publishes it
+template <typename T, class P> __device__ __forceinline__ void nt_wbar_fill_scales(const P& p, T* sc, int64_t m0) {
+  for (int e = threadIdx.x; e < p.K * GDRF_TILE; e += 256) {
+    const int k = e / GDRF_TILE, r = e - k * GDRF_TILE;
+    sc[e] = (m0 + r < p.nrows) ? T(2) * p.vbar[(int64_t)k * p.ldk + m0 + r] : T(0);
+  }
+}
+// rank-K epilogue term locbar^T U as extra MFMA chunk(s): As[row][kk] = locbar[k][m0+row], Bs[col][kk] = U[k][n0+col]
+template <typename T> __device__ __forceinline__ int nt_wbar_extra_chunks(int K) { return (K + NTCfg<T>::BK - 1) / NTCfg<T>::BK; }
+template <typename T, class P> __device__ __forceinline__ void nt_wbar_fill_extra(const P& p, T* As, T* Bs, int x, int64_t m0, int n0) {
+  constexpr int BK = NTCfg<T>::BK, LDK = NTCfg<T>::LDK, CW = NTCfg<T>::CW;
+  for (int e = threadIdx.x; e < GDRF_TILE * BK; e += 256) {
+    const int kk = e / GDRF_TILE, row = e - kk * GDRF_TILE, k = x * BK + kk;
+    As[row * LDK + kk] = (k < p.K && m0 + row < p.nrows) ? p.locbar[(int64_t)k * p.ldk + m0 + row] : T(0);
+  }
+  for (int e = threadIdx.x; e < CW * BK; e += 256) {
+    const int kk = e / CW, col = e - kk * CW, k = x * BK + kk;
+    Bs[col * LDK + kk] = (k < p.K && n0 + col < p.M) ? p.U[(int64_t)k * p.M + n0 + col] : T(0);
+  }
+}
+// Wbar = acc - 2 asum W over the tile
+template <typename T, class P, class Acc, int NB_>
+__device__ __forceinline__ void nt_wbar_tile_done(const P& p, Acc (&acc)[4][NB_], int64_t m0, int n0, int wr, int wc, int lane) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t m = m0 + nt_acc_row<T>(wr, a, lane, r);
+      if (m >= p.nrows) continue;
+      const T as2 = T(2) * p.asum[m];
+#pragma unroll
+      for (int b = 0; b < NTCfg<T>::NB; ++b) {
+        const int n = n0 + nt_acc_col<T>(wc, b, lane);
+        if (n >= p.Mp) continue;
+        T v = acc[a][b][r] - as2 * p.W[m * p.Mp + n];
+        p.Wbar[m * p.Mp + n] = v;
+      }
+    }
+}
+
 // (3) Wbar = sum_k diag(2 vbar_k) W B_k + locbar^T U - 2 diag(asum) W.  One staged chunk of W serves all K
 //     topics (a_reuse = K): the per-(topic,row) factor 2 vbar_kn sits in an LDS table and scales the A fragments.
 template <typename T> struct BwdWbarProb : NTXcdMap, NTPlainA<T> {
@@ -546,11 +588,7 @@ template <typename T> struct BwdWbarProb : NTXcdMap, NTPlainA<T> {
   __device__ __forceinline__ int a_reuse() const { return K; }
   __device__ __forceinline__ void krange(int64_t, int, int, int& kb, int& ke) const { kb = 0; ke = Mp; }
   __device__ __forceinline__ void prepA(ACtx& c, int64_t m0, int, char* extra) const {
-    T* sc = reinterpret_cast<T*>(extra);          // [K][128]
-    for (int e = threadIdx.x; e < K * GDRF_TILE; e += 256) {
-      const int k = e / GDRF_TILE, r = e - k * GDRF_TILE;
-      sc[e] = (m0 + r < nrows) ? T(2) * vbar[(int64_t)k * ldk + m0 + r] : T(0);
-    }
+    nt_wbar_fill_scales<T>(*this, reinterpret_cast<T*>(extra), m0);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NTCfg<T>::VPT; ++i) {
@@ -566,36 +604,11 @@ template <typename T> struct BwdWbarProb : NTXcdMap, NTPlainA<T> {
     const int c = n0 + nt_stage_row<T>(i);
     return (c < Mp) ? *reinterpret_cast<const V*>(Bm + ((int64_t)rep * Mp + c) * Mp + k) : vzero<T>();
   }
-  // rank-K epilogue term locbar^T U as extra MFMA chunk(s): As[row][kk] = locbar[k][m0+row], Bs[col][kk] = U[k][n0+col]
-  __device__ __forceinline__ int extra_chunks() const { return (K + NTCfg<T>::BK - 1) / NTCfg<T>::BK; }
-  __device__ __forceinline__ void fill_extra(T* As, T* Bs, int x, int64_t m0, int n0) const {
-    constexpr int BK = NTCfg<T>::BK, LDK = NTCfg<T>::LDK, CW = NTCfg<T>::CW;
-    for (int e = threadIdx.x; e < GDRF_TILE * BK; e += 256) {
-      const int kk = e / GDRF_TILE, row = e - kk * GDRF_TILE, k = x * BK + kk;
-      As[row * LDK + kk] = (k < K && m0 + row < nrows) ? locbar[(int64_t)k * ldk + m0 + row] : T(0);
-    }
-    for (int e = threadIdx.x; e < CW * BK; e += 256) {
-      const int kk = e / CW, col = e - kk * CW, k = x * BK + kk;
-      Bs[col * LDK + kk] = (k < K && n0 + col < M) ? U[(int64_t)k * M + n0 + col] : T(0);
-    }
-  }
+  __device__ __forceinline__ int extra_chunks() const { return nt_wbar_extra_chunks<T>(K); }
+  __device__ __forceinline__ void fill_extra(T* As, T* Bs, int x, int64_t m0, int n0) const { nt_wbar_fill_extra<T>(*this, As, Bs, x, m0, n0); }
   template <class Acc, int NB_>
   __device__ __forceinline__ void tile_done(Acc (&acc)[4][NB_], int64_t m0, int n0, int, ECtx&, int wr, int wc, int lane) const {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t m = m0 + nt_acc_row<T>(wr, a, lane, r);
-        if (m >= nrows) continue;
-        const T as2 = T(2) * asum[m];
-#pragma unroll
-        for (int b = 0; b < NTCfg<T>::NB; ++b) {
-          const int n = n0 + nt_acc_col<T>(wc, b, lane);
-          if (n >= Mp) continue;
-          T v = acc[a][b][r] - as2 * W[m * Mp + n];
-          Wbar[m * Mp + n] = v;
-        }
-      }
+    nt_wbar_tile_done<T>(*this, acc, m0, n0, wr, wc, lane);
   }
   __device__ __forceinline__ void finish(int64_t, int, ECtx&, char*, int, int, int) const {}
 };
@@ -620,11 +633,7 @@ template <typename T> struct BwdWbarTProb : NTXcdPairMap, NTPlainA<T> {
     kb = 0; ke = n0 + NTCfg<T>::CW; if (ke > Mp) ke = Mp;
   }
   __device__ __forceinline__ void prepA(ACtx& c, int64_t m0, int, char* extra) const {
-    T* sc = reinterpret_cast<T*>(extra);          // [K][128]
-    for (int e = threadIdx.x; e < K * GDRF_TILE; e += 256) {
-      const int k = e / GDRF_TILE, r = e - k * GDRF_TILE;
-      sc[e] = (m0 + r < nrows) ? T(2) * vbar[(int64_t)k * ldk + m0 + r] : T(0);
-    }
+    nt_wbar_fill_scales<T>(*this, reinterpret_cast<T*>(extra), m0);
     __syncthreads();
     c.tile_off = (m0 / GDRF_TILE) * t_ts;
     c.ok = m0 < nrows;       // the launch grid is rounded up to a multiple of 8: padding workgroups own no tile
@@ -642,36 +651,11 @@ template <typename T> struct BwdWbarTProb : NTXcdPairMap, NTPlainA<T> {
     const int c = n0 + nt_stage_row<T>(i);
     return (c < Mp) ? *reinterpret_cast<const V*>(S + ((int64_t)rep * Mp + c) * Mp + k) : vzero<T>();
   }
-  // rank-K epilogue term locbar^T U as extra MFMA chunk(s): As[row][kk] = locbar[k][m0+row], Bs[col][kk] = U[k][n0+col]
-  __device__ __forceinline__ int extra_chunks() const { return (K + NTCfg<T>::BK - 1) / NTCfg<T>::BK; }
-  __device__ __forceinline__ void fill_extra(T* As, T* Bs, int x, int64_t m0, int n0) const {
-    constexpr int BK = NTCfg<T>::BK, LDK = NTCfg<T>::LDK, CW = NTCfg<T>::CW;
-    for (int e = threadIdx.x; e < GDRF_TILE * BK; e += 256) {
-      const int kk = e / GDRF_TILE, row = e - kk * GDRF_TILE, k = x * BK + kk;
-      As[row * LDK + kk] = (k < K && m0 + row < nrows) ? locbar[(int64_t)k * ldk + m0 + row] : T(0);
-    }
-    for (int e = threadIdx.x; e < CW * BK; e += 256) {
-      const int kk = e / CW, col = e - kk * CW, k = x * BK + kk;
-      Bs[col * LDK + kk] = (k < K && n0 + col < M) ? U[(int64_t)k * M + n0 + col] : T(0);
-    }
-  }
+  __device__ __forceinline__ int extra_chunks() const { return nt_wbar_extra_chunks<T>(K); }
+  __device__ __forceinline__ void fill_extra(T* As, T* Bs, int x, int64_t m0, int n0) const { nt_wbar_fill_extra<T>(*this, As, Bs, x, m0, n0); }
   template <class Acc, int NB_>
   __device__ __forceinline__ void tile_done(Acc (&acc)[4][NB_], int64_t m0, int n0, int, ECtx&, int wr, int wc, int lane) const {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t m = m0 + nt_acc_row<T>(wr, a, lane, r);
-        if (m >= nrows) continue;
-        const T as2 = T(2) * asum[m];
-#pragma unroll
-        for (int b = 0; b < NTCfg<T>::NB; ++b) {
-          const int n = n0 + nt_acc_col<T>(wc, b, lane);
-          if (n >= Mp) continue;
-          T v = acc[a][b][r] - as2 * W[m * Mp + n];
-          Wbar[m * Mp + n] = v;
-        }
-      }
+    nt_wbar_tile_done<T>(*this, acc, m0, n0, wr, wc, lane);
   }
   __device__ __forceinline__ void finish(int64_t, int, ECtx&, char*, int, int, int) const {}
 };
