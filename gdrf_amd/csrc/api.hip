@@ -1036,6 +1036,21 @@ template <typename T, typename TS> struct Impl {
             // few rows (streaming mini-batches): a handful of workgroups would each walk all K x Mp / 64 chunks one after the other
             // (0.19 ms at n = 64); the reduction blocks are split over gridDim.y slices into slabs, summed in a fixed order
             const int nkb = Mp / 64;
+            // many rows (no slices) and at most 16 topics: one wave per SIMD, B_k fragments straight from L2 into registers
+            if (pairs * nct_ > 32 && K <= 16) {
+              const size_t lds_w1 = 8 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * (size_t)(K + 1) * GDRF_TILE * sizeof(float);
+              const dim3 grid((unsigned)round_up(pairs * nct_, 8));
+              auto launch = [&](auto kern) {
+                HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w1));
+                hipLaunchKernelGGL(kern, grid, dim3(256), lds_w1, s, a);
+                return 0;
+              };
+              // W-image requests per wave and phase: the 16 of a block fit into its K phases
+              if (int rc = K >= 8 ? launch(bwd_wbar_f16_w1_kernel<2>) : (K >= 4 ? launch(bwd_wbar_f16_w1_kernel<4>) : launch(bwd_wbar_f16_w1_kernel<8>))) return rc;
+              c->forms[GDRF_FORM_WBAR] = 7; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
+              LAUNCHCHK("wbar_split");
+              return 0;
+            }
             int nslice = 1;
             if (pairs * nct_ <= 32 && nkb >= 2) nslice = std::min(nkb, 8);
             if ((size_t)nslice * round_up(n, 256) * Mp > (size_t)c->nsplit_cap * (K + 1) * Mp * Mp) nslice = 1;   // the TN slab buffer is idle now

@@ -26,6 +26,7 @@
 //
 // All keep the tiling, block maps, deterministic slab reduction and epilogues of the f32 forms they replace.
 #pragma once
+#include <utility>
 #include "common.h"
 #include "gemm_nt.h"
 #include "kernels_mm.h"
@@ -168,6 +169,13 @@ __device__ __forceinline__ void glds16_asm_s(const void* sbase, unsigned voff, u
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
 }
+
+// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}).  (A `#pragma unroll` of 20 stages x 24
+// MFMAs with inline asm in the body is refused by hipcc's unroller - "loop not unrolled" - and the accumulator arrays land in scratch.)
+template <int... Is, class F> __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
+  (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
 // ---- device helpers shared by the W-bar and tt kernels ------------------------------------------------------------------------
 // A kernel below is its staging and its phase schedule on top of these.  All of them inline; what a kernel does not use costs nothing.
@@ -829,6 +837,316 @@ __global__ __launch_bounds__(512, 2) void bwd_wbar_f16_k64_kernel(BwdWbarSplitAr
   if (g.wbar_max && g.nslice == 1) wave_max_publish(g.wbar_max, wmax);   // sliced: wbar_slab_sum_kernel publishes the maximum of the sum
 }
 
+
+// bwd_wbar, ONE WAVE PER SIMD, B_k fed from L2 to registers (f16x3 only; unsliced reductions, 2 <= K <= 16, Mp % 64 == 0).
+//
+// What bwd_wbar_f16_k64_kernel spends beside its MFMAs (profiles/r03/README.md item 3) is almost all B_k: four of a wave's ~4.8 LDS-DMA
+// requests per phase, the B fragment reads out of the shared image, and the vmcnt(0) + barrier over 8 waves that every phase ends in because
+// B_k goes through that image.  Bh is stored k-blocked ([piece][topic][k / 32][column][32]) and the MFMA operand lane is (lr = column, lg =
+// k quad) in natural k order, so a 16-column x 32-k fragment is 1 024 contiguous bytes and ONE global_load_dwordx4 per wave delivers it
+// finished from the XCD's L2 (where the block map keeps the column tile's panels) - no M0, no LDS image, no ds_read, no barrier.  That needs
+// registers k64 (256 VGPRs at two waves per SIMD) does not have.  Here four waves, one per SIMD, share the same 256 x 128 workgroup tile:
+// wave w owns the 128 rows of row tile w >> 1 and the 64 columns of half w & 1.  Per lane:
+//   VGPR  acc 128, P of one 16-column group 32, the topic's row factors 32, addresses
+//   AGPR  a[0:127]    W fragments of the current 64-deep block: [k-step][row group 0-7][piece]
+//         a[128:255]  B_k fragment ring: [phase parity][k-step][column group 0-3][piece]
+// MFMA A/B operands, ds_read and global-load destinations may be AGPRs on gfx950; VALU cannot address them, which is why the accumulators
+// stay in VGPRs.  The AGPRs are named literally in the asm (the compiler never sees them; every statement that writes them lists all 256
+// as clobbers, which also makes the kernel descriptor allocate them), the MFMAs are issued from asm with C/D in VGPRs.
+// THIS IS A CONTRACT HIPCC DOES NOT KNOW ABOUT: the MFMA statements read a[0:255] without declaring them, so the kernel is right only while
+// the compiler puts nothing of its own into an AGPR between the prologue's barrier and the end of the loop - no spill, no copy - with the
+// VGPRs at exactly 256.  It holds for all three instantiations today.  After ANY edit of this kernel, and after a compiler change, repeat
+// the check: `hipcc -save-temps`, then in each instantiation's assembly no `v_accvgpr_*` and no `scratch_*` between the first `s_barrier`
+// and the `s_waitcnt vmcnt(0)` that follows the loop (hipcc may and does use the AGPRs as spill space in the epilogue, where they are dead),
+// and `make resources`: ScratchSize 0.  tests/test_gpu_wbar_w1.py runs every instantiation (K = 10, 9, 16: <2>; K = 5: <4>; K = 2, 3: <8>).
+//
+// Schedule.  A phase = (reduction block q, topic rep) = 4 column groups x 48 MFMAs.  P of a group is written product-major, (k-step, product,
+// row group): per accumulator the same six products in the same order as k64.  `acc += s P` of group b sits in front of the first eight
+// MFMAs of group b + 1 (of the next phase for b = 3), one row group each: P[a] was finished seven MFMAs earlier and is overwritten by the MFMA
+// that follows its update.  Behind group 0's MFMAs: the phase's row factors, R requests of the NEXT block's W image (LDS-DMA, double-buffered
+// now that B_k needs no LDS: 16 requests per wave and block, R = 2 / 4 / 8 per phase so that K >= 8 / 4 / 2 phases carry them all) and the 16
+// B loads of the NEXT phase into the other half of the ring.  The counts are the same in every phase (the last phase re-requests itself, a
+// finished block re-requests itself into the idle buffer), so every wait is a literal vmcnt(n): in front of group b, the 4 (3 - b) later
+// loads of this phase's B and - for b > 0 - the R + 16 requests issued behind group 0 may still be in flight.  One workgroup barrier per
+// reduction block publishes the W image; phases are barrier-free.  The loop body is two phases (the ring halves are register names); an odd
+// phase count runs one more phase with all-zero row factors.
+#define GDRF_A10(p) "a" p "0", "a" p "1", "a" p "2", "a" p "3", "a" p "4", "a" p "5", "a" p "6", "a" p "7", "a" p "8", "a" p "9"
+#define GDRF_A100(p) GDRF_A10(p "0"), GDRF_A10(p "1"), GDRF_A10(p "2"), GDRF_A10(p "3"), GDRF_A10(p "4"), GDRF_A10(p "5"), GDRF_A10(p "6"), \
+                     GDRF_A10(p "7"), GDRF_A10(p "8"), GDRF_A10(p "9")
+#define GDRF_ALL_AGPRS "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", GDRF_A10("1"), GDRF_A10("2"), GDRF_A10("3"), GDRF_A10("4"), \
+                       GDRF_A10("5"), GDRF_A10("6"), GDRF_A10("7"), GDRF_A10("8"), GDRF_A10("9"), GDRF_A100("1"), GDRF_A10("20"), GDRF_A10("21"), \
+                       GDRF_A10("22"), GDRF_A10("23"), GDRF_A10("24"), "a250", "a251", "a252", "a253", "a254", "a255"
+constexpr int wb1_wreg(int ks, int a, int p) { return ((ks * 8 + a) * 2 + p) * 4; }
+constexpr int wb1_breg(int h, int ks, int b, int p) { return 128 + (((h * 2 + ks) * 4 + b) * 2 + p) * 4; }
+// P = (or +=) W fragment a[WA:WA+3] x B fragment a[BA:BA+3]
+template <int WA, int BA, bool ZERO> __device__ __forceinline__ void wb1_mfma(f32x4& P) {
+  if constexpr (ZERO) asm volatile("v_mfma_f32_16x16x32_f16 %0, a[%c1:%c2], a[%c3:%c4], 0" : "=v"(P) : "i"(WA), "i"(WA + 3), "i"(BA), "i"(BA + 3));
+  else asm volatile("v_mfma_f32_16x16x32_f16 %0, a[%c1:%c2], a[%c3:%c4], %0" : "+v"(P) : "i"(WA), "i"(WA + 3), "i"(BA), "i"(BA + 3));
+}
+// a[REG:REG+3] = the lane's 16 bytes at sbase (wave-uniform) + voff + OFF.  Not counted by hipcc: the caller waits by vmcnt(n).
+template <int REG, int OFF> __device__ __forceinline__ void wb1_gload(const void* sbase, unsigned voff) {
+  asm volatile("global_load_dwordx4 a[%c2:%c3], %0, %1 offset:%c4" : : "v"(voff), "s"(sbase), "i"(REG), "i"(REG + 3), "i"(OFF) : "memory", GDRF_ALL_AGPRS);
+}
+template <int REG, int OFF> __device__ __forceinline__ void wb1_ldsread(unsigned addr) {
+  asm volatile("ds_read_b128 a[%c1:%c2], %0 offset:%c3" : : "v"(addr), "i"(REG), "i"(REG + 3), "i"(OFF) : "memory", GDRF_ALL_AGPRS);
+}
+// c0, c1 += rows R0, R0 + 1 of s P, as two single v_fmac_f32 that stay where they are written
+template <int R0> __device__ __forceinline__ void wb1_update2(float& c0, float& c1, const f32x4& s, const f32x4& p) {
+  asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(c0) : "v"(s[R0]), "v"(p[R0]));
+  asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(c1) : "v"(s[R0 + 1]), "v"(p[R0 + 1]));
+}
+template <int N> __device__ __forceinline__ void wb1_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
+
+template <int R>
+__global__ __launch_bounds__(256, 1) void bwd_wbar_f16_w1_kernel(BwdWbarSplitArgs<SplitF16> g) {
+  using SP = SplitF16;
+  using CF = SplitCfg<SP>;
+  using E = typename SP::E;
+  static_assert(R == 2 || R == 4 || R == 8, "16 requests per block in K >= 16 / R phases");
+  constexpr int PIECE = CF::PIECE;
+  constexpr int WIMG = 4 * PIECE * 2;                                    // bytes of one group's W image: [2 k-steps][2 pieces][128][32] halfwords
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // LDS: W images [2 buffers][2 row tiles] (128 KB), then the row-factor tables [2 row tiles][K + 1][128] (row K: zeros)
+  SplitLane L;
+  const int w = L.wave_u(), gp = w >> 1, wc = w & 1;
+  L.wc = wc;
+  const int K = g.K, Mp = g.Mp;
+  const int tabf = (K + 1) * GDRF_TILE;
+  float* const tab0 = reinterpret_cast<float*>(smem + 4 * WIMG);
+  const int nct = (Mp + GDRF_TILE - 1) / GDRF_TILE;
+  int64_t rtile; int ct;
+  nt_xcd_map_paired(blockIdx.x, nct, gp, rtile, ct);
+  const int64_t m0 = rtile * GDRF_TILE;
+  const int n0 = ct * GDRF_TILE;
+  wbar_fill_scales(g, tab0, (rtile - gp) * GDRF_TILE, L.tid);
+  wbar_fill_scales(g, tab0 + tabf, (rtile - gp + 1) * GDRF_TILE, L.tid);
+  tab0[(L.tid >> 7) * tabf + K * GDRF_TILE + (L.tid & 127)] = 0.0f;
+  const float* const tab = tab0 + gp * tabf;
+
+  const int nk = Mp / 64, nph = nk * K;
+  const int lr = L.lr, lg = L.lg, drow = L.drow(), dq = L.dq();
+  const unsigned w_lds = lds_addr(smem) + (unsigned)(gp * WIMG);       // this row tile's image, buffer 0; buffer 1 is 2 WIMG further
+  const unsigned frag_addr = w_lds + (unsigned)(L.frag() * 2);
+  // Request r = 0 .. 15 of this wave for block q: k-step r >> 3, piece (r >> 2) & 1, row block rbk = wc + 2 (r & 3) of the row tile's eight.  A
+  // wave-uniform base (the tile's first row, or row 0 for a tile wholly past the end) + one 32-bit lane offset per row block, the lane's row
+  // clamped to the last one (clamped rows have factor 0 and are never stored).  In phase rep the wave issues r = min(rep, 16 / R - 1) R + j, j < R
+  // (phases past 16 / R repeat the last ones): j is a literal, so the row block is one too (R >= 4) or one of two (R = 2).
+  // s_nop 4: the base may come straight from v_readfirstlane.
+  const int64_t mbase = m0 < g.nrows ? m0 : 0;
+  auto w_off = [&](int i) {
+    const int64_t rel = (wc + 2 * i) * 16 + drow, last = g.nrows - 1 - mbase;
+    unsigned v = (unsigned)(((int)(rel < last ? rel : last) * Mp + dq) * 2);
+    asm volatile("" : "+v"(v));             // four registers, not an array hipcc may index in memory
+    return v;
+  };
+  const unsigned vw0 = w_off(0), vw1 = w_off(1), vw2 = w_off(2), vw3 = w_off(3);
+  const E* const w_row = g.Wh + mbase * Mp;
+  auto dma_w = [&](int q, int buf, int rep_c, auto jc) {
+    constexpr int j = decltype(jc)::value;
+    const int r = rep_c * R + j, ks = r >> 3, p = (r >> 2) & 1;
+    const unsigned va = (j & 1) ? vw1 : vw0, vb = (j & 1) ? vw3 : vw2;
+    const unsigned vo = R >= 4 ? ((j & 2) ? vb : va) : ((rep_c & 1) ? vb : va);
+    const int rbk = wc + 2 * (r & 3);
+    const E* src = w_row + (p ? g.w_stride : 0) + q * 64 + ks * 32;
+    const unsigned dst = w_lds + (unsigned)(buf * 2 * WIMG + (ks * 2 + p) * PIECE * 2 + rbk * 1024);
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(src), "s"(dst) : "memory");
+  };
+  // B fragments of phase (q, rep): a wave-uniform base per (k-step, piece), one lane offset, the column group in the immediate offset
+  const int col0 = (n0 + wc * 64 < Mp) ? n0 + wc * 64 : 0;            // Mp % 64 == 0: a wave's 64 columns are inside or past the end together
+  const unsigned voff_b = (unsigned)((lr * 32 + 8 * lg) * 2);
+  const int64_t b_ks = (int64_t)Mp * 32, b_rep = (int64_t)(Mp >> 5) * b_ks;   // elements per 32-deep k block and per topic
+  const E* sb[2][2];
+  auto b_bases = [&](const E* b0) {
+    sb[0][0] = b0; sb[1][0] = b0 + b_ks; sb[0][1] = b0 + g.piece_stride; sb[1][1] = b0 + b_ks + g.piece_stride;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) asm volatile("" : "+s"(sb[i >> 1][i & 1]));   // they exist here, far ahead of the loads that read them
+  };
+  const E* b_blk = g.Bh + (int64_t)col0 * 32;   // k-step 0, piece 0 of (block q, topic 0) and of the current phase
+  const E* b_cur = b_blk;
+
+  // the accumulators as single registers (row group, column group, row 4 lg + r): the updates below are single v_fmac_f32 - beside MFMAs a
+  // packed-f32 instruction costs more than the two it replaces -, and nothing in the loop needs them as tuples
+  float acc[8][4][4];
+  f32x4 P[8], s8[8];
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+    P[a] = f32x4{0, 0, 0, 0}; s8[a] = f32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0f;
+  }
+  // prologue: the first block's W image, the first phase's B fragments
+  for (int rp = 0; rp < 16 / R; ++rp) static_for<R>([&](auto jc) { dma_w(0, 0, rp, jc); });
+  b_bases(b_cur);
+  static_for<16>([&](auto jc) {
+    constexpr int j = decltype(jc)::value, bb = j >> 2, ks = (j >> 1) & 1, p = j & 1;
+    wb1_gload<wb1_breg(0, ks, bb, p), bb * 1024>(sb[ks][p], voff_b);
+  });
+  wb1_vmcnt<0>();
+  __syncthreads();                            // also publishes the factor tables
+
+  // Where things sit in a phase (gap m = behind MFMA m of a column group; an MFMA holds the issue port for 8 of its 16 cycles, so a gap
+  // hides two 4-cycle instructions or one dearer one):
+  //   MFMAs      two halves of 24, row groups 0 - 3 then 4 - 7, each (k-step, product, row group); P[a] starts from 0 in its first
+  //   updates    gaps 4 - 11 of a half, two v_fmac each: in the first half the row groups 4 - 7 of the column group BEFORE (finished 8 MFMAs
+  //              earlier, overwritten from gap 24 on), in the second half the row groups 0 - 3 of this one
+  //   factors    group 0: rows of the row groups 0 - 3 in gaps 0 - 3, of 4 - 7 in gaps 13 - 19 (behind the last update with the old ones)
+  //   B loads    of the next phase: 8 in group 0, 8 in group 1, gaps 12, 14 .. 26
+  //   W requests R / 2 in group 0 and R / 2 in group 2, gaps 38, 40 ..: far apart - a request waits for M0 until the one before has read it
+  constexpr int N1 = R / 2, N2 = R / 2;
+  int c = 0, q = 0, rep = 0;
+  for (int it = 0; it < (nph + 1) / 2; ++it) {
+    static_for<2>([&](auto hc) {
+      constexpr int h = decltype(hc)::value;  // phase c multiplies ring half h and fills half 1 - h
+      const bool live = c < nph;
+      const int qq = q < nk ? q : nk - 1;
+      if (live && rep == 0) {                 // a new reduction block: its W image is complete and every wave is done with the one before
+        if (c > 0) { wb1_vmcnt<0>(); gdrf_raw_barrier(); }
+        const unsigned fa = frag_addr + (unsigned)((qq & 1) * 2 * WIMG);
+        static_for<32>([&](auto fc) {
+          constexpr int f = decltype(fc)::value, ks = f >> 4, p = (f >> 3) & 1, a = f & 7;
+          wb1_ldsread<wb1_wreg(ks, a, p), ((ks * 2 + p) * PIECE + a * 16 * 32) * 2>(fa);
+        });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }
+      const unsigned saddr = lds_addr(tab + (live ? rep : K) * GDRF_TILE + lg * 4);
+      // the next phase (the last one re-requests itself) and the next block (likewise)
+      const E* const b_next = c + 1 >= nph ? b_cur : (rep + 1 == K ? b_blk + 2 * b_ks : b_cur + b_rep);
+      b_bases(b_next);
+      const int qn = qq + 1 < nk ? qq + 1 : nk - 1, bufn = (qq + 1) & 1;
+      const int rep_c = (live && rep < 16 / R) ? rep : 16 / R - 1;
+      static_for<4>([&](auto bc) {
+        constexpr int b = decltype(bc)::value;
+        // in flight behind the four loads this group needs (issued one phase ago): the later loads of that phase, its requests, and what
+        // this phase has issued so far
+        wb1_vmcnt<b == 0 ? 12 + N1 + N2 : (b == 1 ? 16 + 2 * N1 + N2 : (b == 2 ? 20 + N1 + N2 : 16 + N1 + 2 * N2))>();
+        static_for<48>([&](auto mc) {
+          constexpr int m = decltype(mc)::value, half = m / 24, mm = m % 24, ks = mm / 12, t = (mm >> 2) % 3, a = half * 4 + (mm & 3);
+          wb1_mfma<wb1_wreg(ks, a, SP::pa(t)), wb1_breg(h, ks, b, SP::pb(t)), mm < 4>(P[a]);
+          if constexpr (mm >= 4 && mm < 12) {
+            constexpr int i = mm - 4, au = (half == 0 ? 4 : 0) + (i >> 1), bu = half == 0 ? (b + 3) & 3 : b;
+            wb1_update2<2 * (i & 1)>(acc[au][bu][2 * (i & 1)], acc[au][bu][2 * (i & 1) + 1], s8[au], P[au]);
+          }
+          if constexpr (b == 0) {             // this phase's row factors (asm reads: hipcc neither counts nor moves them; waited for in gap 27)
+            if constexpr (m < 4) asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(s8[m]) : "v"(saddr), "i"(m * 64) : "memory");
+            if constexpr (m >= 13 && m < 20 && (m & 1)) asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(s8[4 + (m - 13) / 2]) : "v"(saddr), "i"((4 + (m - 13) / 2) * 64) : "memory");
+            if constexpr (m == 27) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s8[0]), "+v"(s8[1]), "+v"(s8[2]), "+v"(s8[3]), "+v"(s8[4]), "+v"(s8[5]), "+v"(s8[6]), "+v"(s8[7]) : : "memory");
+          }
+          if constexpr (b < 2 && m >= 12 && m < 28 && (m & 1) == 0) {
+            constexpr int j = 8 * b + (m - 12) / 2, bb = j >> 2, ks2 = (j >> 1) & 1, p2 = j & 1;
+            wb1_gload<wb1_breg(1 - h, ks2, bb, p2), bb * 1024>(sb[ks2][p2], voff_b);
+          }
+          if constexpr ((b == 0 || b == 2) && m >= 38 && m < 38 + 2 * N1 && (m & 1) == 0)
+            dma_w(qn, bufn, rep_c, std::integral_constant<int, (b == 0 ? 0 : N1) + (m - 38) / 2>{});
+        });
+      });
+      ++c;
+      b_cur = b_next;
+      if (++rep == K) { rep = 0; ++q; b_blk += 2 * b_ks; }
+    });
+  }
+  wb1_vmcnt<0>();
+  // the last column group's row groups 4 - 7: their MFMAs' results are not covered by following MFMAs
+  asm volatile("s_nop 15\n\ts_nop 15" : "+v"(P[4]), "+v"(P[5]), "+v"(P[6]), "+v"(P[7]));
+  static_for<8>([&](auto ic) {
+    constexpr int i = decltype(ic)::value;
+    wb1_update2<2 * (i & 1)>(acc[4 + (i >> 1)][3][2 * (i & 1)], acc[4 + (i >> 1)][3][2 * (i & 1) + 1], s8[4 + (i >> 1)], P[4 + (i >> 1)]);
+  });
+  f32x4 accv[2][4][4];                        // the epilogue takes them as the MFMA's tuples
+#pragma unroll
+  for (int a = 0; a < 8; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) accv[a >> 2][a & 3][b] = f32x4{acc[a][b][0], acc[a][b][1], acc[a][b][2], acc[a][b][3]};
+
+  // the lane's place again, from the hardware lane counter: the values derived from threadIdx before the loop need not live through it
+  L.lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  L.lr = L.lane & 15; L.lg = L.lane >> 4;
+  // ---- epilogue, as k64's: the global loads up front from clamped addresses (the lower 64 rows' W tile behind the upper rows' first store),
+  // the rank-K term on the f32 MFMA - from asm: in a kernel that may use more than 256 registers hipcc gives every builtin MFMA the AGPR form
+  // and would shuttle the accumulators -, then out = acc - 2 asum W through the wave's transposition tile, 32 rows at a time.
+  f32x4 wv[2][2][8];
+  float as2v[2][2][8];
+  auto load_w = [&](int hr) {
+    L.wr = hr;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int64_t m = m0 + wbar_seg_row(L, h, i);
+        const int n = n0 + wbar_seg_col(L);
+        wv[hr][h][i] = *reinterpret_cast<const f32x4*>(g.W + (m < g.nrows ? m : 0) * Mp + (n < Mp ? n : 0));
+      }
+  };
+  load_w(0);
+#pragma unroll
+  for (int hr = 0; hr < 2; ++hr) {
+    L.wr = hr;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int64_t m = m0 + wbar_seg_row(L, h, i);
+        as2v[hr][h][i] = 2.0f * g.asum[m < g.nrows ? m : 0];
+      }
+  }
+  for (int kb = 0; kb < K; kb += 8) {
+    float av[2][8], bv[2][4];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int k = kb + 4 * it + L.lg, kc = k < K ? k : 0;
+#pragma unroll
+      for (int a = 0; a < 8; ++a) {
+        const int64_t row = m0 + a * 16 + L.lr;
+        const float v = g.locbar[(int64_t)kc * g.ldk + (row < g.nrows ? row : 0)];
+        av[it][a] = (k < K && row < g.nrows) ? v : 0.0f;
+      }
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int col = n0 + wc * 64 + b * 16 + L.lr;
+        const float v = g.U[(int64_t)kc * g.M + (col < g.M ? col : 0)];
+        bv[it][b] = (k < K && col < g.M) ? v : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      if (kb + 4 * it < K) {
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b)      // s_nop 1: av / bv / acc may come straight from compiler VALU code
+            asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(accv[a >> 2][a & 3][b]) : "v"(av[it][a]), "v"(bv[it][b]));
+      }
+    }
+  }
+#pragma unroll
+  for (int hr = 0; hr < 2; ++hr)            // the rank-K MFMAs' results (inline asm: outside hipcc's hazard tables)
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+      asm volatile("s_nop 15" : "+v"(accv[hr][a][0]), "+v"(accv[hr][a][1]), "+v"(accv[hr][a][2]), "+v"(accv[hr][a][3]));
+  __syncthreads();                            // every wave is done with the W images, and every request into them has landed
+  float wmax = 0.0f;
+  L.wave = w;
+  float* tile = wbar_tile(smem, 0, L);
+#pragma unroll
+  for (int hr = 0; hr < 2; ++hr) {
+    L.wr = hr;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      wbar_tile_put(tile, accv[hr], h, L);
+      if (hr == 0 && h == 1) { load_w(1); L.wr = 0; }         // the lower rows' W tile: requested while the upper rows' second half is stored
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int64_t m = m0 + wbar_seg_row(L, h, i);
+        const int n = n0 + wbar_seg_col(L);
+        const f32x4 t = wbar_tile_get(tile, i, L);
+        if (m < g.nrows && n < Mp) wbar_seg_store(g.Wbar + m * Mp + n, t, as2v[hr][h][i], wv[hr][h][i], wmax);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // reads done before the tile is overwritten with the next half
+    }
+  }
+  if (g.wbar_max) wave_max_publish(g.wbar_max, wmax);
+}
 
 // Wbar = the sum of the slices' partial sums (fixed order), and its maximum for the block scale of the G^T operand
 __global__ __launch_bounds__(256) void wbar_slab_sum_kernel(const float* __restrict__ slab, int64_t slab_stride, int nslice, int64_t n4 /*float4 count*/,

@@ -26,17 +26,9 @@
 // Three buffers: the DMA runs two chunks (~5 us) ahead - with one chunk of lookahead the HBM latency under load showed (timing-only
 // ablation without the DMA: 11.4 -> 8.1 ms).
 #pragma once
-#include <utility>
 #include "gemm_tn_topics.h"
 
 namespace gdrf {
-
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}).  (A `#pragma unroll` of 20 stages x 24
-// MFMAs with inline asm in the body is refused by hipcc's unroller - "loop not unrolled" - and the accumulator arrays land in scratch.)
-template <int... Is, class F> __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
 constexpr int TN1_CH = 64;                        // rows per chunk
 constexpr int TN1_XBLK = 1056;                    // bytes per four-row block of the x image

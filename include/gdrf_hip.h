@@ -496,7 +496,7 @@ int gdrf_get_timing(gdrf_ctx* ctx, double* ms_out, int64_t* count_out, int nslot
 /* The kernel form each stage that the host picks from K, Mp or n launched in the most recent call that ran it (host bookkeeping,
  * no synchronisation; 0 = not run yet in this context).  out[i] = slot i for i < n (slots past GDRF_NFORMS read 0):
  *   GDRF_FORM_WBAR         Wbar: 1 gemm_nt (dense B_k), 2 gemm_nt on the stored T_k, 3 bwd_wbar_split<SP,1>, 4 bwd_wbar_split<SP,2>,
- *                          5 bwd_wbar_split_cc, 6 bwd_wbar_f16_k64
+ *                          5 bwd_wbar_split_cc, 6 bwd_wbar_f16_k64, 7 bwd_wbar_f16_w1 (one wave per SIMD, B_k from L2 to registers)
  *   GDRF_FORM_WBAR_NSLICE  reduction slices of the k64 form (> 1: partial sums in slabs, then wbar_slab_sum); 1 for the others
  *   GDRF_FORM_AK           A_k: 1 gemm_tn, 2 gemm_tn_split, 3 tn_topics_f16 (two waves per SIMD), 4 tn_topics_w2 (one wave per SIMD)
  *   GDRF_FORM_AK_KGROUPS   10-topic groups of forms 3 and 4 (0 for the others)
