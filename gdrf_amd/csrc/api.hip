@@ -976,6 +976,32 @@ template <typename T, typename TS> struct Impl {
       const int64_t pairs = (rtiles + 1) / 2;
       const int rt8 = (int)((pairs + 7) / 8);
       FwdTSplitArgs<SP> a{(const E*)c->Wh, (int64_t)c->ncap * Mp, n, Mp, K, KG, rt8, (const E*)c->STh, nb, (float*)c->tt, c->ldk, (const float*)c->ssc};
+      if constexpr (std::is_same<SP, SplitF16>::value) {
+        // many rows and at most 16 topics (the gate of the W-bar form of the same geometry): one wave per SIMD, S_k^T fragments straight from
+        // L2 into registers
+        const int nct_ = (Mp + GDRF_TILE - 1) / GDRF_TILE;
+        if ((Mp % 64) == 0 && K >= 2 && K <= 16 && pairs * nct_ > 32) {
+          // topics in fours on the quad form (one row tile, four topics per workgroup: half the W traffic per topic), the K % 4 left over on
+          // the pair form (two row tiles, two topics), in L2 groups of KGP pairs whose workgroups share the W blocks they stream
+          const int KQ = K / 4 * 4;
+          if (KQ) {
+            a.k_lo = 0; a.k_n = KQ; a.KG = 1; a.rt8 = (int)((rtiles + 7) / 8);
+            constexpr int lds_q = 2 * W1_WIMG + 16 * GDRF_TILE * 4;             // + the row-sum slots
+            HIPCHK(hipFuncSetAttribute((const void*)fwd_t_f16_w1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q));
+            hipLaunchKernelGGL(fwd_t_f16_w1_kernel<true>, dim3((unsigned)(8 * (KQ / 4) * a.rt8)), dim3(256), lds_q, s, a);
+          }
+          const int KP = (K - KQ + 1) / 2, KGP = std::min(KP, FWD_T_W1_KGP);
+          if (KP) {
+            a.k_lo = KQ; a.k_n = K - KQ; a.KG = KGP; a.rt8 = rt8;
+            constexpr int lds_p = 4 * W1_WIMG + 16 * GDRF_TILE * 4;
+            HIPCHK(hipFuncSetAttribute((const void*)fwd_t_f16_w1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
+            hipLaunchKernelGGL(fwd_t_f16_w1_kernel<false>, dim3((unsigned)(8 * KP * rt8)), dim3(256), lds_p, s, a);
+          }
+          c->forms[GDRF_FORM_FWD_T] = 4; c->forms[GDRF_FORM_FWD_T_KG] = KQ ? 4 : 2 * KGP;
+          LAUNCHCHK("fwd_t_split");
+          return 0;
+        }
+      }
       if constexpr (SP::NP == 2) {       // 256 x 256 workgroup tiles (two-piece modes: eight operand images in 128 KB)
         constexpr int lds4 = 8 * SplitCfg<SP>::IMG * 2 + 8 * GDRF_TILE * 4;      // + the row-sum slots
         HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_q4_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4));

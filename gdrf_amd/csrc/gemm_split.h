@@ -897,6 +897,48 @@ template <int R0> __device__ __forceinline__ void wb1_update2(float& c0, float& 
 }
 template <int N> __device__ __forceinline__ void wb1_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
 
+// The W side of the one-wave-per-SIMD kernels (bwd_wbar_f16_w1_kernel, fwd_t_f16_w1_kernel): NW = 2 or 4 waves stage and read the image of one
+// 128-row tile's 64-deep reduction block - [2 k-steps][2 pieces][128][32] halfwords, swizzled (SplitLane), 32 LDS-DMA requests of 16 rows -,
+// wave wsub of them the row blocks wsub + NW i, i < 8 / NW.  Buffer buf of the double-buffered image lies buf * buf_stride bytes behind w_lds.
+// Request r = 0 .. 32 / NW - 1 of a wave for block q: (k-step, piece, i) = r in mixed radix (2, 2, 8 / NW).  A wave-uniform base (the tile's
+// first row, or row 0 for a tile wholly past the end) + one 32-bit lane offset per row block, the lane's row clamped to the last one (clamped
+// rows are never stored).  A caller that spreads its requests over its phases R at a time issues r = rep_c R + j, j < R: j is a literal, so the
+// row block is one too (R a multiple of 8 / NW) or one of two (NW = 2, R = 2).  s_nop 4: the base may come straight from v_readfirstlane.
+constexpr int W1_WIMG = 4 * SplitCfg<SplitF16>::PIECE * 2;              // bytes of one row tile's image
+template <int NW> struct W1Image {
+  static_assert(NW == 2 || NW == 4, "row blocks per wave: 4 or 2");
+  static constexpr int PER = 8 / NW;
+  const _Float16* w_row; int64_t w_stride;
+  unsigned w_lds, buf_stride;
+  int wsub;
+  unsigned vw0, vw1, vw2, vw3;
+  __device__ __forceinline__ W1Image(const _Float16* Wh, int64_t w_stride_, int64_t nrows, int Mp, int64_t m0, unsigned w_lds_, unsigned buf_stride_, int wsub_,
+                                     const SplitLane& L)
+      : w_stride(w_stride_), w_lds(w_lds_), buf_stride(buf_stride_), wsub(wsub_) {
+    const int drow = L.drow(), dq = L.dq();
+    const int64_t mbase = m0 < nrows ? m0 : 0;
+    auto w_off = [&](int i) {
+      const int64_t rel = (wsub + NW * i) * 16 + drow, last = nrows - 1 - mbase;
+      unsigned v = (unsigned)(((int)(rel < last ? rel : last) * Mp + dq) * 2);
+      asm volatile("" : "+v"(v));             // single registers, not an array hipcc may index in memory
+      return v;
+    };
+    vw0 = w_off(0); vw1 = w_off(1);
+    if constexpr (NW == 2) { vw2 = w_off(2); vw3 = w_off(3); } else { vw2 = 0; vw3 = 0; }
+    w_row = Wh + mbase * Mp;
+  }
+  template <int R, int J> __device__ __forceinline__ void request(int q, int buf, int rep_c) const {
+    static_assert(NW == 2 || R % 2 == 0, "the row block must follow from J");
+    const int r = rep_c * R + J, ks = r / (2 * PER), p = (r / PER) & 1;
+    const unsigned va = (J & 1) ? vw1 : vw0, vb = (J & 1) ? vw3 : vw2;
+    const unsigned vo = NW == 4 ? va : (R >= 4 ? ((J & 2) ? vb : va) : ((rep_c & 1) ? vb : va));
+    const int rbk = wsub + NW * (r & (PER - 1));
+    const _Float16* src = w_row + (p ? w_stride : 0) + q * 64 + ks * 32;
+    const unsigned dst = w_lds + (unsigned)buf * buf_stride + (unsigned)((ks * 2 + p) * SplitCfg<SplitF16>::PIECE * 2 + rbk * 1024);
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(src), "s"(dst) : "memory");
+  }
+};
+
 template <int R>
 __global__ __launch_bounds__(256, 1) void bwd_wbar_f16_w1_kernel(BwdWbarSplitArgs<SplitF16> g) {
   using SP = SplitF16;
@@ -924,33 +966,13 @@ __global__ __launch_bounds__(256, 1) void bwd_wbar_f16_w1_kernel(BwdWbarSplitArg
   const float* const tab = tab0 + gp * tabf;
 
   const int nk = Mp / 64, nph = nk * K;
-  const int lr = L.lr, lg = L.lg, drow = L.drow(), dq = L.dq();
+  const int lr = L.lr, lg = L.lg;
   const unsigned w_lds = lds_addr(smem) + (unsigned)(gp * WIMG);       // this row tile's image, buffer 0; buffer 1 is 2 WIMG further
   const unsigned frag_addr = w_lds + (unsigned)(L.frag() * 2);
-  // Request r = 0 .. 15 of this wave for block q: k-step r >> 3, piece (r >> 2) & 1, row block rbk = wc + 2 (r & 3) of the row tile's eight.  A
-  // wave-uniform base (the tile's first row, or row 0 for a tile wholly past the end) + one 32-bit lane offset per row block, the lane's row
-  // clamped to the last one (clamped rows have factor 0 and are never stored).  In phase rep the wave issues r = min(rep, 16 / R - 1) R + j, j < R
-  // (phases past 16 / R repeat the last ones): j is a literal, so the row block is one too (R >= 4) or one of two (R = 2).
-  // s_nop 4: the base may come straight from v_readfirstlane.
-  const int64_t mbase = m0 < g.nrows ? m0 : 0;
-  auto w_off = [&](int i) {
-    const int64_t rel = (wc + 2 * i) * 16 + drow, last = g.nrows - 1 - mbase;
-    unsigned v = (unsigned)(((int)(rel < last ? rel : last) * Mp + dq) * 2);
-    asm volatile("" : "+v"(v));             // four registers, not an array hipcc may index in memory
-    return v;
-  };
-  const unsigned vw0 = w_off(0), vw1 = w_off(1), vw2 = w_off(2), vw3 = w_off(3);
-  const E* const w_row = g.Wh + mbase * Mp;
-  auto dma_w = [&](int q, int buf, int rep_c, auto jc) {
-    constexpr int j = decltype(jc)::value;
-    const int r = rep_c * R + j, ks = r >> 3, p = (r >> 2) & 1;
-    const unsigned va = (j & 1) ? vw1 : vw0, vb = (j & 1) ? vw3 : vw2;
-    const unsigned vo = R >= 4 ? ((j & 2) ? vb : va) : ((rep_c & 1) ? vb : va);
-    const int rbk = wc + 2 * (r & 3);
-    const E* src = w_row + (p ? g.w_stride : 0) + q * 64 + ks * 32;
-    const unsigned dst = w_lds + (unsigned)(buf * 2 * WIMG + (ks * 2 + p) * PIECE * 2 + rbk * 1024);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(src), "s"(dst) : "memory");
-  };
+  // The W image's requests (W1Image): in phase rep the wave issues r = min(rep, 16 / R - 1) R + j, j < R (phases past 16 / R repeat the last
+  // ones).  Clamped rows have factor 0.
+  const W1Image<2> WI(g.Wh, g.w_stride, g.nrows, Mp, m0, w_lds, 2 * WIMG, wc, L);
+  auto dma_w = [&](int q, int buf, int rep_c, auto jc) { WI.template request<R, decltype(jc)::value>(q, buf, rep_c); };
   // B fragments of phase (q, rep): a wave-uniform base per (k-step, piece), one lane offset, the column group in the immediate offset
   const int col0 = (n0 + wc * 64 < Mp) ? n0 + wc * 64 : 0;            // Mp % 64 == 0: a wave's 64 columns are inside or past the end together
   const unsigned voff_b = (unsigned)((lr * 32 + 8 * lg) * 2);
@@ -1176,9 +1198,10 @@ template <class SP> struct FwdTSplitArgs {
   const typename SP::E* STh; int64_t piece_stride;    // STh[p][k][i / 32][j][i % 32] = pieces of S_k[i][j] (k-blocked)
   float* tt; int64_t ldt;
   const float* sc;
+  int k_lo = 0, k_n = 0;                      // fwd_t_f16_w1_kernel only: the topics [k_lo, k_lo + k_n) of this launch
 };
 
-// Block map of both tt kernels.  Grid: 8 * K * rt8 with rt8 = ceil(row-tile pairs / 8).  XCD = blockIdx & 7 owns the pairs r * 8 + xcd; topics
+// Block map of the tt kernels.  Grid: 8 * K * rt8 with rt8 = ceil(row-tile pairs / 8).  XCD = blockIdx & 7 owns the pairs r * 8 + xcd; topics
 // go in groups of KG, group-major (every XCD first runs all its pairs for topics [0, KG), then [KG, 2 KG), ...) so that only KG topics'
 // S^T pieces are live in its 4 MB L2 at a time; the KG workgroups of one pair are adjacent.  rt0: the pair's first row tile; bz: the topic.
 template <class SP> __device__ __forceinline__ void fwd_t_map_block(const FwdTSplitArgs<SP>& g, int64_t& rt0, int& bz) {
@@ -1195,6 +1218,18 @@ template <class SP> __device__ __forceinline__ void fwd_t_map_block(const FwdTSp
 // its loop.
 __device__ __forceinline__ bool fwd_t_col_ok(int ct, int b, int Mp, const SplitLane& L) { return ct * GDRF_TILE + L.wc * 64 + b * 16 + L.lr < Mp; }
 __device__ __forceinline__ float fwd_t_sq(float x, bool cok) { return cok ? x * x : 0.0f; }
+// Lane 0 of every 16-lane row gets the row's sum (the other lanes get it in other orders of addition): four DPP rotations on the VALU instead of
+// group16_sum's four trips through the LDS crossbar.  Fixed order, so deterministic.
+__device__ __forceinline__ float row16_sum_lane0(float v) {
+  auto rot = [](float x, auto nc) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + decltype(nc)::value, 0xf, 0xf, false));   // row_ror:n
+  };
+  v += rot(v, std::integral_constant<int, 8>{});
+  v += rot(v, std::integral_constant<int, 4>{});
+  v += rot(v, std::integral_constant<int, 2>{});
+  v += rot(v, std::integral_constant<int, 1>{});
+  return v;
+}
 // tt of row m0 + tid (tid < 128) and topic bz from its sum of squares v; the block scales of W and S_k^T come off here
 template <class SP> __device__ __forceinline__ void fwd_t_store_tt(const FwdTSplitArgs<SP>& g, int bz, int64_t m0, int tid, float v) {
   const int64_t m = m0 + tid;
@@ -1487,6 +1522,263 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
   if (gc == 0 && tid < GDRF_TILE) {
     const float* q = reinterpret_cast<const float*>(smem + (size_t)8 * IMG * 2) + (gr * 2) * 2 * GDRF_TILE + tid;
     fwd_t_store_tt(g, bz, m0, tid, (q[0] + q[GDRF_TILE]) + (q[2 * GDRF_TILE] + q[3 * GDRF_TILE]));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// tt, ONE WAVE PER SIMD, S_k^T fed from L2 to registers (f16x3 only; Mp % 64 == 0, 2 <= K <= 16, many rows: the gate of bwd_wbar_f16_w1_kernel).
+//
+// What fwd_t_split_q4_kernel spends beside its MFMAs is requests and fragment reads behind a 16-wave barrier per 32-deep chunk, half of them
+// for the small operand.  STh has Bh's k-blocked layout, so - as in bwd_wbar_f16_w1_kernel - a 16-column x 32-k MFMA B fragment is 1 024
+// contiguous bytes and one global_load_dwordx4 per wave delivers it finished from the XCD's L2: no M0, no image, no ds_read, no barrier.
+// 256 threads, one wave per SIMD; a wave owns 128 rows and, of the current 128-column tile, the 64 columns of half w & 1, for TWO topics.  Two
+// geometries of a workgroup (g.KG counts its topic groups per L2 group; the launch covers the topics [g.k_lo, g.k_lo + g.k_n), a topic past
+// the end is the last one again and is not stored):
+//   pair (QUAD = false)  two row tiles x two topics: wave pair w >> 1 = row tile, W-bar w1's geometry, 16 W requests per wave and block.  Every
+//                        column tile re-streams its W blocks for two topics only (25 GB per launch at the headline shape unless the KG adjacent
+//                        workgroups of a row pair share them in L2): alone it only matched q4
+//   quad (QUAD = true)   ONE row tile x four topics: wave pair w >> 1 = topic pair, all four waves read one 32 KB image, 8 requests per wave and
+//                        block, g.rt8 counts single row tiles.  Half the W bytes per topic and row with no reliance on L2 sharing
+// The host runs K / 4 * 4 topics on the quad form and the rest on the pair form.  The workgroup walks the column tiles ct and, per tile, the
+// 64-deep reduction blocks q = 2 ct .. Mp / 64 - 1 (S_k^T is zero above the diagonal); the triangle is kept at 64 columns per wave: the waves of
+// column half 1 sit out a tile's first block and only issue their share of its W requests.  Per lane, ALL named literally in the asm:
+//   a[0:255]    accumulators [topic 0/1][row group 0-7][column group 0-3][4]: C/D of MFMAs with A/B in VGPRs.  Nothing but MFMAs writes them
+//               until a column tile is finished; a tile's first product of each uses C = 0 (the wave's first block of a tile is a second
+//               instantiation of the block body): nothing is ever cleared
+//   v[64:191]   W fragments of the block [k-step][row group][piece], ds_read_b128 once per block from the double-buffered image (W1Image)
+//   v[192:255]  S_k^T fragment ring [column group][k-step][piece]: a register is requested again, for the next (block, topic) phase, right
+//               behind its last MFMA of this phase - every load is three column groups (~2 300 pipe cycles) ahead of its use
+//   v[0:63]     hipcc's
+// (Compiler-allocated f16x8 variables for the fragments and the ring, loaded by asm with "+v": hipcc copied and spilled ring registers whose
+// loads were in flight - 201 spilled VGPRs.)
+// THE REGISTERS ARE A CONTRACT HIPCC DOES NOT KNOW ABOUT: it sees them only as clobbers - of the first MFMA of a column group, of every
+// statement that loads a fragment, of the fold's reads (the ring is live, even in flight, across the fold) -, which keeps everything of its own
+// that lives across such a statement in v[0:63] and makes the kernel descriptor allocate 256 + 256.  The kernel is right only while no
+// compiler-generated instruction touches v[64:255] or an AGPR between the prologue's barrier and the final one, and while hipcc issues no
+// vector-memory or scalar-memory instruction of its own there (the waits are literal counts).  After ANY edit of this kernel or of W1Image, and
+// after a compiler change, repeat the check: `hipcc -save-temps`; in the assembly of both instantiations, between those barriers, no instruction
+// outside the #ASMSTART / #ASMEND pairs names v64 or higher or an AGPR, the 256 `v_accvgpr_read_b32` all belong to the fold, and there is no
+// `v_accvgpr_write`, no `scratch_`, no `s_load`, no `global_load` / `buffer_load` of hipcc's; and `make resources`: VGPRs 256, AGPRs 256,
+// ScratchSize 0, occupancy 1.  tests/test_gpu_fwd_t_w1.py runs both instantiations at every edge.
+//
+// Schedule of a phase = (block, topic) = 4 column groups x 48 MFMAs, each group two halves of 24 (row groups 0 - 3, then 4 - 7; per half
+// k-step-major, then the products SP::pa/pb(t): per accumulator q4's six products per 64-deep block in q4's order).  Behind MFMA m of a group:
+//   W requests   of the NEXT block's image: NG = 4 (pair) or 2 (quad) behind m = 2, 8, .. of the groups 0 and 2 (1 per 24 / 48 MFMAs, far
+//                apart: a request waits for M0 until the one before has read it)
+//   ring loads   of the group's own registers for the next phase, behind m = 27, 35, 39, 47: the last MFMA that reads each
+//   W fragments  eight are read behind the block's barrier, the other 24 one per gap behind the first 24 MFMAs of the block, in the order
+//                of their first use; LDS returns in order, so MFMA m waits by lgkmcnt(issued so far - needed so far)
+// The counts are the same in every phase (the last phase re-requests itself, the last block's image goes to the idle buffer), so every wait
+// is a literal vmcnt: in front of a group, the 12 + NG (even group) or 12 + 2 NG (odd group) operations issued since its loads; in front of a
+// block's barrier the 8 ring loads issued behind the last W request (0 after a block the wave sat out).  vmcnt retires in order: the requests
+// of a phase have to land within one phase, whatever the depth of the image's buffering.  One workgroup barrier per block publishes the image.
+// The fold of a finished tile (two s_nop 15, then v_accvgpr_read, the squares masked by fwd_t_col_ok and summed over the four column groups,
+// the 16 lanes by row16_sum_lane0) adds into one LDS slot per (topic, row tile, tile parity, column half, row) in q4's order; the final sum is
+// q4's too: (q0 + q1) + (q2 + q3).  No atomics: tt is bit-identical from run to run.
+constexpr int FWD_T_W1_KGP = 2;             // topic pairs per L2 group of the pair form: four S_k^T panels, ~2.6 MB at Mp = 512, as the quad form holds
+constexpr int ft1_acc(int tp, int a, int b) { return ((tp * 8 + a) * 4 + b) * 4; }
+// v64 .. v255, as GDRF_ALL_AGPRS
+#define GDRF_V10(p) "v" p "0", "v" p "1", "v" p "2", "v" p "3", "v" p "4", "v" p "5", "v" p "6", "v" p "7", "v" p "8", "v" p "9"
+#define GDRF_RING_VGPRS "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", GDRF_V10("20"), GDRF_V10("21"), GDRF_V10("22"), \
+                        GDRF_V10("23"), GDRF_V10("24"), "v250", "v251", "v252", "v253", "v254", "v255"
+#define GDRF_W1_VGPRS "v64", "v65", "v66", "v67", "v68", "v69", GDRF_V10("7"), GDRF_V10("8"), GDRF_V10("9"), GDRF_V10("10"), GDRF_V10("11"), \
+                      GDRF_V10("12"), GDRF_V10("13"), GDRF_V10("14"), GDRF_V10("15"), GDRF_V10("16"), GDRF_V10("17"), GDRF_V10("18"), "v190", "v191", \
+                      GDRF_RING_VGPRS
+constexpr int ft1_wreg(int ks, int a, int p) { return 64 + ((ks * 8 + a) * 2 + p) * 4; }
+constexpr int ft1_rreg(int b, int ks, int p) { return 192 + ((b * 2 + ks) * 2 + p) * 4; }
+// a[D:D+3] = (ZERO ? 0 : a[D:D+3]) + W fragment v[WA:WA+3] x S_k^T fragment v[RB:RB+3]; CLOB: tell hipcc that the registers are in use
+template <int D, int WA, int RB, bool ZERO, bool CLOB> __device__ __forceinline__ void ft1_mfma() {
+  if constexpr (ZERO && CLOB)
+    asm volatile("v_mfma_f32_16x16x32_f16 a[%c0:%c1], v[%c2:%c3], v[%c4:%c5], 0" : : "i"(D), "i"(D + 3), "i"(WA), "i"(WA + 3), "i"(RB), "i"(RB + 3) : GDRF_ALL_AGPRS, GDRF_W1_VGPRS);
+  else if constexpr (ZERO)
+    asm volatile("v_mfma_f32_16x16x32_f16 a[%c0:%c1], v[%c2:%c3], v[%c4:%c5], 0" : : "i"(D), "i"(D + 3), "i"(WA), "i"(WA + 3), "i"(RB), "i"(RB + 3));
+  else if constexpr (CLOB)
+    asm volatile("v_mfma_f32_16x16x32_f16 a[%c0:%c1], v[%c2:%c3], v[%c4:%c5], a[%c0:%c1]" : : "i"(D), "i"(D + 3), "i"(WA), "i"(WA + 3), "i"(RB), "i"(RB + 3) : GDRF_ALL_AGPRS, GDRF_W1_VGPRS);
+  else
+    asm volatile("v_mfma_f32_16x16x32_f16 a[%c0:%c1], v[%c2:%c3], v[%c4:%c5], a[%c0:%c1]" : : "i"(D), "i"(D + 3), "i"(WA), "i"(WA + 3), "i"(RB), "i"(RB + 3));
+}
+// v[REG:REG+3] = the lane's 16 bytes at sbase (wave-uniform) + voff + OFF / at LDS address addr + OFF.  Not counted by hipcc: the caller waits
+// by vmcnt(n) / lgkmcnt(n).
+template <int REG, int OFF> __device__ __forceinline__ void ft1_gload(const void* sbase, unsigned voff) {
+  asm volatile("global_load_dwordx4 v[%c2:%c3], %0, %1 offset:%c4" : : "v"(voff), "s"(sbase), "i"(REG), "i"(REG + 3), "i"(OFF) : "memory", GDRF_W1_VGPRS);
+}
+template <int REG, int OFF> __device__ __forceinline__ void ft1_ldsread(unsigned addr) {
+  asm volatile("ds_read_b128 v[%c1:%c2], %0 offset:%c3" : : "v"(addr), "i"(REG), "i"(REG + 3), "i"(OFF) : "memory", GDRF_W1_VGPRS);
+}
+// the fold's reads: the ring is live (in flight, even) across them
+template <int REG> __device__ __forceinline__ float ft1_accread() {
+  float x;
+  asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "i"(REG) : GDRF_ALL_AGPRS, GDRF_RING_VGPRS);
+  return x;
+}
+
+template <bool QUAD>
+__global__ __launch_bounds__(256, 1) void fwd_t_f16_w1_kernel(FwdTSplitArgs<SplitF16> g) {
+  using SP = SplitF16;
+  using CF = SplitCfg<SP>;
+  using E = typename SP::E;
+  constexpr int PIECE = CF::PIECE, WIMG = W1_WIMG;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // LDS: W images [2 buffers][NT row tiles] (128 or 64 KB), then the row sums: pair form [topic 0/1][row tile][tile parity][column half][128],
+  // quad form [topic 0-3][tile parity][column half][128]
+  constexpr int NT = QUAD ? 1 : 2, G = QUAD ? 4 : 2;                    // row tiles and topics of a workgroup
+  constexpr int RS_TP = QUAD ? 4 : 8;                                   // slots between a wave's two topics
+  SplitLane L;
+  const int w = L.wave_u(), gp = w >> 1, wc = w & 1;
+  L.wc = wc;
+  const int Mp = g.Mp;
+  const int nk = Mp / 64, nct = (Mp + GDRF_TILE - 1) / GDRF_TILE;
+  FwdTSplitArgs<SP> gm = g;
+  gm.K = (g.k_n + G - 1) / G;                                             // the block map deals topic groups (and row-tile pairs)
+  int64_t rt0; int bp;
+  fwd_t_map_block(gm, rt0, bp);
+  if constexpr (QUAD) rt0 >>= 1;                                          // ... single row tiles here: gm.rt8 counts them
+  // pair form: wave pair gp = row tile gp, both on the group's two topics; quad form: one row tile, wave pair gp = the group's topic pair gp
+  const int k_end = g.k_lo + g.k_n, kw = g.k_lo + G * bp + (QUAD ? 2 * gp : 0);
+  const int k0 = min(kw, k_end - 1), k1 = min(kw + 1, k_end - 1);      // a topic past the end: the last one again, never stored
+  const int64_t m0 = (rt0 + (QUAD ? 0 : gp)) * GDRF_TILE;               // a tile past the end runs on clamped rows; its tt is never stored
+  const int lr = L.lr, lg = L.lg;
+  const unsigned w_lds = lds_addr(smem) + (unsigned)(QUAD ? 0 : gp * WIMG);
+  const unsigned frag_addr = w_lds + (unsigned)(L.frag() * 2);
+  const W1Image<QUAD ? 4 : 2> WI(g.Wh, g.w_stride, g.nrows, Mp, m0, w_lds, NT * WIMG, QUAD ? w : wc, L);
+  constexpr int NREQ = 32 / (QUAD ? 4 : 2), RQ = NREQ / 2, NG = RQ / 2; // requests per wave and block, per topic phase, per column group 0 / 2
+  float* const rs_base = reinterpret_cast<float*>(smem + 2 * NT * WIMG);
+  float* const rs_wave = rs_base + ((QUAD ? gp * 8 : gp * 4) + wc) * GDRF_TILE;           // + (topic * RS_TP + 2 * parity) * 128
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    rs_wave[((i >> 1) * RS_TP + 2 * (i & 1)) * GDRF_TILE + L.lane] = 0.0f;
+    rs_wave[((i >> 1) * RS_TP + 2 * (i & 1)) * GDRF_TILE + 64 + L.lane] = 0.0f;
+  }
+
+  // S_k^T fragments of phase (ct, q, topic): a wave-uniform base per (k-step, piece), one lane offset, the column group in the immediate offset
+  const unsigned voff_b = (unsigned)((lr * 32 + 8 * lg) * 2);
+  const int64_t b_ks = (int64_t)Mp * 32, b_top = (int64_t)(Mp >> 5) * b_ks;     // elements per 32-deep k block and per topic
+  const int64_t dtop = (int64_t)(k1 - k0) * b_top;
+  const E* const st0 = g.STh + (int64_t)k0 * b_top;
+  const int64_t p_stride = g.piece_stride;
+  auto phase_base = [&](int ct, int q) {    // topic k0; a column half past Mp is never multiplied: its loads read the tile's first columns
+    const int col = ct * GDRF_TILE + wc * 64;
+    return st0 + (int64_t)(2 * q) * b_ks + (int64_t)(col < Mp ? col : ct * GDRF_TILE) * 32;
+  };
+  const E* sb[2][2];
+  auto b_bases = [&](const E* b0) {
+    sb[0][0] = b0; sb[1][0] = b0 + b_ks; sb[0][1] = b0 + p_stride; sb[1][1] = b0 + b_ks + p_stride;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) asm volatile("" : "+s"(sb[i >> 1][i & 1]));   // they exist here, far ahead of the loads that read them
+  };
+
+
+  // prologue: the first block's W image, the fragments of the wave's first phase (column half 1: block 1, if there is one)
+  static_for<NREQ>([&](auto jc) { WI.template request<RQ, decltype(jc)::value % RQ>(0, 0, decltype(jc)::value / RQ); });
+  const E* b_cur = phase_base(0, wc < nk ? wc : 0);
+  b_bases(b_cur);
+  static_for<16>([&](auto jc) {
+    constexpr int j = decltype(jc)::value, bb = j >> 2, ks = (j >> 1) & 1, p = j & 1;
+    ft1_gload<ft1_rreg(bb, ks, p), bb * 1024>(sb[ks][p], voff_b);
+  });
+  wb1_vmcnt<0>();
+  __syncthreads();
+
+  // one active block: both topic phases.  FIRST: the wave's first block of the column tile
+  auto block_body = [&](auto firstc, int qn, int bufn, const E* next_blk, unsigned fa) {
+    constexpr bool FIRST = decltype(firstc)::value;
+    // W fragment f = 0 .. 31, in the order of their first use: (half, k-step, piece, row group of the half).  Eight up front, the others one per
+    // gap behind the first 24 MFMAs; LDS returns in order, so MFMA m waits for its fragments by lgkmcnt(issued so far - needed so far)
+    auto wread = [&](auto fc) {
+      constexpr int f = decltype(fc)::value, ks = (f >> 3) & 1, p = (f >> 2) & 1, a = (f >> 4) * 4 + (f & 3);
+      ft1_ldsread<ft1_wreg(ks, a, p), ((ks * 2 + p) * PIECE + a * 16 * 32) * 2>(fa);
+    };
+    static_for<8>(wread);
+    static_for<2>([&](auto tc) {
+      constexpr int tp = decltype(tc)::value;
+      const E* const b_next = tp == 0 ? b_cur + dtop : next_blk;
+      b_bases(b_next);
+      static_for<4>([&](auto bc) {
+        constexpr int b = decltype(bc)::value;
+        wb1_vmcnt<(b & 1) ? 12 + 2 * NG : 12 + NG>();
+        static_for<48>([&](auto mc) {
+          constexpr int m = decltype(mc)::value, half = m / 24, mm = m % 24, ks = mm / 12, t = (mm >> 2) % 3, a = half * 4 + (mm & 3);
+          if constexpr (tp == 0 && b == 0) {
+            if constexpr (m == 0 || m == 4 || m == 36) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
+            if constexpr (m == 12 || m == 16 || m == 28) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+            if constexpr (m == 24) asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
+            if constexpr (m == 40) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          }
+          ft1_mfma<ft1_acc(tp, a, b), ft1_wreg(ks, a, SP::pa(t)), ft1_rreg(b, ks, SP::pb(t)), FIRST && mm < 4, m == 0>();
+          if constexpr (tp == 0 && b == 0 && m < 24) wread(std::integral_constant<int, 8 + m>{});
+          if constexpr ((b == 0 || b == 2) && m < 6 * NG && m % 6 == 2) WI.template request<RQ, (b == 0 ? 0 : NG) + (m - 2) / 6>(qn, bufn, tp);
+          if constexpr (m == 27) ft1_gload<ft1_rreg(b, 0, 1), b * 1024>(sb[0][1], voff_b);
+          if constexpr (m == 35) ft1_gload<ft1_rreg(b, 0, 0), b * 1024>(sb[0][0], voff_b);
+          if constexpr (m == 39) ft1_gload<ft1_rreg(b, 1, 1), b * 1024>(sb[1][1], voff_b);
+          if constexpr (m == 47) ft1_gload<ft1_rreg(b, 1, 0), b * 1024>(sb[1][0], voff_b);
+        });
+      });
+      b_cur = b_next;
+    });
+  };
+
+  int ct = 0, q = 0, s = 0;
+  bool sat = false;
+#pragma unroll 1
+  for (;;) {
+    // the workgroup's next block (the last one requests its own image again, into the idle buffer)
+    int ctn = ct, qn = q + 1;
+    bool more = true;
+    if (qn >= nk) {
+      ctn = ct + 1; qn = 2 * ctn;
+      if (ctn >= nct) { more = false; ctn = ct; qn = q; }
+    }
+    const int bufn = (s + 1) & 1;
+    if (s > 0) {                              // this block's W image is complete and every wave has read the one before
+      if (sat) wb1_vmcnt<0>(); else wb1_vmcnt<8>();
+      gdrf_raw_barrier();
+    }
+    if (q >= 2 * ct + wc) {
+      // the wave's next block (the last phase requests its own fragments again)
+      const E* next_blk = b_cur + dtop;
+      if (q + 1 < nk) next_blk = phase_base(ct, q + 1);
+      else if (ct + 1 < nct && 2 * (ct + 1) + wc < nk) next_blk = phase_base(ct + 1, 2 * (ct + 1) + wc);
+      const unsigned fa = frag_addr + (unsigned)((s & 1) * NT * WIMG);
+      if (q == 2 * ct + wc) block_body(std::true_type{}, qn, bufn, next_blk, fa);
+      else block_body(std::false_type{}, qn, bufn, next_blk, fa);
+      sat = false;
+    } else {                                  // column half 1, first block of a tile: only its share of the next image
+      static_for<NREQ>([&](auto jc) { WI.template request<RQ, decltype(jc)::value % RQ>(qn, bufn, decltype(jc)::value / RQ); });
+      sat = true;
+    }
+    if (q == nk - 1) {                        // fold the finished column tile into the row sums; the next tile's first products start from 0
+      asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+      float* const slot = rs_wave + 2 * (ct & 1) * GDRF_TILE + lg * 4;
+      bool cok[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) cok[b] = fwd_t_col_ok(ct, b, Mp, L);
+      static_for<16>([&](auto ic) {
+        constexpr int tp = decltype(ic)::value >> 3, a = decltype(ic)::value & 7;
+        f32x4 v;
+        static_for<4>([&](auto rc) {
+          constexpr int r = decltype(rc)::value;
+          const float x0 = fwd_t_sq(ft1_accread<ft1_acc(tp, a, 0) + r>(), cok[0]), x1 = fwd_t_sq(ft1_accread<ft1_acc(tp, a, 1) + r>(), cok[1]);
+          const float x2 = fwd_t_sq(ft1_accread<ft1_acc(tp, a, 2) + r>(), cok[2]), x3 = fwd_t_sq(ft1_accread<ft1_acc(tp, a, 3) + r>(), cok[3]);
+          v[r] = row16_sum_lane0((x0 + x1) + (x2 + x3));
+        });
+        if (lr == 0) {
+          f32x4* const p = reinterpret_cast<f32x4*>(slot + tp * RS_TP * GDRF_TILE + a * 16);
+          *p = *p + v;
+        }
+      });
+    }
+    if (!more) break;
+    ct = ctn; q = qn; ++s;
+  }
+  wb1_vmcnt<0>();
+  // the four partial sums of a row (2 tile parities x 2 column halves), added in a fixed order; an odd K's second topic is the first again
+  __syncthreads();
+  for (int e = L.tid; e < 4 * GDRF_TILE; e += 256) {
+    const int sl = e >> 7, row = e & 127;                                // pair form: slot group (topic, row tile); quad form: topic
+    const int kt = g.k_lo + G * bp + (QUAD ? sl : sl >> 1);
+    const float* qd = rs_base + sl * 4 * GDRF_TILE + row;
+    if (kt < k_end)
+      fwd_t_store_tt(g, kt, (rt0 + (QUAD ? 0 : sl & 1)) * GDRF_TILE, row, (qd[0] + qd[GDRF_TILE]) + (qd[2 * GDRF_TILE] + qd[3 * GDRF_TILE]));
   }
 }
 

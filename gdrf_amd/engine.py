@@ -511,7 +511,7 @@ class Engine:
     FORM_SLOTS = ("wbar", "wbar_nslice", "a_k", "a_k_kgroups", "fwd_t", "fwd_t_kg", "loc", "ubar_q4", "rows", "rows_kt", "rows_vt", "gt",
                   "hyper", "predict", "predict_nb")
     FORM_NAMES = dict(wbar=("gemm_nt", "gemm_nt_t", "split<1>", "split<2>", "split_cc", "k64", "w1"), a_k=("gemm_tn", "tn_split", "tn_topics", "w2"),
-                      fwd_t=("gemm_nt", "q4", "cc"), loc=("rows", "gemm_nt", "gemm_nt_wide"), rows=("mfma", "thread", "streamed"),
+                      fwd_t=("gemm_nt", "q4", "cc", "w1"), loc=("rows", "gemm_nt", "gemm_nt_wide"), rows=("mfma", "thread", "streamed"),
                       gt=("gemm_tn", "tn_split"), hyper=("f64", "tn"), predict=("mfma", "rows_lds", "rows_mem", "rows_bigk", "streamed"))
 
     def last_forms(self) -> Dict[str, object]:

@@ -500,8 +500,9 @@ int gdrf_get_timing(gdrf_ctx* ctx, double* ms_out, int64_t* count_out, int nslot
  *   GDRF_FORM_WBAR_NSLICE  reduction slices of the k64 form (> 1: partial sums in slabs, then wbar_slab_sum); 1 for the others
  *   GDRF_FORM_AK           A_k: 1 gemm_tn, 2 gemm_tn_split, 3 tn_topics_f16 (two waves per SIMD), 4 tn_topics_w2 (one wave per SIMD)
  *   GDRF_FORM_AK_KGROUPS   10-topic groups of forms 3 and 4 (0 for the others)
- *   GDRF_FORM_FWD_T        tt: 1 gemm_nt, 2 fwd_t_split_q4, 3 fwd_t_split_cc
- *   GDRF_FORM_FWD_T_KG     topics per L2 group of forms 2 and 3 (0 for gemm_nt)
+ *   GDRF_FORM_FWD_T        tt: 1 gemm_nt, 2 fwd_t_split_q4, 3 fwd_t_split_cc, 4 fwd_t_f16_w1 (one wave per SIMD, two topics per wave,
+ *                          S_k^T from L2 to registers)
+ *   GDRF_FORM_FWD_T_KG     topics per L2 group of forms 2, 3 and 4 (0 for gemm_nt)
  *   GDRF_FORM_LOC          loc = W U^T: 1 loc_rows, 2 gemm_nt, 3 gemm_nt with two column tiles (f64, K > 64)
  *   GDRF_FORM_UBAR_Q4      topic quads per pass of ubar_part
  *   GDRF_FORM_ROWS         row terms: 1 elbo_rows_mfma, 2 elbo_rows (one thread per row), 3 vocabulary-streamed
