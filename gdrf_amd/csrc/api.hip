@@ -21,6 +21,7 @@
 #include "rows_csr.h"
 #include "hyper_tn.h"
 #include "optim.h"
+#include "forms.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,6 +33,17 @@
 #include <vector>
 
 using namespace gdrf;
+namespace F = gdrf::forms;
+
+// forms.h restates the constants its rules share with the kernels: each one is tied to its original here
+static_assert(F::F_TILE == GDRF_TILE && F::F_MPAD == GDRF_MPAD && F::F_DMAX == GDRF_DMAX && F::F_KMAX == GDRF_KMAX && F::F_LOC_KMAX == LOC_KMAX, "forms.h");
+static_assert(F::F_TNT_KT == TNT_KT && F::F_TN1_CH == TN1_CH && F::F_W1_WIMG == W1_WIMG, "forms.h");
+static_assert(F::F_IMG_F16 == SplitCfg<SplitF16>::IMG && F::F_IMG_BF16 == SplitCfg<SplitBf16>::IMG, "forms.h");
+static_assert(F::F_VEC == sizeof(Vec16<float>::type) && F::F_VEC == sizeof(Vec16<double>::type), "forms.h");
+static_assert(F::F_RATIONALQUADRATIC == GDRF_RATIONALQUADRATIC && 128 / sizeof(float) == TNCfg<float>::BR && 128 / sizeof(double) == TNCfg<double>::BR, "forms.h");
+static_assert(NTCfg<float>::CW == 128 && NTCfg<double>::CW == 64, "forms.h: FormShape::nct_solve, loc_plan");
+static_assert(F::WBAR_LAST == 7 && F::AK_LAST == 4 && F::FWD_T_LAST == 4 && F::LOC_LAST == 3 && F::ROWS_LAST == 3 && F::GT_LAST == 2 && F::HYPER_LAST == 2 &&
+              F::PREDICT_LAST == 5, "the form codes of include/gdrf_hip.h");
 
 static thread_local std::string g_err;
 static int fail(int code, const char* what, const char* detail) {
@@ -263,68 +275,17 @@ static CoordTab coord_tab(const gdrf_ctx* c) {
 static bool ard_fwd(const gdrf_ctx* c) { return c->ard && !c->per; }
 int gdrf_mean_param_layout(const gdrf_ctx* c, int64_t out[2]) { out[0] = param_lay(c).mean; out[1] = c->mean_count; return 0; }
 
-// row blocks of the ubar partial kernel: ~1024 workgroups, multiples of its 256-row staging step
-static int64_t ubar_rows_per_block(int64_t n) { return std::max<int64_t>(256, round_up((n + 1023) / 1024, 256)); }
-
-// number of row splits of the TN kernels: fill the chip's resident-workgroup slots (256 CUs x 3) with as
-// little last-round idling as possible, keep >= 8 chunks per split, cap the slab memory
-static int tn_nsplit(const gdrf_ctx* c, int64_t n, int BR, int wg_per_cu = 3) {
-  const int tiles = c->K * c->nt * (c->nt + 1) / 2;
-  const double slots = 256.0 * wg_per_cu;
-  int64_t maxs = (n + 8 * BR - 1) / (8 * BR);
-  if (maxs > 64) maxs = 64;
-  if (maxs < 1) maxs = 1;
-  int best = 1; double best_eff = 0;
-  for (int ns = 1; ns <= maxs; ++ns) {
-    const double rounds = tiles * (double)ns / slots;
-    const double eff = rounds / std::ceil(rounds);
-    if (eff > best_eff + 1e-9 || (eff > best_eff - 0.02 && rounds >= 2.0 && tiles * (double)best / slots < 2.0)) { best_eff = eff; best = ns; }
-  }
-  return best;
+// What the planning rules of forms.h read of the context, for a call on n rows
+static F::FormShape form_shape(const gdrf_ctx* c, int64_t n, int predict_mode = 0) {
+  F::FormShape f;
+  f.n = n; f.n_cap = c->ncap; f.M = c->M; f.Mp = c->Mp; f.K = c->K; f.V = c->V; f.D = c->D;
+  f.esz = (int)c->esz; f.ssz = (int)c->ssz; f.split = c->split; f.stored_t = c->Tst != nullptr;
+  f.rows_form = c->rows_form; f.csr = c->csr_crow != nullptr;
+  f.hyper_tn = c->hyper_tn; f.learn_z = c->learn_z; f.ard = c->ard; f.per = c->per; f.kind = c->kind;
+  f.nsplit_cap = c->nsplit_cap; f.erows_grid_cap = c->erows_grid_cap; f.predict_mode = predict_mode;
+  return f;
 }
-
-// Row splits of the G^T = W^T Wbar contraction on the bf16 TN kernel.  Its nt*nt tiles are few, so the split count decides both the
-// fill and the block -> XCD map: with a multiple of 8 every XCD owns whole row slabs and the 16 tiles of a slab share their W / Wbar
-// panels through that XCD's L2 (measured at N = 1e6, M = 512: 18.8 -> 8.2 GB fetched, 4.46 -> 3.22 ms at 64 splits).
-static int tn_nsplit_gt(const gdrf_ctx* c, int64_t n, int BR) {
-  int64_t maxs = (n + 8 * BR - 1) / (8 * BR);
-  if (maxs > 64) maxs = 64;
-  if (maxs < 8) return tn_nsplit(c, n, BR, 2);
-  const int tiles = c->nt * c->nt;
-  int best = 8; double best_eff = 0;
-  for (int ns = 8; ns <= maxs; ns += 8) {
-    const double rounds = tiles * (double)ns / 512.0;
-    const double eff = rounds / std::ceil(rounds);
-    if (eff > best_eff + 1e-9 || (eff > best_eff - 0.02 && rounds >= 2.0 && tiles * (double)best / 512.0 < 2.0)) { best_eff = eff; best = ns; }
-  }
-  return best;
-}
-
-// K_nm parts of the hyper-parameter gradients through Hd = dK^T Wbar on the split-fp16 TN kernel (hyper_tn.h): f16x3 contexts with the f64
-// solve, fixed inducing inputs (their gradient needs Kbar itself), kernels whose only shape parameter is the lengthscale
-static bool hyper_tn_on(const gdrf_ctx* c) {
-  return c->hyper_tn && c->split == 2 && c->ssz == 8 && !c->learn_z && !c->ard && !c->per && c->kind != GDRF_RATIONALQUADRATIC && !c->Tst && (c->Mp / 8) <= 256;
-}
-// Row splits of the all-topics A_k kernel (gemm_tn_topics.h): one 512-thread workgroup per CU, tiles x topic groups x splits
-// workgroups; fill the 256 CUs' rounds, >= 16 chunks per split, at most 64 splits
-static int tn_topics_nsplit(const gdrf_ctx* c, int64_t n) {
-  const int units = tnt_ntiles(c->Mp) * ((c->K + TNT_KT - 1) / TNT_KT);
-  int64_t maxs = (n + 16 * 32 - 1) / (16 * 32);
-  if (maxs > 64) maxs = 64;
-  if (maxs < 1) maxs = 1;
-  // cost model (relative units): rounds of one workgroup per CU, each walking n / ns rows, plus the slab traffic that grows with ns (K Mp^2
-  // floats written and read per split: 0.13 ms at 64 splits, M = 512, K = 10 - a fixed cost that does not shrink with a rank's share
-  // of the rows; at the 8-GPU per-rank size of the headline workload the optimum moves from 64 to ~25 splits)
-  const double chunk_us = 3.7;                                   // one 32-row chunk of a (tile, topic group) unit: 9.0 ms at N = 1e6, M = 512, K = 10
-  const double slab_us_per_split = 2.0 * (double)c->K * c->Mp * c->Mp * 4.0 / 5.0e6;       // bytes at ~5 TB/s, in us
-  int best = 1; double best_t = 1e300;
-  for (int ns = 1; ns <= maxs; ++ns) {
-    const double rounds = std::ceil(units * (double)ns / 256.0);
-    const double t = rounds * std::ceil((double)n / (32.0 * ns)) * chunk_us + ns * slab_us_per_split;
-    if (t < best_t * 0.995) { best_t = t; best = ns; }
-  }
-  return best;
-}
+static bool hyper_tn_on(const gdrf_ctx* c) { return F::hyper_tn_on(form_shape(c, 0)); }
 
 // Device memory the context owns until gdrf_ctx_destroy.  A block that a later call replaces (Wh, Xe, opt_part) stays owned as well: queued
 // work may still read it.  `what` labels the error of a failed allocation.
@@ -397,8 +358,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
     const size_t tbytes = (size_t)K * c->t_bs * c->esz;
     if (store_t == GDRF_STORE_T_ON) { AL(c->Tst, tbytes) }
   }
-  c->nsplit_cap = tn_nsplit(c, n_cap, (int)(128 / c->esz));
-  if (c->esz == 4) c->nsplit_cap = std::max({c->nsplit_cap, tn_nsplit(c, n_cap, 32, 2), tn_nsplit_gt(c, n_cap, 32), 64});   // the split TN forms run 2 workgroups per CU; the all-topics form up to 64 splits
+  c->nsplit_cap = F::nsplit_cap_rule(K, c->Mp, n_cap, (int)c->esz);
   AL(c->slab, (size_t)c->nsplit_cap * (K + 2) * mm)          // K batches of A_k, one of G^T, one of Hd = dK^T Wbar
   AL(c->hpart, (size_t)std::max(4096, c->Mp + 2048) * sizeof(double))
   c->ubar_blocks_cap = std::min<int64_t>(1025, (n_cap + 255) / 256);     // upper bound of ubar_blocks(n) over n <= n_cap
@@ -953,7 +913,7 @@ template <typename T, typename TS> struct Impl {
 
   // pieces of S_k^T (and of W in the all-fp32 mode), then tt on the 16-bit matrix path (f32 contexts only)
   template <class SP>
-  static int fwd_t_split(gdrf_ctx* c, int64_t n, int64_t rtiles, hipStream_t s) {
+  static int fwd_t_split(gdrf_ctx* c, int64_t n, hipStream_t s) {
     if constexpr (std::is_same<T, float>::value) {
       using E = typename SP::E;
       const int Mp = c->Mp, K = c->K;
@@ -968,49 +928,36 @@ template <typename T, typename TS> struct Impl {
                              (int64_t)c->ncap * Mp, (const float*)c->ssc + SL.w());
       }
       ScopedTimer tm(c, 5, s);
-      // topics per group: as many lower-triangular S^T piece panels (NP x ~0.6 Mp^2 halfwords each) as fit in 2 MB
-      const double panel = 0.625 * 2.0 * SP::NP * (double)Mp * Mp;
-      const int KG = std::max(1, std::min(K, (int)(2.0 * 1024 * 1024 / panel)));
-      c->forms[GDRF_FORM_FWD_T] = SP::NP == 2 ? 2 : 3; c->forms[GDRF_FORM_FWD_T_KG] = KG;
-      // two row tiles per 512-thread workgroup (two phase-shifted wave groups, LDS-DMA staging): 6 operand images
-      const int64_t pairs = (rtiles + 1) / 2;
-      const int rt8 = (int)((pairs + 7) / 8);
-      FwdTSplitArgs<SP> a{(const E*)c->Wh, (int64_t)c->ncap * Mp, n, Mp, K, KG, rt8, (const E*)c->STh, nb, (float*)c->tt, c->ldk, (const float*)c->ssc};
-      if constexpr (std::is_same<SP, SplitF16>::value) {
-        // many rows and at most 16 topics (the gate of the W-bar form of the same geometry): one wave per SIMD, S_k^T fragments straight from
-        // L2 into registers
-        const int nct_ = (Mp + GDRF_TILE - 1) / GDRF_TILE;
-        if ((Mp % 64) == 0 && K >= 2 && K <= 16 && pairs * nct_ > 32) {
-          // topics in fours on the quad form (one row tile, four topics per workgroup: half the W traffic per topic), the K % 4 left over on
-          // the pair form (two row tiles, two topics), in L2 groups of KGP pairs whose workgroups share the W blocks they stream
-          const int KQ = K / 4 * 4;
-          if (KQ) {
-            a.k_lo = 0; a.k_n = KQ; a.KG = 1; a.rt8 = (int)((rtiles + 7) / 8);
-            constexpr int lds_q = 2 * W1_WIMG + 16 * GDRF_TILE * 4;             // + the row-sum slots
-            HIPCHK(hipFuncSetAttribute((const void*)fwd_t_f16_w1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q));
-            hipLaunchKernelGGL(fwd_t_f16_w1_kernel<true>, dim3((unsigned)(8 * (KQ / 4) * a.rt8)), dim3(256), lds_q, s, a);
+      const F::FwdTPlan pl = F::fwd_t_plan(form_shape(c, n));
+      c->forms[GDRF_FORM_FWD_T] = pl.form; c->forms[GDRF_FORM_FWD_T_KG] = pl.KG;
+      FwdTSplitArgs<SP> a{(const E*)c->Wh, (int64_t)c->ncap * Mp, n, Mp, K, pl.KG, pl.rt8, (const E*)c->STh, nb, (float*)c->tt, c->ldk, (const float*)c->ssc};
+      auto launch = [&](auto kern, unsigned grid, int threads, int lds) {
+        HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
+        return 0;
+      };
+      int rc = 0;
+      switch (pl.form) {
+        case F::FWD_T_W1:
+          if constexpr (std::is_same<SP, SplitF16>::value) {
+            if (pl.KQ) {
+              a.k_lo = 0; a.k_n = pl.KQ; a.KG = 1; a.rt8 = pl.rt8_q;
+              if ((rc = launch(fwd_t_f16_w1_kernel<true>, pl.grid_q, pl.threads, pl.lds_q))) return rc;
+            }
+            if (pl.KP) {
+              a.k_lo = pl.KQ; a.k_n = K - pl.KQ; a.KG = pl.KGP; a.rt8 = pl.rt8;
+              if ((rc = launch(fwd_t_f16_w1_kernel<false>, pl.grid_p, pl.threads, pl.lds_p))) return rc;
+            }
           }
-          const int KP = (K - KQ + 1) / 2, KGP = std::min(KP, FWD_T_W1_KGP);
-          if (KP) {
-            a.k_lo = KQ; a.k_n = K - KQ; a.KG = KGP; a.rt8 = rt8;
-            constexpr int lds_p = 4 * W1_WIMG + 16 * GDRF_TILE * 4;
-            HIPCHK(hipFuncSetAttribute((const void*)fwd_t_f16_w1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
-            hipLaunchKernelGGL(fwd_t_f16_w1_kernel<false>, dim3((unsigned)(8 * KP * rt8)), dim3(256), lds_p, s, a);
-          }
-          c->forms[GDRF_FORM_FWD_T] = 4; c->forms[GDRF_FORM_FWD_T_KG] = KQ ? 4 : 2 * KGP;
-          LAUNCHCHK("fwd_t_split");
-          return 0;
-        }
+          break;
+        case F::FWD_T_Q4:
+          if constexpr (SP::NP == 2) rc = launch(fwd_t_split_q4_kernel<SP>, pl.grid, pl.threads, pl.lds);
+          break;
+        default:
+          if constexpr (SP::NP != 2) rc = launch(fwd_t_split_cc_kernel<SP>, pl.grid, pl.threads, pl.lds);
+          break;
       }
-      if constexpr (SP::NP == 2) {       // 256 x 256 workgroup tiles (two-piece modes: eight operand images in 128 KB)
-        constexpr int lds4 = 8 * SplitCfg<SP>::IMG * 2 + 8 * GDRF_TILE * 4;      // + the row-sum slots
-        HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_q4_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4));
-        hipLaunchKernelGGL(fwd_t_split_q4_kernel<SP>, dim3((unsigned)(8 * K * rt8)), dim3(1024), lds4, s, a);
-      } else {
-        constexpr int lds2 = 6 * SplitCfg<SP>::IMG * 2;
-        HIPCHK(hipFuncSetAttribute((const void*)fwd_t_split_cc_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-        hipLaunchKernelGGL(fwd_t_split_cc_kernel<SP>, dim3((unsigned)(8 * K * rt8)), dim3(512), lds2, s, a);
-      }
+      if (rc) return rc;
       LAUNCHCHK("fwd_t_split");
       return 0;
     } else {
@@ -1039,7 +986,7 @@ template <typename T, typename TS> struct Impl {
 
   // Wbar on the 16-bit matrix path (f32 contexts only)
   template <class SP>
-  static int wbar_split(gdrf_ctx* c, int64_t n, const T* U, int64_t rtiles, hipStream_t s) {
+  static int wbar_split(gdrf_ctx* c, int64_t n, const T* U, hipStream_t s) {
     if constexpr (std::is_same<T, float>::value) {
       using E = typename SP::E;
       const int Mp = c->Mp, K = c->K;
@@ -1050,63 +997,36 @@ template <typename T, typename TS> struct Impl {
       BwdWbarSplitArgs<SP> a{(const float*)c->W, (const E*)c->Wh, (int64_t)c->ncap * Mp, n, c->M, Mp, K, (const E*)c->Bh, nb,
                              (const float*)c->vbar, (const float*)c->locbar, c->ldk, (const float*)c->asum, (const float*)U, (float*)c->Wbar,
                              (const float*)c->ssc, c->smx + SL.mx_wbar()};
-      const size_t grp = SplitCfg<SP>::LDS_BYTES + (((size_t)K * GDRF_TILE * sizeof(float) + 15) & ~(size_t)15);
-      const int nct_ = (Mp + GDRF_TILE - 1) / GDRF_TILE;
-      if (K >= 2 && 2 * grp <= 160 * 1024) {   // two phase-shifted wave groups per workgroup (own A images, shared double-buffered B, LDS-DMA staging)
-        const int64_t pairs = (rtiles + 1) / 2;
-        const size_t tabb = ((size_t)K * GDRF_TILE * sizeof(float) + 15) & ~(size_t)15;
-        const size_t lds_cc = 6 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * tabb;
-        if (std::is_same<SP, SplitF16>::value && K >= 2 && (Mp % 64) == 0 && 8 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * tabb <= 160 * 1024) {
+      const F::WbarPlan pl = F::wbar_plan(form_shape(c, n));
+      if (!pl.fits) return fail(-1, "wbar_split", "too many topics for the LDS scale table");
+      auto launch = [&](auto kern) {
+        HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(kern, dim3(pl.grid, (unsigned)pl.nslice), dim3(pl.threads), pl.lds, s, a);
+        return 0;
+      };
+      int rc = 0;
+      switch (pl.form) {
+        case F::WBAR_W1:
+          if constexpr (std::is_same<SP, SplitF16>::value)
+            rc = pl.R == 2 ? launch(bwd_wbar_f16_w1_kernel<2>) : (pl.R == 4 ? launch(bwd_wbar_f16_w1_kernel<4>) : launch(bwd_wbar_f16_w1_kernel<8>));
+          break;
+        case F::WBAR_K64:
           if constexpr (std::is_same<SP, SplitF16>::value) {
-            const size_t lds64 = 8 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * tabb;
-            // few rows (streaming mini-batches): a handful of workgroups would each walk all K x Mp / 64 chunks one after the other
-            // (0.19 ms at n = 64); the reduction blocks are split over gridDim.y slices into slabs, summed in a fixed order
-            const int nkb = Mp / 64;
-            // many rows (no slices) and at most 16 topics: one wave per SIMD, B_k fragments straight from L2 into registers
-            if (pairs * nct_ > 32 && K <= 16) {
-              const size_t lds_w1 = 8 * (size_t)SplitCfg<SP>::IMG * 2 + 2 * (size_t)(K + 1) * GDRF_TILE * sizeof(float);
-              const dim3 grid((unsigned)round_up(pairs * nct_, 8));
-              auto launch = [&](auto kern) {
-                HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w1));
-                hipLaunchKernelGGL(kern, grid, dim3(256), lds_w1, s, a);
-                return 0;
-              };
-              // W-image requests per wave and phase: the 16 of a block fit into its K phases
-              if (int rc = K >= 8 ? launch(bwd_wbar_f16_w1_kernel<2>) : (K >= 4 ? launch(bwd_wbar_f16_w1_kernel<4>) : launch(bwd_wbar_f16_w1_kernel<8>))) return rc;
-              c->forms[GDRF_FORM_WBAR] = 7; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
-              LAUNCHCHK("wbar_split");
-              return 0;
-            }
-            int nslice = 1;
-            if (pairs * nct_ <= 32 && nkb >= 2) nslice = std::min(nkb, 8);
-            if ((size_t)nslice * round_up(n, 256) * Mp > (size_t)c->nsplit_cap * (K + 1) * Mp * Mp) nslice = 1;   // the TN slab buffer is idle now
-            if (nslice > 1) { a.slab = (float*)c->slab; a.slab_stride = (int64_t)round_up(n, 256) * Mp; a.nslice = nslice; }
-            c->forms[GDRF_FORM_WBAR] = 6; c->forms[GDRF_FORM_WBAR_NSLICE] = nslice;
-            HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_f16_k64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
-            hipLaunchKernelGGL(bwd_wbar_f16_k64_kernel, dim3((unsigned)round_up(pairs * nct_, 8), (unsigned)nslice), dim3(512), lds64, s, a);
-            if (nslice > 1) {
+            if (pl.nslice > 1) { a.slab = (float*)c->slab; a.slab_stride = (int64_t)round_up(n, 256) * Mp; a.nslice = pl.nslice; }
+            if ((rc = launch(bwd_wbar_f16_k64_kernel))) return rc;
+            if (pl.nslice > 1) {
               const int64_t n4 = n * Mp / 4;
-              hipLaunchKernelGGL(wbar_slab_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float*)a.slab, a.slab_stride, nslice, n4,
+              hipLaunchKernelGGL(wbar_slab_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float*)a.slab, a.slab_stride, pl.nslice, n4,
                                  (float*)c->Wbar, a.wbar_max);
             }
           }
-        } else if (lds_cc <= 160 * 1024) {
-          HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_cc_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cc));
-          hipLaunchKernelGGL((bwd_wbar_split_cc_kernel<SP>), dim3((unsigned)round_up(pairs * nct_, 8)), dim3(512), lds_cc, s, a);
-          c->forms[GDRF_FORM_WBAR] = 5; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
-        } else {
-          const size_t lds = std::max<size_t>(2 * grp, 8 * 32 * 68 * sizeof(float));      // the epilogue's transposition tiles
-          HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_kernel<SP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          hipLaunchKernelGGL((bwd_wbar_split_kernel<SP, 2>), dim3((unsigned)round_up(pairs * nct_, 8)), dim3(512), lds, s, a);
-          c->forms[GDRF_FORM_WBAR] = 4; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
-        }
-      } else {
-        if (grp > 160 * 1024) return fail(-1, "wbar_split", "too many topics for the LDS scale table");
-        const size_t lds = std::max<size_t>(grp, 4 * 32 * 68 * sizeof(float));
-        HIPCHK(hipFuncSetAttribute((const void*)bwd_wbar_split_kernel<SP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((bwd_wbar_split_kernel<SP, 1>), dim3((unsigned)round_up(rtiles * nct_, 8)), dim3(256), lds, s, a);
-        c->forms[GDRF_FORM_WBAR] = 3; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
+          break;
+        case F::WBAR_SPLIT_CC: rc = launch(bwd_wbar_split_cc_kernel<SP>); break;
+        case F::WBAR_SPLIT2: rc = launch(bwd_wbar_split_kernel<SP, 2>); break;
+        default: rc = launch(bwd_wbar_split_kernel<SP, 1>); break;
       }
+      if (rc) return rc;
+      c->forms[GDRF_FORM_WBAR] = pl.form; c->forms[GDRF_FORM_WBAR_NSLICE] = pl.nslice;
       LAUNCHCHK("wbar_split");
       return 0;
     } else {
@@ -1347,27 +1267,24 @@ template <typename T, typename TS> struct Impl {
     HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
     {
       ScopedTimer tm(c, 4, c->side);
-      const size_t ulds = (size_t)K * Mp * sizeof(T);
-      if (K <= LOC_KMAX && Mp % (16 * Vec16<T>::N) == 0 && ulds <= 150 * 1024) {
-        const int64_t blocks = std::min<int64_t>((n + 31) / 32, 256 * 8);
-        if ((rc = launch_lds(loc_rows_kernel<T>, dim3((unsigned)blocks), dim3(256), ulds, c->side, (const T*)P(c->W), n, Mp, K, (const T*)P(c->Upad),
-                             P(c->loc), ldk))) return rc;
-        c->forms[GDRF_FORM_LOC] = 1;
-      } else {
-        bool wide = false;
-        if constexpr (sizeof(T) == 8) {
-          if (K > C::CW) {       // f64 with K > 64: two column tiles
+      const F::LocPlan pl = F::loc_plan(form_shape(c, n));
+      switch (pl.form) {
+        case F::LOC_ROWS:
+          if ((rc = launch_lds(loc_rows_kernel<T>, dim3((unsigned)pl.blocks), dim3(256), pl.lds, c->side, (const T*)P(c->W), n, Mp, K, (const T*)P(c->Upad),
+                               P(c->loc), ldk))) return rc;
+          break;
+        case F::LOC_GEMM_NT_WIDE:       // f64 with K > 64: two column tiles
+          if constexpr (sizeof(T) == 8) {
             LocProb<T, true> p{{}, {}, {}, P(c->W), n, Mp, K, P(c->Upad), P(c->loc), ldk};
-            hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T, true>>), dim3((unsigned)rtiles), dim3(256), C::LDS_BYTES, c->side, p);
-            wide = true;
+            hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T, true>>), dim3((unsigned)pl.blocks), dim3(256), C::LDS_BYTES, c->side, p);
           }
-        }
-        if (!wide) {
+          break;
+        default: {
           LocProb<T> p{{}, {}, {}, P(c->W), n, Mp, K, P(c->Upad), P(c->loc), ldk};
-          hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T>>), dim3((unsigned)rtiles), dim3(256), C::LDS_BYTES, c->side, p);
+          hipLaunchKernelGGL((gemm_nt_kernel<T, LocProb<T>>), dim3((unsigned)pl.blocks), dim3(256), C::LDS_BYTES, c->side, p);
         }
-        c->forms[GDRF_FORM_LOC] = wide ? 3 : 2;
       }
+      c->forms[GDRF_FORM_LOC] = pl.form;
     }
     HIPCHK(hipEventRecord(c->ev_loc, c->side));
     if constexpr (std::is_same<T, float>::value && sizeof(TS) == 8) {
@@ -1385,12 +1302,12 @@ template <typename T, typename TS> struct Impl {
     }
     // (2) tt_kn = ||S_k^T w_n||^2
     if (c->split) {
-      if ((rc = BY_SPLIT(c, fwd_t_split, c, n, rtiles, s))) return rc;
+      if ((rc = BY_SPLIT(c, fwd_t_split, c, n, s))) return rc;
     } else {
       ScopedTimer tm(c, 5, s);
       FwdTProb<T> p{{K}, {}, {}, P(c->W), n, Mp, P(c->ST), P(c->tt), ldk, P(c->Tst), c->t_bs, c->t_ts};
       hipLaunchKernelGGL((gemm_nt_kernel<T, FwdTProb<T>>), dim3((unsigned)(8 * K * ((rtiles + 7) / 8))), dim3(256), C::LDS_BYTES, s, p);
-      c->forms[GDRF_FORM_FWD_T] = 1; c->forms[GDRF_FORM_FWD_T_KG] = 0;
+      c->forms[GDRF_FORM_FWD_T] = F::FWD_T_GEMM_NT; c->forms[GDRF_FORM_FWD_T_KG] = 0;
     }
     LAUNCHCHK("forward");
     HIPCHK(hipStreamWaitEvent(s, c->ev_loc, 0));
@@ -1401,45 +1318,33 @@ template <typename T, typename TS> struct Impl {
   static int step_rows(gdrf_ctx* c, const int32_t* ws, const T* eps, int64_t n, T* redT, double* redd, hipStream_t s) {
     const int K = c->K, V = c->V;
     const int64_t ldk = c->ldk;
-    int rc, egrid;
+    int rc;
     ScopedTimer tm(c, 6, s);
-    if (c->rows_form == 1 || c->csr_crow) {
+    const F::RowsPlan pl = F::rows_plan(form_shape(c, n));
+    if (pl.form == F::ROWS_STREAMED) {
       if ((rc = rows_streamed(c, ws, eps, n, redT, redd, s))) return rc;
-      c->forms[GDRF_FORM_ROWS] = 3; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
     } else {
       if ((rc = phibar_part_ensure(c))) return rc;
-      auto rows = [&](auto kern, int threads, size_t lds) {         // the LDS row forms take the same arguments
-        return launch_lds(kern, dim3(egrid), dim3(threads), lds, s, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt), eps, ldk, n, ws, P(c->phi),
-                          (const T*)c->mean, c->mean_sk, c->mean_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart, P(c->phibar_part));
+      if (!pl.fits)
+        return fail(-1, "gdrf_step_local", "num_topic_categories x num_observation_categories too large: the row kernel keeps the "
+                                           "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB); "
+                                           GDRF_STREAMED_HINT);
+      auto rows = [&](auto kern) {         // the LDS row forms take the same arguments
+        return launch_lds(kern, dim3(pl.egrid), dim3(pl.threads), pl.lds, s, n, K, V, c->hyp, P(c->qpart), nct<TS>(c), P(c->loc), P(c->tt), eps, ldk, n, ws,
+                          P(c->phi), (const T*)c->mean, c->mean_sk, c->mean_sn, P(c->q), P(c->vbar), P(c->locbar), P(c->asum), P(c->mu), c->dpart,
+                          P(c->phibar_part));
       };
-      // matrix-core form (rows_mfma.h): 16 rows per wave, the three K x V products of a row block as 16x16x4 matrix instructions on
-      // register-resident operands; K <= 32, V <= 64 and 32-bit offsets.  The one-thread-per-row kernel serves the other sizes
-      if (K <= 32 && V <= 64 && rows_mfma_offsets_fit<T>(K, nct<TS>(c), ldk, n)) {
-        const int nkt = K <= 16 ? 1 : 2, nvt = V <= 32 ? 2 : 4;
-        c->forms[GDRF_FORM_ROWS] = 1; c->forms[GDRF_FORM_ROWS_KT] = nkt; c->forms[GDRF_FORM_ROWS_VT] = nvt;
-        const size_t lds = rows_mfma_lds<T>(K, V, nkt, nvt, 4);
-        const int64_t groups = (n + 15) / 16;
-        egrid = (int)std::min<int64_t>((groups + 3) / 4, c->erows_grid_cap);
-        if ((rc = rows(nkt == 1 ? (nvt == 2 ? elbo_rows_mfma_kernel<T, 1, 2> : elbo_rows_mfma_kernel<T, 1, 4>)
-                                : (nvt == 2 ? elbo_rows_mfma_kernel<T, 2, 2> : elbo_rows_mfma_kernel<T, 2, 4>), 256, lds))) return rc;
+      if (pl.form == F::ROWS_MFMA) {       // 16 rows per wave (rows_mfma.h)
+        if ((rc = rows(pl.nkt == 1 ? (pl.nvt == 2 ? elbo_rows_mfma_kernel<T, 1, 2> : elbo_rows_mfma_kernel<T, 1, 4>)
+                                   : (pl.nvt == 2 ? elbo_rows_mfma_kernel<T, 2, 2> : elbo_rows_mfma_kernel<T, 2, 4>)))) return rc;
         LAUNCHCHK("elbo_rows (mfma)");
-      } else {
-        const bool kreg = K <= GDRF_KMAX;
-        auto lds_for = [&](int rb) { return 128 + ((size_t)2 * K * V + (size_t)rb * (K + 1) * (kreg ? 1 : 2) + (size_t)rb * (V + 1)) * sizeof(T); };
-        int RB = 128;
-        while (RB > 32 && lds_for(RB) > 150 * 1024) RB >>= 1;
-        const size_t lds = lds_for(RB);
-        if (lds > 150 * 1024)
-          return fail(-1, "gdrf_step_local", "num_topic_categories x num_observation_categories too large: the row kernel keeps the "
-                                             "(K, V) word-topic matrix and its gradient in LDS (2*K*V + 32*(2K + V + 3) elements <= 150 KB); "
-                                             GDRF_STREAMED_HINT);
-        c->forms[GDRF_FORM_ROWS] = 2; c->forms[GDRF_FORM_ROWS_KT] = c->forms[GDRF_FORM_ROWS_VT] = 0;
-        egrid = (int)std::min<int64_t>((n + RB - 1) / RB, c->erows_grid_cap);
-        if ((rc = rows(kreg ? elbo_rows_kernel<T, true> : elbo_rows_kernel<T, false>, RB, lds))) return rc;
+      } else {                             // one thread per row, K <= GDRF_KMAX topics in registers
+        if ((rc = rows(pl.kreg ? elbo_rows_kernel<T, true> : elbo_rows_kernel<T, false>))) return rc;
         LAUNCHCHK("elbo_rows");
       }
-      rows_reduce(c, P(c->phibar_part), egrid, redT, redd, s);
+      rows_reduce(c, P(c->phibar_part), pl.egrid, redT, redd, s);
     }
+    c->forms[GDRF_FORM_ROWS] = pl.form; c->forms[GDRF_FORM_ROWS_KT] = pl.nkt; c->forms[GDRF_FORM_ROWS_VT] = pl.nvt;
     return 0;
   }
 
@@ -1464,9 +1369,8 @@ template <typename T, typename TS> struct Impl {
   static int bwd_ubar(gdrf_ctx* c, int64_t n, T* redT, hipStream_t ss) {
     const int Mp = c->Mp, K = c->K;
     ScopedTimer tm(c, 12, ss);
-    const int64_t rpb = ubar_rows_per_block(n), nb = (n + rpb - 1) / rpb;
+    const auto [kq, rpb, nb] = F::ubar_plan(form_shape(c, n));
     if (nb > c->ubar_blocks_cap) return fail(-1, "gdrf_step_local", "ubar partial buffer too small");
-    const int kq = K <= 16 ? (K + 3) / 4 : 4;
     c->forms[GDRF_FORM_UBAR_Q4] = kq;
     hipLaunchKernelGGL((kq == 1 ? ubar_part_kernel<T, 1> : kq == 2 ? ubar_part_kernel<T, 2> : kq == 3 ? ubar_part_kernel<T, 3> : ubar_part_kernel<T, 4>),
                        dim3((unsigned)nb, (Mp + 255) / 256), dim3(256), 0, ss, P(c->W), n, Mp, K, P(c->locbar), c->ldk, rpb, P(c->ubar_part));
@@ -1485,27 +1389,26 @@ template <typename T, typename TS> struct Impl {
       BwdWbarTProb<T> p{{}, {}, P(c->Tst), c->t_bs, c->t_ts, P(c->W), n, M, Mp, K, P(c->S), P(c->vbar), P(c->locbar), ldk,
                         P(c->asum), U, P(c->Wbar)};
       if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarTProb<T>>, grid, dim3(256), lds, s, p))) return rc;
-      c->forms[GDRF_FORM_WBAR] = 2; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
+      c->forms[GDRF_FORM_WBAR] = F::WBAR_GEMM_NT_T; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
     } else if (c->split) {
-      if ((rc = BY_SPLIT(c, wbar_split, c, n, U, rtiles, s))) return rc;
+      if ((rc = BY_SPLIT(c, wbar_split, c, n, U, s))) return rc;
       split_scales(c, SPLIT_SC_WBAR, s);           // max |Wbar| came out of the epilogue: scale of the G^T contraction's operand
     } else {
       BwdWbarProb<T> p{{}, {}, P(c->W), n, M, Mp, K, P(c->Bm), P(c->vbar), P(c->locbar), ldk, P(c->asum), U, P(c->Wbar)};
       if ((rc = launch_lds(gemm_nt_kernel<T, BwdWbarProb<T>>, grid, dim3(256), lds, s, p))) return rc;
-      c->forms[GDRF_FORM_WBAR] = 1; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
+      c->forms[GDRF_FORM_WBAR] = F::WBAR_GEMM_NT; c->forms[GDRF_FORM_WBAR_NSLICE] = 1;
     }
     return 0;
   }
   // G^T = W^T Wbar, where it fills the last-round tails of bwd_knm and the A_k contraction on the main stream.  Stream ss (side), behind ev_fork2.
   static int bwd_gt(gdrf_ctx* c, int64_t n, T* redT, hipStream_t ss) {
-    const int Mp = c->Mp, K = c->K, BR = TNCfg<T>::BR;
-    const int ns = std::min(c->split ? tn_nsplit_gt(c, n, BR) : tn_nsplit(c, n, BR, 3), c->nsplit_cap);
-    const int64_t rps = round_up((n + ns - 1) / ns, BR);
+    const int Mp = c->Mp, K = c->K;
+    const auto [form, ns, rps] = F::gt_plan(form_shape(c, n));
     T* slab_gt = P(c->slab) + (int64_t)c->nsplit_cap * K * Mp * Mp;           // the (K+1)-th batch region of the slab buffer
     TNArgs<T> b{P(c->W), Mp, P(c->Wbar), Mp, nullptr, 0, n, rps, Mp, 0, slab_gt, 1, ns};
     { ScopedTimer tm(c, 10, ss);
-      c->forms[GDRF_FORM_GT] = c->split ? 2 : 1;
-      if (c->split) {
+      c->forms[GDRF_FORM_GT] = form;
+      if (form == F::GT_TN_SPLIT) {
         const int ib = SplitLay{K}.wbar();
         if (int rc = BY_SPLIT(c, tn_split, c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, (float*)slab_gt, 1, ns, c->nt * c->nt, ib, 0, ss)) return rc;
       } else {
@@ -1522,12 +1425,11 @@ template <typename T, typename TS> struct Impl {
   // Otherwise the bwd_knm fan and its reductions: stream s (main), no event.
   static int bwd_hyper(gdrf_ctx* c, const StepRows& r, int64_t n, double* redd, hipStream_t s, hipStream_t ss) {
     const int Mp = c->Mp, M = c->M;
+    const auto [form, ns, rps] = F::hyper_plan(form_shape(c, n));
+    c->forms[GDRF_FORM_HYPER] = form;
     if constexpr (std::is_same<T, float>::value && sizeof(TS) == 8) {
-      if (hyper_tn_on(c)) {
+      if (form == F::HYPER_TN) {
         ScopedTimer tm(c, 8, ss);
-        const int BR = TNCfg<T>::BR;
-        const int ns = std::min(tn_nsplit_gt(c, n, BR), c->nsplit_cap);
-        const int64_t rps = round_up((n + ns - 1) / ns, BR);
         float* slab_hd = (float*)c->slab + (int64_t)c->nsplit_cap * (c->K + 1) * Mp * Mp;
         const SplitLay SL{c->K};
         if (int rc = tn_split<SplitF16>(c, (const float*)c->Wbar, nullptr, 0, n, rps, 0, slab_hd, 1, ns, c->nt * c->nt, SL.wbar(), 0, ss, c->dKh, SL.dk())) return rc;
@@ -1537,12 +1439,10 @@ template <typename T, typename TS> struct Impl {
         hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, ss, c->hpart + Mp, (int64_t)2048, 1, redd + 4);
         HIPCHK(hipMemsetAsync(redd + 6, 0, sizeof(double), ss));
         LAUNCHCHK("hyper_tn");
-        c->forms[GDRF_FORM_HYPER] = 2;
         return 0;
       }
     }
     ScopedTimer tm(c, 8, s);
-    c->forms[GDRF_FORM_HYPER] = 1;
     const int64_t rtiles = row_tiles(n), nb = nt_xcd_row_grid(rtiles, nct<TS>(c));
     if (3 * nb > c->dpart_len) return fail(-1, "gdrf_step_local", "n_local exceeds the context capacity");
     const T *X = r.X, *Xr = r.Xr;
@@ -1565,33 +1465,18 @@ template <typename T, typename TS> struct Impl {
     const int Mp = c->Mp, K = c->K;
     const int64_t ldk = c->ldk;
     int rc;
-    const int BR = TNCfg<T>::BR;
-    const int ns = std::min(tn_nsplit(c, n, BR, c->split ? 2 : 3), c->nsplit_cap);
-    const int64_t rps = round_up((n + ns - 1) / ns, BR);
-    TNArgs<T> a{P(c->W), Mp, P(c->W), Mp, P(c->vbar), ldk, n, rps, Mp, 1, P(c->slab), K, ns};
-    int red_ns = ns, red_qd = GDRF_TILE / 2;
+    const F::AkPlan pl = F::ak_plan(form_shape(c, n));
+    c->forms[GDRF_FORM_AK] = pl.form; c->forms[GDRF_FORM_AK_KGROUPS] = pl.kgroups;
     { ScopedTimer tm(c, 9, s);
-      if (c->split == 2) {
-        if constexpr (std::is_same<T, float>::value) {
-          const SplitLay SL{K};
-          const int nst = std::min(tn_topics_nsplit(c, n), c->nsplit_cap);
-          const int64_t rpst = round_up((n + nst - 1) / nst, 32);
-          const int ntl = tnt_ntiles(Mp), kgroups = (K + TNT_KT - 1) / TNT_KT;
-          TNTopicsArgs ta{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbar, ldk, n, rpst, Mp,
-                          (float*)c->slab, K, nst, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
-          // The one-wave forms run every stage of their 10-topic groups whatever K: with more than 40 % of the topic slots empty (K <= 5, K = 11)
-          // the two-wave form, which walks the topic pairs that exist, is the faster one.
-          c->forms[GDRF_FORM_AK_KGROUPS] = kgroups;
-          if (10 * K >= 6 * kgroups * TNT_KT) {      // one-wave-per-SIMD form (gemm_tn_topics1.h): 128 rows per wave
-            c->forms[GDRF_FORM_AK] = 4;
-            int ns1 = c->nsplit_cap < 64 ? c->nsplit_cap : 64;                            // 8 k splits: every XCD owns whole splits
-            while (ns1 > 8 && (n + ns1 - 1) / ns1 < 8 * TN1_CH) ns1 -= 8;                 // at least 8 chunks per split
-            if (ns1 >= 8) ns1 &= ~7;
-            const int64_t rps1 = round_up((n + ns1 - 1) / ns1, TN1_CH);
+      switch (pl.form) {
+        case F::AK_W2:           // one-wave-per-SIMD form (gemm_tn_topics1.h): 128 rows per wave
+          if constexpr (std::is_same<T, float>::value) {
+            const SplitLay SL{K};
+            const int ntl = tnt_ntiles(Mp), kgroups = pl.kgroups, ns1 = pl.ns1;
             const int64_t lds64 = round_up(c->ncap, 64);
             hipLaunchKernelGGL(tn1_scale_rows_kernel, dim3(256, K), dim3(256), 0, s, (const float*)c->vbar, ldk, n, (float*)c->vbs, lds64,
                                (const float*)c->ssc, SL.v(0));
-            TNTopicsArgs t1{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbs, lds64, n, rps1, Mp,
+            TNTopicsArgs t1{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbs, lds64, n, pl.rps1, Mp,
                             (float*)c->slab, K, ns1, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
             // two launches: the tiles whose upper 64 rows lie above the diagonal (J = 2 I + 1) multiply half the A tiles (gemm_tn_topics1.h)
             const int nth = tn2_ntiles_half(Mp);
@@ -1602,24 +1487,30 @@ template <typename T, typename TS> struct Impl {
             if (t0.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<0>, dim3((unsigned)(t0.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t0);
             if (t4.ntiles > 0) hipLaunchKernelGGL(tn_topics_w2_kernel<4>, dim3((unsigned)(t4.ntiles * kgroups * ns1)), dim3(256), tn2_lds_bytes(), s, t4);
             LAUNCHCHK("tn_topics_w2");
-            red_ns = ns1; red_qd = 32;
-          } else {
-            c->forms[GDRF_FORM_AK] = 3;
-            HIPCHK(hipFuncSetAttribute((const void*)tn_topics_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tnt_lds_bytes()));
-            hipLaunchKernelGGL(tn_topics_f16_kernel, dim3((unsigned)(ntl * kgroups * nst)), dim3(512), tnt_lds_bytes(), s, ta);
-            LAUNCHCHK("tn_topics");
-            red_ns = nst; red_qd = 32;
           }
+          break;
+        case F::AK_TN_TOPICS:    // two waves per SIMD (gemm_tn_topics.h)
+          if constexpr (std::is_same<T, float>::value) {
+            const SplitLay SL{K};
+            const int ntl = tnt_ntiles(Mp);
+            TNTopicsArgs ta{(const _Float16*)c->Wh, (int64_t)c->ncap * Mp, Mp, (const float*)c->W, Mp, (const float*)c->vbar, ldk, n, pl.rpst, Mp,
+                            (float*)c->slab, K, pl.nst, ntl, (const float*)c->ssc, SL.w(), SL.v(0)};
+            HIPCHK(hipFuncSetAttribute((const void*)tn_topics_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tnt_lds_bytes()));
+            hipLaunchKernelGGL(tn_topics_f16_kernel, dim3((unsigned)(ntl * pl.kgroups * pl.nst)), dim3(512), tnt_lds_bytes(), s, ta);
+            LAUNCHCHK("tn_topics");
+          }
+          break;
+        case F::AK_TN_SPLIT: {   // bf16x6
+          const int ib = SplitLay{K}.v(0), ntl = c->nt * (c->nt + 1) / 2;
+          if ((rc = tn_split<SplitBf16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, pl.rps, 1, (float*)c->slab, K, pl.ns, ntl, ib, 2, s))) return rc;
+          break;
         }
-      } else if (c->split) {
-        c->forms[GDRF_FORM_AK] = 2; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
-        const int ib = SplitLay{K}.v(0), ntl = c->nt * (c->nt + 1) / 2;
-        // bf16x6 (f16x3 took the branch above)
-        if ((rc = tn_split<SplitBf16>(c, (const float*)c->W, (const float*)c->vbar, ldk, n, rps, 1, (float*)c->slab, K, ns, ntl, ib, 2, s))) return rc;
-      } else {
-        c->forms[GDRF_FORM_AK] = 1; c->forms[GDRF_FORM_AK_KGROUPS] = 0;
-        hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * (c->nt + 1) / 2 * K * ns)), dim3(256), TNCfg<T>::LDS_BYTES, s, a);
+        default: {
+          TNArgs<T> a{P(c->W), Mp, P(c->W), Mp, P(c->vbar), ldk, n, pl.rps, Mp, 1, P(c->slab), K, pl.ns};
+          hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3((unsigned)(c->nt * (c->nt + 1) / 2 * K * pl.ns)), dim3(256), TNCfg<T>::LDS_BYTES, s, a);
+        }
       } }
+    const int red_ns = pl.red_ns, red_qd = pl.red_qd;
     { ScopedTimer tm(c, 11, s);
       dim3 gr((Mp + 255) / 256, Mp, K);
       hipLaunchKernelGGL(reduce_slabs_kernel<T>, gr, dim3(256), 0, s, P(c->slab), red_ns, K, Mp, 1, redT + red_lay(c).A, red_qd); }
@@ -1878,51 +1769,55 @@ template <typename T, typename TS> struct Impl {
     if (int rc = step_inputs(c, X, n, params, s, &r)) return rc;
     X = r.X;
     if (mode >= 2) hipLaunchKernelGGL(build_phi_kernel<T>, dim3(K), dim3(64), 0, s, params + param_lay(c).phi, K, V, P(c->phi));
-    if (c->rows_form == 1 || (mode == 3 && c->csr_crow)) {
-      // form 1: the any-K row kernel without Phi in LDS gives f_loc / topic_probs; for word_probs and perplexity it writes topic_probs of
-      // up to n_cap rows at a time into the form's scratch and the streamed product over Phi tiles (rows_vstream.h) finishes them
+    const F::PredictPlan pl = F::predict_plan(form_shape(c, n, mode));
+    const size_t lds = pl.lds;
+    const int64_t ldo = mode == 0 ? n : (mode == 1 ? K : V);
+    int64_t blocks = (n + 127) / 128; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+    if (pl.form != F::PREDICT_MFMA)      // the row forms read the coefficients Cf = L^-T u
       hipLaunchKernelGGL((predict_coeff_kernel<TS, T>), dim3((M + 127) / 128, K), dim3(128), 0, s, (const TS*)Q(c->Linv), U, M, Mp, K, Q(c->Cf));
-      const size_t lds = 128 + (size_t)M * c->D * sizeof(TS);
-      if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D solve-precision elements exceed the LDS budget (150 KB)");
-      auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
-      c->forms[GDRF_FORM_PREDICT] = 5; c->forms[GDRF_FORM_PREDICT_NB] = 0;
-      if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      auto rows = [&](const T* Xc, int64_t m, int md, T* o, int64_t ldo) {
-        int64_t blocks = (m + 127) / 128; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, Xc, m, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf),
-                           K, V, (const T*)P(c->phi), ws, md, o, ldo, c->dpart);
-      };
-      if (mode <= 1) {
-        rows(X, n, mode, out, mode == 0 ? n : K);
+    if (!pl.fits)
+      return fail(-1, "gdrf_predict", pl.form == F::PREDICT_STREAMED    ? "M*D solve-precision elements exceed the LDS budget (150 KB)"
+                                      : pl.form == F::PREDICT_ROWS_BIGK ? "M*D + K*V + 128*(V+1) solve-precision elements exceed the LDS budget (150 KB)"
+                                                                        : "M*D + K*V solve-precision elements exceed the LDS budget (150 KB)");
+    c->forms[GDRF_FORM_PREDICT] = pl.form; c->forms[GDRF_FORM_PREDICT_NB] = pl.NB;
+    switch (pl.form) {
+      case F::PREDICT_STREAMED: {
+        // form 1: the any-K row kernel without Phi in LDS gives f_loc / topic_probs; for word_probs and perplexity it writes topic_probs of
+        // up to n_cap rows at a time into the form's scratch and the streamed product over Phi tiles (rows_vstream.h) finishes them
+        auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
+        if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        auto rows = [&](const T* Xc, int64_t m, int md, T* o, int64_t ldo) {
+          int64_t blocks = (m + 127) / 128; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+          hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(128), lds, s, Xc, m, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf),
+                             K, V, (const T*)P(c->phi), ws, md, o, ldo, c->dpart);
+        };
+        if (mode <= 1) {
+          rows(X, n, mode, out, mode == 0 ? n : K);
+          LAUNCHCHK("predict (streamed form)");
+          return 0;
+        }
+        if (int rc = vs_ensure(c, mode == 3)) return rc;
+        const int G = vs_grid(c, std::min<int64_t>(n, c->ncap), mode == 3);
+        for (int64_t off = 0; off < n; off += c->ncap) {
+          const int64_t m = std::min<int64_t>(c->ncap, n - off);
+          rows(X + off * c->D, m, 1, (T*)c->vs_tmp, K);
+          int rc;
+          if (mode == 2) rc = vs_launch<VS_WORDP>(c, m, G, (const T*)c->vs_tmp, 1, K, nullptr, out + off * V, V, nullptr, 0, s);
+          else rc = vs_launch<VS_PERP>(c, m, G, (const T*)c->vs_tmp, 1, K, ws ? ws + off * V : nullptr, nullptr, 0, c->dpart, off > 0, s, off);
+          if (rc) return rc;
+        }
+        if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 2, out_d);
         LAUNCHCHK("predict (streamed form)");
         return 0;
       }
-      if (int rc = vs_ensure(c, mode == 3)) return rc;
-      const int G = vs_grid(c, std::min<int64_t>(n, c->ncap), mode == 3);
-      for (int64_t off = 0; off < n; off += c->ncap) {
-        const int64_t m = std::min<int64_t>(c->ncap, n - off);
-        rows(X + off * c->D, m, 1, (T*)c->vs_tmp, K);
-        int rc;
-        if (mode == 2) rc = vs_launch<VS_WORDP>(c, m, G, (const T*)c->vs_tmp, 1, K, nullptr, out + off * V, V, nullptr, 0, s);
-        else rc = vs_launch<VS_PERP>(c, m, G, (const T*)c->vs_tmp, 1, K, ws ? ws + off * V : nullptr, nullptr, 0, c->dpart, off > 0, s, off);
-        if (rc) return rc;
-      }
-      if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, (int64_t)G, 2, out_d);
-      LAUNCHCHK("predict (streamed form)");
-      return 0;
-    }
-    {
-      // matrix-core form (predict.h): a wave owns 16 rows, one covariance value per lane and step is the A operand of the 16x16x4
-      // matrix instruction, the padded transposed coefficients CfT its B operand.  K <= 32, the scaled inducing inputs in LDS.
-      const int M4 = (int)round_up(M, 4), NB = K <= 16 ? 1 : 2, DDt = c->D <= 2 ? 2 : GDRF_DMAX;
-      const size_t lds = 128 + ((size_t)M4 * DDt + (size_t)K * V + (size_t)4 * 16 * (16 * NB + 1)) * sizeof(TS);
-      if (K <= 32 && lds <= 64 * 1024) {
+      case F::PREDICT_MFMA: {
+        // matrix-core form (predict.h): a wave owns 16 rows, one covariance value per lane and step is the A operand of the 16x16x4
+        // matrix instruction, the padded transposed coefficients CfT its B operand.  K <= 32, the scaled inducing inputs in LDS.
+        const int M4 = (int)round_up(M, 4), NB = pl.NB, DDt = c->D <= 2 ? 2 : GDRF_DMAX;
         const int ldc = 16 * NB;
-        c->forms[GDRF_FORM_PREDICT] = 1; c->forms[GDRF_FORM_PREDICT_NB] = NB;
         hipLaunchKernelGGL((predict_coeff_t_kernel<TS, T>), dim3(M4), dim3(64), 0, s, (const TS*)Q(c->LinvT), U, M, Mp, M4, K, ldc, Q(c->CfT));
         const int64_t groups = (n + 15) / 16;
-        int64_t blocks = (groups + 3) / 4; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-        const int64_t ldo = mode == 0 ? n : (mode == 1 ? K : V);
+        blocks = (groups + 3) / 4; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
         auto go = [&](auto kern) {
           return launch_lds(kern, dim3((unsigned)blocks), dim3(256), lds, s, X, n, (const TS*)Q(c->Zs), M, M4, c->D, c->kind, c->hyp, (const TS*)Q(c->CfT), K, V,
                             (const T*)P(c->phi), ws, mode, out, ldo, c->dpart);
@@ -1937,26 +1832,18 @@ template <typename T, typename TS> struct Impl {
         LAUNCHCHK("predict (mfma)");
         return 0;
       }
-    }
-    hipLaunchKernelGGL((predict_coeff_kernel<TS, T>), dim3((M + 127) / 128, K), dim3(128), 0, s, (const TS*)Q(c->Linv), U, M, Mp, K, Q(c->Cf));
-    int64_t blocks = (n + 127) / 128; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-    const int64_t ldo = mode == 0 ? n : (mode == 1 ? K : V);
-    if (K > GDRF_KMAX) {
-      const size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)128 * (V + 1)) * sizeof(TS);
-      if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V + 128*(V+1) solve-precision elements exceed the LDS budget (150 KB)");
-      auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
-      c->forms[GDRF_FORM_PREDICT] = 4; c->forms[GDRF_FORM_PREDICT_NB] = 0;
-      if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
-                              (const T*)P(c->phi), ws, mode, out, ldo, c->dpart)) return rc;
-    } else {
-      size_t lds = 128 + ((size_t)M * c->D + (size_t)K * V + (size_t)K * M) * sizeof(TS);
-      int in_lds = 1;
-      if (lds > 64 * 1024) { in_lds = 0; lds -= (size_t)K * M * sizeof(TS); }
-      if (lds > 150 * 1024) return fail(-1, "gdrf_predict", "M*D + K*V solve-precision elements exceed the LDS budget (150 KB)");
-      auto kfn = ard_fwd(c) ? predict_rows_kernel<TS, T, true> : predict_rows_kernel<TS, T>;
-      c->forms[GDRF_FORM_PREDICT] = in_lds ? 2 : 3; c->forms[GDRF_FORM_PREDICT_NB] = 0;
-      if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
-                              (const T*)P(c->phi), ws, mode, out, ldo, c->dpart, in_lds)) return rc;
+      case F::PREDICT_ROWS_BIGK: {
+        auto kfn = ard_fwd(c) ? predict_rows_bigk_kernel<TS, T, true> : predict_rows_bigk_kernel<TS, T>;
+        if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
+                                (const T*)P(c->phi), ws, mode, out, ldo, c->dpart)) return rc;
+        break;
+      }
+      default: {                  // predict_rows, the coefficients in LDS or read from memory
+        auto kfn = ard_fwd(c) ? predict_rows_kernel<TS, T, true> : predict_rows_kernel<TS, T>;
+        const int in_lds = pl.form == F::PREDICT_ROWS_LDS;
+        if (int rc = launch_lds(kfn, dim3((unsigned)blocks), dim3(128), lds, s, X, n, (const TS*)Q(c->Zs), M, c->D, c->kind, c->hyp, (const TS*)Q(c->Cf), K, V,
+                                (const T*)P(c->phi), ws, mode, out, ldo, c->dpart, in_lds)) return rc;
+      }
     }
     if (mode == 3) hipLaunchKernelGGL(reduce_dparts_kernel, dim3(1), dim3(1024), 0, s, c->dpart, blocks, 2, out_d);
     LAUNCHCHK("predict");

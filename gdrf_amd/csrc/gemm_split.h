@@ -1575,7 +1575,6 @@ __global__ __launch_bounds__(1024) void fwd_t_split_q4_kernel(FwdTSplitArgs<SP> 
 // The fold of a finished tile (two s_nop 15, then v_accvgpr_read, the squares masked by fwd_t_col_ok and summed over the four column groups,
 // the 16 lanes by row16_sum_lane0) adds into one LDS slot per (topic, row tile, tile parity, column half, row) in q4's order; the final sum is
 // q4's too: (q0 + q1) + (q2 + q3).  No atomics: tt is bit-identical from run to run.
-constexpr int FWD_T_W1_KGP = 2;             // topic pairs per L2 group of the pair form: four S_k^T panels, ~2.6 MB at Mp = 512, as the quad form holds
 constexpr int ft1_acc(int tp, int a, int b) { return ((tp * 8 + a) * 4 + b) * 4; }
 // v64 .. v255, as GDRF_ALL_AGPRS
 #define GDRF_V10(p) "v" p "0", "v" p "1", "v" p "2", "v" p "3", "v" p "4", "v" p "5", "v" p "6", "v" p "7", "v" p "8", "v" p "9"

@@ -1,10 +1,11 @@
 // Timing-only harness: the two f16x3 W-bar kernels (gemm_split.h: one wave per SIMD / k64) alone at the headline shape on pseudo-random operands,
-// launched as api.hip launches them.  Results are not checked.  Build and run from the repository root:
+// on the grid and LDS bytes of csrc/forms.h's plan, as api.hip launches them.  Results are not checked.  Build and run from the repository root:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -o /tmp/wbar_time tools/wbar_kernel_time.hip && /tmp/wbar_time
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include "../gdrf_amd/csrc/gemm_split.h"
+#include "../gdrf_amd/csrc/forms.h"
 using namespace gdrf;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
 __global__ void fill_h(_Float16* p, size_t n, float amp) { for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) { unsigned h = (unsigned)(i * 2654435761u); h ^= h >> 15; p[i] = (_Float16)(amp * ((int)(h & 0xffff) - 32768) / 32768.0f); } }
@@ -18,11 +19,13 @@ int main(int argc, char** argv) {
   fill_f<<<1024, 256>>>(vbar, K * n, 1.f); fill_f<<<1024, 256>>>(locbar, K * n, 1.f); fill_f<<<256, 256>>>(asum, n, 1.f); fill_f<<<16, 256>>>(U, K * Mp, 1.f); fill_f<<<1, 256>>>(sc, 256, 1e-6f);
   CK(hipMemset(mx, 0, 1024));
   BwdWbarSplitArgs<SplitF16> a{W, Wh, n * Mp, n, Mp, Mp, K, Bh, (int64_t)K * Mp * Mp, vbar, locbar, n, asum, U, Wbar, sc, mx};
-  const int64_t rtiles = (n + 127) / 128, pairs = (rtiles + 1) / 2; const int nct = (Mp + 127) / 128;
-  const unsigned grid = (unsigned)((pairs * nct + 7) / 8 * 8);
+  // the plan of the shape (one wave per SIMD), and the k64 form's of the same shape: what the host took before, K past the w1 gate aside
+  forms::FormShape f; f.n = f.n_cap = n; f.M = f.Mp = Mp; f.K = K; f.split = 2; f.nsplit_cap = forms::nsplit_cap_rule(K, Mp, n, 4);
+  const forms::WbarPlan pw = forms::wbar_plan(f);
+  if (pw.form != forms::WBAR_W1 || pw.R != 2) { printf("the shape does not take the one-wave form with two requests per phase\n"); return 1; }
+  const unsigned grid = pw.grid;
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  const size_t lds_w1 = 8 * (size_t)SplitCfg<SplitF16>::IMG * 2 + 2 * (size_t)(K + 1) * 128 * 4;
-  const size_t lds64 = 8 * (size_t)SplitCfg<SplitF16>::IMG * 2 + 2 * (size_t)K * 128 * 4;
+  const size_t lds_w1 = pw.lds, lds64 = forms::wbar_k64_lds(K);
   CK(hipFuncSetAttribute((const void*)bwd_wbar_f16_w1_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w1));
   CK(hipFuncSetAttribute((const void*)bwd_wbar_f16_k64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
   for (int which = 0; which < 2; ++which) {
