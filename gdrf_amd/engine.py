@@ -185,6 +185,44 @@ def check_select_args(count, noise, n: int, given=None, dims: Optional[int] = No
     return cnt, noise, G
 
 
+def param_table(K: int, M: int, V: int, D: int, kernel: str = "rbf", *, ard: bool = False, period_count: int = 0, product=None,
+                learn_inducing: bool = False, mean_shapes=None, raw) -> Dict[str, tuple]:
+    """{name: (offset, shape)} of every learnt parameter tensor of a context, in the order of Engine.param_names (that of state_dict(),
+    parameters() and the optimizer state).  Pure: ``raw`` holds what the library's layout calls returned, {"param": gdrf_param_layout,
+    "inducing": gdrf_inducing_layout, "ard": gdrf_ard_layout, "periodic": gdrf_periodic_layout, "product": gdrf_product_layout, "mean":
+    gdrf_mean_param_layout}; only the entries the configuration reads have to be there.  ``product`` is the factor table of
+    Engine(kernel="product"), ``mean_shapes`` {name: shape} of the mean_function's parameters."""
+    lay = raw["param"]
+    vec = lambda n: () if n == 1 else (int(n),)
+    t: Dict[str, tuple] = {}
+    if product is not None:                       # the factors' segments in place of slots 0 and 1
+        ov, _, ol, _, op, _ = raw["product"]
+        for f, fac in enumerate(product):
+            pre = fac["name"] + "." if fac["name"] else ""
+            nl, npr = int(fac["lengthscales"]), int(fac.get("periods", 0))
+            t[pre + "log_variance"] = (ov + f, ())
+            t[pre + "log_lengthscale"] = (ol, vec(nl))
+            ol += nl
+            if npr:
+                t[pre + "log_period"] = (op, vec(npr))
+                op += npr
+    else:
+        t["log_lengthscale"] = (raw["ard"][0], (D,)) if ard else (lay[0], ())
+        t["log_variance"] = (lay[1], ())
+    t.update(log_noise=(lay[2], ()), u_loc=(lay[3], (K, M)), phi_unc=(lay[4], (K, V)), u_scale_tril_unc=(lay[5], (K, M, M)))
+    if kernel == "rationalquadratic":
+        t["log_scale_mixture"] = (3, ())
+    if period_count:
+        t["log_period"] = (raw["periodic"][0], vec(period_count))
+    if learn_inducing:
+        t["inducing_unc"] = (raw["inducing"][0], (M, D))
+    o = raw["mean"][0] if mean_shapes else 0
+    for name, shape in (mean_shapes or {}).items():
+        t[name] = (o, tuple(shape))
+        o += math.prod(shape)
+    return t
+
+
 class Engine:
     """One device context for fixed (n_cap, M, K, V, D, dtype, kernel)."""
 
@@ -192,9 +230,6 @@ class Engine:
     last_joint_level: Optional[int] = None
 
     opt_extra: Optional[torch.Tensor] = None     # third optimizer state vector (RMSprop with momentum and centered), on demand
-    period_count = 0                             # log-periods of a Periodic kernel's context (1 or D), 0 for the other kernels
-    product = None                               # a product context's factor table (Engine(kernel="product", product=...)), else None
-    _prod_views: Dict[str, tuple] = {}           # its parameter views: {name: (offset, shape)}
 
     def __init__(self, n_cap: int, M: int, K: int, V: int, D: int, *, dtype=torch.float32, kernel: str = "rbf",
                  device="cuda:0", jitter: float = 1e-8, maxjitter: int = 15, process_group="auto", pure_fp32: bool = False,
@@ -269,38 +304,13 @@ class Engine:
         # a lone kernel on a subset of the axes), "kind": "rbf" | "periodic", "active_dims", "lengthscales": 1 or len(active_dims),
         # "periods": 0 for RBF, 1 or len(active_dims)}.  Each factor's parameters are views "<name>.log_variance", "<name>.log_lengthscale",
         # "<name>.log_period" ("log_variance", ... for the name "") into the three segments of gdrf_product_layout.
-        self._prod_views: Dict[str, tuple] = {}
-        if kernel == "product":
-            self._set_product(product)
-        lay = (C.c_int64 * 7)()
-        _lib.check(self.lib.gdrf_param_layout(self.ctx, lay), "gdrf_param_layout")
-        zl = (C.c_int64 * 2)()
-        _lib.check(self.lib.gdrf_inducing_layout(self.ctx, zl), "gdrf_inducing_layout")
-        self.layout = dict(log_lengthscale=lay[0], log_variance=lay[1], log_noise=lay[2], log_scale_mixture=3, u_loc=lay[3],
-                           phi_unc=lay[4], u_scale_tril_unc=lay[5], inducing_unc=zl[0], total=lay[6])
-        if self.ard:
-            al = (C.c_int64 * 2)()
-            _lib.check(self.lib.gdrf_ard_layout(self.ctx, al), "gdrf_ard_layout")
-            self.layout["log_lengthscale"] = al[0]
-        if self.period_count:
-            pl = (C.c_int64 * 2)()
-            _lib.check(self.lib.gdrf_periodic_layout(self.ctx, pl), "gdrf_periodic_layout")
-            self.layout["log_period"] = pl[0]
+        self.product = self._set_product(product) if kernel == "product" else None
         # trainable mean_function parameters (gdrf_set_mean_params): {name: shape} in order, one segment of the parameter vector; their
         # sums of d elbo / d theta are written by the host into the last doubles of red_d (_write_mean_grads)
         self.mean_shapes = {str(k): torch.Size(v) for k, v in (mean_params or {}).items()}
         self.mean_count = sum(math.prod(v) for v in self.mean_shapes.values())
-        self._mean_offsets = {}
         if self.mean_count:
             _lib.check(self.lib.gdrf_set_mean_params(self.ctx, self.mean_count), "gdrf_set_mean_params")
-            _lib.check(self.lib.gdrf_param_layout(self.ctx, lay), "gdrf_param_layout")
-            ml = (C.c_int64 * 2)()
-            _lib.check(self.lib.gdrf_mean_param_layout(self.ctx, ml), "gdrf_mean_param_layout")
-            self.layout["mean"], self.layout["total"] = ml[0], lay[6]
-            o = ml[0]
-            for name, shape in self.mean_shapes.items():
-                self._mean_offsets[name] = o
-                o += math.prod(shape)
         # fixed_inducing_points=False of the reference: Z = sigmoid(unconstrained block), refreshed before every evaluation
         self.learn_inducing = bool(learn_inducing)
         if self.learn_inducing:
@@ -308,6 +318,22 @@ class Engine:
         self.whiten = bool(whiten)
         if not self.whiten:
             _lib.check(self.lib.gdrf_set_whiten(self.ctx, 0), "gdrf_set_whiten")
+        # the library's offsets, asked once after every gdrf_set_* above, and the one table of the learnt parameters built from them
+        raw = {}
+        for key, size in (("param", 7), ("inducing", 2), ("ard", 2), ("periodic", 2), ("product", 6), ("mean", 2)):
+            out = (C.c_int64 * size)()
+            fn = "gdrf_mean_param_layout" if key == "mean" else f"gdrf_{key}_layout"
+            _lib.check(getattr(self.lib, fn)(self.ctx, out), fn)
+            raw[key] = tuple(out)
+        lay = raw["param"]
+        self.table = param_table(self.K, self.M, self.V, self.D, kernel, ard=self.ard, period_count=self.period_count, product=self.product,
+                                 learn_inducing=self.learn_inducing, mean_shapes=self.mean_shapes, raw=raw)
+        # name -> offset: the fixed slots of every context, then whatever the table places elsewhere or adds
+        self.layout = dict(log_lengthscale=lay[0], log_variance=lay[1], log_noise=lay[2], log_scale_mixture=3, u_loc=lay[3], phi_unc=lay[4],
+                           u_scale_tril_unc=lay[5], inducing_unc=raw["inducing"][0], total=lay[6])
+        if self.mean_count:
+            self.layout["mean"] = raw["mean"][0]
+        self.layout.update({n: o for n, (o, _) in self.table.items()})
         red = (C.c_int64 * 6)()
         _lib.check(self.lib.gdrf_red_layout(self.ctx, red), "gdrf_red_layout")
         self.red_layout = dict(ubar=red[0], phibar=red[1], A=red[2], GT=red[3], total_T=red[4], total_d=red[5], mean=red[5] - self.mean_count)
@@ -351,19 +377,7 @@ class Engine:
             for k, v in enumerate(row):
                 arr[8 * f + k] = v
         _lib.check(self.lib.gdrf_set_product(self.ctx, len(table), arr), "gdrf_set_product")
-        pl = (C.c_int64 * 6)()
-        _lib.check(self.lib.gdrf_product_layout(self.ctx, pl), "gdrf_product_layout")
-        ol, op = pl[2], pl[4]
-        for f, fac in enumerate(table):
-            pre = fac["name"] + "." if fac["name"] else ""
-            nl, npr = int(fac["lengthscales"]), int(fac.get("periods", 0))
-            self._prod_views[pre + "log_variance"] = (pl[0] + f, ())
-            self._prod_views[pre + "log_lengthscale"] = (ol, () if nl == 1 else (nl,))
-            ol += nl
-            if npr:
-                self._prod_views[pre + "log_period"] = (op, () if npr == 1 else (npr,))
-                op += npr
-        self.product = table
+        return table
 
     def set_allreduce(self, fn):
         """Register the step's collective behind the C ABI (gdrf_set_allreduce): ``fn(buf_ptr, count, is_double, stream_ptr)`` sums the flat
@@ -402,50 +416,24 @@ class Engine:
     # ---- parameter views (natural shapes) ---------------------------------------------------------
     def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
         buf = self.params if buf is None else buf
-        if name in self.mean_shapes:
-            return self._mean_view(name, buf)
-        if name in self._prod_views:
-            o, shape = self._prod_views[name]
-            return buf[o:o + math.prod(shape)].view(shape)
-        if self.product is not None and name in ("log_lengthscale", "log_variance", "log_period", "log_scale_mixture"):
-            raise KeyError(f"{name}: a product context's kernel parameters are {tuple(self._prod_views)}")
-        o = self.layout[name]
-        K, M, V = self.K, self.M, self.V
-        if name == "log_lengthscale" and self.ard:
-            return buf[o:o + self.D].view(self.D)
-        if name == "log_period":
-            return buf[o:o + 1].view(()) if self.period_count == 1 else buf[o:o + self.D].view(self.D)
-        if name in ("log_lengthscale", "log_variance", "log_noise", "log_scale_mixture"):
-            return buf[o:o + 1].view(())
-        if name == "u_loc":
-            return buf[o:o + K * M].view(K, M)
-        if name == "phi_unc":
-            return buf[o:o + K * V].view(K, V)
-        if name == "u_scale_tril_unc":
-            return buf[o:o + K * M * M].view(K, M, M)
-        if name == "inducing_unc":
-            return buf[o:o + M * self.D].view(M, self.D)
-        raise KeyError(name)
-
-    def _mean_view(self, name: str, buf: torch.Tensor) -> torch.Tensor:
-        o, shape = self._mean_offsets[name], self.mean_shapes[name]
+        if name not in self.table:
+            if self.product is not None and name in ("log_lengthscale", "log_variance", "log_period", "log_scale_mixture"):
+                names = tuple(self.table)
+                raise KeyError(f"{name}: a product context's kernel parameters are {names[:names.index('log_noise')]}")
+            raise KeyError(name)
+        o, shape = self.table[name]
         return buf[o:o + math.prod(shape)].view(shape)
 
     PARAM_NAMES = ("log_lengthscale", "log_variance", "log_noise", "u_loc", "phi_unc", "u_scale_tril_unc")
 
     @property
     def param_names(self):
-        """PARAM_NAMES plus the blocks only some configurations learn (RationalQuadratic's scale_mixture, inducing inputs, the
-        mean_function's parameters)."""
-        extra = (("log_scale_mixture",) if self.kernel == "rationalquadratic" else ()) + \
-                (("log_period",) if self.period_count else ()) + \
-                (("inducing_unc",) if self.learn_inducing else ()) + tuple(self.mean_shapes)
-        if self.product is not None:          # the factors' segments in place of slots 0 and 1
-            return tuple(self._prod_views) + self.PARAM_NAMES[2:] + extra
-        return self.PARAM_NAMES + extra
+        """PARAM_NAMES (a product context: its factors' segments in place of slots 0 and 1) plus the blocks only some configurations learn
+        (RationalQuadratic's scale_mixture, a Periodic kernel's period, inducing inputs, the mean_function's parameters)."""
+        return tuple(self.table)
 
     def named_views(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        return {n: self.view(n, buf) for n in self.param_names}
+        return {n: self.view(n, buf) for n in self.table}
 
     def set_inducing_points(self, Z: torch.Tensor):
         Z = Z.to(device=self.device, dtype=self.dtype).contiguous()
@@ -828,8 +816,7 @@ class Engine:
 
     def segments(self) -> Dict[str, tuple]:
         """{name: (offset, length)} of every learnt parameter tensor in the flat vector (the segments of optim_step)."""
-        base, esz = self.params.data_ptr(), self.params.element_size()
-        return {n: ((v.data_ptr() - base) // esz, v.numel()) for n, v in self.named_views().items()}
+        return {n: (o, math.prod(shape)) for n, (o, shape) in self.table.items()}
 
     def state_buffer(self, slot: int) -> torch.Tensor:
         """Optimizer state vector 1 (exp_avg), 2 (exp_avg_sq) or 3 (opt_extra, allocated on first use)."""

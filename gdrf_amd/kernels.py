@@ -27,6 +27,8 @@ class Kernel:
     name = None
     kernel_id = None
     subset_dims = False          # True for the kinds that may read a proper subset of the input axes (RBF, Periodic)
+    params = ("variance", "lengthscale")      # a leaf's positive learnable parameters, in the order the engine names them ("log_" + name)
+    coords_per_axis = 1                       # embedded coordinates the device evaluates each of its axes on
 
     def __init__(self, input_dim: int, variance=None, lengthscale=None, active_dims=None):
         self.active_dims, self.explicit_active_dims = _active_dims(input_dim, active_dims)
@@ -59,6 +61,10 @@ class Kernel:
     def to(self, device):
         return self
 
+    def factors(self, prefix: str = ""):
+        """The leaf factors as [(path, kernel)]: a leaf is its own single factor, with the empty path."""
+        return [("", self)]
+
     def __repr__(self):
         ls = self.lengthscale.tolist() if self.ard else float(self.lengthscale)
         return f"{type(self).__name__}(input_dim={self.input_dim}, lengthscale={ls}, variance={float(self.variance)})"
@@ -90,6 +96,7 @@ class RationalQuadratic(Kernel):
     hyper-parameter (pyro.contrib.gp.kernels.RationalQuadratic(input_dim, variance, lengthscale, scale_mixture))."""
     name = "rationalquadratic"
     kernel_id = 4
+    params = Kernel.params + ("scale_mixture",)
 
     def __init__(self, input_dim: int, variance=None, lengthscale=None, scale_mixture=None, active_dims=None):
         super().__init__(input_dim, variance=variance, lengthscale=lengthscale, active_dims=active_dims)
@@ -107,6 +114,8 @@ class Periodic(Kernel):
     name = "periodic"
     kernel_id = 5
     subset_dims = True
+    params = Kernel.params + ("period",)
+    coords_per_axis = 2
 
     def __init__(self, input_dim: int, variance=None, lengthscale=None, period=None, active_dims=None):
         super().__init__(input_dim, variance=variance, lengthscale=lengthscale, active_dims=active_dims)
@@ -133,6 +142,7 @@ class Product(Kernel):
     device evaluates it on the factors' embedded coordinates (one per RBF axis, two per Periodic axis, at most 4 in all)."""
     name = "product"
     kernel_id = 6
+    params = ()                  # its leaves hold them all
 
     def __init__(self, kern0, kern1):
         for k in (kern0, kern1):
@@ -171,8 +181,7 @@ class Sum(Kernel):
 
 def embedded_coordinates(kernel) -> int:
     """The embedded coordinates the device evaluates ``kernel`` on: one per RBF axis, two per Periodic axis."""
-    leaves = kernel.factors() if isinstance(kernel, Product) else [("", kernel)]
-    return sum((2 if k.name == "periodic" else 1) * k.input_dim for _, k in leaves)
+    return sum(k.coords_per_axis * k.input_dim for _, k in kernel.factors())
 
 
 KERNEL_DICT = {"rbf": RBF, "matern32": Matern32, "matern52": Matern52, "exponential": Exponential,

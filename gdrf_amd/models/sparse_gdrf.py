@@ -47,23 +47,20 @@ def state_key(name: str) -> str:
 def product_table(kernel: Kernel, n_dims: int):
     """The factor table a kernel runs with on a product context (Engine(kernel="product", product=...)), or None when it runs as its own
     kind: a Product, or a lone RBF / Periodic whose explicit active_dims are not all of the world's axes (a one-factor product)."""
-    if isinstance(kernel, Product):
-        leaves = kernel.factors()
-    elif kernel.name in ("rbf", "periodic") and kernel.explicit_active_dims and kernel.active_dims != list(range(n_dims)):
-        leaves = [("", kernel)]
-    else:
+    lone_subset = kernel.subset_dims and kernel.explicit_active_dims and kernel.active_dims != list(range(n_dims))
+    if kernel.name != Product.name and not lone_subset:
         return None
     return [dict(name=path, kind=k.name, active_dims=list(k.active_dims), lengthscales=k.lengthscale.numel(),
-                 periods=k.period.numel() if k.name == "periodic" else 0) for path, k in leaves]
+                 periods=k.period.numel() if "period" in k.params else 0) for path, k in kernel.factors()]
 
 
 def kernel_spec(kernel: Kernel) -> dict:
     """The structure of a kernel as plain values (a checkpoint's meta): kinds, active_dims and parameter counts, no values."""
-    if isinstance(kernel, Product):
+    if kernel.name == Product.name:
         return dict(kind="product", kern0=kernel_spec(kernel.kern0), kern1=kernel_spec(kernel.kern1))
     spec = dict(kind=kernel.name, input_dim=kernel.input_dim, lengthscales=kernel.lengthscale.numel(),
                 active_dims=list(kernel.active_dims) if kernel.explicit_active_dims else None)
-    if kernel.name == "periodic":
+    if "period" in kernel.params:
         spec["periods"] = kernel.period.numel()
     return spec
 
@@ -79,6 +76,17 @@ def kernel_from_spec(spec: dict) -> Kernel:
         npr = int(spec["periods"])
         return Periodic(period=torch.ones(npr) if npr > 1 else 1.0, **kw)
     return KERNEL_DICT[spec["kind"]](**kw)
+
+
+def legacy_kernel_spec(meta: dict, state: Dict[str, torch.Tensor]) -> dict:
+    """The kernel_spec of a checkpoint written before every snapshot carried one (``meta["kernel_spec"]`` absent or None): a lone kernel
+    over all D axes, ARD or per-axis periods exactly when the stored log-lengthscales or log-periods are (D,) vectors."""
+    D = int(meta["D"])
+    count = lambda name: D if state[_PARAM_KEYS[name]].dim() == 1 else 1
+    spec = dict(kind=meta["kernel"], input_dim=D, lengthscales=count("log_lengthscale"), active_dims=None)
+    if _PARAM_KEYS["log_period"] in state:
+        spec["periods"] = count("log_period")
+    return spec
 
 
 MEAN_PREFIX = "_mean_function."      # + the name from named_parameters(): a trainable parameter of a torch.nn.Module mean_function
@@ -182,22 +190,10 @@ class ModelSnapshot:
     def restore(self, device: Optional[str] = None, mean_function: Callable = None, link_function: Callable = None):
         """A ``SparseMultinomialGDRF`` on ``device`` (default: the device the snapshot was taken on) holding these parameters.  A
         ``torch.nn.Module`` mean_function receives the stored ``_mean_function.*`` values; without one those entries are not used."""
-        from ..kernels import KERNEL_DICT, Periodic
         m = self.meta
         if self._model is not None and device is None and mean_function is None and link_function is None:
             return self._model
-        if m.get("kernel_spec") is not None:      # a product, or a kernel on a subset of the axes: rebuilt from its structure
-            kern = kernel_from_spec(m["kernel_spec"])
-        else:
-            ls = self._state[_PARAM_KEYS["log_lengthscale"]]
-            # an ARD checkpoint stores (D,) log-lengthscales: rebuild an ARD kernel (the values come from load_state_dict below)
-            lsk = torch.ones(int(m["D"])) if ls.dim() == 1 else 1.0
-            if m["kernel"] == Periodic.name:          # the period's shape, () or (D,), from the checkpoint as well
-                per = self._state[_PARAM_KEYS["log_period"]]
-                kern = Periodic(input_dim=int(m["D"]), lengthscale=lsk, variance=1.0,
-                                period=torch.ones(int(m["D"])) if per.dim() == 1 else 1.0)
-            else:
-                kern = KERNEL_DICT[m["kernel"]](input_dim=int(m["D"]), lengthscale=lsk, variance=1.0)
+        kern = kernel_from_spec(m.get("kernel_spec") or legacy_kernel_spec(m, self._state))
         dtype = getattr(torch, m["dtype"])
         model = SparseMultinomialGDRF(
             num_observation_categories=int(m["V"]), num_topic_categories=int(m["K"]), world=[tuple(w) for w in m["world"]],
@@ -427,25 +423,11 @@ class SparseMultinomialGDRF:
     def _init_params(self, eng: Engine):
         """sparse_gdrf.py:96-122 and abstract_gdrf.py:57-84."""
         with torch.no_grad():
-            if self._product:
-                leaves = self._kernel.factors() if isinstance(self._kernel, Product) else [("", self._kernel)]
-                for path, k in leaves:
-                    pre = path + "." if path else ""
-                    eng.view(pre + "log_variance").fill_(float(k.variance.log()))
-                    eng.view(pre + "log_lengthscale").copy_(k.lengthscale.log().reshape(eng.view(pre + "log_lengthscale").shape))
-                    if k.name == "periodic":
-                        eng.view(pre + "log_period").copy_(k.period.log().reshape(eng.view(pre + "log_period").shape))
-            elif self._kernel.ard:
-                eng.view("log_lengthscale").copy_(self._kernel.lengthscale.log())
-            else:
-                eng.view("log_lengthscale").fill_(float(self._kernel.lengthscale.log()))
-            if not self._product:
-                eng.view("log_variance").fill_(float(self._kernel.variance.log()))
+            for path, k in self._kernel.factors():
+                for name in k.params:
+                    v = eng.view((path + "." if path else "") + "log_" + name)
+                    v.copy_(getattr(k, name).log().reshape(v.shape))
             eng.view("log_noise").fill_(float(torch.tensor(self._init_noise, dtype=torch.float64).log()))
-            if self._kernel.name == "periodic" and not self._product:
-                eng.view("log_period").copy_(self._kernel.period.log().reshape(eng.view("log_period").shape))
-            if self._kernel.name == "rationalquadratic":
-                eng.view("log_scale_mixture").fill_(float(self._kernel.scale_mixture.log()))
             eng.view("u_loc").zero_()
             ret = torch.softmax(self._dirichlet_param, dim=-2)           # over K (abstract_gdrf.py:68-69)
             if self._randomize_wt:
@@ -1048,5 +1030,5 @@ class SparseMultinomialGDRF:
                     inducing_points=self._engine.Z.detach().cpu().clone(), dtype=str(self.dtype).replace("torch.", ""),
                     device=str(self.device), pure_fp32=self._pure_fp32, mfma_mode=self._mfma_mode, seed=self.rng_seed,
                     guide_rescale=self._guide_rescale, rows_form=self._rows_form,
-                    kernel_spec=kernel_spec(self._kernel) if self._product else None)
+                    kernel_spec=kernel_spec(self._kernel))
         return ModelSnapshot(self.state_dict(), meta)

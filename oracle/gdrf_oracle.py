@@ -57,7 +57,33 @@ def square_scaled_dist(X: torch.Tensor, Z: torch.Tensor, lengthscale: torch.Tens
     return r2.clamp(min=0)
 
 
-def kernel_matrix(kind: str, X: torch.Tensor, Z: torch.Tensor, lengthscale, variance, scale_mixture=None) -> torch.Tensor:
+def periodic_matrix(X, Z, lengthscale, variance, period) -> torch.Tensor:
+    """pyro 1.8.0 contrib/gp/kernels/periodic.py: variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / period_d) / lengthscale_d^2)."""
+    s = torch.sin(math.pi * (X[:, None, :] - Z[None, :, :]) / period)
+    return variance * torch.exp(-2.0 * ((s / lengthscale) ** 2).sum(-1))
+
+
+def product_matrix(X, Z, factors) -> torch.Tensor:
+    """pyro's Product: kern0(X, Z) * kern1(X, Z) over ``factors`` = [(kind, active_dims, lengthscale, variance, period)] with kind "rbf"
+    (the direct form variance * exp(-0.5 sum_d ((x_d - z_d) / lengthscale_d)^2)) or "periodic", each on its own active_dims."""
+    K = None
+    for kind, dims, ls, var, per in factors:
+        Xf, Zf = X[:, dims], Z[:, dims]
+        if kind == "rbf":
+            k = var * torch.exp(-0.5 * (((Xf[:, None, :] - Zf[None, :, :]) / ls) ** 2).sum(-1))
+        else:
+            k = periodic_matrix(Xf, Zf, ls, var, per)
+        K = k if K is None else K * k
+    return K
+
+
+def kernel_matrix(kind: str, X: torch.Tensor, Z: torch.Tensor, lengthscale, variance, scale_mixture=None, *, period=None,
+                  factors=None) -> torch.Tensor:
+    """``scale_mixture`` is RationalQuadratic's, ``period`` Periodic's, ``factors`` the list a "product" multiplies (product_matrix)."""
+    if kind == "periodic":
+        return periodic_matrix(X, Z, lengthscale, variance, period)
+    if kind == "product":
+        return product_matrix(X, Z, factors)
     r2 = square_scaled_dist(X, Z, lengthscale)
     if kind == "rbf":
         return variance * torch.exp(-0.5 * r2)
@@ -111,11 +137,12 @@ def jitter_total(jitter: float, level: int) -> float:
 # --------------------------------------------------------------------------
 # pyro.contrib.gp.util.conditional, full_cov=False, whiten=True  
 # --------------------------------------------------------------------------
-def conditional(kind, Xnew, Z, lengthscale, variance, u_loc, u_scale_tril, Lff, scale_mixture=None, whiten=True):
+def conditional(kind, Xnew, Z, lengthscale, variance, u_loc, u_scale_tril, Lff, scale_mixture=None, whiten=True, *, period=None,
+                factors=None):
     M = Z.size(0)
     K = u_loc.size(0)
     N = Xnew.size(0)
-    Kfs = kernel_matrix(kind, Z, Xnew, lengthscale, variance, scale_mixture)            # (M,N)
+    Kfs = kernel_matrix(kind, Z, Xnew, lengthscale, variance, scale_mixture, period=period, factors=factors)            # (M,N)
     v_2D = u_loc.reshape(-1, M).t()                                      # (M,K)
     S_2D = u_scale_tril.reshape(-1, M, M).permute(1, 2, 0).reshape(M, -1)  # (M, M*K): col = j*K + k
     W = torch.linalg.solve_triangular(Lff, Kfs, upper=False).t()         # (N,M)
@@ -171,7 +198,7 @@ class RefShapedGDRF:
                  Z: Optional[torch.Tensor] = None, optimizer="adam", lr=1e-3,
                  force_jitter_level: Optional[int] = None, learn_inducing: bool = False, scale_mixture: float = 1.0,
                  whiten: bool = True, mean_function=None, world: Optional[Sequence[Tuple[float, float]]] = None,
-                 guide_rescale: bool = True, link_function=None):
+                 guide_rescale: bool = True, link_function=None, period: float = 1.0):
         self.dtype = dtype
         # topic_model.py:148-198: inputs are mapped to the unit cube by (x - lower) / delta.  With world=None the inputs are taken as
         # already scaled (what train() builds: world = [(0, 1)]^D, train_script.py:261-271).  Quirk Q3 (sparse_gdrf.py:376-380): the
@@ -202,7 +229,8 @@ class RefShapedGDRF:
         ls = torch.tensor(float(lengthscale), dtype=dtype)
         var = torch.tensor(float(variance), dtype=dtype)
         sm = torch.tensor(float(scale_mixture), dtype=dtype)
-        Kuu = kernel_matrix(kind, self.Z, self.Z, ls, var, sm)
+        per = torch.tensor(float(period), dtype=dtype)
+        Kuu = kernel_matrix(kind, self.Z, self.Z, ls, var, sm, period=per)
         L0, self.init_jitter_level = jittercholesky(Kuu, self.M, jitter, maxjitter,
                                                     force_level=force_jitter_level)
         wt = torch.softmax(self.alpha, dim=-2)           # abstract_gdrf.py:68-69 (over K)
@@ -216,6 +244,9 @@ class RefShapedGDRF:
         }
         if kind == "rationalquadratic":
             self.params["log_scale_mixture"] = sm.log().clone()          # positive constraint -> exp
+        if kind == "periodic":
+            self.params["log_period"] = per.log().clone()                # () here; a (D,) vector by substitution, like an ARD lengthscale
+        self.factor_spec: List[tuple] = []                               # set_factors: [(parameter prefix, kind, active_dims)]
         self.whiten = bool(whiten)
         self.learn_inducing = bool(learn_inducing)
         if self.learn_inducing:
@@ -237,11 +268,39 @@ class RefShapedGDRF:
             return transform_to(constraints.interval(0.0, 1.0))(self.params["inducing_unc"])
         return self.Z
 
+    def set_factors(self, factors):
+        """Make this a product of ``factors`` = [(pyro path, "rbf" | "periodic", active_dims, lengthscale, variance, period)]: the kind
+        becomes "product", and each factor's log-variance, log-lengthscale and log-period replace the lone kernel's two parameters, under
+        the engine's names ("kern0.log_variance", ...; "log_variance", ... for a lone factor with the path "").  The variational
+        parameters stay those of the kernel the oracle was built with."""
+        self.kind = "product"
+        del self.params["log_lengthscale"], self.params["log_variance"]
+        t = lambda v: torch.as_tensor(v, dtype=self.dtype).log().clone().requires_grad_(True)
+        for name, kind, dims, ls, var, per in factors:
+            pre = name + "." if name else ""
+            self.factor_spec.append((pre, kind, dims))
+            self.params[pre + "log_variance"] = t(var)
+            self.params[pre + "log_lengthscale"] = t(ls)
+            if kind == "periodic":
+                self.params[pre + "log_period"] = t(per)
+
+    def factors(self):
+        """What product_matrix takes: [(kind, active_dims, lengthscale, variance, period or None)], constrained."""
+        p = self.params
+        return [(kind, dims, p[pre + "log_lengthscale"].exp(), p[pre + "log_variance"].exp(),
+                 p[pre + "log_period"].exp() if kind == "periodic" else None) for pre, kind, dims in self.factor_spec]
+
     def constrained(self):
         p = self.params
+        fs = self.factors()
+        if fs:                                     # kernel_diag takes the product of the factors' variances
+            variance = fs[0][3]
+            for f in fs[1:]:
+                variance = variance * f[3]
         return dict(
-            lengthscale=p["log_lengthscale"].exp(),
-            variance=p["log_variance"].exp(),
+            lengthscale=None if fs else p["log_lengthscale"].exp(),
+            variance=variance if fs else p["log_variance"].exp(),
+            kernel_kw=dict(period=p["log_period"].exp() if "log_period" in p else None, factors=fs or None),
             u_loc=p["u_loc"],
             u_scale_tril=transform_to(constraints.lower_cholesky)(p["u_scale_tril_unc"]),
             noise=p["log_noise"].exp(),
@@ -255,7 +314,7 @@ class RefShapedGDRF:
 
     def _luu(self, c):
         Zc = self.inducing()
-        Kuu = kernel_matrix(self.kind, Zc, Zc, c["lengthscale"], c["variance"], c["scale_mixture"]).contiguous()
+        Kuu = kernel_matrix(self.kind, Zc, Zc, c["lengthscale"], c["variance"], c["scale_mixture"], **c["kernel_kw"]).contiguous()
         L, lvl = jittercholesky(Kuu, self.M, self.jitter, self.maxjitter, force_level=self.force_jitter_level)
         self.last_jitter_level = lvl
         return L
@@ -272,7 +331,7 @@ class RefShapedGDRF:
         # guide: sparse_gdrf.py:375-409
         Luu = self._luu(c)
         f_loc, f_var = conditional(self.kind, xs_g, self.inducing(), c["lengthscale"], c["variance"],
-                                   c["u_loc"], c["u_scale_tril"], Luu, c["scale_mixture"], self.whiten)
+                                   c["u_loc"], c["u_scale_tril"], Luu, c["scale_mixture"], self.whiten, **c["kernel_kw"])
         if self.mean_function is not None:
             f_loc = f_loc + self.mean_function(xs_g)      # sparse_gdrf.py:395
         q_mu = Normal(f_loc, f_var)                       # Q1: variance passed as scale
@@ -281,7 +340,7 @@ class RefShapedGDRF:
         # model (replayed with mu, phi): sparse_gdrf.py:323-373
         Luu2 = self._luu(c)
         f_loc2, f_var2 = conditional(self.kind, xs, self.inducing(), c["lengthscale"], c["variance"],
-                                     c["u_loc"], c["u_scale_tril"], Luu2, c["scale_mixture"], self.whiten)
+                                     c["u_loc"], c["u_scale_tril"], Luu2, c["scale_mixture"], self.whiten, **c["kernel_kw"])
         if self.mean_function is not None:
             f_loc2 = f_loc2 + self.mean_function(xs)      # sparse_gdrf.py:346
         lp_mu = Normal(f_loc2, f_var2 + c["noise"]).log_prob(mu).sum()
@@ -304,7 +363,7 @@ class RefShapedGDRF:
         c = self.constrained()
         Luu = self._luu(c) if Luu is None else Luu
         f_loc, f_var = conditional(self.kind, xs, self.inducing(), c["lengthscale"], c["variance"],
-                                   c["u_loc"], c["u_scale_tril"], Luu, c["scale_mixture"], self.whiten)
+                                   c["u_loc"], c["u_scale_tril"], Luu, c["scale_mixture"], self.whiten, **c["kernel_kw"])
         if self.mean_function is not None:
             f_loc = f_loc + self.mean_function(xs)
         mu = f_loc + f_var * eps
@@ -388,7 +447,7 @@ class RefShapedGDRF:
         c = self.constrained()
         Luu = self._luu(c)
         f_loc, _ = conditional(self.kind, xs, self.inducing(), c["lengthscale"], c["variance"],
-                               c["u_loc"], c["u_scale_tril"], Luu, c["scale_mixture"], self.whiten)
+                               c["u_loc"], c["u_scale_tril"], Luu, c["scale_mixture"], self.whiten, **c["kernel_kw"])
         return f_loc
 
     def topic_probs(self, xs=None):

@@ -2,79 +2,26 @@
 computes them by parameter substitution: a (D,) log-lengthscale broadcasts X / lengthscale exactly as pyro's Isotropy._scale does."""
 import copy
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle.gdrf_oracle import RefShapedGDRF, conditional, synth_circles
+from tests._util import (LOSS_TOL_VS_TORCH, NPTS, check_grads, check_loss_and_grads, dev, engine_for as ard_engine, relerr, run_two_ranks,
+                         variant_oracle)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOSS_TOL_VS_TORCH = 1e-6          # as in tests/test_gpu_parity.py: torch's float32 lgamma of the int32 counts
 LS = (0.12, 0.35, 0.2)
 KINDS = ["rbf", "matern52", "matern32", "exponential", "rationalquadratic"]
-NPTS = {1: (8,), 2: (4, 3), 3: (3, 3, 2)}
 
 
-def relerr(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-300))
-
-
-def ard_oracle(kind="rbf", D=2, ls=LS, learn=False, whiten=True, dtype=torch.float64, seed=1, W=16, H=9, V=20, K=4, **kw):
+def ard_oracle(kind="rbf", D=2, ls=LS, **kw):
     """The oracle of tests/_util.make_oracle with the (D,) lengthscale vector ``ls`` substituted for its scalar one."""
-    xs, ws, _ = synth_circles(W, H, V, K, seed=seed, one_d=(D == 1))
-    xs = torch.from_numpy(xs).double()
-    g = torch.Generator().manual_seed(seed + 100)
-    if D == 3:
-        xs = torch.cat([xs, torch.rand(xs.shape[0], 1, generator=g, dtype=torch.float64)], 1)
-    M = int(np.prod(NPTS[D]))
-    Z = (0.05 + 0.9 * torch.rand(M, D, generator=g, dtype=torch.float64)) if learn else None
-    m = RefShapedGDRF(xs, ws, kind=kind, K=K, n_points=NPTS[D], dtype=dtype, jitter=1e-6, lengthscale=0.2, Z=Z, learn_inducing=learn,
-                      whiten=whiten, scale_mixture=1.3, **kw)
-    with torch.no_grad():
-        m.params["u_loc"].add_(0.3 * torch.randn(m.params["u_loc"].shape, generator=g, dtype=torch.float64).to(dtype))
-        m.params["u_scale_tril_unc"].add_(0.1 * torch.randn(m.params["u_scale_tril_unc"].shape, generator=g, dtype=torch.float64).tril().to(dtype))
-        m.params["phi_unc"].add_(0.5 * torch.randn(m.params["phi_unc"].shape, generator=g, dtype=torch.float64).to(dtype))
-        m.params["log_noise"].add_(0.2)
-    m.params["log_lengthscale"] = torch.tensor(ls[:D], dtype=dtype).log().requires_grad_(True)
-    eps = torch.randn(K, m.N, generator=g, dtype=torch.float64).to(dtype)
-    return m, eps
-
-
-def ard_engine(m, ard=True, dtype=None, n_cap=None, **kw):
-    """gdrf_amd.Engine (ARD context) holding exactly the oracle's parameters, inducing points and Dirichlet prior."""
-    from gdrf_amd.engine import Engine
-    eng = Engine(n_cap or m.N, m.M, m.K, m.V, m.D, dtype=dtype or m.dtype, kernel=m.kind, jitter=m.jitter, maxjitter=m.maxjitter,
-                 process_group=None, learn_inducing=m.learn_inducing, whiten=m.whiten, ard=ard, **kw)
-    eng.set_inducing_points(m.Z)
-    eng.set_dirichlet(m.alpha)
-    for name in eng.param_names:
-        v, p = eng.view(name), m.params[name].detach().to(eng.dtype)
-        v.copy_(p.reshape(v.shape) if p.numel() == v.numel() else p.flatten()[0])    # an isotropic engine takes the first entry
-    return eng
-
-
-def dev(t, eng, dtype=None):
-    return torch.as_tensor(t).to(device=eng.device, dtype=dtype or eng.dtype).contiguous()
-
-
-def check_loss_and_grads(eng, m, eps, tl=LOSS_TOL_VS_TORCH, tg=1e-7, **kw):
-    xs, ws = dev(m.xs, eng), dev(m.ws, eng, torch.int32)
-    eng.loss_and_grads(xs, ws, dev(eps, eng), **kw)
-    out = eng.read_out()
-    m.force_jitter_level = eng.last_jitter_level
-    loss_ref, grads_ref = m.loss_and_grads(eps)
-    assert abs(out["loss"] - loss_ref) <= tl * abs(loss_ref), (out["loss"], loss_ref)
-    gv = eng.named_views(eng.grads)
-    assert set(gv) == set(grads_ref), (set(gv), set(grads_ref))
-    for name, g in gv.items():
-        assert tuple(g.shape) == tuple(grads_ref[name].shape), name
-        assert relerr(g.cpu().numpy(), grads_ref[name].numpy()) < tg, name
-    assert float(eng.grads[0]) == 0.0                     # slot 0 is not a parameter of an ARD context
+    def substitute(m):
+        m.params["log_lengthscale"] = torch.tensor(ls[:D], dtype=m.dtype).log().requires_grad_(True)
+    return variant_oracle(D, substitute, kind=kind, lengthscale=0.2, scale_mixture=1.3, shared_generator=True, **kw)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -94,6 +41,7 @@ def test_loss_and_every_gradient_fp64(kind, D, learn, whiten):
     if D == 1 and (learn or kind == "exponential"):
         tg = 5e-6
     check_loss_and_grads(eng, m, eps, tg=tg)
+    assert float(eng.grads[0]) == 0.0                     # slot 0 is not a parameter of an ARD context
 
 
 def _iso_pair(kind="rbf", D=2, dtype=torch.float64, **kw):
@@ -335,9 +283,7 @@ def test_non_unit_world_against_the_oracle():
     eng.loss_and_grads(dev(xs_m, eng), dev(m.ws, eng, torch.int32), dev(eps, eng), xs_guide=dev(m.scale(xs_m), eng),
                        force_level=m.last_jitter_level)
     assert abs(eng.read_out()["loss"] - loss_ref) <= LOSS_TOL_VS_TORCH * abs(loss_ref)
-    gv = eng.named_views(eng.grads)
-    for name in gv:
-        assert relerr(gv[name].cpu().numpy(), grads_ref[name].numpy()) < 1e-7, name
+    check_grads(eng, grads_ref)
 
 
 def test_particles_and_renyi():
@@ -360,9 +306,7 @@ def test_particles_and_renyi():
     m.force_jitter_level = eng.last_jitter_level
     loss_ref, grads_ref = m.loss_and_grads(eps3, renyi_alpha=0.5)
     assert abs(eng.read_out()["loss"] - loss_ref) <= LOSS_TOL_VS_TORCH * abs(loss_ref)
-    gv = eng.named_views(eng.grads)
-    for name in gv:
-        assert relerr(gv[name].cpu().numpy(), grads_ref[name].numpy()) < 1e-7, name
+    check_grads(eng, grads_ref)
 
 
 def test_streaming_minibatch_with_n_global():
@@ -374,9 +318,7 @@ def test_streaming_minibatch_with_n_global():
     m.force_jitter_level = eng.last_jitter_level
     loss_ref, grads_ref = m.loss_and_grads(eps_b, xs=xs_b, ws=ws_b, n_global=m.N)
     assert abs(eng.read_out()["loss"] - loss_ref) <= LOSS_TOL_VS_TORCH * abs(loss_ref)
-    gv = eng.named_views(eng.grads)
-    for name in gv:
-        assert relerr(gv[name].cpu().numpy(), grads_ref[name].numpy()) < 1e-7, name
+    check_grads(eng, grads_ref)
 
 
 def test_mean_function_and_custom_link():
@@ -386,6 +328,7 @@ def test_mean_function_and_custom_link():
     eng = ard_engine(m)
     eng.link_function = link
     check_loss_and_grads(eng, m, eps, mean=dev(mf(m.xs), eng))
+    assert float(eng.grads[0]) == 0.0
 
 
 def test_hyper_backward_tn_request_falls_back_to_f64():
@@ -400,40 +343,13 @@ def test_hyper_backward_tn_request_falls_back_to_f64():
     assert torch.equal(e_tn.grads, e_64.grads)
 
 
-def _dist_worker(rank, world, port, tmp, via):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)          # both ranks share the box's single GPU
-    model, svi, _, xs, ws = _build(dtype=torch.float64)
-    N = len(xs)
-    lo, hi = rank * N // world, (rank + 1) * N // world
-    svi.row_offset = lo
-    if via == "c_abi_hook":
-        eng = model._engine_for(hi - lo)
-        eng.pg = None
-
-        def allreduce(buf, count, is_double, stream):
-            assert buf == eng.red_T.data_ptr() and count == eng.red_T.numel()
-            dist.all_reduce(eng.red_T)
-            return 0
-        eng.set_allreduce(allreduce)
-    losses = [svi.step(xs=xs[lo:hi], ws=ws[lo:hi], subsample=False) for _ in range(3)]
-    torch.save({"losses": losses, "params": model._engine.params.cpu()}, os.path.join(tmp, f"r{rank}.pt"))
-    dist.destroy_process_group()
-
-
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("via", ["torch_distributed", "c_abi_hook"])
 def test_two_ranks_on_one_gpu_match_a_single_rank(tmp_path, via):
-    import torch.multiprocessing as mp
     port = 27600 + (os.getpid() % 2000) + (7 if via == "c_abi_hook" else 0)
-    mp.spawn(_dist_worker, args=(2, port, str(tmp_path), via), nprocs=2, join=True)
+    r0, r1 = run_two_ranks(_build, via, port, tmp_path)
     model, svi, _, xs, ws = _build(dtype=torch.float64)
     ref = [svi.step(xs=xs, ws=ws, subsample=False) for _ in range(3)]
-    r0 = torch.load(tmp_path / "r0.pt", weights_only=True)
-    r1 = torch.load(tmp_path / "r1.pt", weights_only=True)
     assert r0["losses"] == r1["losses"]
     assert np.allclose(r0["losses"], ref, rtol=1e-10)
     assert torch.equal(r0["params"], r1["params"])

@@ -3,19 +3,17 @@ SVI.step against torch.autograd through the reference-shaped oracle (which diffe
 trajectory against torch optimizers on the module, the unchanged data path of plain callables, two ranks, and checkpoints."""
 import copy
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle.gdrf_oracle import RefShapedGDRF, _ClippedAdam, synth_circles
+from tests._util import LOSS_TOL_VS_TORCH, perturb_posterior, run_two_ranks
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
-LOSS_TOL_VS_TORCH = 1e-6          # as in tests/test_gpu_parity.py: torch's float32 lgamma of the int32 counts
 K, V, NPTS = 4, 12, (4, 3)
 WORLD = [(2.0, 5.0), (-1.0, 3.0)]
 SIGMOID_LINK = lambda mu: 0.05 + torch.sigmoid(0.02 * mu)       # noqa: E731  (not shift-invariant over the topics, unlike softmax)
@@ -84,11 +82,7 @@ def setup(mean="trend_kn", dtype=torch.float64, whiten=True, learn=False, ard=Fa
     Z = (0.05 + 0.9 * torch.rand(int(np.prod(NPTS)), 2, generator=g, dtype=torch.float64)) if learn else None
     m = RefShapedGDRF(xs, ws, kind="rbf", K=K, n_points=NPTS, dtype=torch.float64, jitter=1e-6, lengthscale=0.2, Z=Z, learn_inducing=learn,
                       whiten=whiten, mean_function=mod_ref, world=WORLD if world else None, link_function=link, optimizer=opt, lr=lr)
-    with torch.no_grad():
-        m.params["u_loc"].add_(0.3 * torch.randn(m.params["u_loc"].shape, generator=g, dtype=torch.float64))
-        m.params["u_scale_tril_unc"].add_(0.1 * torch.randn(m.params["u_scale_tril_unc"].shape, generator=g, dtype=torch.float64).tril())
-        m.params["phi_unc"].add_(0.5 * torch.randn(m.params["phi_unc"].shape, generator=g, dtype=torch.float64))
-        m.params["log_noise"].add_(0.2)
+    perturb_posterior(m, g)
     ls = [0.15, 0.3] if ard else 0.2
     if ard:
         m.params["log_lengthscale"] = torch.tensor(ls, dtype=torch.float64).log().requires_grad_(True)
@@ -249,42 +243,24 @@ def test_plain_callables_and_frozen_modules_take_the_data_path(kind):
     assert torch.equal(eng.grads, grads0)
 
 
-def _dist_worker(rank, world, port, tmp):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)          # both ranks share the box's single GPU
+def _dist_build():
     m, model, svi, _, xs, ws, _ = setup()
-    N = len(xs)
-    lo, hi = rank * N // world, (rank + 1) * N // world
-    svi.row_offset = lo
-    if os.environ.get("GDRF_TEST_C_ABI_ALLREDUCE") == "1":
-        eng = model._engine_for(hi - lo)
-        eng.pg = None
+    return model, svi, xs, ws
 
-        def allreduce(buf, count, is_double, stream):
-            dist.all_reduce(eng.red_T)
-            return 0
-        eng.set_allreduce(allreduce)
-    losses = [svi.step(xs=xs[lo:hi], ws=ws[lo:hi], subsample=False) for _ in range(3)]
-    torch.save({"losses": losses, "w": model._mean_function.w.detach().cpu()}, os.path.join(tmp, f"r{rank}.pt"))
-    dist.destroy_process_group()
+
+def _save_w(model):
+    return {"w": model._mean_function.w.detach().cpu()}
 
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("via", ["torch_distributed", "c_abi_hook"])
-def test_two_ranks_on_one_gpu_match_a_single_rank(tmp_path, via, monkeypatch):
+def test_two_ranks_on_one_gpu_match_a_single_rank(tmp_path, via):
     """The mean segment rides in the step's single collective: two ranks on halves of the rows train the module like one rank."""
-    import torch.multiprocessing as mp
-    monkeypatch.setenv("GDRF_TEST_C_ABI_ALLREDUCE", "1" if via == "c_abi_hook" else "0")
     port = 29800 + (os.getpid() % 2000) + (7 if via == "c_abi_hook" else 0)
-    mp.spawn(_dist_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    r0, r1 = run_two_ranks(_dist_build, via, port, tmp_path, save=_save_w)
     m, model, svi, _, xs, ws, _ = setup()
     w0 = model._mean_function.w.detach().cpu().clone()
     ref = [svi.step(xs=xs, ws=ws, subsample=False) for _ in range(3)]
-    r0 = torch.load(tmp_path / "r0.pt", weights_only=True)
-    r1 = torch.load(tmp_path / "r1.pt", weights_only=True)
     assert np.allclose(r0["losses"], ref, rtol=1e-10)
     assert torch.equal(r0["w"], r1["w"])
     w = model._mean_function.w.detach().cpu()

@@ -3,125 +3,45 @@
 
     k(x, z) = variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / period_d) / lengthscale_d^2),   k(x, x) = variance
 
-The oracle is RefShapedGDRF with kind "periodic": its kernel_matrix is wrapped here so that this kind evaluates the sine form, and the
-period rides in the slot the oracle passes scale_mixture through (no other kind reads it for "periodic")."""
+The oracle is RefShapedGDRF with kind "periodic" (oracle/gdrf_oracle.py::periodic_matrix)."""
 import copy
 import math
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import oracle.gdrf_oracle as go
-from oracle.gdrf_oracle import RefShapedGDRF, synth_circles
+from oracle.gdrf_oracle import RefShapedGDRF, periodic_matrix, synth_circles
+from tests._util import (LOSS_TOL_VS_TORCH, NPTS, check_grads, check_loss_and_grads, dev, engine_for as per_engine, relerr, run_two_ranks,
+                         variant_oracle)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOSS_TOL_VS_TORCH = 1e-6          # as in tests/test_gpu_ard.py
-NPTS = {1: (8,), 2: (4, 3)}
 LS = {1: (0.8,), 2: (0.7, 1.1)}
 PER = {1: (0.37,), 2: (0.45, 0.6)}
 
 
-def periodic_matrix(X, Z, lengthscale, variance, period):
-    """The sine form, straight from the formula."""
-    s = torch.sin(math.pi * (X[:, None, :] - Z[None, :, :]) / period)
-    return variance * torch.exp(-2.0 * ((s / lengthscale) ** 2).sum(-1))
+def with_periodic_params(m, lengthscale, period):
+    """``m`` (built with a scalar lengthscale and period) with log-lengthscale and log-period of shape () or (D,) substituted."""
+    for name, value in (("log_lengthscale", lengthscale), ("log_period", period)):
+        m.params[name] = torch.as_tensor(value, dtype=m.dtype).log().clone().requires_grad_(True)
+    return m
 
 
-_kernel_matrix = go.kernel_matrix
+def periodic_ref(xs, ws, *, period, lengthscale, **kw):
+    return with_periodic_params(RefShapedGDRF(xs, ws, kind="periodic", period=float(torch.as_tensor(period).flatten()[0]), **kw),
+                                lengthscale, period)
 
 
-def _kernel_matrix_with_periodic(kind, X, Z, lengthscale, variance, scale_mixture=None):
-    if kind == "periodic":
-        return periodic_matrix(X, Z, lengthscale, variance, scale_mixture)
-    return _kernel_matrix(kind, X, Z, lengthscale, variance, scale_mixture)
-
-
-@pytest.fixture(autouse=True)
-def _periodic_oracle(monkeypatch):
-    monkeypatch.setattr(go, "kernel_matrix", _kernel_matrix_with_periodic)
-
-
-class PeriodicRef(RefShapedGDRF):
-    """RefShapedGDRF with a Periodic kernel: log_period is a learnt parameter (shape () or (D,)) beside the others."""
-
-    def __init__(self, xs, ws, *, period, lengthscale, **kw):
-        with pytest.MonkeyPatch.context() as mp:
-            mp.setattr(go, "kernel_matrix", _kernel_matrix_with_periodic)
-            super().__init__(xs, ws, kind="periodic", scale_mixture=float(torch.as_tensor(period).flatten()[0]), **kw)
-        self.params["log_lengthscale"] = torch.as_tensor(lengthscale, dtype=self.dtype).log().clone().requires_grad_(True)
-        self.params["log_period"] = torch.as_tensor(period, dtype=self.dtype).log().clone().requires_grad_(True)
-
-    def constrained(self):
-        c = super().constrained()
-        c["scale_mixture"] = self.params["log_period"].exp()
-        return c
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-300))
-
-
-def per_oracle(D=1, per_axis=False, learn=False, whiten=True, dtype=torch.float64, seed=1, W=16, H=9, V=20, K=4, ls=None, period=None, **kw):
-    xs, ws, _ = synth_circles(W, H, V, K, seed=seed, one_d=(D == 1))
-    xs = torch.from_numpy(xs).double()
-    g = torch.Generator().manual_seed(seed + 100)
-    M = int(np.prod(NPTS[D]))
-    Z = (0.05 + 0.9 * torch.rand(M, D, generator=g, dtype=torch.float64)) if learn else None
+def per_oracle(D=1, per_axis=False, ls=None, period=None, **kw):
     ls = LS[D] if ls is None else ls
     period = PER[D] if period is None else period
     if not per_axis:
         ls, period = ls[0], period[0]
-    m = PeriodicRef(xs, ws, K=K, n_points=NPTS[D], dtype=dtype, jitter=1e-6, Z=Z, learn_inducing=learn, whiten=whiten, variance=4.0,
-                    lengthscale=ls, period=period, **kw)
-    with torch.no_grad():
-        m.params["u_loc"].add_(0.3 * torch.randn(m.params["u_loc"].shape, generator=g, dtype=torch.float64).to(dtype))
-        m.params["u_scale_tril_unc"].add_(0.1 * torch.randn(m.params["u_scale_tril_unc"].shape, generator=g, dtype=torch.float64).tril().to(dtype))
-        m.params["phi_unc"].add_(0.5 * torch.randn(m.params["phi_unc"].shape, generator=g, dtype=torch.float64).to(dtype))
-        m.params["log_noise"].add_(0.2)
-    eps = torch.randn(K, m.N, generator=g, dtype=torch.float64).to(dtype)
-    return m, eps
-
-
-def per_engine(m, dtype=None, n_cap=None, **kw):
-    """gdrf_amd.Engine (periodic context) holding exactly the oracle's parameters, inducing points and Dirichlet prior."""
-    from gdrf_amd.engine import Engine
-    eng = Engine(n_cap or m.N, m.M, m.K, m.V, m.D, dtype=dtype or m.dtype, kernel="periodic", jitter=m.jitter, maxjitter=m.maxjitter,
-                 process_group=None, learn_inducing=m.learn_inducing, whiten=m.whiten, ard=m.params["log_lengthscale"].dim() == 1,
-                 period_count=m.params["log_period"].numel(), **kw)
-    eng.set_inducing_points(m.Z)
-    eng.set_dirichlet(m.alpha)
-    for name in eng.param_names:
-        v = eng.view(name)
-        v.copy_(m.params[name].detach().to(eng.dtype).reshape(v.shape))
-    return eng
-
-
-def dev(t, eng, dtype=None):
-    return torch.as_tensor(t).to(device=eng.device, dtype=dtype or eng.dtype).contiguous()
-
-
-def check_grads(eng, grads_ref, tg=1e-7):
-    gv = eng.named_views(eng.grads)
-    assert set(gv) == set(grads_ref), (set(gv), set(grads_ref))
-    for name, g in gv.items():
-        assert tuple(g.shape) == tuple(grads_ref[name].shape), name
-        assert relerr(g.cpu().numpy(), grads_ref[name].numpy()) < tg, (name, relerr(g.cpu().numpy(), grads_ref[name].numpy()))
-
-
-def check_loss_and_grads(eng, m, eps, tg=1e-7, **kw):
-    xs, ws = dev(m.xs, eng), dev(m.ws, eng, torch.int32)
-    eng.loss_and_grads(xs, ws, dev(eps, eng), **kw)
-    out = eng.read_out()
-    m.force_jitter_level = eng.last_jitter_level
-    loss_ref, grads_ref = m.loss_and_grads(eps)
-    assert abs(out["loss"] - loss_ref) <= LOSS_TOL_VS_TORCH * abs(loss_ref), (out["loss"], loss_ref)
-    check_grads(eng, grads_ref, tg)
+    return variant_oracle(D, lambda m: with_periodic_params(m, ls, period), kind="periodic", variance=4.0,
+                          period=float(torch.as_tensor(period).flatten()[0]), **kw)
 
 
 CASES = [(1, False), (2, False), (2, True)]        # (D, per-axis lengthscale and period); one element is the shared form at D = 1
@@ -148,7 +68,7 @@ def test_mixed_shapes_of_lengthscale_and_period(ls, period):
 def test_knm_against_the_sine_form(D):
     m, _ = per_oracle(D, per_axis=True)
     c = m.constrained()
-    ref = periodic_matrix(m.xs, m.Z, c["lengthscale"].detach(), c["variance"].detach(), c["scale_mixture"].detach()).numpy()
+    ref = periodic_matrix(m.xs, m.Z, c["lengthscale"].detach(), c["variance"].detach(), c["kernel_kw"]["period"].detach()).numpy()
     e64 = per_engine(m)
     assert relerr(e64.knm(dev(m.xs, e64)).cpu().numpy(), ref) < 1e-12
     e32 = per_engine(m, dtype=torch.float32)
@@ -184,7 +104,7 @@ def test_predictive_path(D, dtype, tol):
     c = m.constrained()
     with torch.no_grad():
         loc, var = go.conditional("periodic", m.xs, m.inducing(), c["lengthscale"], c["variance"], c["u_loc"], c["u_scale_tril"],
-                                  m._luu(c), c["scale_mixture"], whiten=True)
+                                  m._luu(c), whiten=True, **c["kernel_kw"])
     lv = eng.predict(xs, 4).cpu()
     assert relerr(lv[0].numpy(), loc.numpy()) < tol and relerr(lv[1].numpy(), var.numpy()) < tol
     # model.forward(xs): the same conditional through the public surface
@@ -307,7 +227,7 @@ def test_non_unit_world_against_the_oracle():
     lower = torch.tensor([w[0] for w in world], dtype=torch.float64)
     delta = torch.tensor([w[1] - w[0] for w in world], dtype=torch.float64)
     xs_w = torch.from_numpy(xs).double() * delta + lower
-    m = PeriodicRef(xs_w, ws, K=3, n_points=(5, 4), jitter=1e-6, world=world, variance=4.0, lengthscale=(0.6, 0.9), period=(0.5, 0.7))
+    m = periodic_ref(xs_w, ws, K=3, n_points=(5, 4), jitter=1e-6, world=world, variance=4.0, lengthscale=(0.6, 0.9), period=(0.5, 0.7))
     g = torch.Generator().manual_seed(5)
     with torch.no_grad():
         m.params["u_loc"].add_(0.3 * torch.randn(m.params["u_loc"].shape, generator=g, dtype=torch.float64))
@@ -362,38 +282,11 @@ def test_mean_function_module_trains_beside_the_period():
     assert float(model._mean_function.a) != a0 and float(model.kernel_period) != p0
 
 
-def _dist_worker(rank, world, port, tmp):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)          # both ranks share the box's single GPU
-    model, svi, _, xs, ws = _build(dtype=torch.float64)
-    N = len(xs)
-    lo, hi = rank * N // world, (rank + 1) * N // world
-    svi.row_offset = lo
-    eng = model._engine_for(hi - lo)
-    eng.pg = None
-
-    def allreduce(buf, count, is_double, stream):
-        assert buf == eng.red_T.data_ptr() and count == eng.red_T.numel()
-        dist.all_reduce(eng.red_T)
-        return 0
-    eng.set_allreduce(allreduce)
-    losses = [svi.step(xs=xs[lo:hi], ws=ws[lo:hi], subsample=False) for _ in range(3)]
-    torch.save({"losses": losses, "params": model._engine.params.cpu()}, os.path.join(tmp, f"r{rank}.pt"))
-    dist.destroy_process_group()
-
-
 @pytest.mark.timeout(600)
 def test_two_ranks_through_the_c_abi_hook_match_a_single_rank(tmp_path):
-    import torch.multiprocessing as mp
-    port = 28700 + (os.getpid() % 2000)
-    mp.spawn(_dist_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    r0, r1 = run_two_ranks(_build, "c_abi_hook", 28700 + (os.getpid() % 2000), tmp_path)
     model, svi, _, xs, ws = _build(dtype=torch.float64)
     ref = [svi.step(xs=xs, ws=ws, subsample=False) for _ in range(3)]
-    r0 = torch.load(tmp_path / "r0.pt", weights_only=True)
-    r1 = torch.load(tmp_path / "r1.pt", weights_only=True)
     assert r0["losses"] == r1["losses"]
     assert np.allclose(r0["losses"], ref, rtol=1e-10)
     assert torch.equal(r0["params"], r1["params"])

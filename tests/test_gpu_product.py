@@ -5,25 +5,21 @@ CPU oracle with pyro's formulas for the factors (pyro 1.8.0 contrib/gp/kernels/i
     Periodic:  variance * exp(-2 sum_d sin^2(pi (x_d - z_d) / period_d) / lengthscale_d^2)
     Product:   kern0(X, Z) * kern1(X, Z), each factor reading its own active_dims
 
-The oracle is RefShapedGDRF with kind "product": kernel_matrix is wrapped so that this kind multiplies the factors, which ride in the slot
-the oracle passes scale_mixture through, and the variance it hands kernel_diag is the product of the factors' variances."""
+The oracle is RefShapedGDRF turned into a product by set_factors (oracle/gdrf_oracle.py::product_matrix): the variance it hands kernel_diag
+is the product of the factors' variances."""
 import copy
-import math
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
-from torch.distributions import constraints, transform_to
 
 import oracle.gdrf_oracle as go
-from oracle.gdrf_oracle import RefShapedGDRF, synth_circles
+from oracle.gdrf_oracle import product_matrix
+from tests._util import (LOSS_TOL_VS_TORCH, NPTS, check_loss_and_grads, dev, engine_for, grid_inputs as inputs, load_params as load, relerr,
+                         run_two_ranks, variant_oracle)
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOSS_TOL_VS_TORCH = 1e-6          # as in tests/test_gpu_periodic.py
 
 # (name, kind, active_dims, lengthscale, variance, period) per leaf factor, pyro module paths as names
 CASES = {
@@ -33,154 +29,19 @@ CASES = {
     "nested_three_factors_2d": (2, [("kern0.kern0", "rbf", [0], 0.7, 1.5, None), ("kern0.kern1", "periodic", [1], 0.9, 1.2, 0.4),
                                     ("kern1", "rbf", [1], 1.3, 2.0, None)]),
 }
-NPTS = {1: (8,), 2: (4, 3), 3: (3, 3, 2)}
 
 
-def factor_matrix(kind, X, Z, ls, var, period):
-    if kind == "rbf":
-        return var * torch.exp(-0.5 * (((X[:, None, :] - Z[None, :, :]) / ls) ** 2).sum(-1))
-    s = torch.sin(math.pi * (X[:, None, :] - Z[None, :, :]) / period)
-    return var * torch.exp(-2.0 * ((s / ls) ** 2).sum(-1))
-
-
-def product_matrix(X, Z, factors):
-    """factors: [(kind, active_dims, lengthscale, variance, period)] with tensor values."""
-    K = None
-    for kind, dims, ls, var, per in factors:
-        k = factor_matrix(kind, X[:, dims], Z[:, dims], ls, var, per)
-        K = k if K is None else K * k
-    return K
-
-
-_kernel_matrix = go.kernel_matrix
-
-
-def _kernel_matrix_with_product(kind, X, Z, lengthscale, variance, scale_mixture=None):
-    if kind == "product":
-        return product_matrix(X, Z, scale_mixture)
-    return _kernel_matrix(kind, X, Z, lengthscale, variance, scale_mixture)
-
-
-@pytest.fixture(autouse=True)
-def _product_oracle(monkeypatch):
-    monkeypatch.setattr(go, "kernel_matrix", _kernel_matrix_with_product)
-
-
-class ProductRef(RefShapedGDRF):
-    """RefShapedGDRF with a product kernel: each factor's log-variance, log-lengthscale and log-period are learnt parameters named as the
-    engine names them ("kern0.log_variance", ...; "log_variance", ... for a lone factor named "")."""
-
-    def __init__(self, xs, ws, *, factors, **kw):
-        super().__init__(xs, ws, kind="rbf", lengthscale=0.5, variance=1.0, **kw)
-        self.kind = "product"
-        self.factor_kinds = [(kind, dims) for _, kind, dims, *_ in factors]
-        self.factor_names = [name + "." if name else "" for name, *_ in factors]
-        del self.params["log_lengthscale"], self.params["log_variance"]
-        t = lambda v: torch.as_tensor(v, dtype=self.dtype).log().clone().requires_grad_(True)
-        for name, kind, dims, ls, var, per in factors:
-            pre = name + "." if name else ""
-            self.params[pre + "log_variance"] = t(var)
-            self.params[pre + "log_lengthscale"] = t(ls)
-            if kind == "periodic":
-                self.params[pre + "log_period"] = t(per)
-
-    def factors(self):
-        p = self.params
-        return [(kind, dims, p[pre + "log_lengthscale"].exp(), p[pre + "log_variance"].exp(),
-                 p[pre + "log_period"].exp() if kind == "periodic" else None) for (kind, dims), pre in zip(self.factor_kinds, self.factor_names)]
-
-    def constrained(self):
-        p = self.params
-        fs = self.factors()
-        var = fs[0][3]
-        for f in fs[1:]:
-            var = var * f[3]
-        return dict(lengthscale=None, variance=var, u_loc=p["u_loc"],
-                    u_scale_tril=transform_to(constraints.lower_cholesky)(p["u_scale_tril_unc"]), noise=p["log_noise"].exp(),
-                    phi=torch.softmax(p["phi_unc"], dim=-1), scale_mixture=fs)
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-300))
-
-
-def inputs(D, seed=1, W=16, H=9, V=20, K=4):
-    xs, ws, _ = synth_circles(W, H, V, K, seed=seed, one_d=(D == 1))
-    xs = torch.from_numpy(xs).double()
-    if D == 3:
-        xs = torch.cat([xs, torch.rand(xs.shape[0], 1, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)], 1)
-    return xs, ws
-
-
-def prod_oracle(case, learn=False, whiten=True, dtype=torch.float64, seed=1, factors=None, D=None, **kw):
+def prod_oracle(case, factors=None, D=None, **kw):
+    """The oracle starts as an RBF(0.5, 1.0) one - its initial S_k is that kernel's L_uu - and takes the factors' parameters after."""
     D0, fac = CASES[case] if case else (D, factors)
-    sizes = {k: kw.pop(k) for k in ("W", "H", "V", "K") if k in kw}
-    xs, ws = inputs(D0, seed, **sizes)
-    K = sizes.get("K", 4)
-    g = torch.Generator().manual_seed(seed + 100)
-    M = int(np.prod(NPTS[D0]))
-    Z = (0.05 + 0.9 * torch.rand(M, D0, generator=g, dtype=torch.float64)) if learn else None
-    m = ProductRef(xs, ws, factors=fac, K=K, n_points=NPTS[D0], dtype=dtype, jitter=1e-6, Z=Z, learn_inducing=learn, whiten=whiten, **kw)
-    with torch.no_grad():
-        m.params["u_loc"].add_(0.3 * torch.randn(m.params["u_loc"].shape, generator=g, dtype=torch.float64).to(dtype))
-        m.params["u_scale_tril_unc"].add_(0.1 * torch.randn(m.params["u_scale_tril_unc"].shape, generator=g, dtype=torch.float64).tril().to(dtype))
-        m.params["phi_unc"].add_(0.5 * torch.randn(m.params["phi_unc"].shape, generator=g, dtype=torch.float64).to(dtype))
-        m.params["log_noise"].add_(0.2)
-    eps = torch.randn(K, m.N, generator=g, dtype=torch.float64).to(dtype)
-    return m, eps
-
-
-def table(factors):
-    return [dict(name=name, kind=kind, active_dims=dims, lengthscales=torch.as_tensor(ls).numel(),
-                 periods=(torch.as_tensor(per).numel() if kind == "periodic" else 0)) for name, kind, dims, ls, var, per in factors]
-
-
-def prod_engine(m, factors, dtype=None, n_cap=None, **kw):
-    """gdrf_amd.Engine (product context) holding exactly the oracle's parameters, inducing points and Dirichlet prior."""
-    from gdrf_amd.engine import Engine
-    eng = Engine(n_cap or m.N, m.M, m.K, m.V, m.D, dtype=dtype or m.dtype, kernel="product", product=table(factors), jitter=m.jitter,
-                 maxjitter=m.maxjitter, process_group=None, learn_inducing=m.learn_inducing, whiten=m.whiten, **kw)
-    eng.set_inducing_points(m.Z)
-    eng.set_dirichlet(m.alpha)
-    load(eng, m)
-    return eng
-
-
-def load(eng, m):
-    for name in eng.param_names:
-        v = eng.view(name)
-        v.copy_(m.params[name].detach().to(eng.dtype).reshape(v.shape))
-
-
-def dev(t, eng, dtype=None):
-    return torch.as_tensor(t).to(device=eng.device, dtype=dtype or eng.dtype).contiguous()
-
-
-def check_grads(eng, grads_ref, tg=1e-7):
-    gv = eng.named_views(eng.grads)
-    assert set(gv) == set(grads_ref), (set(gv), set(grads_ref))
-    for name, g in gv.items():
-        assert tuple(g.shape) == tuple(grads_ref[name].shape), name
-        assert relerr(g.cpu().numpy(), grads_ref[name].numpy()) < tg, (name, relerr(g.cpu().numpy(), grads_ref[name].numpy()))
-
-
-def check_loss_and_grads(eng, m, eps, tg=1e-7, **kw):
-    xs, ws = dev(m.xs, eng), dev(m.ws, eng, torch.int32)
-    eng.loss_and_grads(xs, ws, dev(eps, eng), **kw)
-    out = eng.read_out()
-    m.force_jitter_level = eng.last_jitter_level
-    loss_ref, grads_ref = m.loss_and_grads(eps)
-    assert abs(out["loss"] - loss_ref) <= LOSS_TOL_VS_TORCH * abs(loss_ref), (out["loss"], loss_ref)
-    check_grads(eng, grads_ref, tg)
-    return grads_ref
+    return variant_oracle(D0, lambda m: m.set_factors(fac), kind="rbf", lengthscale=0.5, variance=1.0, **kw)
 
 
 @pytest.mark.parametrize("case", list(CASES))
 @pytest.mark.parametrize("learn,whiten", [(False, True), (True, True), (False, False)])
 def test_loss_and_every_gradient_fp64(case, learn, whiten):
     m, eps = prod_oracle(case, learn=learn, whiten=whiten)
-    eng = prod_engine(m, CASES[case][1])
+    eng = engine_for(m)
     assert eng.hyper_backward == "f64" and "log_variance" not in eng.param_names
     check_loss_and_grads(eng, m, eps)
 
@@ -191,17 +52,17 @@ def test_knm_against_the_formula(case):
     fac = CASES[case][1]
     with torch.no_grad():
         ref = product_matrix(m.xs, m.Z, m.factors()).numpy()
-    e64 = prod_engine(m, fac)
+    e64 = engine_for(m)
     assert relerr(e64.knm(dev(m.xs, e64)).cpu().numpy(), ref) < 1e-12
-    e32 = prod_engine(m, fac, dtype=torch.float32)
+    e32 = engine_for(m, dtype=torch.float32)
     assert relerr(e32.knm(dev(m.xs, e32)).cpu().numpy(), ref) < 2e-6
-    big = prod_engine(m, fac, n_cap=16)          # more rows than the context holds: gdrf_knm grows its scratch
+    big = engine_for(m, n_cap=16)          # more rows than the context holds: gdrf_knm grows its scratch
     assert relerr(big.knm(dev(m.xs, big)).cpu().numpy(), ref) < 1e-12
 
 
 def test_shifting_the_periodic_axis_by_one_period_leaves_knm_unchanged():
     m, _ = prod_oracle("rbf0_periodic1_2d")
-    eng = prod_engine(m, CASES["rbf0_periodic1_2d"][1])
+    eng = engine_for(m)
     g = torch.Generator().manual_seed(2)
     xs = 0.5 * torch.rand(500, 2, generator=g, dtype=torch.float64)
     k0 = eng.knm(dev(xs, eng)).cpu().numpy()
@@ -214,7 +75,7 @@ def test_shifting_the_periodic_axis_by_one_period_leaves_knm_unchanged():
 @pytest.mark.parametrize("dtype,tol", [(torch.float64, 1e-9), (torch.float32, 5e-4)])
 def test_predictive_path(case, dtype, tol):
     m, _ = prod_oracle(case, W=23, H=11, V=9, K=5)
-    eng = prod_engine(m, CASES[case][1], dtype=dtype)
+    eng = engine_for(m, dtype=dtype)
     xs, ws = dev(m.xs, eng), dev(m.ws, eng, torch.int32)
     m.force_jitter_level = eng.factorize()
     assert relerr(eng.predict(xs, 0).cpu().numpy(), m.log_topic_probs().detach().numpy()) < tol
@@ -225,14 +86,14 @@ def test_predictive_path(case, dtype, tol):
     c = m.constrained()
     with torch.no_grad():
         loc, var = go.conditional("product", m.xs, m.inducing(), None, c["variance"], c["u_loc"], c["u_scale_tril"], m._luu(c),
-                                  c["scale_mixture"], whiten=True)
+                                  whiten=True, **c["kernel_kw"])
     lv = eng.predict(xs, 4).cpu()
     assert relerr(lv[0].numpy(), loc.numpy()) < tol and relerr(lv[1].numpy(), var.numpy()) < tol
 
 
 def test_streamed_rows_form():
     m, eps = prod_oracle("rbf_ard01_periodic2_3d")
-    eng = prod_engine(m, CASES["rbf_ard01_periodic2_3d"][1], rows_form="streamed")
+    eng = engine_for(m, rows_form="streamed")
     assert eng.rows_form == "streamed"
     check_loss_and_grads(eng, m, eps)
 
@@ -248,7 +109,7 @@ def test_product_of_two_rbf_factors_is_rbf_ard():
     from gdrf_amd.engine import Engine
     fac = [("kern0", "rbf", [0], 0.6, 2.0, None), ("kern1", "rbf", [1], 0.9, 1.5, None)]
     m, eps = prod_oracle(None, factors=fac, D=2)
-    ep = prod_engine(m, fac)
+    ep = engine_for(m)
     ea = Engine(m.N, m.M, m.K, m.V, 2, dtype=torch.float64, kernel="rbf", jitter=m.jitter, maxjitter=m.maxjitter, process_group=None, ard=True)
     ea.set_inducing_points(m.Z)
     ea.set_dirichlet(m.alpha)
@@ -271,7 +132,7 @@ def test_product_of_two_periodic_factors_is_per_axis_periodic():
     from gdrf_amd.engine import Engine
     fac = [("kern0", "periodic", [0], 0.7, 2.0, 0.45), ("kern1", "periodic", [1], 1.1, 1.5, 0.6)]
     m, eps = prod_oracle(None, factors=fac, D=2)
-    ep = prod_engine(m, fac)
+    ep = engine_for(m)
     ea = Engine(m.N, m.M, m.K, m.V, 2, dtype=torch.float64, kernel="periodic", jitter=m.jitter, maxjitter=m.maxjitter, process_group=None,
                 ard=True, period_count=2)
     ea.set_inducing_points(m.Z)
@@ -293,7 +154,7 @@ def test_product_of_two_periodic_factors_is_per_axis_periodic():
 
 def test_five_adam_steps_fp64():
     m, _ = prod_oracle("rbf_ard01_periodic2_3d", optimizer="adam", lr=1e-2)
-    eng = prod_engine(m, CASES["rbf_ard01_periodic2_3d"][1])
+    eng = engine_for(m)
     xs, ws = dev(m.xs, eng), dev(m.ws, eng, torch.int32)
     g = torch.Generator().manual_seed(5)
     for step in range(5):
@@ -355,7 +216,7 @@ def test_unread_axis_gets_a_zero_inducing_gradient():
     """A lone Periodic on axis 1 of a 2-D world: the covariance ignores axis 0, so the learnable inducing inputs' axis-0 gradient is 0."""
     fac = [("", "periodic", [1], 0.8, 2.0, 0.4)]
     m, eps = prod_oracle(None, factors=fac, D=2, learn=True)
-    eng = prod_engine(m, fac)
+    eng = engine_for(m)
     assert set(eng.param_names) >= {"log_variance", "log_lengthscale", "log_period"}
     grads_ref = check_loss_and_grads(eng, m, eps)
     gz = eng.view("inducing_unc", eng.grads).cpu()
@@ -442,42 +303,17 @@ def test_optim_args_callable_sees_the_factor_names():
     assert float(p1["kern1.period"]) == float(p0["kern1.period"]) and float(p1["kern1.variance"]) != float(p0["kern1.variance"])
 
 
-def _dist_worker(rank, world, port, tmp):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)          # both ranks share the box's single GPU
+def _dist_build():
     xs, ws = _data()
     model = _model(st_kernel(), xs, ws)
-    svi = _svi(model, xs)
-    N = len(xs)
-    lo, hi = rank * N // world, (rank + 1) * N // world
-    svi.row_offset = lo
-    eng = model._engine_for(hi - lo)
-    eng.pg = None
-
-    def allreduce(buf, count, is_double, stream):
-        assert buf == eng.red_T.data_ptr() and count == eng.red_T.numel()
-        dist.all_reduce(eng.red_T)
-        return 0
-    eng.set_allreduce(allreduce)
-    losses = [svi.step(xs=xs[lo:hi], ws=ws[lo:hi], subsample=False) for _ in range(3)]
-    torch.save({"losses": losses, "params": model._engine.params.cpu()}, os.path.join(tmp, f"r{rank}.pt"))
-    dist.destroy_process_group()
+    return model, _svi(model, xs), xs, ws
 
 
 @pytest.mark.timeout(600)
 def test_two_ranks_through_the_c_abi_hook_match_a_single_rank(tmp_path):
-    import torch.multiprocessing as mp
-    port = 29700 + (os.getpid() % 2000)
-    mp.spawn(_dist_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
-    xs, ws = _data()
-    model = _model(st_kernel(), xs, ws)
-    svi = _svi(model, xs)
+    r0, r1 = run_two_ranks(_dist_build, "c_abi_hook", 29700 + (os.getpid() % 2000), tmp_path)
+    model, svi, xs, ws = _dist_build()
     ref = [svi.step(xs=xs, ws=ws, subsample=False) for _ in range(3)]
-    r0 = torch.load(tmp_path / "r0.pt", weights_only=True)
-    r1 = torch.load(tmp_path / "r1.pt", weights_only=True)
     assert r0["losses"] == r1["losses"]
     assert np.allclose(r0["losses"], ref, rtol=1e-10)
     assert torch.equal(r0["params"], r1["params"])

@@ -1,5 +1,6 @@
 """GPU: the reference's Python surface for the hot path, used the way gdrf/train_script.py uses it."""
 import copy
+import functools
 import os
 import sys
 
@@ -8,6 +9,7 @@ import pytest
 import torch
 
 from gdrf_amd.data import synth_circles
+from tests._util import run_two_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,43 +102,13 @@ def test_free_running_eps_is_reproducible_for_a_seed():
     assert a == b
 
 
-def _dist_worker(rank, world, port, tmp):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)          # both ranks share the box's single GPU
-    model, svi, _, xs, ws = _build(dtype=torch.float64)
-    N = len(xs)
-    lo, hi = rank * N // world, (rank + 1) * N // world
-    svi.row_offset = lo
-    if os.environ.get("GDRF_TEST_C_ABI_ALLREDUCE") == "1":
-        # the collective registered behind the C ABI (gdrf_set_allreduce / gdrf_payload_allreduce) instead of the engine's own
-        # torch.distributed call: what a non-Python host would do with ncclAllReduce on its RCCL communicator
-        eng = model._engine_for(hi - lo)
-        eng.pg = None
-
-        def allreduce(buf, count, is_double, stream):
-            assert buf == eng.red_T.data_ptr() and count == eng.red_T.numel() and is_double == (eng.dtype == torch.float64)
-            dist.all_reduce(eng.red_T)
-            return 0
-        eng.set_allreduce(allreduce)
-    losses = [svi.step(xs=xs[lo:hi], ws=ws[lo:hi], subsample=False) for _ in range(3)]
-    torch.save({"losses": losses, "params": model._engine.params.cpu()}, os.path.join(tmp, f"r{rank}.pt"))
-    dist.destroy_process_group()
-
-
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("via", ["torch_distributed", "c_abi_hook"])
-def test_two_ranks_on_one_gpu_match_a_single_rank(tmp_path, via, monkeypatch):
-    import torch.multiprocessing as mp
-    monkeypatch.setenv("GDRF_TEST_C_ABI_ALLREDUCE", "1" if via == "c_abi_hook" else "0")
+def test_two_ranks_on_one_gpu_match_a_single_rank(tmp_path, via):
     port = 29600 + (os.getpid() % 2000) + (7 if via == "c_abi_hook" else 0)
-    mp.spawn(_dist_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    r0, r1 = run_two_ranks(functools.partial(_build, dtype=torch.float64), via, port, tmp_path)
     model, svi, _, xs, ws = _build(dtype=torch.float64)
     ref = [svi.step(xs=xs, ws=ws, subsample=False) for _ in range(3)]
-    r0 = torch.load(tmp_path / "r0.pt", weights_only=True)
-    r1 = torch.load(tmp_path / "r1.pt", weights_only=True)
     assert r0["losses"] == r1["losses"]
     assert np.allclose(r0["losses"], ref, rtol=1e-10)                      # Philox keyed by the global row: same eps
     assert torch.equal(r0["params"], r1["params"])
@@ -203,32 +175,13 @@ def _build_lz_renyi(dtype=torch.float64):
     return model, svi, xs, ws
 
 
-def _dist_worker_lz(rank, world, port, tmp):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    model, svi, xs, ws = _build_lz_renyi()
-    N = len(xs)
-    lo, hi = rank * N // world, (rank + 1) * N // world
-    svi.row_offset = lo
-    losses = [svi.step(xs=xs[lo:hi], ws=ws[lo:hi], subsample=False) for _ in range(3)]
-    torch.save({"losses": losses, "params": model._engine.params.cpu()}, os.path.join(tmp, f"lz{rank}.pt"))
-    dist.destroy_process_group()
-
-
 @pytest.mark.timeout(600)
 def test_two_ranks_with_learnable_inducing_points_and_renyi_match_a_single_rank(tmp_path):
     """The all-reduced payload also carries the inducing-input sums, and RenyiELBO's particle weights need the particles' ELBO
     over ALL ranks: two ranks (gloo, one GPU) must reproduce the single-rank losses and parameters."""
-    import torch.multiprocessing as mp
-    port = 31600 + (os.getpid() % 2000)
-    mp.spawn(_dist_worker_lz, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    r0, r1 = run_two_ranks(_build_lz_renyi, "torch_distributed", 31600 + (os.getpid() % 2000), tmp_path)
     model, svi, xs, ws = _build_lz_renyi()
     ref = [svi.step(xs=xs, ws=ws, subsample=False) for _ in range(3)]
-    r0 = torch.load(tmp_path / "lz0.pt", weights_only=True)
-    r1 = torch.load(tmp_path / "lz1.pt", weights_only=True)
     assert r0["losses"] == r1["losses"] and torch.equal(r0["params"], r1["params"])
     assert np.allclose(r0["losses"], ref, rtol=1e-9)
     assert (r0["params"] - model._engine.params.cpu()).abs().max() < 1e-8

@@ -4,7 +4,7 @@ stand-in with the real Engine's naming and view methods over CPU buffers."""
 import pytest
 import torch
 
-from gdrf_amd.engine import Engine
+from gdrf_amd.engine import Engine, param_table
 from gdrf_amd.models.sparse_gdrf import MEAN_PREFIX, SparseMultinomialGDRF, learnable_mean_parameters
 from gdrf_amd.kernels import RBF
 from gdrf_amd.optim import Adam
@@ -35,19 +35,15 @@ def host_model(mean_function):
     """A SparseMultinomialGDRF whose engine is a CPU stand-in: the layout a context with these sizes reports, laid out by hand."""
     named = learnable_mean_parameters(mean_function)
     eng = Engine.__new__(Engine)
-    eng.K, eng.M, eng.V, eng.D, eng.ard, eng.kernel, eng.learn_inducing = K, M, V, D, False, "rbf", False
+    eng.K, eng.M, eng.V, eng.D, eng.ard, eng.kernel, eng.learn_inducing, eng.product = K, M, V, D, False, "rbf", False, None
     o_phi = 4 + K * M
     o_s = o_phi + K * V
     o_mean = o_s + K * M * M
-    eng.layout = dict(log_lengthscale=0, log_variance=1, log_noise=2, log_scale_mixture=3, u_loc=4, phi_unc=o_phi, u_scale_tril_unc=o_s)
     eng.mean_shapes = {n: p.shape for n, p in named}
     eng.mean_count = sum(p.numel() for _, p in named)
-    eng._mean_offsets, o = {}, o_mean
-    for n, p in named:
-        eng._mean_offsets[n] = o
-        o += p.numel()
-    eng.layout["mean"] = o_mean
-    total = o
+    eng.table = param_table(K, M, V, D, "rbf", mean_shapes=eng.mean_shapes, raw=dict(param=(0, 1, 2, 4, o_phi, o_s, o_mean + eng.mean_count),
+                                                                                    mean=(o_mean, eng.mean_count)))
+    total = o_mean + eng.mean_count
     eng.params, eng.grads = torch.arange(total, dtype=torch.float64), torch.zeros(total, dtype=torch.float64)
     eng.exp_avg, eng.exp_avg_sq = torch.full((total,), 0.5, dtype=torch.float64), torch.full((total,), 0.25, dtype=torch.float64)
     eng.opt_step = 7
