@@ -473,7 +473,7 @@ class Engine:
             return flat.view(self.n_cap, Mp)[:n, :self.M].clone()
         if name in ("q", "asum"):
             return flat[:n].clone()
-        if name in ("loc", "tt", "vbar", "locbar", "mu"):
+        if name in ("loc", "tt", "vbar", "locbar", "mu", "g_locbar"):
             return flat.view(self.K, ldk)[:, :n].clone()
         if name in ("Kuu", "L", "Linv", "LinvT"):
             return flat.view(Mp, Mp)[:self.M, :self.M].clone()
