@@ -65,6 +65,7 @@ SIGNATURES = {
     "gdrf_predict": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "gdrf_predict_mc": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _int, C.c_uint64, _i64, _vp, _vp, _vp, _vp]),
     "gdrf_predict_info": (_int, [_vp, _vp, _i64, _vp, _vp, _int, C.c_uint64, _i64, _vp, _vp, _vp]),
+    "gdrf_predict_quant": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _int, C.c_uint64, _i64, _vp, C.POINTER(_dbl), _int, _vp, _int, _vp, _vp]),
     "gdrf_fold_in": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp]),
     "gdrf_sample_counts": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _int, _int, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gdrf_predict_cov": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp]),
@@ -79,6 +80,7 @@ SIGNATURES = {
     "gdrf_set_timing": (_int, [_vp, _int]),
     "gdrf_get_timing": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_i64), _int]),
     "gdrf_last_forms": (_int, [_vp, C.POINTER(_int), _int]),
+    "gdrf_quant_last_plan": (_int, [_vp, C.POINTER(_int)]),
 }
 
 

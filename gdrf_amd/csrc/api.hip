@@ -11,6 +11,7 @@
 #include "predict.h"
 #include "predict_mc.h"
 #include "predict_info.h"
+#include "predict_quant.h"
 #include "foldin.h"
 #include "sample_counts.h"
 #include "predict_cov.h"
@@ -146,6 +147,7 @@ struct gdrf_ctx {
   std::vector<hipEvent_t> ev_pool;
   double t_ms[GDRF_NSLOTS]; int64_t t_cnt[GDRF_NSLOTS];
   int forms[GDRF_NFORMS];     // gdrf_last_forms: the form each shape-dispatched stage launched last (host bookkeeping, GDRF_FORM_* of gdrf_hip.h)
+  int quant_plan[3];          // gdrf_quant_last_plan: (RP, CP, LDS bytes) of the last gdrf_predict_quant launch
 };
 
 struct ScopedTimer {
@@ -577,6 +579,11 @@ int gdrf_get_rows_form(const gdrf_ctx* c) { return c->rows_form; }
 int gdrf_last_forms(const gdrf_ctx* c, int* out, int n) {
   if (!c || (n > 0 && !out)) return fail(-1, "gdrf_last_forms", "null argument");
   for (int i = 0; i < n; ++i) out[i] = i < GDRF_NFORMS ? c->forms[i] : 0;
+  return 0;
+}
+int gdrf_quant_last_plan(const gdrf_ctx* c, int out[3]) {
+  if (!c || !out) return fail(-1, "gdrf_quant_last_plan", "null argument");
+  for (int i = 0; i < 3; ++i) out[i] = c->quant_plan[i];
   return 0;
 }
 
@@ -1886,6 +1893,35 @@ template <typename T, typename TS> struct Impl {
     });
   }
 
+  // Quantile, exceedance and dominant-topic maps (predict_quant.h): the step's forward as in mode 4 of predict, then one kernel over the
+  // rows.  The quantile mode keeps the samples of CP components of RP rows in LDS per workgroup pass (forms.h::quant_plan); the counter
+  // modes take 256 / LG rows per pass and only the theta slots
+  static int predict_quant(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, int mode, int S, uint64_t seed, int64_t row_offset,
+                           const T* eps, const QuantLevels& lev, int nlev, const int32_t* words, int nwords, double* out, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    const bool use_words = nwords > 0;
+    const int C = use_words ? nwords : K;
+    return predictive_form(K, [&](auto fm) -> int {
+      using F = decltype(fm);
+      constexpr int RPB = 256 / F::LG;
+      int RP = RPB, CP = use_words ? std::min(C, F::LG * QUANT_WJ) : K, P = 1;
+      size_t lds = quant_theta_lds<T>(F::LG, F::KJ);
+      if (mode == QUANT_Q) {
+        const forms::QuantPlan pl = forms::quant_plan(K, C, S, (int)sizeof(T), F::LG);
+        RP = pl.RP; CP = pl.CP; P = pl.P; lds = pl.lds;
+      }
+      c->quant_plan[0] = RP; c->quant_plan[1] = CP; c->quant_plan[2] = (int)lds;
+      if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+      const int64_t nblk = (n + RP - 1) / RP;
+      const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
+      if (int rc = launch_lds(predict_quant_kernel<T, F::LG, F::KJ>, dim3(grid), dim3(256), lds, s, mode, n, K, V, S, (const Hyper*)c->hyp,
+                              (const T*)Impl::P(c->qpart), nct<TS>(c), (const T*)Impl::P(c->loc), (const T*)Impl::P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk,
+                              c->mean_sn, eps, seed, row_offset, (const T*)Impl::P(c->phi), words, C, use_words, nlev, lev, RP, CP, P, out)) return rc;
+      LAUNCHCHK("predict_quant");
+      return 0;
+    });
+  }
+
   // Fold-in (foldin.h): the step's forward as in mode 4 of predict, then one kernel that runs the per-row MAP from the rows' own counts -
   // dense (Phi, the counts and c in LDS) or CSR (the stored entries only, Phi from global memory); mode 3 ends in the partials' sum
   static int fold_in(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, const int64_t* crow, const int32_t* col,
@@ -2371,6 +2407,39 @@ int gdrf_predict_info(gdrf_ctx* c, const void* X, int64_t n, const void* Z, cons
   if (!out) return fail(-1, "gdrf_predict_info", "out is required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict_info, c, (const T*)X, n, (const T*)Z, (const T*)params, num_samples, seed, row_offset, (const T*)eps, out, s);
+}
+
+int gdrf_predict_quant(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, int mode, int num_samples, uint64_t seed,
+                       int64_t row_offset, const void* eps, const double* levels, int nlevels, const int32_t* words, int nwords, double* out,
+                       void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  const char* fn = "gdrf_predict_quant";
+  if (mode < QUANT_Q || mode > QUANT_DOMINANT) return fail(-1, fn, "mode");
+  if (n < 1) return fail(-1, fn, "n must be >= 1");
+  if (n > c->ncap) return fail(-1, fn, "needs n <= n_cap");
+  if (num_samples < 1) return fail(-1, fn, "num_samples must be >= 1");
+  if (mode == QUANT_Q && num_samples > GDRF_QUANT_MAX_SAMPLES) return fail(-1, fn, "the quantile mode takes at most GDRF_QUANT_MAX_SAMPLES samples");
+  if (mode != QUANT_Q && num_samples > 65535) return fail(-1, fn, "a call takes at most 65535 samples");
+  if (row_offset < 0) return fail(-1, fn, "row_offset must be >= 0");
+  if (nwords < 0 || (nwords > 0) != (words != nullptr)) return fail(-1, fn, "words_dev and nwords go together");
+  if (mode == QUANT_DOMINANT && nwords) return fail(-1, fn, "the dominant-topic mode is over topics: no words");
+  if (mode == QUANT_DOMINANT ? nlevels != 0 : (nlevels < 1 || nlevels > GDRF_QUANT_MAX_LEVELS || !levels))
+    return fail(-1, fn, "needs 1 .. GDRF_QUANT_MAX_LEVELS levels (none for the dominant-topic mode)");
+  if (!out) return fail(-1, fn, "out is required");
+  QuantLevels lev{};
+  for (int t = 0; t < nlevels; ++t) {
+    if (mode == QUANT_Q) {
+      if (!(levels[t] >= 0.0 && levels[t] <= 1.0)) return fail(-1, fn, "a quantile level must be in [0, 1]");
+      const double hh = levels[t] * (double)(num_samples - 1), lo = std::floor(hh);
+      lev.lo[t] = (int)lo; lev.v[t] = hh - lo;
+    } else {
+      if (!std::isfinite(levels[t])) return fail(-1, fn, "a threshold must be finite");
+      lev.v[t] = levels[t];
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, predict_quant, c, (const T*)X, n, (const T*)Z, (const T*)params, mode, num_samples, seed, row_offset, (const T*)eps, lev, nlevels, words,
+         nwords, out, s);
 }
 
 int gdrf_fold_in(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, const int32_t* ws, const int64_t* crow, const int32_t* col,

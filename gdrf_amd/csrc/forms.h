@@ -355,5 +355,34 @@ inline PredictPlan predict_plan(const FormShape& f) {
   return {in_lds ? PREDICT_ROWS_LDS : PREDICT_ROWS_MEM, 0, lds, lds <= LDS_ROWS};
 }
 
+// ---- gdrf_predict_quant, the quantile mode (predict_quant.h): a workgroup pass keeps the S samples of CP components of RP rows in LDS
+//   theta [256 / LG][Kp] | samples [RP][CP (P + 1) + LG],  P = S rounded up to a power of two, Kp = K rounded up to whole lanes of the group
+// within QUANT_LDS = 64 KB: two workgroups on a CU (two waves per SIMD, so one group's LDS latency in the ordering network hides behind
+// the other's draws) with a quarter of the LDS left over.  The draws are regenerated for each of the ceil(C / CP) passes and a row's
+// draws cost more than ordering all of its components, so the plan minimises the regenerated draws per row, ceil(C / CP) / RP, over
+// RP = 1 .. 256 / LG with CP the most components that fit beside RP rows (at most C); equal cost: the larger RP, which keeps more
+// groups busy in the ordering.  The comparison is in integers.  The largest unit (S = 1024 in double beside K = 128) is 12.5 KB: RP = 1, CP = 1
+// always fits.
+constexpr size_t QUANT_LDS = 64 * 1024;
+struct QuantPlan { int RP, CP, P; size_t lds; };
+inline QuantPlan quant_plan(int K, int C, int S, int esz, int LG) {
+  const int RPB = 256 / LG, Kp = (K + LG - 1) / LG * LG;
+  int P = 1;
+  while (P < S) P <<= 1;
+  const size_t theta = (size_t)RPB * Kp * esz;
+  auto lds_for = [&](int rp, int cp) { return theta + (size_t)rp * ((size_t)cp * (P + 1) + LG) * esz; };
+  QuantPlan best{0, 0, P, 0};
+  int64_t best_passes = 0;
+  for (int rp = 1; rp <= RPB; ++rp) {
+    if (lds_for(rp, 1) > QUANT_LDS) break;
+    const int64_t room = (int64_t)((QUANT_LDS - theta) / ((size_t)rp * esz)) - LG;      // elements a row may take
+    const int cp = (int)std::min<int64_t>(C, room / (P + 1));
+    const int64_t passes = (C + cp - 1) / cp;
+    if (!best.RP || passes * best.RP <= best_passes * rp) { best.RP = rp; best.CP = cp; best_passes = passes; }
+  }
+  best.lds = lds_for(best.RP, best.CP);
+  return best;
+}
+
 }  // namespace forms
 }  // namespace gdrf

@@ -77,6 +77,55 @@ def check_fold_args(num_iters, tol, n: int, V: int, ws, ws_score=None):
 INFO_NAMES = ("topic_entropy", "topic_expected_entropy", "topic_information", "word_entropy", "word_expected_entropy", "word_information")
 INFO_V_CHUNK = 128
 
+# Engine.predict_quant (gdrf_predict_quant, csrc/predict_quant.h): its modes, the most samples the quantile mode orders in LDS and the most
+# levels (quantile levels or thresholds) of a call - GDRF_QUANT_* of include/gdrf_hip.h.  The counter modes take the 65535 samples of
+# their siblings.
+QUANT_QUANTILE, QUANT_EXCEED, QUANT_DOMINANT = 0, 1, 2
+QUANT_MAX_SAMPLES = 1024
+QUANT_MAX_LEVELS = 16
+
+
+def check_quant_args(mode, num_samples, K: int, V: int, n: int, levels=None, words=None, eps=None):
+    """The argument errors of the quantile, exceedance and dominant-topic calls (Engine.predict_quant and the model methods above it),
+    raised before the device is touched: a known ``mode``; ``num_samples`` >= 1, at most QUANT_MAX_SAMPLES for quantiles and 65535
+    otherwise; an injected ``eps`` of shape (num_samples, K, n); 1 .. QUANT_MAX_LEVELS ``levels`` - quantile levels in [0, 1] or finite
+    thresholds, a scalar counts as one -, none for the dominant-topic mode; ``words`` a non-empty 1-D list of integers in [0, V), none for
+    the dominant-topic mode.  The word list is validated here and nowhere below: the library reads it on the device only.
+    Returns (num_samples, levels as a list of floats, number of words or 0)."""
+    if isinstance(mode, bool) or mode not in (QUANT_QUANTILE, QUANT_EXCEED, QUANT_DOMINANT):
+        raise ValueError(f"predict_quant: mode must be 0 (quantiles), 1 (exceedance) or 2 (dominant topic), got {mode!r}")
+    S = check_mc_args(num_samples, K, n, eps)
+    cap = QUANT_MAX_SAMPLES if mode == QUANT_QUANTILE else 65535
+    if S > cap:
+        raise ValueError(f"num_samples must be <= {cap} for this mode, got {S}")
+    lv = []
+    if mode == QUANT_DOMINANT:
+        if levels is not None:
+            raise ValueError("the dominant-topic mode takes no levels")
+        if words is not None:
+            raise ValueError("the dominant-topic mode is over topics: it takes no words")
+    else:
+        what = "quantile level" if mode == QUANT_QUANTILE else "threshold"
+        lv = [] if levels is None else [float(v) for v in torch.as_tensor(levels, dtype=torch.float64).reshape(-1)]
+        if not 1 <= len(lv) <= QUANT_MAX_LEVELS:
+            raise ValueError(f"needs between 1 and QUANT_MAX_LEVELS = {QUANT_MAX_LEVELS} {what}s, got {len(lv)}")
+        for v in lv:
+            if mode == QUANT_QUANTILE and not 0.0 <= v <= 1.0:
+                raise ValueError(f"a quantile level must be in [0, 1], got {v}")
+            if mode == QUANT_EXCEED and not math.isfinite(v):
+                raise ValueError(f"a threshold must be finite, got {v}")
+    nw = 0
+    if words is not None:
+        w = torch.as_tensor(words)
+        if w.dim() != 1 or w.numel() < 1 or w.dtype.is_floating_point or w.dtype.is_complex or w.dtype == torch.bool:
+            raise ValueError(f"words must be a non-empty 1-D list of integer word indices, got shape {tuple(w.shape)} of {w.dtype}")
+        lo, hi = int(w.min()), int(w.max())
+        if lo < 0 or hi >= V:
+            raise ValueError(f"every word index must be in [0, V = {V}), got {lo if lo < 0 else hi}")
+        nw = int(w.numel())
+    return S, lv, nw
+
+
 # The most words (V) the count sampler serves (GDRF_SC_MAX_V of include/gdrf_hip.h): a wave keeps a row's CDF, counts and p in LDS.
 SAMPLE_COUNTS_MAX_V = 4096
 
@@ -513,6 +562,13 @@ class Engine:
             if v:
                 out[slot] = self.FORM_NAMES[slot][v - 1] if slot in self.FORM_NAMES else v
         return out
+
+    def last_quant_plan(self) -> Dict[str, int]:
+        """(rows per workgroup pass, components per pass, dynamic LDS bytes) of the most recent predict_quant launch
+        (gdrf_quant_last_plan), as a dict with the keys RP, CP and lds; zeros before the first call."""
+        arr = (C.c_int * 3)()
+        _lib.check(self.lib.gdrf_quant_last_plan(self.ctx, arr), "gdrf_quant_last_plan")
+        return dict(RP=arr[0], CP=arr[1], lds=arr[2])
 
     # ---- primitives ------------------------------------------------------------------------------
     def _chk_rows(self, xs: torch.Tensor, ws: Optional[torch.Tensor] = None):
@@ -983,6 +1039,36 @@ class Engine:
             _lib.check(self.lib.gdrf_predict_info(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), S, seed,
                                                   int(row_offset), eps.data_ptr() if eps is not None else None, out.data_ptr(),
                                                   _stream_ptr(self.device)), "gdrf_predict_info")
+            return out
+
+        with self._borrowed_mean(mean, n):
+            return self._speculated(run)
+
+    def predict_quant(self, xs: torch.Tensor, mode: int, num_samples: int, levels=None, words: Optional[torch.Tensor] = None,
+                      seed: Optional[int] = None, row_offset: int = 0, eps: Optional[torch.Tensor] = None,
+                      mean: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Credible-interval, exceedance and dominant-topic maps at the rows ``xs`` (gdrf_predict_quant, csrc/predict_quant.h) over the
+        ``num_samples`` draws predict_mc makes under the same ``seed`` / ``row_offset`` / ``eps`` / ``mean``, float64: mode QUANT_QUANTILE
+        the type-7 sample quantiles at the ``levels`` (Q, n, C), QUANT_EXCEED the share of draws strictly above each threshold of
+        ``levels`` (Tn, n, C), QUANT_DOMINANT the share of draws in which each topic is the largest (n, K).  The C components are the K
+        topic proportions or, with ``words`` (an int32 index tensor on the device; may repeat, any order), the chosen entries of theta Phi.
+        n <= n_cap.  Same jitter-level protocol as predict()."""
+        S, lv, nw = check_quant_args(mode, num_samples, self.K, self.V, int(xs.shape[0]), levels, words, eps)
+        self._chk_rows(xs, None)
+        n = xs.shape[0]
+        if nw and (not torch.is_tensor(words) or words.device != self.device or words.dtype != torch.int32 or not words.is_contiguous()):
+            raise ValueError(f"words must be a contiguous int32 tensor on {self.device}")
+        seed = self._mc_seed("predict_quant", n, eps, seed)
+        self.refresh_inducing()
+        ncomp = nw if nw else self.K
+        levels_c = (C.c_double * len(lv))(*lv) if lv else None
+
+        def run():
+            out = torch.empty((n, self.K) if mode == QUANT_DOMINANT else (len(lv), n, ncomp), dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.gdrf_predict_quant(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), int(mode), S, seed,
+                                                   int(row_offset), eps.data_ptr() if eps is not None else None, levels_c, len(lv),
+                                                   words.data_ptr() if nw else None, nw, out.data_ptr(), _stream_ptr(self.device)),
+                       "gdrf_predict_quant")
             return out
 
         with self._borrowed_mean(mean, n):

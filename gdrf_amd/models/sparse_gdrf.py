@@ -15,7 +15,8 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
-from ..engine import INFO_NAMES, Engine, check_count_args, check_fold_args, check_joint_args, check_mc_args, check_select_args
+from ..engine import (INFO_NAMES, QUANT_DOMINANT, QUANT_EXCEED, QUANT_QUANTILE, Engine, check_count_args, check_fold_args, check_joint_args,
+                      check_mc_args, check_quant_args, check_select_args)
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -239,6 +240,18 @@ class ModelSnapshot:
     def most_informative(self, xs, count, criterion="word_information", num_samples=256, seed=None):
         return self.restore().most_informative(xs, count, criterion, num_samples, seed=seed)
 
+    def topic_probs_quantiles(self, xs, q=(0.05, 0.5, 0.95), num_samples=256, seed=None, eps=None):
+        return self.restore().topic_probs_quantiles(xs, q, num_samples, seed=seed, eps=eps)
+
+    def word_probs_quantiles(self, xs, q=(0.05, 0.5, 0.95), words=None, num_samples=256, seed=None, eps=None):
+        return self.restore().word_probs_quantiles(xs, q, words, num_samples, seed=seed, eps=eps)
+
+    def exceedance(self, xs, thresholds, what="topic", words=None, num_samples=256, seed=None, eps=None):
+        return self.restore().exceedance(xs, thresholds, what, words, num_samples, seed=seed, eps=eps)
+
+    def dominant_topic_probs(self, xs, num_samples=256, seed=None, eps=None):
+        return self.restore().dominant_topic_probs(xs, num_samples, seed=seed, eps=eps)
+
     def select_batch(self, xs, count, noise=None, given=None, return_variance=False):
         return self.restore().select_batch(xs, count, noise=noise, given=given, return_variance=return_variance)
 
@@ -268,6 +281,24 @@ class ModelSnapshot:
 
     def predictive_check(self, xs, ws, num_samples=200, seed=None, coherent=False):
         return self.restore().predictive_check(xs, ws, num_samples, seed=seed, coherent=coherent)
+
+
+def _all_words(V: int, words):
+    """the word list of a call: None is every word"""
+    return torch.arange(V, dtype=torch.int32) if words is None else words
+
+
+def _predict_quant(model, name: str, xs, mode: int, levels, words, num_samples, seed, eps) -> torch.Tensor:
+    """What topic_probs_quantiles, word_probs_quantiles, exceedance and dominant_topic_probs share: the link refusal, the argument checks
+    (before the device is touched), the word list as the device takes it, and Engine.predict_quant over pieces of at most the engine's
+    n_cap rows (_predict_mc)."""
+    if model._link_function is not None:
+        raise NotImplementedError(f"{name} with a custom link_function: the kernel fuses the softmax link")
+    n = int(torch.as_tensor(xs).shape[0])
+    S, lv, nw = check_quant_args(mode, num_samples, model._K, model._V, n, levels, words, eps)
+    xs_s, _ = model._prepare_inputs(xs)
+    w = torch.as_tensor(words).to(device=model.device, dtype=torch.int32).contiguous() if nw else None
+    return model._predict_mc(xs_s, ("quant", mode, lv if lv else None, w), S, seed=seed, eps=eps)
 
 
 class SparseMultinomialGDRF:
@@ -638,7 +669,7 @@ class SparseMultinomialGDRF:
 
     # ------------------------------------------------------------------ Monte-Carlo predictive path (csrc/predict_mc.h)
     def _predict_mc(self, xs_s: torch.Tensor, mode: int, S: int, ws_d=None, seed=None, eps=None) -> torch.Tensor:
-        """Engine.predict_mc (``mode`` "info": Engine.predict_info) on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows, each with its row_offset: the draws are keyed by the global row, so
+        """Engine.predict_mc (``mode`` "info": Engine.predict_info; a tuple ("quant", mode, levels, words): Engine.predict_quant) on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows, each with its row_offset: the draws are keyed by the global row, so
         the result does not depend on the piece size.  The pieces are joined along the row axis; mode 2's two sums are added."""
         n = xs_s.shape[0]
         eng = self._engine_for(min(n, MC_PIECE_ROWS))
@@ -652,11 +683,15 @@ class SparseMultinomialGDRF:
         for a in range(0, n, eng.n_cap):
             b = min(n, a + eng.n_cap)
             kw = dict(seed=seed, row_offset=a, eps=None if eps is None else eps[:, :, a:b].contiguous(), mean=None if mean is None else mean[:, a:b])
+            if isinstance(mode, tuple):                  # ("quant", mode, levels, words): Engine.predict_quant
+                parts.append(eng.predict_quant(xs_s[a:b], mode[1], S, levels=mode[2], words=mode[3], **kw))
+                continue
             parts.append(eng.predict_info(xs_s[a:b], S, **kw) if mode == "info" else
                          eng.predict_mc(xs_s[a:b], mode, S, ws=None if ws_d is None else ws_d[a:b], **kw))
         if mode == 2:
             return torch.stack(parts).sum(0)
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=2 if mode == 3 else 1)
+        rows = 2 if mode == 3 else 0 if isinstance(mode, tuple) and mode[1] == QUANT_DOMINANT else 1
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=rows)
 
     def sample_topic_probs(self, xs, num_samples, seed=None, eps=None) -> torch.Tensor:
         """(S, N, K) samples of the topic proportions under the guide's posterior: theta_s = link(mu_s), mu_s = f_loc + mean + f_var eps_s
@@ -712,6 +747,34 @@ class SparseMultinomialGDRF:
         xs_s, _ = self._prepare_inputs(xs)
         out = self._predict_mc(xs_s, "info", S, seed=seed, eps=eps)
         return dict(zip(INFO_NAMES, out))
+
+    # ------------------------------------------------------------------ credible intervals, exceedance, dominance (csrc/predict_quant.h)
+    def topic_probs_quantiles(self, xs, q=(0.05, 0.5, 0.95), num_samples: int = 256, seed=None, eps=None) -> torch.Tensor:
+        """(Q, N, K) float64 credible bands of the topic proportions: the type-7 ("linear") sample quantiles at the levels ``q`` in [0, 1]
+        (at most QUANT_MAX_LEVELS) of the ``num_samples`` <= QUANT_MAX_SAMPLES draws theta_s of sample_topic_probs (the same ``seed`` /
+        ``eps``), ordered on the device without the (S, N, K) samples ever being stored."""
+        return _predict_quant(self, "topic_probs_quantiles", xs, QUANT_QUANTILE, q, None, num_samples, seed, eps)
+
+    def word_probs_quantiles(self, xs, q=(0.05, 0.5, 0.95), words=None, num_samples: int = 256, seed=None, eps=None) -> torch.Tensor:
+        """(Q, N, W) float64 credible bands of the word probabilities p_s = theta_s Phi at the word indices ``words`` (any order, may
+        repeat; None: all V), as topic_probs_quantiles."""
+        return _predict_quant(self, "word_probs_quantiles", xs, QUANT_QUANTILE, q, _all_words(self._V, words), num_samples, seed, eps)
+
+    def exceedance(self, xs, thresholds, what: str = "topic", words=None, num_samples: int = 256, seed=None, eps=None) -> torch.Tensor:
+        """(Tn, N, C) float64: the share of the ``num_samples`` draws in which the proportion of a topic (``what`` = "topic", C = K) or the
+        probability of a word (``what`` = "word", the indices ``words``, None: all V) is strictly above each of the finite
+        ``thresholds`` (at most QUANT_MAX_LEVELS; a scalar keeps the leading axis at length 1).  Counted on the device, no sample stored."""
+        if what not in ("topic", "word"):
+            raise ValueError(f'what must be "topic" or "word", got {what!r}')
+        if what == "topic" and words is not None:
+            raise ValueError('words goes with what="word"')
+        return _predict_quant(self, "exceedance", xs, QUANT_EXCEED, thresholds, _all_words(self._V, words) if what == "word" else None,
+                                   num_samples, seed, eps)
+
+    def dominant_topic_probs(self, xs, num_samples: int = 256, seed=None, eps=None) -> torch.Tensor:
+        """(N, K) float64: the share of the ``num_samples`` draws in which each topic is the largest one at x (equal values to the
+        lower index) - the honest version of ml_topics.  Each row sums to one."""
+        return _predict_quant(self, "dominant_topic_probs", xs, QUANT_DOMINANT, None, None, num_samples, seed, eps)
 
     def most_informative(self, xs, count: int, criterion: str = "word_information", num_samples: int = 256,
                          seed=None) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -360,6 +360,34 @@ int gdrf_predict_mc(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_d
 int gdrf_predict_info(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, int num_samples, uint64_t seed,
                       int64_t row_offset, const void* eps_dev, double* out_dev, void* stream);
 
+/* Credible-interval, exceedance and dominant-topic maps (csrc/predict_quant.h): uncertainty of the field at the n new inputs in a form
+ * that can be shown.  Over the S = num_samples draws gdrf_predict_mc makes (the same mu[s][k] = f_loc[k][n] + mean[k][n] +
+ * f_var[k][n] eps[s][k][n] with f_var as the scale, theta_s = softmax(mu_s), the same eps_dev / seed / row_offset, bit for bit) a
+ * component c of a row is a topic, x_s = theta_s[c] (words_dev NULL, nwords 0: C = K), or a chosen word v = words_dev[c],
+ * x_s = sum_k theta_s[k] Phi[k][v] formed in the array precision with k ascending (C = nwords; the list is int32 on the device, may
+ * repeat and be in any order).  By mode:
+ *   GDRF_QUANT_QUANTILE  out_dev (nlevels, n, C): the type-7 ("linear") sample quantile of x_0 .. x_{S-1} at the levels q =
+ *                        levels_host[i] in [0, 1]: with h = q (S - 1), lo = floor(h), hi = min(lo + 1, S - 1), frac = h - lo (formed here,
+ *                        on the host, in double) and x_(r) the r-th order statistic, (double)x_(lo) + frac ((double)x_(hi) - (double)x_(lo)).
+ *                        1 <= num_samples <= GDRF_QUANT_MAX_SAMPLES.
+ *   GDRF_QUANT_EXCEED    out_dev (nlevels, n, C): #{s : x_s > tau} / S for the finite thresholds tau = levels_host[i], strict, the integer
+ *                        count divided once in double.  1 <= num_samples <= 65535.
+ *   GDRF_QUANT_DOMINANT  out_dev (n, K): #{s : argmax_k theta_s = k} / S, equal values to the lower topic; topics only (nwords 0) and
+ *                        nlevels 0.  1 <= num_samples <= 65535.
+ * 1 <= nlevels <= GDRF_QUANT_MAX_LEVELS for the first two modes.  No V and no K the context supports is refused.  The entries of
+ * words_dev must lie in [0, V): the library does not read the list on the host, the Python layer (engine.check_quant_args) validates it
+ * before the call.  n <= n_cap.  Runs the step's forward (as mode 4 of gdrf_predict), so it overwrites the same workspaces; every step
+ * recomputes them.  Every output is bit-identical however the rows are batched (no atomics, nothing shared between rows).  Needs
+ * gdrf_factorize().  gdrf_quant_last_plan: (rows per workgroup pass RP, components per pass CP, dynamic LDS bytes) of the last call's
+ * launch - the quantile mode's plan is csrc/forms.h::quant_plan. */
+#define GDRF_QUANT_MAX_SAMPLES 1024
+#define GDRF_QUANT_MAX_LEVELS 16
+enum { GDRF_QUANT_QUANTILE = 0, GDRF_QUANT_EXCEED = 1, GDRF_QUANT_DOMINANT = 2 };
+int gdrf_predict_quant(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, int mode, int num_samples,
+                       uint64_t seed, int64_t row_offset, const void* eps_dev, const double* levels_host, int nlevels,
+                       const int32_t* words_dev, int nwords, double* out_dev, void* stream);
+int gdrf_quant_last_plan(const gdrf_ctx* ctx, int out[3]);
+
 /* Fold-in (csrc/foldin.h): the topic proportions of OBSERVED rows from their own counts, with the GP as the prior.  For row n, with
  *   m_k = f_loc[k][n] + mean[k][n],  s_k = f_var[k][n] + noise   ((f_loc, f_var) as mode 4 of gdrf_predict gives them; s_k is the scale of the
  *   model's mu site, Normal(f_loc, f_var + noise), gdrf/models/sparse_gdrf.py:354-357),  R = sum_v w_v,  theta = softmax(mu),  p = theta Phi:
