@@ -44,7 +44,8 @@ static_assert(F::F_VEC == sizeof(Vec16<float>::type) && F::F_VEC == sizeof(Vec16
 static_assert(F::F_RATIONALQUADRATIC == GDRF_RATIONALQUADRATIC && 128 / sizeof(float) == TNCfg<float>::BR && 128 / sizeof(double) == TNCfg<double>::BR, "forms.h");
 static_assert(NTCfg<float>::CW == 128 && NTCfg<double>::CW == 64, "forms.h: FormShape::nct_solve, loc_plan");
 static_assert(F::WBAR_LAST == 7 && F::AK_LAST == 4 && F::FWD_T_LAST == 4 && F::LOC_LAST == 3 && F::ROWS_LAST == 3 && F::GT_LAST == 2 && F::HYPER_LAST == 2 &&
-              F::PREDICT_LAST == 5, "the form codes of include/gdrf_hip.h");
+              F::PREDICT_LAST == 5 && F::MM_LAST == 2, "the form codes of include/gdrf_hip.h");
+static_assert(F::mm_bk(4) == NTCfg<float>::BK && F::mm_bk(8) == NTCfg<double>::BK, "forms.h: mm_plan");
 
 static thread_local std::string g_err;
 static int fail(int code, const char* what, const char* detail) {
@@ -284,7 +285,7 @@ static F::FormShape form_shape(const gdrf_ctx* c, int64_t n, int predict_mode = 
   f.esz = (int)c->esz; f.ssz = (int)c->ssz; f.split = c->split; f.stored_t = c->Tst != nullptr;
   f.rows_form = c->rows_form; f.csr = c->csr_crow != nullptr;
   f.hyper_tn = c->hyper_tn; f.learn_z = c->learn_z; f.ard = c->ard; f.per = c->per; f.kind = c->kind;
-  f.nsplit_cap = c->nsplit_cap; f.erows_grid_cap = c->erows_grid_cap; f.predict_mode = predict_mode;
+  f.nsplit_cap = c->nsplit_cap; f.erows_grid_cap = c->erows_grid_cap; f.predict_mode = predict_mode; f.unwhitened = c->unwhitened;
   return f;
 }
 static bool hyper_tn_on(const gdrf_ctx* c) { return F::hyper_tn_on(form_shape(c, 0)); }
@@ -334,7 +335,7 @@ int gdrf_ctx_create_ex(gdrf_ctx** out, int device, int64_t n_cap, int M, int K, 
   auto A = [&](auto** p, size_t bytes) { return ctx_alloc(c, p, bytes ? bytes : 16, "hipMalloc"); };
 #define AL(ptr, bytes) if (int rc = A(&(ptr), (bytes))) { gdrf_ctx_destroy(c); return rc; }
   AL(c->Kuu, mms) AL(c->Lw, mms) AL(c->Lo, mms)
-  c->mmslab_bytes = 8 * mms;
+  c->mmslab_bytes = F::mm_slab_bytes(c->Mp, (int)c->ssz);
   AL(c->snap, (size_t)(4 + (size_t)c->M * D + (c->prod ? 3 : 1) * GDRF_DMAX) * c->esz)
   AL(c->mmslab, c->mmslab_bytes) AL(c->L, mms) AL(c->LT, mms) AL(c->Linv, mms) AL(c->LinvT, mms)
   AL(c->Dinv, (size_t)(c->Mp / 32) * 1024 * c->ssz)
@@ -750,22 +751,21 @@ template <typename T, typename TS> struct Impl {
   // column tiles of the NT core for element type E (128 wide for f32, 64 for f64); row tiles are always 128
   template <typename E> static int nct(const gdrf_ctx* c) { return (c->Mp + NTCfg<E>::CW - 1) / NTCfg<E>::CW; }
 
+  // C = alpha A B^T on M x M operands, `batch` of them.  The plan (forms.h: mm_plan) splits the reduction of a single product over slices
+  // into the context's one slab buffer, added in a fixed order; `beside_chain`: the product runs on the side stream while the Cholesky-backward
+  // chain uses that buffer on the main one, and is launched directly.  `slot`: the slot of gdrf_last_forms that reports the form, or -1.
   template <typename E>
   static int mm_nt(gdrf_ctx* c, const E* A, int64_t abs_, const E* Bt, int64_t bbs, E* Cm, int64_t cbs, E alpha, int batch,
-                   hipStream_t s) {
-    // a single M x M product is 16 workgroups of the NT core (45 us at M = 512 in double, four of them in a row in every step's
-    // Cholesky backward), a batch of K = 10 is 160 (one per CU for the whole reduction): the reduction is split over S slices into
-    // slabs, which are added in double in a fixed order.  S: 8 for a single product, 4 for small batches.
+                   hipStream_t s, bool beside_chain = false, int slot = -1) {
     const int64_t mm = (int64_t)c->Mp * c->Mp;
     const int tiles = c->nt * nct<E>(c);
-    const int S = batch == 1 ? 8 : 4, kw = c->Mp / S;
-    // (batches: measured SLOWER - 160 workgroups already fill most CUs and the slab sum of K matrices costs more than the split saves)
-    if (batch == 1 && c->mmslab && tiles * batch <= 256 && c->Mp >= 256 && c->Mp % S == 0 && kw % NTCfg<E>::BK == 0 &&
-        (size_t)S * batch * mm * sizeof(E) <= c->mmslab_bytes) {
-      MMProb<E> p{{}, {}, {}, A, abs_, Bt, bbs, (E*)c->mmslab, mm, c->Mp, alpha, kw, batch};
-      dim3 grid(tiles, S * batch);
+    const F::MmPlan pl = F::mm_plan(c->Mp, (int)sizeof(E), batch, tiles, c->mmslab ? c->mmslab_bytes : 0, beside_chain);
+    if (slot >= 0) c->forms[slot] = pl.form;
+    if (pl.split()) {
+      MMProb<E> p{{}, {}, {}, A, abs_, Bt, bbs, (E*)c->mmslab, mm, c->Mp, alpha, pl.kw, batch};
+      dim3 grid(tiles, pl.S * batch);
       hipLaunchKernelGGL((gemm_nt_kernel<E, MMProb<E>>), grid, dim3(256), NTCfg<E>::LDS_BYTES, s, p);
-      hipLaunchKernelGGL(reduce_slabs_kernel<E>, dim3((c->Mp + 255) / 256, c->Mp, batch), dim3(256), 0, s, (const E*)c->mmslab, S, batch, c->Mp, 0, Cm, GDRF_TILE / 2);
+      hipLaunchKernelGGL(reduce_slabs_kernel<E>, dim3((c->Mp + 255) / 256, c->Mp, batch), dim3(256), 0, s, (const E*)c->mmslab, pl.S, batch, c->Mp, 0, Cm, GDRF_TILE / 2);
       LAUNCHCHK("mm_nt split-K");
       return 0;
     }
@@ -1680,14 +1680,14 @@ template <typename T, typename TS> struct Impl {
     if (sbar_aside) {
       HIPCHK(hipEventRecord(c->ev_fork, s));
       HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-      if ((rc = mm_nt<T>(c, Ak, mm, P(c->ST), mm, P(c->Sbar), mm, T(2), K, c->side))) return rc;
+      if ((rc = mm_nt<T>(c, Ak, mm, P(c->ST), mm, P(c->Sbar), mm, T(2), K, c->side, true, GDRF_FORM_MM_SBAR))) return rc;
       hipLaunchKernelGGL(grad_s_kernel<T>, g3, dim3(256), 0, c->side, P(c->Sbar), P(c->S), M, Mp, -1.0 / n_global, grads + pl.S);
       HIPCHK(hipEventRecord(c->ev_join, c->side));
     }
     // Cholesky / inverse backward in the solve precision
     hipLaunchKernelGGL((cast_kernel<T, TS>), dim3((unsigned)((mm + 255) / 256)), dim3(256), 0, s, mm, GT, Q(c->GTs));
     // HT = GT Linv ; LbarT = -triu(HT)
-    if ((rc = mm_nt<TS>(c, Q(c->GTs), 0, Q(c->LinvT), 0, Q(c->t0), 0, TS(1), 1, s))) return rc;
+    if ((rc = mm_nt<TS>(c, Q(c->GTs), 0, Q(c->LinvT), 0, Q(c->t0), 0, TS(1), 1, s, false, GDRF_FORM_MM_CHAIN))) return rc;
     if (c->unwhitened) {
       // Sbar'^T = 2 S'^T A_k (A_k symmetric) -> Sbar = L^-T Sbar' -> P_k = S'_k Sbar_k^T ; ubar = L^-T ubar' ; HT += sum_k (P_k + u'_k ubar_k^T)
       if ((rc = mm_nt<T>(c, P(c->ST), mm, Ak, mm, P(c->Sbar), mm, T(2), K, s))) return rc;
@@ -1731,7 +1731,7 @@ template <typename T, typename TS> struct Impl {
     if (sbar_aside) {
       HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
     } else {
-      if ((rc = mm_nt<T>(c, Ak, mm, P(c->ST), mm, P(c->Sbar), mm, T(2), K, s))) return rc;
+      if ((rc = mm_nt<T>(c, Ak, mm, P(c->ST), mm, P(c->Sbar), mm, T(2), K, s, false, GDRF_FORM_MM_SBAR))) return rc;
       hipLaunchKernelGGL(grad_s_kernel<T>, g3, dim3(256), 0, s, P(c->Sbar), P(c->S), M, Mp, -1.0 / n_global, grads + pl.S);
     }
     hipLaunchKernelGGL(grad_small_kernel<T>, dim3(1), dim3(256), 0, s, M, Mp, K, V, c->hyp, redd, c->dsmall, ubar, phib, P(c->phi),

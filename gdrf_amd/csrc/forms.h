@@ -37,6 +37,7 @@ enum LocForm { LOC_NONE = 0, LOC_ROWS, LOC_GEMM_NT, LOC_GEMM_NT_WIDE, LOC_LAST =
 enum RowsForm { ROWS_NONE = 0, ROWS_MFMA, ROWS_THREAD, ROWS_STREAMED, ROWS_LAST = ROWS_STREAMED };
 enum GtForm { GT_NONE = 0, GT_GEMM_TN, GT_TN_SPLIT, GT_LAST = GT_TN_SPLIT };
 enum HyperForm { HYPER_NONE = 0, HYPER_F64, HYPER_TN, HYPER_LAST = HYPER_TN };
+enum MmForm { MM_NONE = 0, MM_DIRECT, MM_SPLIT8, MM_LAST = MM_SPLIT8 };
 enum PredictForm { PREDICT_NONE = 0, PREDICT_MFMA, PREDICT_ROWS_LDS, PREDICT_ROWS_MEM, PREDICT_ROWS_BIGK, PREDICT_STREAMED, PREDICT_LAST = PREDICT_STREAMED };
 
 // what the rules read of a context and a call
@@ -52,6 +53,7 @@ struct FormShape {
   int nsplit_cap = 0;            // splits the slab buffer has room for (nsplit_cap_rule)
   int64_t erows_grid_cap = 1024; // workgroups the LDS row forms' Phi-bar partials have room for
   int predict_mode = 0;          // gdrf_predict's mode
+  bool unwhitened = false;       // the guide's u in the unwhitened form: Sbar chained through L^-T on the main stream
 
   int nt() const { return (Mp + F_TILE - 1) / F_TILE; }          // 128-wide tiles over Mp
   int64_t rtiles() const { return (n + F_TILE - 1) / F_TILE; }   // 128-row tiles of the call
@@ -327,6 +329,29 @@ inline RowsPlan rows_plan(const FormShape& f) {
   p.egrid = (int)std::min<int64_t>((f.n + RB - 1) / RB, f.erows_grid_cap);
   return p;
 }
+
+// ---- the small M x M products (Impl::mm_nt).  A single product is 16 workgroups of the NT core (45 us at M = 512 in double, four of them in a
+// row in every step's Cholesky backward): its reduction is split over 8 slices into the context's ONE slab buffer, which reduce_slabs adds
+// in a fixed order.  A batch is launched directly (measured SLOWER split: 160 workgroups at K = 10 already fill most CUs and the slab sum
+// of K matrices costs more than the split saves).  K = 1 makes every batched product a single one, and step_finish runs Sbar_k = 2 A_k S_k
+// on the side stream BESIDE the Cholesky-backward chain: a product beside the chain never takes the slab the chain's products write
+// (`beside_chain`: direct; it hides behind four dependent products).
+constexpr int MM_S = 8;                  // slices of a split product
+constexpr int mm_bk(int esz) { return 128 / esz; }                                        // NTCfg<E>::BK: 32 (f32) / 16 (f64)
+inline int mm_tiles(int Mp, int esz) { const int cw = esz == 4 ? 128 : 64; return ((Mp + F_TILE - 1) / F_TILE) * ((Mp + cw - 1) / cw); }
+inline size_t mm_slab_bytes(int Mp, int ssz) { return (size_t)MM_S * Mp * Mp * ssz; }   // [slices][Mp][Mp] in the solve precision
+struct MmPlan { MmForm form; int S, kw; bool split() const { return form == MM_SPLIT8; } };      // S slices of kw reduction indices each; direct: 1, 0
+inline MmPlan mm_plan(int Mp, int esz, int batch, int tiles, size_t slab_bytes, bool beside_chain) {
+  const int kw = Mp / MM_S;
+  if (!beside_chain && batch == 1 && tiles <= 256 && Mp >= 256 && Mp % MM_S == 0 && kw % mm_bk(esz) == 0 &&
+      (size_t)MM_S * Mp * Mp * esz <= slab_bytes)
+    return {MM_SPLIT8, MM_S, kw};
+  return {MM_DIRECT, 1, 0};
+}
+// step_finish's two kinds of M x M product: the Cholesky-backward chain's single products in the solve precision, and Sbar_k = 2 A_k S_k in the
+// arrays' (whitened: beside the chain, on the side stream; unwhitened: on the main stream, alone)
+inline MmPlan mm_chain_plan(const FormShape& f) { return mm_plan(f.Mp, f.ssz, 1, mm_tiles(f.Mp, f.ssz), mm_slab_bytes(f.Mp, f.ssz), false); }
+inline MmPlan mm_sbar_plan(const FormShape& f) { return mm_plan(f.Mp, f.esz, f.K, mm_tiles(f.Mp, f.esz), mm_slab_bytes(f.Mp, f.ssz), !f.unwhitened); }
 
 // ---- gdrf_predict modes 0-3 (mode 4 runs the step's forward: no form of its own)
 struct PredictPlan { PredictForm form; int NB; size_t lds; bool fits; };

@@ -546,10 +546,11 @@ class Engine:
 
     # gdrf_last_forms slots (include/gdrf_hip.h) and the names of their codes; the slots without names are counts
     FORM_SLOTS = ("wbar", "wbar_nslice", "a_k", "a_k_kgroups", "fwd_t", "fwd_t_kg", "loc", "ubar_q4", "rows", "rows_kt", "rows_vt", "gt",
-                  "hyper", "predict", "predict_nb")
+                  "hyper", "predict", "predict_nb", "mm_chain", "mm_sbar")
     FORM_NAMES = dict(wbar=("gemm_nt", "gemm_nt_t", "split<1>", "split<2>", "split_cc", "k64", "w1"), a_k=("gemm_tn", "tn_split", "tn_topics", "w2"),
                       fwd_t=("gemm_nt", "q4", "cc", "w1"), loc=("rows", "gemm_nt", "gemm_nt_wide"), rows=("mfma", "thread", "streamed"),
-                      gt=("gemm_tn", "tn_split"), hyper=("f64", "tn"), predict=("mfma", "rows_lds", "rows_mem", "rows_bigk", "streamed"))
+                      gt=("gemm_tn", "tn_split"), hyper=("f64", "tn"), predict=("mfma", "rows_lds", "rows_mem", "rows_bigk", "streamed"),
+                      mm_chain=("direct", "split8"), mm_sbar=("direct", "split8"))
 
     def last_forms(self) -> Dict[str, object]:
         """The kernel form each stage that the library picks from K, Mp or n launched in the most recent call that ran it

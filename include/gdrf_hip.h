@@ -540,10 +540,14 @@ int gdrf_get_timing(gdrf_ctx* ctx, double* ms_out, int64_t* count_out, int nslot
  *   GDRF_FORM_PREDICT      gdrf_predict modes 0-3: 1 predict_mfma, 2 predict_rows with the coefficients in LDS, 3 predict_rows reading them
  *                          from memory, 4 predict_rows_bigk (K > 32), 5 the streamed route (row form 1, or mode 3 on a bound CSR matrix);
  *                          mode 4 runs the step's forward and leaves both slots as they are
- *   GDRF_FORM_PREDICT_NB   16-topic column blocks of predict_mfma (0 for the others) */
+ *   GDRF_FORM_PREDICT_NB   16-topic column blocks of predict_mfma (0 for the others)
+ *   GDRF_FORM_MM_CHAIN     the single M x M products of step_finish's Cholesky backward (solve precision): 1 one launch of the NT core,
+ *                          2 the reduction split over 8 slices into the context's slab buffer and summed in a fixed order
+ *   GDRF_FORM_MM_SBAR      Sbar_k = 2 A_k S_k of step_finish (array precision), the same codes: always 1 for K >= 2, and always 1 in the
+ *                          whitened form, where it runs on the side stream beside the chain and must not share the chain's slab buffer */
 enum { GDRF_FORM_WBAR = 0, GDRF_FORM_WBAR_NSLICE, GDRF_FORM_AK, GDRF_FORM_AK_KGROUPS, GDRF_FORM_FWD_T, GDRF_FORM_FWD_T_KG, GDRF_FORM_LOC,
        GDRF_FORM_UBAR_Q4, GDRF_FORM_ROWS, GDRF_FORM_ROWS_KT, GDRF_FORM_ROWS_VT, GDRF_FORM_GT, GDRF_FORM_HYPER, GDRF_FORM_PREDICT,
-       GDRF_FORM_PREDICT_NB, GDRF_NFORMS };
+       GDRF_FORM_PREDICT_NB, GDRF_FORM_MM_CHAIN, GDRF_FORM_MM_SBAR, GDRF_NFORMS };
 int gdrf_last_forms(const gdrf_ctx* ctx, int* out, int n);
 
 #ifdef __cplusplus

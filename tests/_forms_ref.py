@@ -4,9 +4,13 @@
 It was written from the launch code as it stood before the rules moved into forms.h, condition for condition and in that code's nesting, so
 that tests/test_forms_host.py compares two statements of the rules that do not share a line: this one and the table that
 tests/host/forms_table.cpp prints from forms.h.  ``forms(shape)`` gives, for a fresh context after one step on n rows and one
-gdrf_predict(predict_mode) on n rows, the 15 slots by Engine.FORM_SLOTS' names as numbers (0: the stage did not run, or refused the shape)
+gdrf_predict(predict_mode) on n rows, the 17 slots by Engine.FORM_SLOTS' names as numbers (0: the stage did not run, or refused the shape)
 and the split counts of A_k (ns, nst, ns1), G^T (gt_ns) and the hyper-TN form (hyper_ns).  ``resolve`` turns Engine's keywords into a shape
 the way Engine.__init__ and gdrf_ctx_create_ex do.
+
+``mm_plan`` (the M x M products of step_finish, slots mm_chain and mm_sbar) was written from Impl::mm_nt's own condition; ``mm_plan_old`` keeps
+the rule as it stood while Sbar_k = 2 A_k S_k could share the slab buffer with the Cholesky-backward chain (a single product splits,
+whichever stream it runs on), as the simulated fault of tests/test_forms_host.py.
 """
 import functools
 import math
@@ -18,7 +22,7 @@ FWD_T_W1_KGP = 2
 KB = 1024
 KINDS = ("rbf", "matern52", "matern32", "exponential", "rationalquadratic")
 FIELDS = ("n", "n_cap", "M", "K", "V", "D", "esz", "ssz", "split", "stored_t", "rows_form", "csr", "hyper_tn", "learn_z", "ard", "per", "kind",
-          "predict_mode")
+          "predict_mode", "unwhitened")
 EXTRA = ("ns", "nst", "ns1", "gt_ns", "hyper_ns")
 
 
@@ -210,6 +214,37 @@ def _predict(s):
     return (2 if in_lds else 3), 0
 
 
+def mm_plan(Mp, esz, batch, tiles, slab_bytes, beside_chain):
+    """(form, slices, reduction indices per slice) of C = A B^T on `batch` M x M operands of esz-byte elements: 1 one launch, 2 the reduction
+    of a SINGLE product in eight slices through the context's slab buffer - never for a product that runs beside the chain that uses it"""
+    if beside_chain:
+        return 1, 1, 0
+    return mm_plan_old(Mp, esz, batch, tiles, slab_bytes)
+
+
+def mm_plan_old(Mp, esz, batch, tiles, slab_bytes, beside_chain=False):
+    """The rule before `beside_chain` was read: batch == 1 alone selects the split"""
+    S = 8 if batch == 1 else 4
+    kw = Mp // S
+    BK = 32 if esz == 4 else 16
+    if batch == 1 and slab_bytes and tiles * batch <= 256 and Mp >= 256 and Mp % S == 0 and kw % BK == 0 and S * batch * Mp * Mp * esz <= slab_bytes:
+        return 2, S, kw
+    return 1, 1, 0
+
+
+def mm_tiles(Mp, esz):
+    return cdiv(Mp, TILE) * cdiv(Mp, 128 if esz == 4 else 64)
+
+
+def mm_forms(Mp, esz, ssz, K, unwhitened, plan=None):
+    """(mm_chain, mm_sbar) of step_finish: the chain's single products in the solve precision on the main stream; Sbar_k = 2 A_k S_k, K products in
+    the arrays' precision, beside the chain on the side stream in the whitened form and alone on the main stream in the unwhitened one.
+    `plan`: the rule, mm_plan unless given."""
+    plan = plan or mm_plan
+    slab = 8 * Mp * Mp * ssz
+    return plan(Mp, ssz, 1, mm_tiles(Mp, ssz), slab, False)[0], plan(Mp, esz, K, mm_tiles(Mp, esz), slab, not unwhitened)[0]
+
+
 def forms(s):
     """The slots (by Engine.FORM_SLOTS' names, numbers) and the split counts EXTRA of a shape: a dict with the keys FIELDS."""
     n, K, esz = s["n"], s["K"], s["esz"]
@@ -230,11 +265,12 @@ def forms(s):
     out["hyper"] = 2 if tn else 1
     out["hyper_ns"] = min(tn_nsplit_gt(K, nt, n, BR), cap) if tn else 0
     out["predict"], out["predict_nb"] = _predict(s)
+    out["mm_chain"], out["mm_sbar"] = mm_forms(Mp, esz, s["ssz"], K, s["unwhitened"])
     return out
 
 
 def resolve(n, M, K, V, D=2, *, n_cap=None, dtype="f32", pure_fp32=False, store_t="auto", mfma_mode="auto", hyper_backward="auto",
-            rows_form="auto", csr=False, learn_inducing=False, ard=False, kind="rbf", predict_mode=0):
+            rows_form="auto", csr=False, learn_inducing=False, ard=False, kind="rbf", predict_mode=0, whiten=True):
     """Engine's keywords -> a shape, as Engine.__init__ and gdrf_ctx_create_ex resolve them: n_cap defaults to n, store_t "auto" is off,
     mfma_mode "auto" is f32 for float64 arrays or a stored T_k, bf16x6 for the all-fp32 arithmetic, f16x3 otherwise."""
     esz = 8 if dtype == "f64" else 4
@@ -245,7 +281,7 @@ def resolve(n, M, K, V, D=2, *, n_cap=None, dtype="f32", pure_fp32=False, store_
         mfma_mode = "f32" if (esz != 4 or stored_t) else ("bf16x6" if pure else "f16x3")
     return dict(n=n, n_cap=n_cap or n, M=M, K=K, V=V, D=D, esz=esz, ssz=ssz, split={"f32": 0, "bf16x6": 1, "f16x3": 2}[mfma_mode],
                 stored_t=int(stored_t), rows_form=int(rows_form == "streamed"), csr=int(csr), hyper_tn=int(hyper_backward == "tn"),
-                learn_z=int(learn_inducing), ard=int(ard), per=0, kind=KINDS.index(kind), predict_mode=predict_mode)
+                learn_z=int(learn_inducing), ard=int(ard), per=0, kind=KINDS.index(kind), predict_mode=predict_mode, unwhitened=int(not whiten))
 
 
 def line(s):

@@ -1,11 +1,15 @@
 """CPU: the rules that pick a kernel form per stage (gdrf_amd/csrc/forms.h), checked without a GPU through the stand-alone table program
 tests/host/forms_table.cpp, built once per session with the host compiler.
 
-1. Every case of the four GPU form tests (their own tables: SHAPES of test_gpu_wbar_w1 and test_gpu_fwd_t_w1, CASES of test_gpu_topic_forms,
-   GROUPS of _predict_ref) still reaches the form it asserts on the GPU, so a change of a threshold shows here and not only on a GPU.
+1. Every case of the five GPU form tests (their own tables: SHAPES of test_gpu_wbar_w1 and test_gpu_fwd_t_w1, CASES of test_gpu_topic_forms,
+   GROUPS of _predict_ref, A_CASES and B_CASES of test_gpu_finish_k1) still reaches the form it asserts on the GPU, so a change of a
+   threshold shows here and not only on a GPU.
 2. A sweep with both sides of every threshold against tests/_forms_ref.py, an independent Python statement of the rules: every slot and the
    split counts of A_k, G^T and the hyper-TN form.
-3. The highest code of each named slot is the number of names Engine.FORM_NAMES has for it."""
+3. The highest code of each named slot is the number of names Engine.FORM_NAMES has for it.
+4. The M x M products of step_finish (mm_plan; slots mm_chain and mm_sbar): the table against the restatement, the edges of the split-K gate,
+   and the invariant that Sbar_k = 2 A_k S_k, which the whitened form runs on the side stream beside the Cholesky-backward chain, never
+   goes through the slab buffer the chain's products go through - with the old rule kept as a simulated fault that the invariant catches."""
 import itertools
 import os
 import random
@@ -48,8 +52,13 @@ def _named(row):
 
 def _gpu_cases():
     """(id, shape, forms the GPU test asserts, slots it asserts to be unset)"""
-    from tests import test_gpu_fwd_t_w1, test_gpu_topic_forms, test_gpu_wbar_w1
+    from tests import test_gpu_finish_k1, test_gpu_fwd_t_w1, test_gpu_topic_forms, test_gpu_wbar_w1
     cases = []
+    fk = test_gpu_finish_k1                            # engine_from_oracle of make_oracle(W=25, H=16, V=12): n = 400, M = Mp
+    for Mp, K, arrays, whiten in ([(Mp, K, a, w) for Mp, K in fk.A_CASES for a in ("f32", "f64") for w in (True, False)]
+                                  + [(Mp, 1, a, w) for Mp, a, w in fk.B_CASES]):
+        s = FR.resolve(400, Mp, K, 12, dtype="f64" if arrays == "f64" else "f32", pure_fp32=arrays == "pure", whiten=whiten)
+        cases.append((f"finish_k1:Mp{Mp}:K{K}:{arrays}:{whiten}", s, fk._want_forms(Mp, K, arrays, whiten), ()))
     for mod, want in ((test_gpu_wbar_w1, lambda K: dict(wbar="w1", wbar_nslice=1)),
                       (test_gpu_fwd_t_w1, lambda K: dict(fwd_t="w1", fwd_t_kg=4 if K >= 4 else 2 * min(2, (K + 1) // 2)))):
         for name, kw in mod.SHAPES.items():         # make_oracle(V=12, **kw) and engine_from_oracle(m, mfma_mode="f16x3", store_t=False, n_cap=n_cap)
@@ -103,7 +112,7 @@ def _sweep():
         return dict(n=n, n_cap=n * rng.choice((1, 2)), M=Mp - rng.choice((0, 0, 5, 31)), K=K, V=V, D=rng.choice((1, 2, 3, 4)), esz=esz, ssz=ssz,
                     split=split, stored_t=stored_t, rows_form=rows_form, csr=int(rng.random() < 0.1), hyper_tn=rng.choice((0, 1)),
                     learn_z=int(rng.random() < 0.1), ard=int(rng.random() < 0.1), per=int(rng.random() < 0.1), kind=rng.choice(range(5)),
-                    predict_mode=mode)
+                    predict_mode=mode, unwhitened=(K + Mp // 32 + len(shapes)) % 3 == 0)      # no draw: the shapes of the sweep stay the ones they were
 
     for K, Mp, n in itertools.product(KS, MPS, NS):          # the split arithmetics, whose forms depend on all three, and one of the others
         for arith in ("f16x3", "bf16x6", rng.choice(("f32", "all-fp32", "f64", "stored-T"))):
@@ -135,3 +144,70 @@ def test_the_table_agrees_with_the_python_restatement_on_both_sides_of_every_thr
 def test_the_highest_code_of_each_slot_is_the_number_of_its_names(table):
     out = subprocess.run([table, "max"], capture_output=True, text=True, check=True).stdout.split()
     assert dict(zip(out[::2], map(int, out[1::2]))) == {slot: len(names) for slot, names in Engine.FORM_NAMES.items()}
+
+
+# ---- the M x M products of step_finish ---------------------------------------------------------------------------------------------------
+
+MM_MPS = list(range(32, 1025, 32))
+MM_ARRAYS = {"F32": (4, 8), "F64": (8, 8), "PURE": (4, 4)}       # (esz of the arrays, ssz of the solve)
+DIRECT, SPLIT8 = 1, 2
+
+
+def _mm(table, cases):
+    """mm_plan of the program for (Mp, esz, ssz, batch, beside_chain) cases: (form, slices, reduction indices per slice) each"""
+    out = subprocess.run([table, "mm"], input="".join("%d %d %d %d %d\n" % c for c in cases), capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(cases)
+    return [tuple(map(int, row.split())) for row in out]
+
+
+def test_mm_plan_against_the_restatement_and_at_the_edges_of_its_gate(table):
+    cases = [(Mp, esz, ssz, batch, beside) for Mp in MM_MPS for esz, ssz in ((4, 4), (4, 8), (8, 8)) for batch in (1, 2, 4, 10, 128) for beside in (0, 1)]
+    got = dict(zip(cases, _mm(table, cases)))
+    bad = {c: (g, FR.mm_plan(c[0], c[1], c[3], FR.mm_tiles(c[0], c[1]), 8 * c[0] * c[0] * c[2], bool(c[4]))) for c, g in got.items()}
+    bad = {c: v for c, v in bad.items() if v[0] != v[1]}
+    assert not bad, (len(bad), list(bad.items())[:5])
+    split = lambda Mp, esz, batch=1, beside=0: got[(Mp, esz, 8, batch, beside)]
+    # float: eight slices of whole 32-deep chunks - Mp a multiple of 256
+    assert [Mp for Mp in MM_MPS if split(Mp, 4)[0] == SPLIT8] == [256, 512, 768, 1024]
+    assert split(256, 4) == (SPLIT8, 8, 32) and split(512, 4) == (SPLIT8, 8, 64)
+    assert all(split(Mp, 4) == (DIRECT, 1, 0) for Mp in (224, 288, 384))
+    # double: 16-deep chunks - every multiple of 128 from 256
+    assert [Mp for Mp in MM_MPS if split(Mp, 8)[0] == SPLIT8] == list(range(256, 1025, 128))
+    assert split(256, 8) == (SPLIT8, 8, 32) and split(384, 8) == (SPLIT8, 8, 48) and split(512, 8) == (SPLIT8, 8, 64)
+    assert all(split(Mp, 8) == (DIRECT, 1, 0) for Mp in (128, 224, 288, 320))
+    # a batch is never split, nor a product beside the chain
+    assert all(g == (DIRECT, 1, 0) for c, g in got.items() if c[3] >= 2 or c[4])
+    assert any(g[0] == SPLIT8 for c, g in got.items() if c[1] == 4 and c[2] == 4)
+
+
+def _shared_slab(rows):
+    """The cases (Mp, arrays, K, whiten) of `rows` {case: (mm_chain, mm_sbar)} in which the product beside the chain and the chain's products both go
+    through the context's slab buffer.  Unwhitened, Sbar runs behind the chain on the same stream: nothing is beside it."""
+    return sorted(c for c, (chain, sbar) in rows.items() if c[3] and chain == SPLIT8 and sbar == SPLIT8)
+
+
+MM_CASES = [(Mp, a, K, w) for Mp in MM_MPS for a in MM_ARRAYS for K in (1, 2, 10) for w in (0, 1)]
+
+
+def test_the_product_beside_the_chain_never_shares_the_chains_slab(table):
+    shapes = [dict(FR.resolve(1000, Mp, K, 12, whiten=bool(w)), esz=MM_ARRAYS[a][0], ssz=MM_ARRAYS[a][1], split=0) for Mp, a, K, w in MM_CASES]
+    rows = _run(table, shapes)
+    prog = {c: (r["mm_chain"], r["mm_sbar"]) for c, r in zip(MM_CASES, rows)}
+    ref = {c: FR.mm_forms(c[0], *MM_ARRAYS[c[1]], c[2], not c[3]) for c in MM_CASES}
+    assert prog == ref
+    assert _shared_slab(prog) == []
+    # what the plan keeps: the chain splits wherever it did, Sbar still splits where it runs alone (K = 1, unwhitened), and K >= 2 is direct
+    assert all((chain == SPLIT8) == (Mp >= 256 and Mp % (256 if MM_ARRAYS[a][1] == 4 else 128) == 0) for (Mp, a, K, w), (chain, _) in prog.items())
+    assert all((sbar == SPLIT8) == (K == 1 and not w and Mp >= 256 and Mp % (256 if MM_ARRAYS[a][0] == 4 else 128) == 0)
+               for (Mp, a, K, w), (_, sbar) in prog.items())
+
+
+def test_the_slab_invariant_sees_the_old_rule():
+    """Simulated fault: the rule as it stood (a single product splits whichever stream it runs on).  At K = 1 the whitened Sbar product and the
+    chain then share the slab at exactly the sizes at which both split; K >= 2 and the unwhitened form never did."""
+    old = {c: FR.mm_forms(c[0], *MM_ARRAYS[c[1]], c[2], not c[3], plan=FR.mm_plan_old) for c in MM_CASES}
+    shared = _shared_slab(old)
+    assert shared and all(K == 1 and w for _, _, K, w in shared)
+    at = {a: [Mp for Mp, b, _, _ in shared if b == a] for a in MM_ARRAYS}
+    assert at == {"F32": [256, 512, 768, 1024], "F64": list(range(256, 1025, 128)), "PURE": [256, 512, 768, 1024]}
+    assert _shared_slab({c: FR.mm_forms(c[0], *MM_ARRAYS[c[1]], c[2], not c[3]) for c in MM_CASES}) == []

@@ -67,6 +67,7 @@ def _step(eng, d):
     r["A"] = np.tril(red[lay["A"]:lay["A"] + K * Mp * Mp].reshape(K, Mp, Mp)[:, :M, :M])
     r["GT"] = red[lay["GT"]:lay["GT"] + Mp * Mp].reshape(Mp, Mp)[:M, :M]
     r["ubar"] = red[lay["ubar"]:lay["ubar"] + K * Mp].reshape(K, Mp)[:, :M]
+    r["grads"] = eng.grads.cpu().numpy().copy()        # every block, in the arrays' own type: what step_finish left
     return r
 
 
@@ -119,7 +120,7 @@ CASES = {
     "f16_cc_K64": (64, 256, 1500, "f32", {}, dict(wbar="split_cc", a_k="w2", a_k_kgroups=7)),
     "f16_sp2_K65_Mp224": (65, 200, 1500, "f32", {}, dict(wbar="split<2>")),
     "f16_sp2_K96": (96, 256, 1200, "f32", {}, dict(wbar="split<2>")),
-    "f16_sp1_K1": (1, 256, 1500, "f32", {}, dict(wbar="split<1>", fwd_t_kg=1, ubar_q4=1)),
+    "f16_sp1_K1": (1, 256, 1500, "f32", {}, dict(wbar="split<1>", fwd_t_kg=1, ubar_q4=1, mm_chain="split8", mm_sbar="direct")),
     "f16_sp1_K97_Mp128": (97, 128, 1500, "f32", {}, dict(wbar="split<1>", fwd_t="q4", fwd_t_kg=51)),
     "f16_sp1_K128_Mp128": (128, 128, 1500, "f32", {}, dict(wbar="split<1>", fwd_t_kg=51, a_k="w2", a_k_kgroups=13)),
     "f16_sp1_K127_Mp160": (127, 160, 1000, "f32", {}, dict(wbar="split<1>", fwd_t_kg=32, ubar_q4=4)),
@@ -160,8 +161,9 @@ def test_stage_forms_against_fp64_products_of_the_engine_inputs(case):
     assert {k: seen.get(k) for k in forms} == forms, (case, seen)
     # the same step again on the same engine: bit-identical (fixed accumulation order)
     again = _step(eng, d)
-    for q in ("Wbar", "tt", "A", "GT"):
+    for q in ("Wbar", "tt", "A", "GT", "grads"):
         assert np.array_equal(got[q], again[q]), (case, q, float(np.abs(got[q] - again[q]).max()))
+    assert np.isfinite(got["grads"]).all() and np.isfinite(again["grads"]).all(), case
     for q, (g, t) in errs.items():
         assert g < GLOBAL[kind][q] and t < TILE_TOL, (case, q, g, t)
 
