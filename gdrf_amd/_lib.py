@@ -65,6 +65,7 @@ SIGNATURES = {
     "gdrf_predict": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "gdrf_predict_mc": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _int, C.c_uint64, _i64, _vp, _vp, _vp, _vp]),
     "gdrf_predict_info": (_int, [_vp, _vp, _i64, _vp, _vp, _int, C.c_uint64, _i64, _vp, _vp, _vp]),
+    "gdrf_predict_score": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, C.c_uint64, _i64, _vp, _vp, _vp]),
     "gdrf_predict_quant": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _int, C.c_uint64, _i64, _vp, C.POINTER(_dbl), _int, _vp, _int, _vp, _vp]),
     "gdrf_fold_in": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp]),
     "gdrf_sample_counts": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _int, _int, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -11,6 +11,7 @@
 #include "predict.h"
 #include "predict_mc.h"
 #include "predict_info.h"
+#include "predict_score.h"
 #include "predict_quant.h"
 #include "foldin.h"
 #include "sample_counts.h"
@@ -719,7 +720,7 @@ static int rows_lds_fail(const char* fn) {
 
 // The (LG, KJ) forms of the lane-group row kernels (lane_group.h: LG lanes own a row, KJ topics per lane, LG x KJ >= K), by K:
 //   K <=          8        16        32        64       128
-//   predictive  (8, 1)   (16, 1)   (32, 1)   (64, 1)   (64, 2)     predict_mc_kernel, predict_info_kernel, foldin_kernel
+//   predictive  (8, 1)   (16, 1)   (32, 1)   (64, 1)   (64, 2)     predict_mc_kernel, predict_info_kernel, predict_score_kernel, foldin_kernel
 //   sparse      (8, 1)   (16, 2)   (16, 2)   (16, 8)   (16, 8)     rows_csr_kernel, csr_phibar_seg_kernel
 // They differ and are kept: the sparse kernels pay a butterfly over the group (and LG entries fetched) per stored entry, so their groups
 // stop at 16 lanes and more topics go into a lane's registers; the predictive kernels reduce over the group per row and sample only and
@@ -1893,6 +1894,29 @@ template <typename T, typename TS> struct Impl {
     });
   }
 
+  // Per-row log predictive densities (predict_score.h): the step's forward as in mode 4 of predict, then one kernel over the rows that
+  // scores each row's counts under the draws - dense (Phi through LDS in chunks of GDRF_SCORE_V_CHUNK words, the samples in tiles of
+  // GDRF_SCORE_S_TILE) or CSR (the stored entries only, Phi from global memory); no V and no S is too large
+  static int predict_score(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, const int64_t* crow,
+                           const int32_t* col, const int32_t* val, int S, uint64_t seed, int64_t row_offset, const T* eps, double* out,
+                           hipStream_t s) {
+    const int K = c->K, V = c->V;
+    const bool csr = crow != nullptr;
+    return predictive_form(K, [&](auto fm) -> int {
+      using F = decltype(fm);
+      const size_t lds = csr ? score_csr_lds<T>(F::LG, F::KJ) : score_dense_lds<T>(K, V, F::LG, F::KJ);
+      if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+      auto go = [&](auto kern) {
+        return launch_lds(kern, dim3(lane_group_grid(n, F::LG)), dim3(256), lds, s, n, K, V, S, (const Hyper*)c->hyp, (const T*)P(c->qpart), nct<TS>(c),
+                          (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk, c->mean_sn, eps, seed, row_offset,
+                          (const T*)P(c->phi), ws, crow, col, val, out);
+      };
+      if (int rc = csr ? go(predict_score_kernel<T, F::LG, F::KJ, true>) : go(predict_score_kernel<T, F::LG, F::KJ, false>)) return rc;
+      LAUNCHCHK("predict_score");
+      return 0;
+    });
+  }
+
   // Quantile, exceedance and dominant-topic maps (predict_quant.h): the step's forward as in mode 4 of predict, then one kernel over the
   // rows.  The quantile mode keeps the samples of CP components of RP rows in LDS per workgroup pass (forms.h::quant_plan); the counter
   // modes take 256 / LG rows per pass and only the theta slots
@@ -2407,6 +2431,22 @@ int gdrf_predict_info(gdrf_ctx* c, const void* X, int64_t n, const void* Z, cons
   if (!out) return fail(-1, "gdrf_predict_info", "out is required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict_info, c, (const T*)X, n, (const T*)Z, (const T*)params, num_samples, seed, row_offset, (const T*)eps, out, s);
+}
+
+int gdrf_predict_score(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, const int32_t* ws, const int64_t* crow,
+                       const int32_t* col, const int32_t* val, int num_samples, uint64_t seed, int64_t row_offset, const void* eps, double* out,
+                       void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (n < 1) return fail(-1, "gdrf_predict_score", "n must be >= 1");
+  if (n > c->ncap) return fail(-1, "gdrf_predict_score", "needs n <= n_cap");
+  if (num_samples < 1) return fail(-1, "gdrf_predict_score", "num_samples must be >= 1");
+  if (num_samples > 65535) return fail(-1, "gdrf_predict_score", "a call takes at most 65535 samples");
+  if (row_offset < 0) return fail(-1, "gdrf_predict_score", "row_offset must be >= 0");
+  if ((ws != nullptr) == (crow != nullptr)) return fail(-1, "gdrf_predict_score", "needs the counts either dense (ws_dev) or CSR (crow_dev)");
+  if (crow && (!col || !val)) return fail(-1, "gdrf_predict_score", "CSR counts need col_dev and val_dev");
+  if (!out) return fail(-1, "gdrf_predict_score", "out is required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, predict_score, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, crow, col, val, num_samples, seed, row_offset, (const T*)eps, out, s);
 }
 
 int gdrf_predict_quant(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, int mode, int num_samples, uint64_t seed,

@@ -77,6 +77,36 @@ def check_fold_args(num_iters, tol, n: int, V: int, ws, ws_score=None):
 INFO_NAMES = ("topic_entropy", "topic_expected_entropy", "topic_information", "word_entropy", "word_expected_entropy", "word_information")
 INFO_V_CHUNK = 128
 
+# The rows of Engine.predict_score's (5, n) result, in order, the words of Phi its dense form stages in LDS at a time and the samples whose
+# log likelihoods a row keeps there while the chunks pass (GDRF_SCORE_V_CHUNK and GDRF_SCORE_S_TILE of include/gdrf_hip.h): neither limits
+# V or num_samples.
+SCORE_NAMES = ("lpd", "mean_log_lik", "var_log_lik", "total", "log_coef")
+SCORE_V_CHUNK = 128
+SCORE_S_TILE = 64
+
+
+def check_score_args(num_samples, K: int, V: int, n: int, ws, eps=None) -> int:
+    """The argument errors of the per-row predictive score (Engine.predict_score and the model methods above it), raised before the device
+    is touched: an integral ``num_samples`` in 1 .. 65535, an injected ``eps`` of shape (num_samples, K, n), counts ``ws`` of shape
+    (n, V) with n >= 1, dense or CSR.  Returns num_samples as an int."""
+    try:
+        integral = not isinstance(num_samples, bool) and int(num_samples) == num_samples
+    except (TypeError, ValueError, OverflowError):
+        integral = False
+    if not integral:
+        raise ValueError(f"num_samples must be an integer, got {num_samples!r}")
+    S = int(num_samples)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"num_samples must be in 1 .. 65535, got {S}")
+    if n < 1:
+        raise ValueError(f"the predictive score needs at least one row, got {n}")
+    if eps is not None and (not hasattr(eps, "shape") or tuple(eps.shape) != (S, K, n)):
+        raise ValueError(f"eps must have shape (num_samples, K, n) = ({S}, {K}, {n}), got {tuple(getattr(eps, 'shape', ()))}")
+    if ws is None or not hasattr(ws, "shape") or tuple(ws.shape) != (n, V):
+        raise ValueError(f"ws must be counts of shape (n, V) = ({n}, {V}), got {None if ws is None else tuple(getattr(ws, 'shape', ()))}")
+    return S
+
+
 # Engine.predict_quant (gdrf_predict_quant, csrc/predict_quant.h): its modes, the most samples the quantile mode orders in LDS and the most
 # levels (quantile levels or thresholds) of a call - GDRF_QUANT_* of include/gdrf_hip.h.  The counter modes take the 65535 samples of
 # their siblings.
@@ -1040,6 +1070,38 @@ class Engine:
             _lib.check(self.lib.gdrf_predict_info(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), S, seed,
                                                   int(row_offset), eps.data_ptr() if eps is not None else None, out.data_ptr(),
                                                   _stream_ptr(self.device)), "gdrf_predict_info")
+            return out
+
+        with self._borrowed_mean(mean, n):
+            return self._speculated(run)
+
+    def predict_score(self, xs: torch.Tensor, ws: torch.Tensor, num_samples: int, seed: Optional[int] = None, row_offset: int = 0,
+                      eps: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The per-row Monte-Carlo log predictive densities of the counts ``ws`` at the rows ``xs`` (gdrf_predict_score,
+        csrc/predict_score.h), (5, n) float64 in the order of SCORE_NAMES, over the ``num_samples`` draws predict_mc makes under the same
+        ``seed`` / ``row_offset`` / ``eps`` / ``mean`` without storing a sample.  ``ws``: dense (n, V) int32 or ``torch.sparse_csr``; no
+        V is too large.  n <= n_cap.  Same jitter-level protocol as predict()."""
+        S = check_score_args(num_samples, self.K, self.V, int(xs.shape[0]), ws, eps)
+        self._chk_rows(xs, ws)
+        n = xs.shape[0]
+        seed = self._mc_seed("predict_score", n, eps, seed)
+        if is_sparse_counts(ws):
+            crow, col, val = self._csr_arrays(ws)
+            if col.numel() == 0:
+                # An all-empty matrix: torch gives its empty index arrays no address, and the library, which cannot see on the host that
+                # no entry is stored (the row pointers live on the device), insists on col_dev and val_dev.  The stand-in is never read:
+                # every row has crow[n] == crow[n + 1].
+                col = val = torch.zeros(1, dtype=torch.int32, device=self.device)
+            counts = (None, crow.data_ptr(), col.data_ptr(), val.data_ptr())
+        else:
+            counts = (ws.data_ptr(), None, None, None)
+        self.refresh_inducing()
+
+        def run():
+            out = torch.empty(len(SCORE_NAMES), n, dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.gdrf_predict_score(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), *counts, S, seed,
+                                                   int(row_offset), eps.data_ptr() if eps is not None else None, out.data_ptr(),
+                                                   _stream_ptr(self.device)), "gdrf_predict_score")
             return out
 
         with self._borrowed_mean(mean, n):

@@ -15,8 +15,8 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
-from ..engine import (INFO_NAMES, QUANT_DOMINANT, QUANT_EXCEED, QUANT_QUANTILE, Engine, check_count_args, check_fold_args, check_joint_args,
-                      check_mc_args, check_quant_args, check_select_args)
+from ..engine import (INFO_NAMES, QUANT_DOMINANT, QUANT_EXCEED, QUANT_QUANTILE, SCORE_NAMES, Engine, check_count_args, check_fold_args,
+                      check_joint_args, check_mc_args, check_quant_args, check_score_args, check_select_args)
 from ..kernels import Kernel, Product, embedded_coordinates
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
@@ -234,6 +234,15 @@ class ModelSnapshot:
     def predictive_perplexity(self, x, w, num_samples=64, seed=None):
         return self.restore().predictive_perplexity(x, w, num_samples, seed=seed)
 
+    def pointwise_log_likelihood(self, xs, ws, num_samples=64, seed=None, eps=None, normalized=False):
+        return self.restore().pointwise_log_likelihood(xs, ws, num_samples, seed=seed, eps=eps, normalized=normalized)
+
+    def waic(self, xs, ws, num_samples=64, seed=None, normalized=False):
+        return self.restore().waic(xs, ws, num_samples, seed=seed, normalized=normalized)
+
+    def row_perplexity(self, xs, ws, num_samples=64, seed=None):
+        return self.restore().row_perplexity(xs, ws, num_samples, seed=seed)
+
     def information(self, xs, num_samples=256, seed=None, eps=None):
         return self.restore().information(xs, num_samples, seed=seed, eps=eps)
 
@@ -281,6 +290,25 @@ class ModelSnapshot:
 
     def predictive_check(self, xs, ws, num_samples=200, seed=None, coherent=False):
         return self.restore().predictive_check(xs, ws, num_samples, seed=seed, coherent=coherent)
+
+
+# var_log_lik above which a row's WAIC term is held to be unreliable (Vehtari, Gelman & Gabry 2017, section 2.2)
+WAIC_HIGH_VARIANCE = 0.4
+
+
+def waic_from_pointwise(d: Dict[str, torch.Tensor]) -> Dict[str, object]:
+    """WAIC from the (N,) maps of pointwise_log_likelihood (``lpd`` and ``var_log_lik`` are read), in float64 torch on whatever device
+    they live on: ``pointwise`` elpd_n = lpd_n - var_log_lik_n, ``elpd_waic`` its sum, ``p_waic`` = sum_n var_log_lik_n (the effective
+    number of parameters), ``waic`` = -2 elpd_waic, ``se`` = sqrt(N var(elpd_n)) with the unbiased variance over the rows (0 for
+    N = 1), and ``n_high_variance`` the rows with var_log_lik > WAIC_HIGH_VARIANCE."""
+    lpd, var = torch.as_tensor(d["lpd"]).double(), torch.as_tensor(d["var_log_lik"]).double()
+    if lpd.dim() != 1 or lpd.shape != var.shape or lpd.numel() < 1:
+        raise ValueError(f"lpd and var_log_lik must be (N,) maps of the same N >= 1, got {tuple(lpd.shape)} and {tuple(var.shape)}")
+    point = lpd - var
+    N = point.numel()
+    elpd = point.sum()
+    se = torch.sqrt(N * point.var(unbiased=True)) if N > 1 else torch.zeros((), dtype=torch.float64, device=point.device)
+    return dict(elpd_waic=elpd, p_waic=var.sum(), waic=-2.0 * elpd, se=se, pointwise=point, n_high_variance=int((var > WAIC_HIGH_VARIANCE).sum()))
 
 
 def _all_words(V: int, words):
@@ -730,6 +758,55 @@ class SparseMultinomialGDRF:
         xs_s, ws_d = self._prepare_inputs(x, w)
         s = self._predict_mc(xs_s, 2, S, ws_d=ws_d, seed=seed)
         return torch.exp(-s[0] / s[1])
+
+    # ------------------------------------------------------------------ per-row predictive densities and WAIC (csrc/predict_score.h)
+    def pointwise_log_likelihood(self, xs, ws, num_samples: int = 64, seed=None, eps=None, normalized: bool = False) -> Dict[str, torch.Tensor]:
+        """How well the fitted field explains each observed row: a dict of five (N,) float64 tensors over ``num_samples`` draws theta_s of
+        sample_topic_probs (the same ``seed`` / ``eps``), with a_s = sum_v w_v log (theta_s Phi)_v: ``lpd`` logsumexp_s(a_s) - log S (the
+        l_n that predictive_perplexity sums), ``mean_log_lik`` mean_s a_s, ``var_log_lik`` the unbiased variance of a_s over the draws (0
+        for one draw), ``total`` sum_v w_v and ``log_coef`` the log of the row's Multinomial coefficient.  ``lpd`` and ``mean_log_lik``
+        leave that coefficient out, as perplexity does; ``normalized=True`` adds it to both.  ``ws``: dense counts or a
+        ``torch.sparse_csr`` matrix; no V is too large.  Reduced on the device without storing a sample, over pieces of at most the
+        engine's n_cap rows as fold-in cuts them; a row's values do not depend on the pieces."""
+        if self._link_function is not None:
+            raise NotImplementedError("pointwise_log_likelihood with a custom link_function: the kernel fuses the softmax link")
+        n = int(torch.as_tensor(xs).shape[0])
+        S = check_score_args(num_samples, self._K, self._V, n, ws, eps)
+        xs_s, ws_d = self._prepare_inputs(xs, ws)
+        eng = self._engine_for(min(n, MC_PIECE_ROWS))
+        seed = self.rng_seed if seed is None else int(seed)
+        if eps is not None:
+            eps = torch.as_tensor(eps).to(device=self.device, dtype=self.dtype)
+        mean = self._mean_values(xs_s)
+        if mean is not None:
+            mean = self._mean_kn(mean, n)
+        sparse = is_sparse_counts(ws_d)
+        parts = []
+        for a in range(0, n, eng.n_cap):
+            b = min(n, a + eng.n_cap)
+            w = ws_d if (a, b) == (0, n) else csr_rows(ws_d, slice(a, b)) if sparse else ws_d[a:b]
+            parts.append(eng.predict_score(xs_s[a:b], w, S, seed=seed, row_offset=a, eps=None if eps is None else eps[:, :, a:b].contiguous(),
+                                           mean=None if mean is None else mean[:, a:b]))
+        d = dict(zip(SCORE_NAMES, parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)))
+        if normalized:
+            d["lpd"] = d["lpd"] + d["log_coef"]
+            d["mean_log_lik"] = d["mean_log_lik"] + d["log_coef"]
+        return d
+
+    def waic(self, xs, ws, num_samples: int = 64, seed=None, normalized: bool = False) -> Dict[str, object]:
+        """The widely applicable information criterion of the rows (xs, ws) under the guide's posterior, for comparing fits (across K, say):
+        waic_from_pointwise of pointwise_log_likelihood - ``elpd_waic`` = sum_n (lpd_n - var_log_lik_n), ``p_waic``, ``waic`` =
+        -2 elpd_waic, the standard error ``se`` of elpd_waic over the rows, the ``pointwise`` terms and ``n_high_variance``, the number of
+        rows whose var_log_lik is above 0.4 (there WAIC is unreliable).  ``normalized`` as in pointwise_log_likelihood: it shifts every
+        model's elpd on the same data by the same constant."""
+        return waic_from_pointwise(self.pointwise_log_likelihood(xs, ws, num_samples, seed=seed, normalized=normalized))
+
+    def row_perplexity(self, xs, ws, num_samples: int = 64, seed=None) -> torch.Tensor:
+        """(N,) float64: exp(-lpd_n / total_n), the per-token perplexity of each row under the posterior predictive - the map of the samples
+        the fitted field explains badly; NaN where a row has no tokens.  predictive_perplexity is the same over all rows at once."""
+        d = self.pointwise_log_likelihood(xs, ws, num_samples, seed=seed)
+        tot = d["total"]
+        return torch.where(tot > 0, torch.exp(-d["lpd"] / tot.clamp_min(1.0)), torch.full_like(tot, float("nan")))
 
     # ------------------------------------------------------------------ entropy and information-gain maps (csrc/predict_info.h)
     def information(self, xs, num_samples: int = 256, seed=None, eps=None) -> Dict[str, torch.Tensor]:

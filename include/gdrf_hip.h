@@ -360,6 +360,29 @@ int gdrf_predict_mc(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_d
 int gdrf_predict_info(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, int num_samples, uint64_t seed,
                       int64_t row_offset, const void* eps_dev, double* out_dev, void* stream);
 
+/* Per-row Monte-Carlo log predictive densities (csrc/predict_score.h): how well the fitted field explains each of n observed rows, under
+ * its own posterior.  Over the S = num_samples draws gdrf_predict_mc makes (the same mu, theta_s, p_s = theta_s Phi, the same eps_dev /
+ * seed / row_offset, bit for bit) and with the row's counts w, a_s = sum_{v: w_v != 0} w_v log p_s[v], out_dev (5, n) doubles holds the rows
+ *   0  lpd           logsumexp_s(a_s) - log S                      3  total     sum_v w_v
+ *   1  mean_log_lik  (1/S) sum_s a_s                               4  log_coef  lgamma(total + 1) - sum_v lgamma(w_v + 1)
+ *   2  var_log_lik   sum_s (a_s - row 1)^2 / (S - 1), 0 for S = 1
+ * Row 0 is the l_n whose sum over the rows GDRF_MC_SCORE returns; rows 0 and 1 leave the Multinomial coefficient out, as it does, and
+ * row 4 is that coefficient's log.  sum_n (row 0 - row 2) is the WAIC estimate of the expected log pointwise predictive density.
+ * The counts are either dense - ws_dev (n, V) int32, crow_dev NULL - or CSR - ws_dev NULL, crow_dev (n + 1) int64 row pointers from 0,
+ * col_dev / val_dev int32; only the stored entries are visited, a stored zero is an absent entry, a row without entries gives five
+ * zeros.  A CSR matrix bound with gdrf_bind_counts_csr plays no part.  p and its log are formed in the array precision with k ascending,
+ * every sum over words and samples in double (rows 1 and 2 from the sums of a_s - a_0 and of its square: equal draws give a variance of
+ * exactly 0).  No sample is stored.  Dense: Phi passes through LDS in chunks of GDRF_SCORE_V_CHUNK words and the samples are taken in
+ * tiles of GDRF_SCORE_S_TILE, so any V is served; CSR: Phi is read from global memory.  Every K the context supports;
+ * 1 <= num_samples <= 65535.  n <= n_cap.  Runs the step's forward (as mode 4 of gdrf_predict), so it overwrites the same workspaces;
+ * every step recomputes them.  Every output is bit-identical however the rows are batched (no atomics, no sum over rows).  Needs
+ * gdrf_factorize(). */
+#define GDRF_SCORE_V_CHUNK 128
+#define GDRF_SCORE_S_TILE 64
+int gdrf_predict_score(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const int32_t* ws_dev,
+                       const int64_t* crow_dev, const int32_t* col_dev, const int32_t* val_dev, int num_samples, uint64_t seed,
+                       int64_t row_offset, const void* eps_dev, double* out_dev, void* stream);
+
 /* Credible-interval, exceedance and dominant-topic maps (csrc/predict_quant.h): uncertainty of the field at the n new inputs in a form
  * that can be shown.  Over the S = num_samples draws gdrf_predict_mc makes (the same mu[s][k] = f_loc[k][n] + mean[k][n] +
  * f_var[k][n] eps[s][k][n] with f_var as the scale, theta_s = softmax(mu_s), the same eps_dev / seed / row_offset, bit for bit) a
