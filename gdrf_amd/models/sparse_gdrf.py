@@ -10,6 +10,7 @@ guide=model.guide, ...)`` takes them (gdrf/train_script.py:365-371).
 from __future__ import annotations
 
 import copy
+import functools
 from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import torch
@@ -126,6 +127,31 @@ def validate_dirichlet_param(b: torch.Tensor, K: int, V: int) -> torch.Tensor:
 MC_PIECE_ROWS = 65536
 
 
+def row_pieces(n: int, size: int):
+    """The rows [0, n) in pieces of at most ``size``: (a, b, whole) of each piece [a, b), ``whole`` when it is all the rows"""
+    for a in range(0, n, size):
+        b = min(n, a + size)
+        yield a, b, (a, b) == (0, n)
+
+
+def count_rows(w, a: int, b: int, whole: bool = False):
+    """Rows [a, b) of dense or CSR counts.  None stays None; a ``whole`` piece is the caller's object itself, which keeps the engine's
+    per-tensor caches."""
+    if w is None or whole:
+        return w
+    return csr_rows(w, slice(a, b)) if is_sparse_counts(w) else w[a:b]
+
+
+def join_pieces(parts: list, axis):
+    """The results of the pieces as one: joined along ``axis`` (a single part as it is), added when ``axis`` is None.  A tuple of axes
+    joins parts that are tuples, element by element."""
+    if isinstance(axis, tuple):
+        return tuple(join_pieces([p[i] for p in parts], ax) for i, ax in enumerate(axis))
+    if axis is None:
+        return torch.stack(parts).sum(0)
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=axis)
+
+
 class ModelSnapshot:
     """What ``deepcopy(model).half()`` yields for checkpoints (gdrf/train_script.py:490-506): a detached copy of the parameters
     that supports ``.half()/.float()/.state_dict()`` AND the read-only model surface the end-of-run artefact writer uses on a
@@ -210,86 +236,7 @@ class ModelSnapshot:
             self._model = model
         return model
 
-    def log_topic_probs(self, xs):
-        return self.restore().log_topic_probs(xs)
-
-    def topic_probs(self, xs):
-        return self.restore().topic_probs(xs)
-
-    def word_probs(self, xs):
-        return self.restore().word_probs(xs)
-
-    def perplexity(self, x, w):
-        return self.restore().perplexity(x, w)
-
-    def sample_topic_probs(self, xs, num_samples, seed=None, eps=None):
-        return self.restore().sample_topic_probs(xs, num_samples, seed=seed, eps=eps)
-
-    def topic_probs_mc(self, xs, num_samples=256, seed=None):
-        return self.restore().topic_probs_mc(xs, num_samples, seed=seed)
-
-    def word_probs_mc(self, xs, num_samples=256, seed=None):
-        return self.restore().word_probs_mc(xs, num_samples, seed=seed)
-
-    def predictive_perplexity(self, x, w, num_samples=64, seed=None):
-        return self.restore().predictive_perplexity(x, w, num_samples, seed=seed)
-
-    def pointwise_log_likelihood(self, xs, ws, num_samples=64, seed=None, eps=None, normalized=False):
-        return self.restore().pointwise_log_likelihood(xs, ws, num_samples, seed=seed, eps=eps, normalized=normalized)
-
-    def waic(self, xs, ws, num_samples=64, seed=None, normalized=False):
-        return self.restore().waic(xs, ws, num_samples, seed=seed, normalized=normalized)
-
-    def row_perplexity(self, xs, ws, num_samples=64, seed=None):
-        return self.restore().row_perplexity(xs, ws, num_samples, seed=seed)
-
-    def information(self, xs, num_samples=256, seed=None, eps=None):
-        return self.restore().information(xs, num_samples, seed=seed, eps=eps)
-
-    def most_informative(self, xs, count, criterion="word_information", num_samples=256, seed=None):
-        return self.restore().most_informative(xs, count, criterion, num_samples, seed=seed)
-
-    def topic_probs_quantiles(self, xs, q=(0.05, 0.5, 0.95), num_samples=256, seed=None, eps=None):
-        return self.restore().topic_probs_quantiles(xs, q, num_samples, seed=seed, eps=eps)
-
-    def word_probs_quantiles(self, xs, q=(0.05, 0.5, 0.95), words=None, num_samples=256, seed=None, eps=None):
-        return self.restore().word_probs_quantiles(xs, q, words, num_samples, seed=seed, eps=eps)
-
-    def exceedance(self, xs, thresholds, what="topic", words=None, num_samples=256, seed=None, eps=None):
-        return self.restore().exceedance(xs, thresholds, what, words, num_samples, seed=seed, eps=eps)
-
-    def dominant_topic_probs(self, xs, num_samples=256, seed=None, eps=None):
-        return self.restore().dominant_topic_probs(xs, num_samples, seed=seed, eps=eps)
-
-    def select_batch(self, xs, count, noise=None, given=None, return_variance=False):
-        return self.restore().select_batch(xs, count, noise=noise, given=given, return_variance=return_variance)
-
-    def infer_topic_probs(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
-        return self.restore().infer_topic_probs(xs, ws, num_iters, tol, return_diagnostics)
-
-    def infer_log_topic_probs(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
-        return self.restore().infer_log_topic_probs(xs, ws, num_iters, tol, return_diagnostics)
-
-    def topic_counts(self, xs, ws, num_iters=64, tol=1e-6, return_diagnostics=False):
-        return self.restore().topic_counts(xs, ws, num_iters, tol, return_diagnostics)
-
-    def completion_perplexity(self, x, w_fit, w_score, num_iters=64, tol=1e-6, return_diagnostics=False):
-        return self.restore().completion_perplexity(x, w_fit, w_score, num_iters, tol, return_diagnostics)
-
-    def posterior(self, Xnew):
-        return self.restore().posterior(Xnew)
-
-    def sample_fields(self, xs, num_samples, seed=None, xi=None, zeta=None):
-        return self.restore().sample_fields(xs, num_samples, seed=seed, xi=xi, zeta=zeta)
-
-    def sample_topic_maps(self, xs, num_samples, seed=None):
-        return self.restore().sample_topic_maps(xs, num_samples, seed=seed)
-
-    def sample_counts(self, xs, totals, num_samples, seed=None, coherent=False, theta=None, u=None):
-        return self.restore().sample_counts(xs, totals, num_samples, seed=seed, coherent=coherent, theta=theta, u=u)
-
-    def predictive_check(self, xs, ws, num_samples=200, seed=None, coherent=False):
-        return self.restore().predictive_check(xs, ws, num_samples, seed=seed, coherent=coherent)
+    # the predictive methods (SNAPSHOT_METHODS, installed below the model they forward to) all go through restore()
 
 
 # var_log_lik above which a row's WAIC term is held to be unreliable (Vehtari, Gelman & Gabry 2017, section 2.2)
@@ -319,14 +266,15 @@ def _all_words(V: int, words):
 def _predict_quant(model, name: str, xs, mode: int, levels, words, num_samples, seed, eps) -> torch.Tensor:
     """What topic_probs_quantiles, word_probs_quantiles, exceedance and dominant_topic_probs share: the link refusal, the argument checks
     (before the device is touched), the word list as the device takes it, and Engine.predict_quant over pieces of at most the engine's
-    n_cap rows (_predict_mc)."""
+    n_cap rows (_mc_pieces), joined along the row axis: axis 1, axis 0 for the dominant-topic mode."""
     if model._link_function is not None:
         raise NotImplementedError(f"{name} with a custom link_function: the kernel fuses the softmax link")
     n = int(torch.as_tensor(xs).shape[0])
     S, lv, nw = check_quant_args(mode, num_samples, model._K, model._V, n, levels, words, eps)
     xs_s, _ = model._prepare_inputs(xs)
     w = torch.as_tensor(words).to(device=model.device, dtype=torch.int32).contiguous() if nw else None
-    return model._predict_mc(xs_s, ("quant", mode, lv if lv else None, w), S, seed=seed, eps=eps)
+    return model._mc_pieces(xs_s, lambda eng, x, *_, **kw: eng.predict_quant(x, mode, S, levels=lv if lv else None, words=w, **kw),
+                            0 if mode == QUANT_DOMINANT else 1, seed, eps)
 
 
 class SparseMultinomialGDRF:
@@ -696,9 +644,12 @@ class SparseMultinomialGDRF:
         return torch.exp(-s[0] / s[1])
 
     # ------------------------------------------------------------------ Monte-Carlo predictive path (csrc/predict_mc.h)
-    def _predict_mc(self, xs_s: torch.Tensor, mode: int, S: int, ws_d=None, seed=None, eps=None) -> torch.Tensor:
-        """Engine.predict_mc (``mode`` "info": Engine.predict_info; a tuple ("quant", mode, levels, words): Engine.predict_quant) on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows, each with its row_offset: the draws are keyed by the global row, so
-        the result does not depend on the piece size.  The pieces are joined along the row axis; mode 2's two sums are added."""
+    def _mc_pieces(self, xs_s: torch.Tensor, call: Callable, axis, seed=None, eps=None):
+        """A predictive engine call on more rows than one call holds: ``call(eng, xs, a, b, whole, seed=, row_offset=, eps=, mean=)`` for
+        every piece [a, b) (row_pieces) of at most n_cap rows, on an engine grown to hold min(n, MC_PIECE_ROWS) of them, the results joined
+        by join_pieces(axis).  What a call takes is prepared here once - the seed (default: the model's rng_seed), an injected ``eps`` on
+        the device, the mean_function's values as (K, n) - and cut to the piece.  The draws are keyed by the global row, row_offset + row,
+        so a result does not depend on the piece size."""
         n = xs_s.shape[0]
         eng = self._engine_for(min(n, MC_PIECE_ROWS))
         seed = self.rng_seed if seed is None else int(seed)
@@ -707,19 +658,14 @@ class SparseMultinomialGDRF:
         mean = self._mean_values(xs_s)
         if mean is not None:
             mean = self._mean_kn(mean, n)
-        parts = []
-        for a in range(0, n, eng.n_cap):
-            b = min(n, a + eng.n_cap)
-            kw = dict(seed=seed, row_offset=a, eps=None if eps is None else eps[:, :, a:b].contiguous(), mean=None if mean is None else mean[:, a:b])
-            if isinstance(mode, tuple):                  # ("quant", mode, levels, words): Engine.predict_quant
-                parts.append(eng.predict_quant(xs_s[a:b], mode[1], S, levels=mode[2], words=mode[3], **kw))
-                continue
-            parts.append(eng.predict_info(xs_s[a:b], S, **kw) if mode == "info" else
-                         eng.predict_mc(xs_s[a:b], mode, S, ws=None if ws_d is None else ws_d[a:b], **kw))
-        if mode == 2:
-            return torch.stack(parts).sum(0)
-        rows = 2 if mode == 3 else 0 if isinstance(mode, tuple) and mode[1] == QUANT_DOMINANT else 1
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=rows)
+        return join_pieces([call(eng, xs_s[a:b], a, b, whole, seed=seed, row_offset=a, eps=None if eps is None else eps[:, :, a:b].contiguous(),
+                                 mean=None if mean is None else mean[:, a:b]) for a, b, whole in row_pieces(n, eng.n_cap)], axis)
+
+    def _predict_mc(self, xs_s: torch.Tensor, mode: int, S: int, ws_d=None, seed=None, eps=None) -> torch.Tensor:
+        """Engine.predict_mc over row pieces (_mc_pieces), the dense counts sliced for every piece: the samples of modes 0 and 3 and the
+        moments of mode 1 are joined along their row axis, mode 2's two sums are added."""
+        return self._mc_pieces(xs_s, lambda eng, x, a, b, whole, **kw: eng.predict_mc(x, mode, S, ws=count_rows(ws_d, a, b), **kw),
+                               {0: 1, 1: 1, 2: None, 3: 2}[mode], seed, eps)
 
     def sample_topic_probs(self, xs, num_samples, seed=None, eps=None) -> torch.Tensor:
         """(S, N, K) samples of the topic proportions under the guide's posterior: theta_s = link(mu_s), mu_s = f_loc + mean + f_var eps_s
@@ -773,21 +719,8 @@ class SparseMultinomialGDRF:
         n = int(torch.as_tensor(xs).shape[0])
         S = check_score_args(num_samples, self._K, self._V, n, ws, eps)
         xs_s, ws_d = self._prepare_inputs(xs, ws)
-        eng = self._engine_for(min(n, MC_PIECE_ROWS))
-        seed = self.rng_seed if seed is None else int(seed)
-        if eps is not None:
-            eps = torch.as_tensor(eps).to(device=self.device, dtype=self.dtype)
-        mean = self._mean_values(xs_s)
-        if mean is not None:
-            mean = self._mean_kn(mean, n)
-        sparse = is_sparse_counts(ws_d)
-        parts = []
-        for a in range(0, n, eng.n_cap):
-            b = min(n, a + eng.n_cap)
-            w = ws_d if (a, b) == (0, n) else csr_rows(ws_d, slice(a, b)) if sparse else ws_d[a:b]
-            parts.append(eng.predict_score(xs_s[a:b], w, S, seed=seed, row_offset=a, eps=None if eps is None else eps[:, :, a:b].contiguous(),
-                                           mean=None if mean is None else mean[:, a:b]))
-        d = dict(zip(SCORE_NAMES, parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)))
+        out = self._mc_pieces(xs_s, lambda eng, x, a, b, whole, **kw: eng.predict_score(x, count_rows(ws_d, a, b, whole), S, **kw), 1, seed, eps)
+        d = dict(zip(SCORE_NAMES, out))
         if normalized:
             d["lpd"] = d["lpd"] + d["log_coef"]
             d["mean_log_lik"] = d["mean_log_lik"] + d["log_coef"]
@@ -816,14 +749,13 @@ class SparseMultinomialGDRF:
         ``word_entropy`` / ``word_expected_entropy`` / ``word_information`` the same for p.  The information values are the Monte-Carlo
         estimates of the mutual information between one token's topic (word) observed at x and the latent field there (BALD); they are
         not clamped, 0 <= word_information <= topic_information <= log min(K, S) up to rounding.  Reduced on the device without storing
-        a sample, over pieces of at most the engine's n_cap rows as the other Monte-Carlo calls (_predict_mc)."""
+        a sample, over pieces of at most the engine's n_cap rows as the other Monte-Carlo calls (_mc_pieces)."""
         if self._link_function is not None:
             raise NotImplementedError("information with a custom link_function: the kernel fuses the softmax link")
         n = int(torch.as_tensor(xs).shape[0])
         S = check_mc_args(num_samples, self._K, n, eps)
         xs_s, _ = self._prepare_inputs(xs)
-        out = self._predict_mc(xs_s, "info", S, seed=seed, eps=eps)
-        return dict(zip(INFO_NAMES, out))
+        return dict(zip(INFO_NAMES, self._mc_pieces(xs_s, lambda eng, x, *_, **kw: eng.predict_info(x, S, **kw), 1, seed, eps)))
 
     # ------------------------------------------------------------------ credible intervals, exceedance, dominance (csrc/predict_quant.h)
     def topic_probs_quantiles(self, xs, q=(0.05, 0.5, 0.95), num_samples: int = 256, seed=None, eps=None) -> torch.Tensor:
@@ -893,35 +825,20 @@ class SparseMultinomialGDRF:
 
     # ------------------------------------------------------------------ fold-in: observed samples from their own counts (csrc/foldin.h)
     def _fold_in(self, xs, ws, mode: int, num_iters, tol, ws_score=None, return_diagnostics: bool = False):
-        """Engine.fold_in on an engine grown to hold min(n, MC_PIECE_ROWS) rows, over pieces of at most n_cap rows (a row's result depends on
-        no other row, so the pieces change nothing but mode 3's order of summation).  The pieces are joined along the row axis, mode 3's two
-        sums are added; with ``return_diagnostics`` the (3, N) float64 diagnostics - J, |g|_inf / max(1, R), iterations used - follow."""
+        """Engine.fold_in over row pieces (_mc_pieces; a row's result depends on no other row, so the pieces change nothing but mode 3's
+        order of summation); counts that one piece covers go through as the caller's objects.  The pieces are joined along the row axis,
+        mode 3's two sums are added; with ``return_diagnostics`` the (3, N) float64 diagnostics - J, |g|_inf / max(1, R), iterations used -
+        follow."""
         if self._link_function is not None:
             raise NotImplementedError("fold-in with a custom link_function: the kernel fuses the softmax link")
         n = int(torch.as_tensor(xs).shape[0])
         num_iters, tol = check_fold_args(num_iters, tol, n, self._V, ws, ws_score)
         xs_s, ws_d = self._prepare_inputs(xs, ws)
         sc_d = None if ws_score is None else self._prepare_inputs(xs, ws_score)[1]
-        eng = self._engine_for(min(n, MC_PIECE_ROWS))
-        mean = self._mean_values(xs_s)
-        if mean is not None:
-            mean = self._mean_kn(mean, n)
-        rows = lambda w, a, b: None if w is None else (csr_rows(w, slice(a, b)) if is_sparse_counts(w) else w[a:b])
-        parts, diags = [], []
-        for a in range(0, n, eng.n_cap):
-            b = min(n, a + eng.n_cap)
-            one = (a, b) == (0, n)
-            out, diag = eng.fold_in(xs_s[a:b], ws_d if one else rows(ws_d, a, b), mode, num_iters, tol,
-                                    ws_score=sc_d if one else rows(sc_d, a, b), mean=None if mean is None else mean[:, a:b])
-            parts.append(out)
-            diags.append(diag)
-        if mode == 3:
-            res = torch.stack(parts).sum(0)
-        else:
-            res = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1 if mode == 1 else 0)
-        if return_diagnostics:
-            return res, (diags[0] if len(diags) == 1 else torch.cat(diags, dim=1))
-        return res
+        def piece(eng, x, a, b, whole, mean, **draws):          # fold-in draws nothing: the seed, row_offset and eps stay here
+            return eng.fold_in(x, count_rows(ws_d, a, b, whole), mode, num_iters, tol, ws_score=count_rows(sc_d, a, b, whole), mean=mean)
+        res, diag = self._mc_pieces(xs_s, piece, ({0: 0, 1: 1, 2: 0, 3: None}[mode], 1))
+        return (res, diag) if return_diagnostics else res
 
     def infer_topic_probs(self, xs, ws, num_iters: int = 64, tol: float = 1e-6, return_diagnostics: bool = False):
         """(N, K) topic proportions of the OBSERVED samples (xs, ws): theta_hat = softmax(mu_hat), mu_hat the per-row maximiser of
@@ -1023,16 +940,9 @@ class SparseMultinomialGDRF:
         totals = totals.to(device=self.device, dtype=torch.int32).contiguous()
         if u is not None:
             u = torch.as_tensor(u).to(device=self.device, dtype=torch.float64)
-        parts = []
-        for a in range(0, n, MC_PIECE_ROWS):
-            b = min(n, a + MC_PIECE_ROWS)
-            one = (a, b) == (0, n)
-            parts.append(eng.sample_counts(theta if one else theta[:, a:b].contiguous(), totals[a:b], mode,
-                                           ws=None if ws_d is None else ws_d[a:b], seed=seed, row_offset=a,
-                                           u=None if u is None else u[:, a:b].contiguous()))
-        if mode == 0:
-            return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-        return torch.stack([p[0] for p in parts]).sum(0), torch.stack([p[1] for p in parts]).sum(0)
+        return join_pieces([eng.sample_counts(theta if whole else theta[:, a:b].contiguous(), totals[a:b], mode, ws=count_rows(ws_d, a, b),
+                                              seed=seed, row_offset=a, u=None if u is None else u[:, a:b].contiguous())
+                            for a, b, whole in row_pieces(n, MC_PIECE_ROWS)], 1 if mode == 0 else (None, None))
 
     def sample_counts(self, xs, totals, num_samples, seed=None, coherent=False, theta=None, u=None) -> torch.Tensor:
         """(S, N, V) int32 counts drawn from the fitted model, what ``pyro.infer.Predictive(model, guide=guide, num_samples=S)`` samples at
@@ -1172,3 +1082,25 @@ class SparseMultinomialGDRF:
                     guide_rescale=self._guide_rescale, rows_form=self._rows_form,
                     kernel_spec=kernel_spec(self._kernel))
         return ModelSnapshot(self.state_dict(), meta)
+
+
+# The model methods a ModelSnapshot offers by forwarding to the device model it rebuilds; a new predictive method joins by its name.
+SNAPSHOT_METHODS = (
+    "log_topic_probs", "topic_probs", "word_probs", "perplexity", "sample_topic_probs", "topic_probs_mc", "word_probs_mc",
+    "predictive_perplexity", "pointwise_log_likelihood", "waic", "row_perplexity", "information", "most_informative",
+    "topic_probs_quantiles", "word_probs_quantiles", "exceedance", "dominant_topic_probs", "select_batch", "infer_topic_probs",
+    "infer_log_topic_probs", "topic_counts", "completion_perplexity", "posterior", "sample_fields", "sample_topic_maps", "sample_counts",
+    "predictive_check")
+
+
+def _snapshot_method(name: str):
+    """``ModelSnapshot.name``: the model's method on ``restore()``, under the model method's signature and docstring"""
+    @functools.wraps(getattr(SparseMultinomialGDRF, name))
+    def method(self, *args, **kwargs):
+        return getattr(self.restore(), name)(*args, **kwargs)
+    method.__qualname__ = f"ModelSnapshot.{name}"
+    return method
+
+
+for _name in SNAPSHOT_METHODS:
+    setattr(ModelSnapshot, _name, _snapshot_method(_name))

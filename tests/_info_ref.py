@@ -1,5 +1,5 @@
 """The float64 torch restatement of the entropy and information-gain maps (gdrf_predict_info, csrc/predict_info.h), built from
-oracle.gdrf_oracle.conditional and the model's parameters exactly as tests/test_gpu_predict_mc.py::restate builds theta:
+oracle.gdrf_oracle.conditional and the model's parameters exactly as tests/_mc_util.py::restate builds theta:
 
     mu[s,k,n] = f_loc[k,n] + mean[k,n] + f_var[k,n] eps[s,k,n];  theta_s = softmax_k(mu[s]);  p_s = theta_s Phi
     h(q) = -sum_i q_i log q_i  (0 log 0 = 0);  theta_bar = mean_s theta_s;  p_bar = theta_bar Phi
@@ -7,7 +7,7 @@ oracle.gdrf_oracle.conditional and the model's parameters exactly as tests/test_
 (test infrastructure; may import oracle/)."""
 import torch
 
-from tests.test_gpu_predict_mc import restate
+from tests._mc_util import restate
 
 NAMES = ("topic_entropy", "topic_expected_entropy", "topic_information", "word_entropy", "word_expected_entropy", "word_information")
 TOL = {torch.float64: 1e-9, torch.float32: 5e-4}      # the predictive path's, max-abs error over max-abs value

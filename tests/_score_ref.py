@@ -1,5 +1,5 @@
 """The float64 torch restatement of the per-row Monte-Carlo log predictive densities (gdrf_predict_score, csrc/predict_score.h), built
-from oracle.gdrf_oracle.conditional and the model's parameters exactly as tests/test_gpu_predict_mc.py::restate builds theta:
+from oracle.gdrf_oracle.conditional and the model's parameters exactly as tests/_mc_util.py::restate builds theta:
 
     mu[s,k,n] = f_loc[k,n] + mean[k,n] + f_var[k,n] eps[s,k,n];  theta_s = softmax_k(mu[s]);  p_s = theta_s Phi
     a[s,n] = sum_{v: w[n,v] != 0} w[n,v] log p[s,n,v]
@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from tests.test_gpu_predict_mc import restate
+from tests._mc_util import restate
 
 NAMES = ("lpd", "mean_log_lik", "var_log_lik", "total", "log_coef")
 LPD, MLL, VLL, TOT, COEF = range(5)

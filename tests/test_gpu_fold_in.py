@@ -27,7 +27,7 @@ import pytest
 import torch
 
 from tests._util import dev, relerr
-from tests.test_gpu_predict_mc import MEAN_KN, NPTS, build, engine, loc_var
+from tests._mc_util import MEAN_KN, NPTS, build, engine, loc_var
 
 pytestmark = pytest.mark.gpu
 

@@ -13,7 +13,7 @@ import torch
 from gdrf_amd.engine import INFO_NAMES, INFO_V_CHUNK
 from tests._info_ref import NAMES, TOL, entropy, errors, info_ref
 from tests._util import dev, relerr
-from tests.test_gpu_predict_mc import MEAN_KN, _model, build, engine
+from tests._mc_util import MEAN_KN, _model, build, engine
 
 pytestmark = pytest.mark.gpu
 

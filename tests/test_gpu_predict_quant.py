@@ -18,7 +18,7 @@ from gdrf_amd.engine import QUANT_DOMINANT, QUANT_EXCEED, QUANT_QUANTILE
 from tests import _quant_ref as QR
 from tests._info_ref import TOL
 from tests._util import dev, relerr
-from tests.test_gpu_predict_mc import MEAN_KN, _model, build, engine
+from tests._mc_util import MEAN_KN, _model, build, engine
 
 pytestmark = pytest.mark.gpu
 

@@ -23,7 +23,7 @@ from gdrf_amd.data import csr_rows, to_csr
 from gdrf_amd.engine import SCORE_NAMES, SCORE_S_TILE, SCORE_V_CHUNK
 from tests._score_ref import COEF, LPD, MLL, NAMES, TOL, TOT, VLL, counts, errors, log_liks, score_ref, stats
 from tests._util import dev, relerr
-from tests.test_gpu_predict_mc import MEAN_KN, _model, build, engine
+from tests._mc_util import MEAN_KN, _model, build, engine
 
 pytestmark = pytest.mark.gpu
 

@@ -20,7 +20,7 @@ import pytest
 import torch
 
 from tests._util import dev, relerr
-from tests.test_gpu_predict_mc import MEAN_KN, _model, build, engine
+from tests._mc_util import MEAN_KN, _model, build, engine
 
 pytestmark = pytest.mark.gpu
 
