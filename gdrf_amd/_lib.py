@@ -82,6 +82,9 @@ SIGNATURES = {
     "gdrf_get_timing": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_i64), _int]),
     "gdrf_last_forms": (_int, [_vp, C.POINTER(_int), _int]),
     "gdrf_quant_last_plan": (_int, [_vp, C.POINTER(_int)]),
+    "gdrf_predict_loo": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, C.c_uint64, _i64, _vp, _vp, _vp, _vp]),
+    "gdrf_psis_rows": (_int, [_vp, _vp, _int, _int, _i64, _vp, _vp]),
+    "gdrf_loo_last_plan": (_int, [_vp, C.POINTER(_int)]),
 }
 
 

@@ -13,6 +13,7 @@
 #include "predict_info.h"
 #include "predict_score.h"
 #include "predict_quant.h"
+#include "predict_loo.h"
 #include "foldin.h"
 #include "sample_counts.h"
 #include "predict_cov.h"
@@ -150,6 +151,7 @@ struct gdrf_ctx {
   double t_ms[GDRF_NSLOTS]; int64_t t_cnt[GDRF_NSLOTS];
   int forms[GDRF_NFORMS];     // gdrf_last_forms: the form each shape-dispatched stage launched last (host bookkeeping, GDRF_FORM_* of gdrf_hip.h)
   int quant_plan[3];          // gdrf_quant_last_plan: (RP, CP, LDS bytes) of the last gdrf_predict_quant launch
+  int loo_plan[2];            // gdrf_loo_last_plan: (RP, LDS bytes) of the last gdrf_predict_loo / gdrf_psis_rows launch
 };
 
 struct ScopedTimer {
@@ -586,6 +588,12 @@ int gdrf_last_forms(const gdrf_ctx* c, int* out, int n) {
 int gdrf_quant_last_plan(const gdrf_ctx* c, int out[3]) {
   if (!c || !out) return fail(-1, "gdrf_quant_last_plan", "null argument");
   for (int i = 0; i < 3; ++i) out[i] = c->quant_plan[i];
+  return 0;
+}
+
+int gdrf_loo_last_plan(const gdrf_ctx* c, int out[2]) {
+  if (!c || !out) return fail(-1, "gdrf_loo_last_plan", "null argument");
+  for (int i = 0; i < 2; ++i) out[i] = c->loo_plan[i];
   return 0;
 }
 
@@ -1917,6 +1925,33 @@ template <typename T, typename TS> struct Impl {
     });
   }
 
+  // PSIS leave-one-out (predict_loo.h): the step's forward as in mode 4 of predict, then one kernel over the rows that forms each row's
+  // a_s as predict_score does, keeps all S of them in LDS and runs the tail fit and the smoothing on them; RP rows per workgroup pass
+  // (forms.h::loo_plan)
+  static int predict_loo(gdrf_ctx* c, const T* X, int64_t n, const T* Z, const T* params, const int32_t* ws, const int64_t* crow,
+                         const int32_t* col, const int32_t* val, int S, uint64_t seed, int64_t row_offset, const T* eps, double* out,
+                         double* a_out, hipStream_t s) {
+    const int K = c->K, V = c->V;
+    const bool csr = crow != nullptr;
+    return predictive_form(K, [&](auto fm) -> int {
+      using F = decltype(fm);
+      const forms::LooPlan pl = forms::loo_plan(K, V, S, (int)sizeof(T), F::LG, csr);
+      if (pl.lds > forms::LDS_ROWS) return rows_lds_fail("gdrf_predict_loo");      // loo_plan's worst case fits: not reached
+      c->loo_plan[0] = pl.RP; c->loo_plan[1] = (int)pl.lds;
+      if (int rc = predictive_forward(c, X, n, params, s)) return rc;
+      const int64_t nblk = (n + pl.RP - 1) / pl.RP;
+      const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
+      auto go = [&](auto kern) {
+        return launch_lds(kern, dim3(grid), dim3(256), pl.lds, s, n, K, V, S, pl.RP, pl.P, pl.M, pl.stride, (const Hyper*)c->hyp, (const T*)P(c->qpart),
+                          nct<TS>(c), (const T*)P(c->loc), (const T*)P(c->tt), c->ldk, (const T*)c->mean, c->mean_sk, c->mean_sn, eps, seed, row_offset,
+                          (const T*)P(c->phi), ws, crow, col, val, out, a_out);
+      };
+      if (int rc = csr ? go(predict_loo_kernel<T, F::LG, F::KJ, true>) : go(predict_loo_kernel<T, F::LG, F::KJ, false>)) return rc;
+      LAUNCHCHK("predict_loo");
+      return 0;
+    });
+  }
+
   // Quantile, exceedance and dominant-topic maps (predict_quant.h): the step's forward as in mode 4 of predict, then one kernel over the
   // rows.  The quantile mode keeps the samples of CP components of RP rows in LDS per workgroup pass (forms.h::quant_plan); the counter
   // modes take 256 / LG rows per pass and only the theta slots
@@ -2447,6 +2482,43 @@ int gdrf_predict_score(gdrf_ctx* c, const void* X, int64_t n, const void* Z, con
   if (!out) return fail(-1, "gdrf_predict_score", "out is required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, predict_score, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, crow, col, val, num_samples, seed, row_offset, (const T*)eps, out, s);
+}
+
+// the argument errors gdrf_predict_loo and gdrf_psis_rows share
+static int loo_args(const char* fn, int64_t n, int num_samples, int tail_len, const double* out) {
+  if (n < 1) return fail(-1, fn, "n must be >= 1");
+  if (num_samples < GDRF_LOO_MIN_SAMPLES || num_samples > GDRF_LOO_MAX_SAMPLES)
+    return fail(-1, fn, "num_samples must be in GDRF_LOO_MIN_SAMPLES .. GDRF_LOO_MAX_SAMPLES (25 .. 1024)");
+  if (tail_len != forms::loo_tail_len(num_samples)) return fail(-1, fn, "tail_len must be ceil(min(num_samples / 5, 3 sqrt(num_samples)))");
+  if (!out) return fail(-1, fn, "out is required");
+  return 0;
+}
+
+int gdrf_predict_loo(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, const int32_t* ws, const int64_t* crow,
+                     const int32_t* col, const int32_t* val, int num_samples, int tail_len, uint64_t seed, int64_t row_offset, const void* eps,
+                     double* out, double* a_out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (int rc = loo_args("gdrf_predict_loo", n, num_samples, tail_len, out)) return rc;
+  if (n > c->ncap) return fail(-1, "gdrf_predict_loo", "needs n <= n_cap");
+  if (row_offset < 0) return fail(-1, "gdrf_predict_loo", "row_offset must be >= 0");
+  if ((ws != nullptr) == (crow != nullptr)) return fail(-1, "gdrf_predict_loo", "needs the counts either dense (ws_dev) or CSR (crow_dev)");
+  if (crow && (!col || !val)) return fail(-1, "gdrf_predict_loo", "CSR counts need col_dev and val_dev");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, predict_loo, c, (const T*)X, n, (const T*)Z, (const T*)params, ws, crow, col, val, num_samples, seed, row_offset, (const T*)eps, out, a_out, s);
+}
+
+int gdrf_psis_rows(gdrf_ctx* c, const double* log_lik, int num_samples, int tail_len, int64_t n, double* out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (int rc = loo_args("gdrf_psis_rows", n, num_samples, tail_len, out)) return rc;
+  if (!log_lik) return fail(-1, "gdrf_psis_rows", "log_lik is required");
+  const forms::LooPlan pl = forms::loo_plan(0, 0, num_samples, 0, PSIS_LG, true);
+  c->loo_plan[0] = pl.RP; c->loo_plan[1] = (int)pl.lds;
+  const int64_t nblk = (n + pl.RP - 1) / pl.RP;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nblk, 1024));
+  if (int rc = launch_lds(psis_rows_kernel<PSIS_LG>, dim3(grid), dim3(256), pl.lds, (hipStream_t)stream, n, num_samples, pl.RP, pl.P, pl.M, pl.stride,
+                          log_lik, out)) return rc;
+  LAUNCHCHK("psis_rows");
+  return 0;
 }
 
 int gdrf_predict_quant(gdrf_ctx* c, const void* X, int64_t n, const void* Z, const void* params, int mode, int num_samples, uint64_t seed,

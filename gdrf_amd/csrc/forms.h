@@ -409,5 +409,38 @@ inline QuantPlan quant_plan(int K, int C, int S, int esz, int LG) {
   return best;
 }
 
+// ---- gdrf_predict_loo / gdrf_psis_rows (predict_loo.h): a workgroup pass keeps all S log likelihoods of RP rows in LDS, in double
+//   rows [RP][P + M + 3 m] double | Phi chunk [K][W] (dense) | theta [RP][Kp] | counts [RP][W] int32 (dense)
+// P = S rounded up to a power of two (what the ordering network takes), M = loo_tail_len(S) the tail the fit reads and m = 30 +
+// floor(sqrt(M)) its grid: beside its P samples a row keeps the M exceedances (later the smoothed tail) and the grid's b_j, L_j, w_j.
+// W = min(V, 128) (GDRF_SCORE_V_CHUNK), Kp = K rounded up to whole lanes of the group.  The stage kernel is K = 0, V = 0, csr.
+// What the plan optimises: the rows in flight on a compute unit, RP x (workgroups resident there: those whose LDS fits LDS_MAX, and no
+// more than the registers allow - LOO_WG_CU = 2 four-wave workgroups for the fused kernel at its ~200 VGPRs, LOO_STAGE_WG_CU = 3 for the
+// stage kernel) - a row's samples weigh more than its share of anything else, and the ordering network is LDS latency that only other
+// rows' work hides.  The product is maximised over RP = 1 .. 256 / LG with a workgroup's LDS within LDS_ROWS; equal products: the
+// larger RP, which stages Phi less often and leaves fewer groups idle.  In integers.  The largest unit, K = 128 in double at S = 1024
+// (Phi 128 KB, samples and fit 1024 + 96 + 117 doubles, theta 1 KB, counts 512 B): 142504 bytes at RP = 1, which fits.
+constexpr int LOO_WG_CU = 2, LOO_STAGE_WG_CU = 3;
+inline int loo_tail_len(int S) { return (int)std::ceil(std::min((double)S / 5.0, 3.0 * std::sqrt((double)S))); }
+inline int loo_fit_grid(int M) { return 30 + (int)std::floor(std::sqrt((double)M)); }
+struct LooPlan { int RP, P, M, stride; size_t lds; };      // stride: the doubles of a row
+inline LooPlan loo_plan(int K, int V, int S, int esz, int LG, bool csr) {
+  const int RPB = 256 / LG, Kp = (K + LG - 1) / LG * LG, W = std::min(V, 128);
+  int P = 1;
+  while (P < S) P <<= 1;
+  const int M = loo_tail_len(S), stride = P + M + 3 * loo_fit_grid(M);
+  const size_t fixed = csr ? 0 : (size_t)K * W * esz;
+  const size_t row = (size_t)stride * sizeof(double) + (size_t)Kp * esz + (csr ? 0 : (size_t)W * sizeof(int32_t));
+  LooPlan best{1, P, M, stride, fixed + row};
+  int64_t best_rows = 0;
+  for (int rp = 1; rp <= RPB; ++rp) {
+    const size_t lds = fixed + rp * row;
+    if (lds > LDS_ROWS) break;
+    const int64_t rows = (int64_t)rp * std::min<int64_t>(K ? LOO_WG_CU : LOO_STAGE_WG_CU, (int64_t)(LDS_MAX / lds));
+    if (rows >= best_rows) { best.RP = rp; best.lds = lds; best_rows = rows; }
+  }
+  return best;
+}
+
 }  // namespace forms
 }  // namespace gdrf

@@ -12,7 +12,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -105,6 +105,48 @@ def check_score_args(num_samples, K: int, V: int, n: int, ws, eps=None) -> int:
     if ws is None or not hasattr(ws, "shape") or tuple(ws.shape) != (n, V):
         raise ValueError(f"ws must be counts of shape (n, V) = ({n}, {V}), got {None if ws is None else tuple(getattr(ws, 'shape', ()))}")
     return S
+
+
+# The rows of Engine.predict_loo's (6, n) result, in order (Engine.psis_rows returns the first three), and the range of num_samples: all of
+# a row's log likelihoods are kept and ordered in LDS, and a tail of fewer than five values is not fitted (GDRF_LOO_* of
+# include/gdrf_hip.h).
+LOO_NAMES = ("elpd_loo", "pareto_k", "ess", "lpd", "total", "log_coef")
+LOO_MAX_SAMPLES = 1024
+LOO_MIN_SAMPLES = 25
+
+
+def loo_tail_len(num_samples: int) -> int:
+    """M = ceil(min(S / 5, 3 sqrt(S))): the largest importance ratios of a row that PSIS fits the generalised Pareto tail to, in double
+    as the library forms it (csrc/forms.h::loo_tail_len)."""
+    S = int(num_samples)
+    return int(math.ceil(min(S / 5.0, 3.0 * math.sqrt(S))))
+
+
+def _loo_samples(num_samples) -> int:
+    try:
+        integral = not isinstance(num_samples, bool) and int(num_samples) == num_samples
+    except (TypeError, ValueError, OverflowError):
+        integral = False
+    if not integral:
+        raise ValueError(f"num_samples must be an integer, got {num_samples!r}")
+    S = int(num_samples)
+    if not LOO_MIN_SAMPLES <= S <= LOO_MAX_SAMPLES:
+        raise ValueError(f"num_samples must be in {LOO_MIN_SAMPLES} .. {LOO_MAX_SAMPLES}, got {S}")
+    return S
+
+
+def check_loo_args(num_samples, K: int, V: int, n: int, ws, eps=None) -> int:
+    """The argument errors of PSIS leave-one-out (Engine.predict_loo and the model methods above it), raised before the device is
+    touched: those of check_score_args with ``num_samples`` in LOO_MIN_SAMPLES .. LOO_MAX_SAMPLES.  Returns num_samples as an int."""
+    return check_score_args(_loo_samples(num_samples), K, V, n, ws, eps)
+
+
+def check_psis_args(log_lik) -> Tuple[int, int]:
+    """The argument errors of the PSIS stage on a caller's own matrix (Engine.psis_rows, the model's psis): a (S, n) tensor with S in
+    LOO_MIN_SAMPLES .. LOO_MAX_SAMPLES and n >= 1.  Returns (S, n)."""
+    if not torch.is_tensor(log_lik) or log_lik.dim() != 2 or log_lik.shape[1] < 1:
+        raise ValueError(f"log_lik must be a (num_samples, n) tensor with n >= 1, got {tuple(getattr(log_lik, 'shape', ()))}")
+    return _loo_samples(int(log_lik.shape[0])), int(log_lik.shape[1])
 
 
 # Engine.predict_quant (gdrf_predict_quant, csrc/predict_quant.h): its modes, the most samples the quantile mode orders in LDS and the most
@@ -600,6 +642,13 @@ class Engine:
         arr = (C.c_int * 3)()
         _lib.check(self.lib.gdrf_quant_last_plan(self.ctx, arr), "gdrf_quant_last_plan")
         return dict(RP=arr[0], CP=arr[1], lds=arr[2])
+
+    def last_loo_plan(self) -> Dict[str, int]:
+        """(rows per workgroup pass, dynamic LDS bytes) of the most recent predict_loo or psis_rows launch (gdrf_loo_last_plan,
+        csrc/forms.h::loo_plan), as a dict with the keys RP and lds; zeros before the first call."""
+        arr = (C.c_int * 2)()
+        _lib.check(self.lib.gdrf_loo_last_plan(self.ctx, arr), "gdrf_loo_last_plan")
+        return dict(RP=arr[0], lds=arr[1])
 
     # ---- primitives ------------------------------------------------------------------------------
     def _chk_rows(self, xs: torch.Tensor, ws: Optional[torch.Tensor] = None):
@@ -1106,6 +1155,53 @@ class Engine:
 
         with self._borrowed_mean(mean, n):
             return self._speculated(run)
+
+    def _score_counts(self, ws: torch.Tensor):
+        """(ws, crow, col, val) as gdrf_predict_score and gdrf_predict_loo take the counts, dense or CSR"""
+        if not is_sparse_counts(ws):
+            return (ws.data_ptr(), None, None, None), ws
+        crow, col, val = self._csr_arrays(ws)
+        if col.numel() == 0:      # an all-empty matrix: see predict_score
+            col = val = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return (None, crow.data_ptr(), col.data_ptr(), val.data_ptr()), (crow, col, val)
+
+    def predict_loo(self, xs: torch.Tensor, ws: torch.Tensor, num_samples: int, seed: Optional[int] = None, row_offset: int = 0,
+                    eps: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, return_log_lik: bool = False):
+        """Pareto-smoothed importance-sampling leave-one-out of the counts ``ws`` at the rows ``xs`` (gdrf_predict_loo,
+        csrc/predict_loo.h has the definition), (6, n) float64 in the order of LOO_NAMES, from the log likelihoods a_s predict_score
+        forms over the same ``num_samples`` draws (``seed`` / ``row_offset`` / ``eps`` / ``mean`` as there; ``lpd``, ``total`` and
+        ``log_coef`` are its, bit for bit).  LOO_MIN_SAMPLES <= num_samples <= LOO_MAX_SAMPLES.  ``return_log_lik``: also the (S, n)
+        float64 matrix of the a_s, as a second result.  ``ws``: dense (n, V) int32 or ``torch.sparse_csr``; no V is too large.
+        n <= n_cap.  Same jitter-level protocol as predict()."""
+        S = check_loo_args(num_samples, self.K, self.V, int(xs.shape[0]), ws, eps)
+        self._chk_rows(xs, ws)
+        n = xs.shape[0]
+        seed = self._mc_seed("predict_loo", n, eps, seed)
+        counts, _keep = self._score_counts(ws)
+        self.refresh_inducing()
+
+        def run():
+            out = torch.empty(len(LOO_NAMES), n, dtype=torch.float64, device=self.device)
+            a = torch.empty(S, n, dtype=torch.float64, device=self.device) if return_log_lik else None
+            _lib.check(self.lib.gdrf_predict_loo(self.ctx, xs.data_ptr(), n, self.Z.data_ptr(), self.params.data_ptr(), *counts, S,
+                                                 loo_tail_len(S), seed, int(row_offset), eps.data_ptr() if eps is not None else None,
+                                                 out.data_ptr(), a.data_ptr() if a is not None else None, _stream_ptr(self.device)),
+                       "gdrf_predict_loo")
+            return (out, a) if return_log_lik else out
+
+        with self._borrowed_mean(mean, n):
+            return self._speculated(run)
+
+    def psis_rows(self, log_lik: torch.Tensor) -> torch.Tensor:
+        """The PSIS stage alone on a caller's own (S, n) float64 log-likelihood matrix on the device (gdrf_psis_rows): (3, n) float64,
+        ``elpd_loo``, ``pareto_k`` and ``ess`` of every column as predict_loo forms them from its own a_s.  No model quantity is read."""
+        S, n = check_psis_args(log_lik)
+        if log_lik.dtype != torch.float64 or log_lik.device != self.device or not log_lik.is_contiguous():
+            raise ValueError(f"log_lik must be a contiguous float64 tensor on {self.device}")
+        out = torch.empty(3, n, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.gdrf_psis_rows(self.ctx, log_lik.data_ptr(), S, loo_tail_len(S), n, out.data_ptr(), _stream_ptr(self.device)),
+                   "gdrf_psis_rows")
+        return out
 
     def predict_quant(self, xs: torch.Tensor, mode: int, num_samples: int, levels=None, words: Optional[torch.Tensor] = None,
                       seed: Optional[int] = None, row_offset: int = 0, eps: Optional[torch.Tensor] = None,

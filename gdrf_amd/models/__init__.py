@@ -1,7 +1,7 @@
 """Model surface of the reference's ``gdrf.models`` (gdrf/models/__init__.py:1-18) for the SVI hot
 path.  Only ``SparseMultinomialGDRF`` (the north-star model) is built; the other exported names
 exist so that registries written against the reference fail with a clear message."""
-from .sparse_gdrf import ModelSnapshot, SparseMultinomialGDRF, validate_dirichlet_param, waic_from_pointwise
+from .sparse_gdrf import ModelSnapshot, SparseMultinomialGDRF, validate_dirichlet_param, waic_from_pointwise, loo_from_pointwise, compare_pointwise
 
 
 def _out_of_scope(name, why):
@@ -25,4 +25,4 @@ GDRF_MODEL_DICT = {
 }
 
 __all__ = ["GDRF", "MultinomialGDRF", "SparseGDRF", "SparseMultinomialGDRF", "SimpleGDRF", "SimpleMultinomialGDRF",
-           "GDRF_MODEL_DICT", "ModelSnapshot", "validate_dirichlet_param", "waic_from_pointwise"]
+           "GDRF_MODEL_DICT", "ModelSnapshot", "validate_dirichlet_param", "waic_from_pointwise", "loo_from_pointwise", "compare_pointwise"]

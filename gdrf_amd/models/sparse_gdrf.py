@@ -11,12 +11,14 @@ from __future__ import annotations
 
 import copy
 import functools
+import math
 from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
 from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
-from ..engine import (INFO_NAMES, QUANT_DOMINANT, QUANT_EXCEED, QUANT_QUANTILE, SCORE_NAMES, Engine, check_count_args, check_fold_args,
+from ..engine import (INFO_NAMES, LOO_NAMES, QUANT_DOMINANT, QUANT_EXCEED, QUANT_QUANTILE, SCORE_NAMES, Engine, check_count_args, check_fold_args,
+                      check_loo_args, check_psis_args,
                       check_joint_args, check_mc_args, check_quant_args, check_score_args, check_select_args)
 from ..kernels import Kernel, Product, embedded_coordinates
 
@@ -256,6 +258,45 @@ def waic_from_pointwise(d: Dict[str, torch.Tensor]) -> Dict[str, object]:
     elpd = point.sum()
     se = torch.sqrt(N * point.var(unbiased=True)) if N > 1 else torch.zeros((), dtype=torch.float64, device=point.device)
     return dict(elpd_waic=elpd, p_waic=var.sum(), waic=-2.0 * elpd, se=se, pointwise=point, n_high_variance=int((var > WAIC_HIGH_VARIANCE).sum()))
+
+
+def _sum_and_se(point: torch.Tensor):
+    """(sum, sqrt(N var)) of the (N,) pointwise terms, the unbiased variance over the rows, 0 for N = 1 - as waic_from_pointwise forms its own"""
+    N = point.numel()
+    se = torch.sqrt(N * point.var(unbiased=True)) if N > 1 else torch.zeros((), dtype=torch.float64, device=point.device)
+    return point.sum(), se
+
+
+def loo_from_pointwise(d: Dict[str, torch.Tensor], num_samples: Optional[int] = None) -> Dict[str, object]:
+    """PSIS leave-one-out from the (N,) maps of pointwise_loo (``elpd_loo``, ``lpd``, ``pareto_k`` and ``ess`` are read), in float64 torch
+    on whatever device they live on: ``elpd_loo`` the sum of the pointwise terms, ``p_loo`` = sum_n (lpd_n - elpd_loo_n) (the effective
+    number of parameters), ``looic`` = -2 elpd_loo, ``se`` = sqrt(N var(elpd_loo_n)) with the unbiased variance over the rows (0 for
+    N = 1), the ``pointwise`` terms, ``pareto_k`` and ``ess`` as they came, ``k_threshold`` = min(1 - 1 / log10(S), 0.7) (Vehtari et al.
+    2024) with S = ``num_samples`` or, without it, d["num_samples"] or the rows of d["log_lik"], ``n_bad_k`` the rows with pareto_k above
+    the threshold (there the estimate is unreliable; NaN does not count) and ``n_not_fitted`` the rows whose pareto_k is NaN (constant
+    log likelihoods or an underflowing tail: nothing was smoothed)."""
+    point, lpd, k = (torch.as_tensor(d[name]).double() for name in ("elpd_loo", "lpd", "pareto_k"))
+    if point.dim() != 1 or point.numel() < 1 or lpd.shape != point.shape or k.shape != point.shape:
+        raise ValueError(f"elpd_loo, lpd and pareto_k must be (N,) maps of the same N >= 1, got {tuple(point.shape)}, {tuple(lpd.shape)} and {tuple(k.shape)}")
+    if num_samples is None:
+        num_samples = d["num_samples"] if "num_samples" in d else d["log_lik"].shape[0] if "log_lik" in d else None
+    if num_samples is None or int(num_samples) < 2:
+        raise ValueError("loo_from_pointwise needs num_samples >= 2 (as an argument, as d['num_samples'] or through d['log_lik'])")
+    elpd, se = _sum_and_se(point)
+    thr = min(1.0 - 1.0 / math.log10(int(num_samples)), 0.7)
+    return dict(elpd_loo=elpd, p_loo=(lpd - point).sum(), looic=-2.0 * elpd, se=se, pointwise=point, pareto_k=k, ess=torch.as_tensor(d["ess"]).double(),
+                k_threshold=thr, n_bad_k=int((k > thr).sum()), n_not_fitted=int(torch.isnan(k).sum()))
+
+
+def compare_pointwise(a, b) -> Dict[str, torch.Tensor]:
+    """Two fits on the same rows from their (N,) pointwise terms, of WAIC or of LOO (the ``pointwise`` entries): ``elpd_diff`` = sum(a - b),
+    positive where the first fit predicts better, and ``se_diff`` = sqrt(N var(a - b)), the standard error of that difference (the
+    unbiased variance over the rows, 0 for N = 1) - far smaller than the two standard errors suggest, because the rows are paired."""
+    a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
+    if a.dim() != 1 or a.shape != b.shape or a.numel() < 1:
+        raise ValueError(f"the pointwise terms must be (N,) vectors over the same N >= 1 rows, got {tuple(a.shape)} and {tuple(b.shape)}")
+    diff, se = _sum_and_se(a - b)
+    return dict(elpd_diff=diff, se_diff=se)
 
 
 def _all_words(V: int, words):
@@ -733,6 +774,53 @@ class SparseMultinomialGDRF:
         rows whose var_log_lik is above 0.4 (there WAIC is unreliable).  ``normalized`` as in pointwise_log_likelihood: it shifts every
         model's elpd on the same data by the same constant."""
         return waic_from_pointwise(self.pointwise_log_likelihood(xs, ws, num_samples, seed=seed, normalized=normalized))
+
+    # ------------------------------------------------------------------ PSIS leave-one-out (csrc/predict_loo.h)
+    def pointwise_loo(self, xs, ws, num_samples: int = 256, seed=None, eps=None, normalized: bool = False,
+                      return_log_lik: bool = False) -> Dict[str, torch.Tensor]:
+        """Pareto-smoothed importance-sampling leave-one-out, row by row: a dict of six (N,) float64 tensors from the log likelihoods a_s
+        of pointwise_log_likelihood over the same ``num_samples`` draws (``seed`` / ``eps`` as there; 25 .. 1024 draws): ``elpd_loo`` the
+        estimate of the row's log predictive density had the row been held out, ``pareto_k`` the shape of the generalised Pareto tail
+        fitted to the row's largest importance ratios (above min(1 - 1 / log10(S), 0.7) the estimate is unreliable; NaN where nothing is
+        fitted: constant a_s or an underflowing tail), ``ess`` the effective sample size of the smoothed weights, and ``lpd``, ``total``,
+        ``log_coef`` as pointwise_log_likelihood returns them, bit for bit.  ``elpd_loo`` and ``lpd`` leave the Multinomial coefficient
+        out; ``normalized=True`` adds it to both.  ``return_log_lik=True`` adds ``log_lik``, the (S, N) float64 matrix of the a_s.
+        ``ws``: dense counts or a ``torch.sparse_csr`` matrix; no V is too large.  Over pieces of at most the engine's n_cap rows as
+        pointwise_log_likelihood cuts them; a row's values do not depend on the pieces.  (A ModelSnapshot does not forward this method:
+        call it on ``snap.restore()``.)"""
+        if self._link_function is not None:
+            raise NotImplementedError("pointwise_loo with a custom link_function: the kernel fuses the softmax link; form the (S, N) log "
+                                      "likelihoods with torch and hand them to psis")
+        n = int(torch.as_tensor(xs).shape[0])
+        S = check_loo_args(num_samples, self._K, self._V, n, ws, eps)
+        xs_s, ws_d = self._prepare_inputs(xs, ws)
+        call = lambda eng, x, a, b, whole, **kw: eng.predict_loo(x, count_rows(ws_d, a, b, whole), S, return_log_lik=return_log_lik, **kw)
+        out = self._mc_pieces(xs_s, call, (1, 1) if return_log_lik else 1, seed, eps)
+        d = dict(zip(LOO_NAMES, out[0] if return_log_lik else out))
+        if normalized:
+            d["elpd_loo"] = d["elpd_loo"] + d["log_coef"]
+            d["lpd"] = d["lpd"] + d["log_coef"]
+        if return_log_lik:
+            d["log_lik"] = out[1]
+        return d
+
+    def loo(self, xs, ws, num_samples: int = 256, seed=None, normalized: bool = False) -> Dict[str, object]:
+        """PSIS leave-one-out cross-validation of the rows (xs, ws) under the guide's posterior, the remedy where waic reports rows of
+        high variance: loo_from_pointwise of pointwise_loo - ``elpd_loo``, ``p_loo``, ``looic`` = -2 elpd_loo, the standard error ``se``,
+        the ``pointwise`` terms, ``pareto_k``, ``ess``, ``k_threshold``, ``n_bad_k`` and ``n_not_fitted``.  ``normalized`` as in
+        pointwise_loo.  Two fits on the same rows are compared with compare_pointwise of their ``pointwise`` terms.  (A ModelSnapshot does
+        not forward this method: call it on ``snap.restore()``.)"""
+        return loo_from_pointwise(self.pointwise_loo(xs, ws, num_samples, seed=seed, normalized=normalized), int(num_samples))
+
+    def psis(self, log_lik) -> Dict[str, torch.Tensor]:
+        """The PSIS stage on a caller's own (S, n) matrix of log likelihoods - a custom link_function's, or another model's - as a dict of
+        the (n,) float64 maps ``elpd_loo``, ``pareto_k`` and ``ess``, over pieces of at most the engine's n_cap columns.  25 <= S <= 1024.
+        (A ModelSnapshot does not forward this method: call it on ``snap.restore()``.)"""
+        S, n = check_psis_args(torch.as_tensor(log_lik))
+        a = torch.as_tensor(log_lik).to(device=self.device, dtype=torch.float64)
+        eng = self._engine_for(min(n, MC_PIECE_ROWS))
+        out = join_pieces([eng.psis_rows(a[:, lo:hi].contiguous()) for lo, hi, _ in row_pieces(n, eng.n_cap)], 1)
+        return dict(zip(LOO_NAMES[:3], out))
 
     def row_perplexity(self, xs, ws, num_samples: int = 64, seed=None) -> torch.Tensor:
         """(N,) float64: exp(-lpd_n / total_n), the per-token perplexity of each row under the posterior predictive - the map of the samples

@@ -411,6 +411,33 @@ int gdrf_predict_quant(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* 
                        const int32_t* words_dev, int nwords, double* out_dev, void* stream);
 int gdrf_quant_last_plan(const gdrf_ctx* ctx, int out[3]);
 
+/* Pareto-smoothed importance-sampling leave-one-out (csrc/predict_loo.h has the definition, step by step): for each of n observed rows, from
+ * the S = num_samples log likelihoods a_s that gdrf_predict_score forms (the same draws, eps_dev / seed / row_offset, the same counts in
+ * either layout, bit for bit) out_dev (6, n) doubles holds the rows
+ *   0  elpd_loo  the row's held-out log predictive density, logsumexp_s(a_s + lw_s) with the smoothed, truncated, normalised log
+ *                weights lw of the importance ratios 1 / p(w_n | theta_s)
+ *   1  pareto_k  the shape of the generalised Pareto distribution fitted to the M = tail_len largest ratios (Zhang & Stephens 2009 with
+ *                the weakly informative prior of Vehtari et al.); NaN where nothing is fitted: the tail's lower quartile is not above
+ *                the cutoff (constant a_s - an empty row, K = 1, V = 1, eps = 0 - or an underflowing tail)
+ *   2  ess       1 / sum_s exp(2 lw_s), the effective sample size of the weights
+ *   3  lpd  4  total  5  log_coef    rows 0, 3 and 4 of gdrf_predict_score, bit for bit
+ * Rows 0 and 3 leave the Multinomial coefficient out.  Everything from the a_s on is in double.  tail_len must be
+ * ceil(min(S / 5, 3 sqrt(S))) formed in double (the Python layer's engine.loo_tail_len); GDRF_LOO_MIN_SAMPLES <= num_samples <=
+ * GDRF_LOO_MAX_SAMPLES: all S values of a row are kept in LDS and ordered there.  a_out_dev, optional, (S, n) doubles, receives the a_s.
+ * Any V, dense or CSR, every K the context supports; n <= n_cap.  Runs the step's forward (as mode 4 of gdrf_predict), so it overwrites
+ * the same workspaces; every step recomputes them.  Every output is bit-identical however the rows are batched (no atomics, nothing
+ * shared between rows).  Needs gdrf_factorize().
+ * gdrf_psis_rows: the same from a caller's own log_lik_dev (S, n) doubles - out_dev (3, n): elpd_loo, pareto_k, ess - for models whose
+ * a_s the library cannot form; no model quantity is read, no factorisation needed, any n >= 1.
+ * gdrf_loo_last_plan: (rows per workgroup pass RP, dynamic LDS bytes) of the last launch of either - csrc/forms.h::loo_plan. */
+#define GDRF_LOO_MAX_SAMPLES 1024
+#define GDRF_LOO_MIN_SAMPLES 25
+int gdrf_predict_loo(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const int32_t* ws_dev,
+                     const int64_t* crow_dev, const int32_t* col_dev, const int32_t* val_dev, int num_samples, int tail_len, uint64_t seed,
+                     int64_t row_offset, const void* eps_dev, double* out_dev, double* a_out_dev, void* stream);
+int gdrf_psis_rows(gdrf_ctx* ctx, const double* log_lik_dev, int num_samples, int tail_len, int64_t n, double* out_dev, void* stream);
+int gdrf_loo_last_plan(const gdrf_ctx* ctx, int out[2]);
+
 /* Fold-in (csrc/foldin.h): the topic proportions of OBSERVED rows from their own counts, with the GP as the prior.  For row n, with
  *   m_k = f_loc[k][n] + mean[k][n],  s_k = f_var[k][n] + noise   ((f_loc, f_var) as mode 4 of gdrf_predict gives them; s_k is the scale of the
  *   model's mu site, Normal(f_loc, f_var + noise), gdrf/models/sparse_gdrf.py:354-357),  R = sum_v w_v,  theta = softmax(mu),  p = theta Phi:
