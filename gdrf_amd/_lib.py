@@ -74,6 +74,7 @@ SIGNATURES = {
     "gdrf_sample_joint_retry": (_int, [_vp, _i64, _int, _dbl, _vp, _vp]),
     "gdrf_joint_failed": (_int, [_vp, C.POINTER(_int), _vp]),
     "gdrf_select_batch": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp]),
+    "gdrf_select_inducing": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdrf_chol_failed": (_int, [_vp, C.POINTER(_int), _vp]),
     "gdrf_ws_ptr": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_i64)]),
     "gdrf_ws_elem_size": (_int, [_vp, _int]),

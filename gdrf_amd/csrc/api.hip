@@ -18,6 +18,7 @@
 #include "sample_counts.h"
 #include "predict_cov.h"
 #include "select_batch.h"
+#include "select_inducing.h"
 #include "rows_lds.h"
 #include "rows_mfma.h"
 #include "rows_vstream.h"
@@ -2189,6 +2190,77 @@ template <typename T, typename TS> struct Impl {
     LAUNCHCHK("select_batch");
     return 0;
   }
+
+  // ---- the greedy conditional-variance choice of inducing points (select_inducing.h): no factorisation, no forward.  The hyper-parameter block
+  // and, in periodic and product contexts, the embedded rows are the call's own: the context's (c->hyp, c->Xe) belong to its factorisation and
+  // its steps.  Everything the call needs is one block of device memory, released before it returns: (G + count + 1)(n + G) solve-precision
+  // elements and the small pieces behind them.
+  static int select_inducing(gdrf_ctx* c, const T* X, int64_t n, const T* params, const T* given, int G, int count, double floor, int64_t* idx_out,
+                             double* pivots_out, double* trace_out, double* resid_out, int* rank_out, hipStream_t s) {
+    const int Tm = G + count;
+    const int64_t nt = n + G, ntiles = (nt + GDRF_IND_ROWS - 1) / GDRF_IND_ROWS;
+    const int nparts = (int)std::min<int64_t>(ntiles, GDRF_IND_PARTS);
+    const size_t row = (size_t)c->Dr * c->esz;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t o = off; off = (size_t)round_up((int64_t)(off + bytes), 256); return o; };
+    const size_t oC = take((size_t)Tm * nt * sizeof(TS)), oD = take((size_t)nt * sizeof(TS)), oTk = take((size_t)nt * sizeof(int));
+    const size_t oX = take(G > 0 ? (size_t)nt * row : 0), oXe = take(c->per ? (size_t)nt * c->D * c->esz : 0);
+    const size_t oHp = take((size_t)GDRF_INDUCING_MAX_PICKS * sizeof(TS)), oPg = take((size_t)nparts * sizeof(double));
+    const size_t oPi = take((size_t)nparts * sizeof(long long)), oTr = take((size_t)ntiles * sizeof(double));
+    const size_t oPk = take(sizeof(IndPick)), oH = take(sizeof(HyperPer));
+    struct Block {            // released on every way out, once the stream has finished with it
+      char* p = nullptr; hipStream_t s;
+      ~Block() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
+    } blk;
+    blk.s = s;
+    {
+      hipError_t e = hipMalloc((void**)&blk.p, off);
+      if (e != hipSuccess) { blk.p = nullptr; return fail(-(int)e - 1000, "hipMalloc(inducing choice)", hipGetErrorString(e)); }
+    }
+    char* b = blk.p;
+    TS* cbuf = Q(b + oC);
+    TS* d = Q(b + oD);
+    int* taken = (int*)(b + oTk);
+    TS* hp = Q(b + oHp);
+    double* part_g = (double*)(b + oPg);
+    long long* part_i = (long long*)(b + oPi);
+    double* part_tr = (double*)(b + oTr);
+    IndPick* pick = (IndPick*)(b + oPk);
+    Hyper* h = (Hyper*)(b + oH);
+    const T* Xa = X;
+    if (G > 0) {
+      HIPCHK(hipMemcpyAsync(b + oX, X, (size_t)n * row, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(b + oX + (size_t)n * row, given, (size_t)G * row, hipMemcpyDeviceToDevice, s));
+      Xa = (const T*)(b + oX);
+    }
+    if (c->per) {
+      const CoordTab tb = coord_tab(c);
+      const int64_t nx = nt * tb.nsrc;
+      hipLaunchKernelGGL(prep_hyper_per_kernel<T>, dim3(1), dim3(64), 0, s, params, tb, (HyperPer*)h);
+      hipLaunchKernelGGL((embed_per_kernel<T, T>), dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, nt, tb, Xa, params, (T*)(b + oXe), (T*)nullptr);
+      Xa = (const T*)(b + oXe);
+    } else if (c->ard) {
+      hipLaunchKernelGGL(prep_hyper_ard_kernel<T>, dim3(1), dim3(64), 0, s, params, params + param_lay(c).ard, c->D, h);
+    } else {
+      hipLaunchKernelGGL(prep_hyper_kernel<T>, dim3(1), dim3(64), 0, s, params, h);
+    }
+    hipLaunchKernelGGL(inducing_init_kernel<TS>, dim3((unsigned)nparts), dim3(256), 0, s, n, nt, c->kind, (const Hyper*)h, d, taken, part_g, part_i, part_tr);
+    IndPrep<TS> pr{0, G, Tm, nparts, n, nt, ntiles, floor, part_g, part_i, part_tr, (const TS*)cbuf, (const TS*)d, hp, pick, taken,
+                   (long long*)idx_out, pivots_out, trace_out, rank_out};
+    IndPass<TS, T> ps{0, c->D, c->kind, n, nt, (const Hyper*)h, Xa, (const TS*)hp, (const IndPick*)pick, cbuf, d, taken, part_g, part_i, part_tr};
+    for (int t = 0; t <= Tm; ++t) {           // t = Tm: the trace of the last pass
+      pr.t = ps.t = t;
+      hipLaunchKernelGGL(inducing_prep_kernel<TS>, dim3(1), dim3(256), 0, s, pr);
+      if (t == Tm) break;
+      const size_t lds = (size_t)t * sizeof(TS);
+      if (ard_fwd(c)) hipLaunchKernelGGL((inducing_pass_kernel<TS, T, true>), dim3((unsigned)nparts), dim3(256), lds, s, ps);
+      else hipLaunchKernelGGL((inducing_pass_kernel<TS, T, false>), dim3((unsigned)nparts), dim3(256), lds, s, ps);
+    }
+    if (resid_out) hipLaunchKernelGGL(inducing_resid_out_kernel<TS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const TS*)d, n, resid_out);
+    LAUNCHCHK("select_inducing");
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+  }
 };
 
 
@@ -2655,6 +2727,24 @@ int gdrf_select_batch(gdrf_ctx* c, const void* X, int64_t n, const void* Z, cons
   if (!idx_out || !gains_out) return fail(-1, "gdrf_select_batch", "idx_out and gains_out are required");
   hipStream_t s = (hipStream_t)stream;
   TYPED3(c, select_batch, c, (const T*)X, n, (const T*)Z, (const T*)params, (const T*)given, G, count, noise, idx_out, gains_out, var_out, s);
+}
+
+int gdrf_select_inducing(gdrf_ctx* c, const void* X, int64_t n, const void* params, const void* given, int G, int count, double floor, int64_t* idx_out,
+                         double* pivots_out, double* trace_out, double* resid_out, int* rank_out, void* stream) {
+  HIPCHK(hipSetDevice(c->dev));
+  if (n < 1) return fail(-1, "gdrf_select_inducing", "n must be >= 1");
+  if (G < 0) return fail(-1, "gdrf_select_inducing", "G must be >= 0");
+  if (n + G > c->ncap) return fail(-1, "gdrf_select_inducing", "needs n + G <= n_cap");
+  if (count < 0 || count > n) return fail(-1, "gdrf_select_inducing", "count must be in [0, n]");
+  if (G + count < 1) return fail(-1, "gdrf_select_inducing", "needs G + count >= 1");
+  if (G + count > GDRF_INDUCING_MAX_PICKS) return fail(-1, "gdrf_select_inducing", "G + count exceeds GDRF_INDUCING_MAX_PICKS (1024)");
+  if (!(floor >= 0) || !std::isfinite(floor)) return fail(-1, "gdrf_select_inducing", "floor must be finite and >= 0");
+  if (!X || !params) return fail(-1, "gdrf_select_inducing", "X_dev and params_dev are required");
+  if (G > 0 && !given) return fail(-1, "gdrf_select_inducing", "G > 0 needs given_dev");
+  if (!pivots_out || !trace_out || !rank_out || (count > 0 && !idx_out))
+    return fail(-1, "gdrf_select_inducing", "idx_out (count > 0), pivots_out, trace_out and rank_out are required");
+  hipStream_t s = (hipStream_t)stream;
+  TYPED3(c, select_inducing, c, (const T*)X, n, (const T*)params, (const T*)given, G, count, floor, idx_out, pivots_out, trace_out, resid_out, rank_out, s);
 }
 
 int gdrf_joint_failed(gdrf_ctx* c, int* failed, void* stream) {

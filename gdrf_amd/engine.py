@@ -306,6 +306,53 @@ def check_select_args(count, noise, n: int, given=None, dims: Optional[int] = No
     return cnt, noise, G
 
 
+# The most pivots a choice of inducing points takes (Engine.select_inducing): the given rows and the free picks together
+# (GDRF_INDUCING_MAX_PICKS of include/gdrf_hip.h).  Its factor storage is (G + count) x (n + G) solve-precision elements, held for the call.
+INDUCING_MAX_PICKS = 1024
+
+
+def check_inducing_args(count, floor, n: int, given=None, dims: Optional[int] = None):
+    """The argument errors of the choice of inducing points (Engine.select_inducing and the model method above it), raised before the device
+    is touched: an integral ``count`` in [0, n], a ``given`` of shape (G, dims) with 1 <= G + count <= INDUCING_MAX_PICKS, a finite
+    ``floor`` >= 0 (None: the caller fills in the model's own and the check is skipped).  Returns (count as an int, floor as a float or
+    None, G)."""
+    if n < 1:
+        raise ValueError(f"select_inducing needs at least one row, got {n}")
+    if isinstance(count, bool) or isinstance(count, str) or int(count) != count:
+        raise ValueError(f"count must be an integer, got {count!r}")
+    cnt = int(count)
+    if not 0 <= cnt <= n:
+        raise ValueError(f"count must be in [0, N = {n}], got {count}")
+    G = 0
+    if given is not None:
+        shape = tuple(given.shape)
+        if len(shape) == 1 and dims == 1:
+            shape = (shape[0], 1)
+        if len(shape) != 2 or (dims is not None and shape[1] != dims):
+            raise ValueError(f"given must have shape (G, {dims}), the columns of xs, got {tuple(given.shape)}")
+        G = int(shape[0])
+    if G + cnt < 1:
+        raise ValueError("count = 0 needs given rows to score: the given rows and the picks together are at least 1")
+    if G + cnt > INDUCING_MAX_PICKS:
+        raise ValueError(f"the given rows and the picks together are at most INDUCING_MAX_PICKS = {INDUCING_MAX_PICKS}, got {G} + {cnt}")
+    if floor is not None:
+        if isinstance(floor, bool) or not math.isfinite(float(floor)) or not float(floor) >= 0.0:
+            raise ValueError(f"floor must be a finite number >= 0, got {floor!r}")
+        floor = float(floor)
+    return cnt, floor, G
+
+
+def thin_rows(n: int, max_candidates: int) -> Optional[torch.Tensor]:
+    """The rows a choice among more than ``max_candidates`` rows looks at: floor(i n / c) for i < c = max_candidates, increasing and
+    distinct (int64, on the CPU); None when n <= max_candidates: every row."""
+    if isinstance(max_candidates, bool) or int(max_candidates) != max_candidates or int(max_candidates) < 1:
+        raise ValueError(f"max_candidates must be a positive integer, got {max_candidates!r}")
+    c = int(max_candidates)
+    if n <= c:
+        return None
+    return (torch.arange(c, dtype=torch.int64) * n) // c
+
+
 def param_table(K: int, M: int, V: int, D: int, kernel: str = "rbf", *, ard: bool = False, period_count: int = 0, product=None,
                 learn_inducing: bool = False, mean_shapes=None, raw) -> Dict[str, tuple]:
     """{name: (offset, shape)} of every learnt parameter tensor of a context, in the order of Engine.param_names (that of state_dict(),
@@ -1421,3 +1468,34 @@ class Engine:
             return (idx, gains, var) if return_variance else (idx, gains)
 
         return self._speculated(run)
+
+    # ---- the greedy conditional-variance choice of inducing points (csrc/select_inducing.h) ----------------
+    def select_inducing(self, xs: torch.Tensor, count: int, given: Optional[torch.Tensor] = None, floor: float = 0.0,
+                        return_residual: bool = False):
+        """The ``count`` rows of ``xs`` the pivoted partial Cholesky of the prior kernel matrix K_nn picks (gdrf_select_inducing,
+        csrc/select_inducing.h has the definition), at the kernel hyper-parameters in ``params``: (indices (count,) int64 in the order
+        picked, pivots (G + count,) float64, residual trace tr(K_nn - Q_nn) after every pick (G + count,) float64, rank[, residual (n,)
+        float64: diag(K_nn - Q_nn) after the last pick]).  ``given`` (G, D): points already there, forced pivots ahead of the free picks;
+        ``count`` = 0 scores them.  A pivot at or below ``floor`` is degenerate and does not count towards the rank.  All rows at once:
+        n + G <= n_cap and G + count <= INDUCING_MAX_PICKS.  No factorisation is needed and neither Z nor the variational parameters
+        enter; the (G + count + 1) (n + G) solve-precision elements it needs are held for the call only."""
+        count, floor, G = check_inducing_args(count, floor, int(xs.shape[0]), given, int(xs.shape[1]) if xs.dim() == 2 else None)
+        if floor is None:
+            raise ValueError("floor must be a finite number >= 0, got None")
+        self._chk_rows(xs)
+        n = xs.shape[0]
+        if G:
+            self._chk_rows(given)
+        if n + G > self.n_cap:
+            raise ValueError(f"select_inducing needs n + G <= n_cap ({n} + {G} > {self.n_cap})")
+        idx = torch.empty(count, dtype=torch.int64, device=self.device)
+        pivots = torch.empty(G + count, dtype=torch.float64, device=self.device)
+        trace = torch.empty(G + count, dtype=torch.float64, device=self.device)
+        resid = torch.empty(n, dtype=torch.float64, device=self.device) if return_residual else None
+        rank = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gdrf_select_inducing(self.ctx, xs.data_ptr(), n, self.params.data_ptr(), given.data_ptr() if G else None, G, count,
+                                                 floor, idx.data_ptr() if count else None, pivots.data_ptr(), trace.data_ptr(),
+                                                 resid.data_ptr() if resid is not None else None, rank.data_ptr(), _stream_ptr(self.device)),
+                   "gdrf_select_inducing")
+        rank = int(rank.item())
+        return (idx, pivots, trace, rank, resid) if return_residual else (idx, pivots, trace, rank)

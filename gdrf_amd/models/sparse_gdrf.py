@@ -19,8 +19,11 @@ import torch
 from ..data import check_counts, csr_rows, csr_to, is_sparse_counts
 from ..engine import (INFO_NAMES, LOO_NAMES, QUANT_DOMINANT, QUANT_EXCEED, QUANT_QUANTILE, SCORE_NAMES, Engine, check_count_args, check_fold_args,
                       check_loo_args, check_psis_args,
-                      check_joint_args, check_mc_args, check_quant_args, check_score_args, check_select_args)
+                      check_joint_args, check_mc_args, check_quant_args, check_score_args, check_select_args, check_inducing_args, thin_rows)
 from ..kernels import Kernel, Product, embedded_coordinates
+
+# The most rows choose_inducing_points looks at by default (more are thinned), and inducing_init="greedy" always
+GREEDY_MAX_CANDIDATES = 131072
 
 _PARAM_KEYS = {  # state_dict names follow pyro's "<name>_unconstrained" convention
     "log_lengthscale": "_kernel.lengthscale_unconstrained",
@@ -347,8 +350,17 @@ class SparseMultinomialGDRF:
         inducing_points: Optional[torch.Tensor] = None,
         seed: Optional[int] = None,
         guide_rescale: bool = True,
+        inducing_candidates: Optional[torch.Tensor] = None,
         **kwargs,
     ):
+        """``inducing_init``: "random" and "grid" are the reference's tensor-product meshes over the world.  "greedy" chooses the M =
+        prod(n_points) inducing points among rows of the data, by the conditional-variance rule of choose_inducing_points at the kernel's
+        initial hyper-parameters; the candidates are ``inducing_candidates`` (N, D) or, without them, the ``xs`` handed to the constructor
+        (more than 131072 rows are thinned as choose_inducing_points thins them).  It raises a ValueError where the data hold fewer than M
+        distinct places under this kernel.  The ranks of a multi-GPU run do not talk in the constructor: hand every rank the same
+        candidates (not its own shard of the rows), or the ranks start from different inducing points.  An explicit ``inducing_points``
+        tensor takes precedence over ``inducing_init`` (deep copies, snapshots and engine growth pass the stored points: nothing is
+        selected again)."""
         if link_function is not None and not callable(link_function):
             raise TypeError("link_function must be callable")
         # abstract_gdrf.py:34-50: None = softmax over the topics (fused into the row kernel).  A callable maps the (K, N) tensor mu to
@@ -414,6 +426,7 @@ class SparseMultinomialGDRF:
         self.rng_seed = int(torch.initial_seed() if seed is None else seed) & (2 ** 63 - 1)
         gen = torch.Generator().manual_seed(self.rng_seed)
         # ---- inducing points: sparse_gdrf.py:54-77
+        greedy_candidates = None
         if inducing_points is not None:
             Z = torch.as_tensor(inducing_points, dtype=torch.float64)
         else:
@@ -423,11 +436,29 @@ class SparseMultinomialGDRF:
             elif inducing_init == "grid":
                 pts = [torch.arange(b[0], b[1] + (b[1] - b[0]) / (n - 1) - 1e-10, (b[1] - b[0]) / (n - 1), dtype=torch.float64)
                        for b, n in zip(self._world, self._n_points)]
+            elif inducing_init == "greedy":
+                pts = None
             else:
                 raise ValueError(f"inducing_init argument {inducing_init} not valid. Only 'random' and 'grid' are "
-                                 "currently supported")
-            Z = torch.stack([x.flatten() for x in torch.meshgrid(*pts, indexing="ij")]).T
-            Z = (Z - self._lower) / self._delta
+                                 "currently supported, and 'greedy' (inducing points chosen among the rows of the data)")
+            if pts is None:
+                cand = inducing_candidates if inducing_candidates is not None else kwargs.get("xs")
+                if cand is None:
+                    raise ValueError("inducing_init='greedy' chooses the inducing points among rows of the data: pass xs= or "
+                                     "inducing_candidates= to the constructor")
+                cand = torch.as_tensor(cand)
+                if cand.dim() == 1 and self._n_dims == 1:
+                    cand = cand.unsqueeze(-1)
+                M_greedy = math.prod(int(n) for n in self._n_points)
+                if cand.dim() != 2 or cand.shape[1] != self._n_dims:
+                    raise ValueError(f"the candidates of inducing_init='greedy' must have shape (N, {self._n_dims}), got {tuple(cand.shape)}")
+                check_inducing_args(M_greedy, None, min(int(cand.shape[0]), GREEDY_MAX_CANDIDATES))
+                greedy_candidates = cand
+                Z = torch.zeros(M_greedy, self._n_dims, dtype=torch.float64)       # a placeholder until _init_params has chosen
+            else:
+                Z = torch.stack([x.flatten() for x in torch.meshgrid(*pts, indexing="ij")]).T
+                Z = (Z - self._lower) / self._delta
+        self._greedy_candidates = greedy_candidates
         self._inducing_points = Z.to(dtype).contiguous()
         self.M, self.D = int(Z.shape[0]), int(Z.shape[1])
         self.latent_shape = torch.Size([self._K])
@@ -439,7 +470,10 @@ class SparseMultinomialGDRF:
         ws0 = kwargs.get("ws")
         if ws0 is not None and is_sparse_counts(ws0):      # a sparse count matrix: validated here, before the device is touched
             check_counts(ws0, int(xs.shape[0]) if xs is not None else None, self._V)
-        self._engine_for(int(xs.shape[0]) if xs is not None else 1)
+        n0 = int(xs.shape[0]) if xs is not None else 1
+        if greedy_candidates is not None:              # the engine that chooses holds the (thinned) candidates
+            n0 = max(n0, min(int(greedy_candidates.shape[0]), GREEDY_MAX_CANDIDATES))
+        self._engine_for(n0)
 
     # ------------------------------------------------------------------ engine / parameters
     def _engine_for(self, n: int) -> Engine:
@@ -476,6 +510,16 @@ class SparseMultinomialGDRF:
                     v = eng.view((path + "." if path else "") + "log_" + name)
                     v.copy_(getattr(k, name).log().reshape(v.shape))
             eng.view("log_noise").fill_(float(torch.tensor(self._init_noise, dtype=torch.float64).log()))
+            if self._greedy_candidates is not None:
+                # inducing_init="greedy": the kernel's hyper-parameters are in place, nothing below has read Z yet
+                cand, self._greedy_candidates = self._greedy_candidates, None
+                res = self._choose_inducing(eng, cand, self.M, None, GREEDY_MAX_CANDIDATES, False)
+                if res["rank"] < self.M:
+                    raise ValueError(f"inducing_init='greedy': the candidates hold only {res['rank']} distinct places under this kernel "
+                                     f"(the rank of the selection), fewer than the M = {self.M} inducing points asked for: lower n_points "
+                                     "or pass more varied candidates")
+                eng.set_inducing_points(res["scaled"])
+                self._inducing_points = eng.Z
             eng.view("u_loc").zero_()
             ret = torch.softmax(self._dirichlet_param, dim=-2)           # over K (abstract_gdrf.py:68-69)
             if self._randomize_wt:
@@ -911,6 +955,64 @@ class SparseMultinomialGDRF:
             noise = check_select_args(count, float(self.noise), n)[1]
         return eng.select_batch(xs_s, count, noise, given=given_s, return_variance=return_variance)
 
+    # ------------------------------------------------------------------ inducing points from the data (csrc/select_inducing.h)
+    def _kernel_variance_now(self, eng) -> float:
+        """k(x, x) at the engine's current hyper-parameters: the variance, a product kernel's product of its factors' variances"""
+        names = [n for n in eng.param_names if n == "log_variance" or n.endswith(".log_variance")]
+        return math.exp(sum(float(eng.view(n).double().sum()) for n in names))
+
+    def _choose_inducing(self, eng, xs, count, given, max_candidates, return_residual):
+        """choose_inducing_points on the engine ``eng`` (the constructor calls it before the model's engine is in place): the argument
+        checks, the thinning, the scaling, the floor, Engine.select_inducing and the indices mapped back to the rows of ``xs``"""
+        xs_t = torch.as_tensor(xs)
+        g_t = None if given is None else torch.as_tensor(given)
+        n_all = int(xs_t.shape[0])
+        thin = thin_rows(n_all, max_candidates)
+        n = n_all if thin is None else int(thin.numel())
+        count, _, G = check_inducing_args(count, None, n, g_t, 1 if xs_t.dim() == 1 else int(xs_t.shape[1]))
+        if n + G > eng.n_cap:
+            raise ValueError(f"choose_inducing_points needs n + G <= n_cap ({n} + {G} > {eng.n_cap})")
+        xs_c = xs_t if thin is None else xs_t[thin.to(xs_t.device)]
+        xs_s, _ = self._prepare_inputs(xs_c)
+        given_s = self._prepare_inputs(g_t)[0] if G else None
+        eps = torch.finfo(torch.float32 if eng.pure_fp32 else torch.float64).eps
+        floor = max(self._jitter, (G + count) * eps * self._kernel_variance_now(eng))
+        out = eng.select_inducing(xs_s, count, given=given_s, floor=floor, return_residual=return_residual)
+        idx = out[0]
+        idx_all = idx if thin is None else thin.to(idx.device)[idx]
+        res = dict(indices=idx_all, points=xs_t.to(idx.device)[idx_all] if xs_t.dim() == 2 else xs_t.to(idx.device)[idx_all].unsqueeze(-1),
+                   pivots=out[1], residual_trace=out[2], rank=out[3], floor=floor, scaled=xs_s[idx])
+        if return_residual:
+            res["residual"] = out[4]
+        return res
+
+    def choose_inducing_points(self, xs, count: Optional[int] = None, given=None, max_candidates: int = GREEDY_MAX_CANDIDATES,
+                               return_residual: bool = False):
+        """Which ``count`` (default: M) rows of ``xs`` to use as inducing points: the greedy conditional-variance selection (Burt, Rasmussen
+        and van der Wilk 2020, Alg. 1), the pivoted partial Cholesky of the prior kernel matrix K_nn at the kernel's CURRENT
+        hyper-parameters.  Each pick is the row the points chosen so far explain worst, equal values to the lower index.  A dict:
+        ``indices`` (count,) int64 into ``xs`` in the order picked; ``points`` (count, D), those rows in the world's coordinates;
+        ``pivots`` (G + count,) float64, the conditional prior variance of each pick when it was made (the given rows first), never
+        increasing over the free picks; ``residual_trace`` (G + count,) float64, tr(K_nn - Q_nn) after each pick, the quantity the bound
+        on the sparse approximation is written in; ``rank``, the picks whose pivot was above the floor max(jitter, (G + count) eps k(x, x))
+        (fewer than G + count: the rows hold no more distinct places under this kernel, the later picks explain nothing); ``floor``;
+        with ``return_residual`` ``residual`` (n,) float64, diag(K_nn - Q_nn) after the last pick, over the candidate rows.  ``given``
+        (G, D), in the world's coordinates like ``xs``: points already there, conditioned on first; with ``count`` = 0 the call scores
+        them, e.g. the model's own points (``inducing_points`` is in the scaled world: the same thing for a unit world).  More than
+        ``max_candidates`` rows are thinned to the rows floor(i n / max_candidates); ``indices`` still refer to ``xs`` and ``residual`` to
+        the thinned rows.  The model is not changed: M is fixed at construction, SparseMultinomialGDRF(inducing_init="greedy") or
+        inducing_points=... start a model from such a choice.  All candidates in one call, G + count <= INDUCING_MAX_PICKS."""
+        xs_t = torch.as_tensor(xs)
+        n_all = int(xs_t.shape[0])
+        thin = thin_rows(n_all, max_candidates)
+        n = n_all if thin is None else int(thin.numel())
+        g_t = None if given is None else torch.as_tensor(given)
+        count = self.M if count is None else count
+        _, _, G = check_inducing_args(count, None, n, g_t, 1 if xs_t.dim() == 1 else int(xs_t.shape[1]))
+        res = self._choose_inducing(self._engine_for(n + G), xs_t, count, g_t, max_candidates, return_residual)
+        del res["scaled"]
+        return res
+
     # ------------------------------------------------------------------ fold-in: observed samples from their own counts (csrc/foldin.h)
     def _fold_in(self, xs, ws, mode: int, num_iters, tol, ws_score=None, return_diagnostics: bool = False):
         """Engine.fold_in over row pieces (_mc_pieces; a row's result depends on no other row, so the pieces change nothing but mode 3's
@@ -1190,5 +1292,8 @@ def _snapshot_method(name: str):
     return method
 
 
-for _name in SNAPSHOT_METHODS:
+# Forwarded the same way, but no predictive method: it reads the kernel's hyper-parameters alone and chooses points for ANOTHER model
+SNAPSHOT_SETUP_METHODS = ("choose_inducing_points",)
+
+for _name in SNAPSHOT_METHODS + SNAPSHOT_SETUP_METHODS:
     setattr(ModelSnapshot, _name, _snapshot_method(_name))

@@ -85,7 +85,9 @@ def train(data: Union[str, None] = None, xs: Optional[np.ndarray] = None, ws: Op
           streaming_subepochs: int = 1, streaming_batch_splits: int = -1, randomize_wt_matrix: bool = False, seed: int = 1,
           dtype: torch.dtype = torch.float32, perplexity_every: int = 1, rows_form: str = "auto", sparse: bool = False) -> Dict[str, object]:
     """``ws`` may be a ``torch.sparse_csr`` count matrix (int32 values); ``sparse=True`` converts dense counts (an array, or what ``data``
-    loaded) to one.  Either way the model trains and scores on the stored entries alone (csrc/rows_csr.h)."""
+    loaded) to one.  Either way the model trains and scores on the stored entries alone (csrc/rows_csr.h).
+    ``inducing_initialization_method``: "random", "grid", or "greedy": the prod(num_inducing_points) inducing points are chosen among the
+    rows of ``xs`` by conditional variance (SparseMultinomialGDRF.choose_inducing_points) at the initial kernel hyper-parameters."""
     kernel_ls = kernel_lengthscale_arg(kernel_lengthscale, dimensions)
     if data is not None:
         xs, ws = load_csv(data, dimensions)

@@ -552,6 +552,27 @@ int gdrf_joint_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
 int gdrf_select_batch(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* Z_dev, const void* params_dev, const void* given_dev, int G, int count,
                       double noise, int64_t* idx_out_dev, double* gains_out_dev, double* var_out_dev, void* stream);
 
+/* The greedy conditional-variance choice of `count` inducing points among the n rows X (csrc/select_inducing.h): the pivoted partial Cholesky
+ * of the PRIOR kernel matrix K_nn (Burt, Rasmussen, van der Wilk 2020, Alg. 1), gdrf_select_batch's rule without a posterior.  With k the
+ * context's kernel at the hyper-parameters in params_dev (every kind, ARD, Periodic and Product), all in the solve precision:
+ *   d[j] = k(x_j, x_j);   pick t:  p = the t-th given row (t < G), else the candidate not picked yet with the largest d[j], ties to the lower
+ *   index;  piv_t = d[p];  if piv_t > floor:  c_t[j] = (k(x_j, x_p) - sum_{s<t} c_s[j] c_s[p]) / sqrt(piv_t),  d[j] -= c_t[j]^2;  else c_t = 0
+ *   (a degenerate pick: nothing left to explain, or a duplicate among the given rows);  trace_t = sum_{j<n} d[j] = tr(K_nn - Q_nn) so far.
+ *   given_dev   G rows (scaled once, as X), or NULL with G = 0: forced pivots, in their order, ahead of the free picks; they are no candidates
+ *   floor       pivots at or below it are degenerate; the rounding of the history sum, (G + count) eps k(x, x), is the level to pass
+ *   idx_out     count int64 row indices in the order picked (may be NULL when count = 0)
+ *   pivots_out, trace_out   G + count doubles each, the given rows included: d[p] when pick t was made, the residual trace after it
+ *   resid_out   NULL, or (n) doubles: d after the last pick, diag(K_nn - Q_nn)
+ *   rank_out    one int: the picks with piv_t > floor
+ * n >= 1, G >= 0, n + G <= n_cap, 0 <= count <= n, G + count >= 1, G + count <= GDRF_INDUCING_MAX_PICKS, floor finite and >= 0.  count = 0
+ * with G > 0 scores an existing set of points.  Needs no factorisation; neither Z nor the variational parameters enter, and no workspace of the
+ * context is written.  Its buffers, (G + count + 1) (n + G) solve-precision elements, are allocated by the call and released before it
+ * returns, so it synchronises the stream.  Two launches per pick, nothing read back between the picks.  No atomics: bit-identical from call
+ * to call. */
+#define GDRF_INDUCING_MAX_PICKS 1024
+int gdrf_select_inducing(gdrf_ctx* ctx, const void* X_dev, int64_t n, const void* params_dev, const void* given_dev, int G, int count, double floor,
+                         int64_t* idx_out_dev, double* pivots_out_dev, double* trace_out_dev, double* resid_out_dev, int* rank_out_dev, void* stream);
+
 /* Did the last gdrf_factorize() hit a non-positive pivot?  Synchronises the stream. */
 int gdrf_chol_failed(gdrf_ctx* ctx, int* failed_host, void* stream);
 
