@@ -61,6 +61,7 @@ template <class P> struct NTTri<P, decltype((void)P::TRI)> { static constexpr in
 template <class P, class = void> struct NTMinWgs { static constexpr int value = 2; };
 template <class P> struct NTMinWgs<P, decltype((void)P::MIN_WGS)> { static constexpr int value = P::MIN_WGS; };
 
+struct NTNoExtra;
 template <typename T, class P> __device__ __forceinline__ void gemm_nt_body(P& p);
 
 template <typename T, class P>
@@ -77,6 +78,9 @@ __device__ __forceinline__ void gemm_nt_body(P& p) {
   using V = typename Vec16<T>::type;
   using MM = Mfma<T>;
   using acc_t = typename MM::acc_t;
+  // the extra-chunk tail below multiplies with kA = 0, which the triangle test of compute() reads as "first chunk": a TRI == 2 problem with
+  // extra chunks would silently drop them for every MFMA tile with c0 >= BK.  No triangular problem has any; keep it that way.
+  static_assert(NTTri<P>::value == 0 || std::is_base_of<NTNoExtra, P>::value, "a problem that declares TRI must derive from NTNoExtra");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* As = reinterpret_cast<T*>(smem);
   T* Bs = As + GDRF_TILE * C::LDK;
